@@ -27,6 +27,12 @@ Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel
 (the batched gather kernel) by the algorithmic bytes of SURVEY.md 8d divided by
 its average dispatch duration (HIP events bound to every launch); `cpu_baseline` times the CPU
 oracle (single-threaded restatement of the reference loop) on a bounded sample.
+
+--dump-outputs DIR: right after the timed steps (before anything else touches the solver), rank 0
+writes the state they left -- w, intercept, g_sum, g_sum_intercept, g_memory, as SagaSolver.get
+returns them -- to DIR/<name>.npy in float64 (see dump_outputs).  The data and the sample order are
+seeded, so the same arguments give the same inputs on every run and two builds can be compared
+array for array.
 """
 import argparse
 import json
@@ -49,6 +55,37 @@ WORKLOADS = {
     "tiny": (100_000, 1_000, 0.01, "binomial", 1, 7),
 }
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_STATE = ("w", "intercept", "g_sum", "g_sum_intercept", "g_memory")
+DUMP_MAX_ENTRIES = 1 << 20   # per file (8 MB of float64): five arrays and their sample indices stay under 64 MB
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(S, outdir, max_entries=DUMP_MAX_ENTRIES):
+    """Writes S.get(name) for every name of DUMP_STATE to outdir/<name>.npy (float64).  An array of more than
+    `max_entries` entries (g_memory beyond 2^20 samples) is written as a fixed seeded sample of its columns, the
+    same columns on every run, with their indices in outdir/<name>_index.npy.  Returns the bytes written."""
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name in DUMP_STATE:
+        a = S.get(name)
+        files = {name: a}
+        if a.size > max_entries:
+            cols = a.shape[-1]
+            keep = max(1, max_entries // (a.size // cols))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(cols, keep, replace=False))
+            files = {name: a[..., idx], name + "_index": idx.astype(np.float64)}
+        for fname, arr in files.items():
+            arr = np.ascontiguousarray(arr, dtype=np.float64)
+            np.save(os.path.join(outdir, fname + ".npy"), arr)
+            total += arr.nbytes
+    return total
+
+
+def positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
+    return v
 
 
 def self_launch(n_gpus):
@@ -68,7 +105,7 @@ def self_launch(n_gpus):
 def main(merge_override=None, note_override=""):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=positive_int, default=5, help="timed epochs")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="C4", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="staleness window; 0 = automatic (sgdnet_auto_batch)")
@@ -96,6 +133,9 @@ def main(merge_override=None, note_override=""):
                          "falls back to avg where the link cannot be made); avg = periodic RCCL all-reduce of the weighted "
                          "state deltas between local runs; sync = a per-batch all-reduce of the scatter accumulator (exact "
                          "single-GPU iterates)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solver state they computed to DIR/<name>.npy (float64; "
+                         "rank 0's solver when N > 1)")
     args = ap.parse_args()
     if merge_override:                                         # second pass after the peers scheme failed at run time (below)
         args.merge = merge_override
@@ -399,6 +439,11 @@ def main(merge_override=None, note_override=""):
         elapsed = timed_epochs(run_epoch)
 
     note(f"timed region done: {elapsed:.4f}s")
+    if args.dump_outputs and rank == 0:
+        # the state of the last timed step: the profiled epoch, the convergence leg and --alt-merge below all change it
+        note(f"dumped {dump_outputs(S, args.dump_outputs) / 2**20:.1f} MB to {args.dump_outputs}")
+    if args.dump_outputs and world > 1:
+        dist.barrier()                             # the linked epoch kernels below wait for every rank with bounded spins
     # dominant kernel, HIP events around every launch of one more epoch (same stream)
     off = S.rng_next() if pipe else shard.offset
     # sync mode: this rank's share of a global batch, same (global-atomic) gather kernel as the

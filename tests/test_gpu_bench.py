@@ -54,6 +54,27 @@ def test_bench_single_gpu_line_keeps_the_contract(have_gpu):
 
 
 @pytest.mark.timeout(900)
+def test_bench_dumps_the_state_of_its_last_timed_step(have_gpu, tmp_path):
+    # --steps counts timed epochs and the dump is the state after warmup + steps of them: 1 + 3 and 2 + 2 epochs of the
+    # same seeded job end in the same state (up to the batched kernels' summation order), 1 + 2 does not
+    import numpy as np
+    dumps = {}
+    for warmup, steps in ((1, 3), (2, 2), (1, 2)):
+        d = tmp_path / f"w{warmup}s{steps}"
+        out = _run_bench(["--workload", "tiny", "--warmup", str(warmup), "--steps", str(steps), "--no-cpu-baseline",
+                          "--no-convergence", "--dump-outputs", str(d)])
+        assert out["steps"] == steps and out["warmup"] == warmup
+        dumps[warmup, steps] = {f.stem: np.load(f) for f in d.glob("*.npy")}
+    four, also_four, three = dumps[1, 3], dumps[2, 2], dumps[1, 2]
+    assert sorted(four) == sorted(("w", "intercept", "g_sum", "g_sum_intercept", "g_memory"))
+    assert four["w"].shape == (1, 1_000) and four["g_memory"].shape == (1, 100_000)
+    for name, a in four.items():
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)), name
+        np.testing.assert_allclose(also_four[name], a, rtol=1e-9, atol=1e-12 * max(1.0, np.abs(a).max()), err_msg=name)
+    assert np.abs(four["w"] - three["w"]).max() > 1e-6 * np.abs(four["w"]).max()
+
+
+@pytest.mark.timeout(900)
 def test_bench_launches_its_own_ranks(have_gpu):
     # `python bench.py --gpus 2`, not inside torch.distributed.run: bench.py starts the two ranks itself;
     # both share the test box's one GPU and reduce over gloo (RCCL wants one device per rank)
