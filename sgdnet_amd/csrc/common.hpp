@@ -243,35 +243,66 @@ int launch_dense_exact_small(const SagaDev& d, int penalty, const LamParams* lam
                              hipStream_t st);
 size_t dense_exact_lds_bytes(const SagaDev& d, bool stage_state);
 
-int launch_batch_gather(const SagaDev& d, LamParams* lam, int64_t t0_in_epoch, int m, int tail,
-                        int batch_id_offset, hipStream_t st, hipEvent_t ev0 = nullptr,
-                        hipEvent_t ev1 = nullptr);
-int launch_batch_sweep(const SagaDev& d, LamParams* lam, int penalty, int tail, int m, int batch_id_offset,
+// ---- how the batched iteration launches a batch (saga_batched.hip plan_batch: the one rule) ----
+enum class BatchForm {
+  kGlobal,          // global-atomic gather + element sweep
+  kLds,             // sparse x: LDS-privatised gather (three K == 1 variants, K <= 4, class-lane) + slab sweep
+  kBinned,          // sparse x, tables beyond the LDS or 17..64 classes: range-binned gather + range sweep
+  kDense,           // dense x: one LDS copy of the accumulator per workgroup + slab sweep
+  kDenseTiled,      // dense x, table beyond the LDS: gradient changes to d.gcb, D by feature tiles + element sweep
+  kDenseClassLane,  // dense x, 17..64 classes: class-lane gather + tiled accumulate + class-lane sweep
+  kShards,          // virtual shards: one gather and one sweep launch per batch of all V shards, merges between
+  kFusedEpoch,      // virtual shards: the whole epoch in one launch
+};
+struct BatchPlan {
+  BatchForm form;
+  int kw;                // class width of the kernel instances: 1, 4, 16 or 64
+  bool w_lds;            // K == 1 LDS forms: the coefficient snapshot is staged in LDS as well
+  bool lanes8;           // ... and each draw is read by 8 lanes
+  int grid;              // gather workgroups (shards: of all V; fused epoch: + the sample-order generators')
+  int draws_per_block;
+  int chunks;            // tiled forms: draw chunks of the accumulate kernel (blockIdx.y)
+  int draws_per_chunk;
+  size_t lds_bytes;      // dynamic LDS of the gather (fused epoch: of the epoch kernel)
+  int64_t slab_doubles;  // slab storage the plan's launches need
+};
+struct PlanInputs {      // the solver's run-time facts the plan reads besides SagaDev
+  int64_t batch;         // the epoch's full batch (the binned form is chosen for it)
+  bool bins_disabled;    // the bins kept overflowing (solver_grow_bins)
+  bool fused;            // option fused_epoch on, and no fused launch of this solver gave up
+  int cus;               // the device's compute units
+};
+BatchPlan plan_batch(const SagaDev& d, int m, const PlanInputs& in);
+bool wants_binned(const SagaDev& d, int64_t batch);   // ensure_binned builds the binned form's scratch
+bool wants_tiles(const SagaDev& d);                   // ensure_dense_tiled sizes d.gcb
+bool vs_eligible(const SagaDev& d);                   // sgdnet_solver_set_virtual_shards
+bool vs_fused_eligible(const SagaDev& d);             // the linked solvers' check
+int launch_batch_gather(const SagaDev& d, const BatchPlan& g, LamParams* lam, int64_t t0_in_epoch, int m,
+                        int batch_id_offset, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int launch_batch_sweep(const SagaDev& d, const BatchPlan& g, LamParams* lam, int penalty, int tail, int batch_id_offset,
                        hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, double ov_r = 0.0,
                        double ov_ls = 0.0, double ov_m = 0.0);
-int launch_cw_init(const SagaDev& d, const LamParams* lam, hipStream_t st);
-int batch_gather_blocks(const SagaDev& d, int m);
-int64_t batch_gather_slab_doubles(const SagaDev& d, int m);
-int launch_epoch_end(LamParams* lam, int batches, hipStream_t st);
-// virtual shards: one launch covers the same batch of all V shards
-int launch_vs_broadcast(const SagaDev& d, hipStream_t st);
-int launch_vs_gather(const SagaDev& d, LamParams* lam, int64_t t0_in_epoch, int m, hipStream_t st,
+int launch_vs_gather(const SagaDev& d, const BatchPlan& g, LamParams* lam, int64_t t0_in_epoch, int m, hipStream_t st,
                      hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int batch_index = 0);
-int launch_vs_sweep(const SagaDev& d, LamParams* lam, int tail, int m, hipStream_t st, hipEvent_t ev0 = nullptr,
-                    hipEvent_t ev1 = nullptr);
+int launch_vs_sweep(const SagaDev& d, const BatchPlan& g, LamParams* lam, int tail, hipStream_t st,
+                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int launch_vs_epoch(const SagaDev& d, const BatchPlan& g, LamParams* lam, int nb, int every, hipStream_t st,
+                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// a kernel's dynamic-LDS limit, raised once per device and kernel
+int allow_dynamic_lds(const void* kernel, int bytes);
+template <typename F>
+int allow_dynamic_lds(F* kernel, int bytes) { return allow_dynamic_lds(reinterpret_cast<const void*>(kernel), bytes); }
+int launch_cw_init(const SagaDev& d, const LamParams* lam, hipStream_t st);
+int launch_epoch_end(LamParams* lam, int batches, hipStream_t st);
+// virtual shards: the replicas' broadcast, c . w and merges; the fused epoch's buffers
+int launch_vs_broadcast(const SagaDev& d, hipStream_t st);
 int launch_vs_merge(const SagaDev& d, int final_merge, hipStream_t st, LamParams* epoch_end = nullptr, int batches = 0);
 int launch_vs_cw(const SagaDev& d, hipStream_t st);
-bool vs_eligible(const SagaDev& d, int m);
-// the whole epoch of the virtual shards in ONE launch (saga_vs_epoch_kernel)
-bool vs_fused_eligible(const SagaDev& d);
 size_t vs_fused_sync_words();
 size_t vs_fused_sync_sticky_word();
 size_t vs_fused_col_words();
 size_t vs_fused_publish_doubles(const SagaDev& d, int n_shards);
 size_t vs_fused_exchange_doubles(const SagaDev& d, int n_shards);
-int launch_vs_epoch(const SagaDev& d, LamParams* lam, int nb, int every, hipStream_t st, hipEvent_t ev0 = nullptr,
-                    hipEvent_t ev1 = nullptr);
-int vs_fused_rng_workgroups(const SagaDev& d);
 bool compact_eligible(const SagaDev& d);
 int launch_pack_compact(const SagaDev& d, char* P, char* Q, uint32_t* meta, hipStream_t st);
 int compact_entries(const SagaDev& d);
@@ -283,8 +314,6 @@ int launch_delta_export(const SagaDev& d, const double* ref, double* out, double
 int launch_delta_apply(const SagaDev& d, double* ref, const double* merged, double w_weight, hipStream_t st);
 int batched_max_classes();
 int lds_target_grid(const SagaDev& d);   // workgroups of the LDS-privatised gather forms (one per CU)
-// binned form: is it the form launch_batch_gather / launch_batch_sweep would use for m draws?
-bool binned_active(const SagaDev& d, int m);
 int launch_col_count(const SagaDev& d, int64_t nnz, unsigned* counts, hipStream_t st);
 int launch_wpad_refresh(const SagaDev& d, hipStream_t st);
 int launch_range_moment(const SagaDev& d, const uint16_t* feat_range, unsigned long long* sumsq, int R, hipStream_t st);

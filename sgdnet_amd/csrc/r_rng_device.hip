@@ -33,14 +33,8 @@ __global__ __launch_bounds__(kJumpBlock) void r_mt_jump_kernel(const uint32_t* s
 // gens generators, at most `max_wgs` workgroups (each takes its generators in turn)
 int launch_rng_jump(const uint32_t* state_in, uint32_t* state_out, const uint32_t* poly_dev, int gens,
                     hipStream_t st, int max_wgs) {
-  static bool attr_done_dev[64] = {};
-  int cur = 0;
-  (void)hipGetDevice(&cur);
-  if (!attr_done_dev[cur & 63]) {
-    SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(r_mt_jump_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kJumpLds));
-    attr_done_dev[cur & 63] = true;
-  }
+  const int rc = allow_dynamic_lds(r_mt_jump_kernel, (int)kJumpLds);
+  if (rc) return rc;
   int grid = gens;
   if (max_wgs > 0 && grid > max_wgs) grid = max_wgs;
   hipLaunchKernelGGL(r_mt_jump_kernel, dim3(grid), dim3(kJumpBlock), kJumpLds, st, state_in, state_out, poly_dev, gens);

@@ -27,6 +27,11 @@
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 
+#include <mutex>
+#include <set>
+#include <type_traits>
+#include <utility>
+
 #include "device_math.hpp"
 #include "r_rng_word.hpp"
 #include "r_rng_bodies.hpp"
@@ -3428,100 +3433,40 @@ int lds_target_grid(const SagaDev& d) {
   return g < 64 ? 64 : g;
 }
 
-// Launch geometry of the gather for a batch of m draws.  The LDS-privatised form
-// needs the dense K*p table in LDS twice per CU (2 workgroups per CU) and enough
-// draws per workgroup to amortise its flush.
-struct GatherPlan {
-  bool binned;  // range-binned form (tables that fit no LDS)
-  bool lds;     // per-workgroup LDS copies of D flushed as slabs (sparse LDS form and dense form)
-  bool dense;   // dense x: saga_batch_gather_dense_kernel
-  bool tiled;   // dense x, table beyond LDS: gradient changes to d.gcb, D by feature tiles (global sweep)
-  int chunks;   // tiled: draw chunks of the accumulate kernel (blockIdx.y)
-  int draws_per_chunk;
-  bool w_lds;   // K == 1: the coefficient snapshot is staged in LDS as well
-  int grid;
-  int draws_per_block;
-  size_t lds_bytes;
-};
 constexpr size_t kLdsPerCu = 160 * 1024;        // gfx950
 constexpr size_t kLdsStaticReserve = 2 * 1024;  // static __shared__ of the LDS gather kernels
+constexpr size_t kLdsTableMax = 80 * 1024;      // K x p accumulator the LDS forms stage (two workgroups per CU)
+constexpr int kLdsCap = 96 * 1024;              // dynamic-LDS limit of the kernels that stage one such table
+constexpr int kLdsAll = (int)(kLdsPerCu - kLdsStaticReserve);
+constexpr int kDenseVsBlock = 1024;             // dense K == 1 shards: 16 wavefronts share one LDS copy of the accumulator
 
-static GatherPlan plan_gather(const SagaDev& d, int m) {
-  GatherPlan g{};
-  const size_t table = sizeof(double) * (size_t)d.K * (size_t)d.p;
-  static const int force = [] {
-    const char* e = exp_env_str("SGDNET_GATHER");   // "lds" | "global": experiments only
-    return !e ? 0 : (e[0] == 'l' ? 1 : 2);
-  }();
-  const int target_grid = lds_target_grid(d);
-  const bool fits = table <= 80 * 1024;
-  if (d.xd) {   // dense x: wave per draw; LDS table + slabs, or the tiled form for larger tables
-    g.dense = true;
-    g.lds = d.slab != nullptr && fits;
-    const int waves = kDenseBlock / 64;
-    if (d.gcb && d.K <= 64 && (!fits || d.K > 16)) {     // 17..64 classes: always (the class-lane gather, round 4)
-      g.tiled = true;
-      int dpb = (m + 8191) / 8192;               // a row is >= 5 KB here: one or a few draws per wavefront
-      dpb = (dpb + waves - 1) / waves * waves;
-      if (dpb < waves) dpb = waves;
-      g.draws_per_block = dpb;
-      g.grid = (m + dpb - 1) / dpb;
-      if (g.grid < 1) g.grid = 1;
-      const int64_t tiles = (d.p + kTileF - 1) / kTileF;
-      int64_t chunks = (2048 + tiles - 1) / tiles;   // ~2048 workgroups over the chip
-      const int64_t most = (m + 4 * waves - 1) / (4 * waves);
-      if (chunks > most) chunks = most;
-      if (chunks < 1) chunks = 1;
-      if (chunks > 65535) chunks = 65535;
-      g.draws_per_chunk = (int)((m + chunks - 1) / chunks);
-      g.chunks = (int)((m + g.draws_per_chunk - 1) / g.draws_per_chunk);
-      return g;
-    }
-    int dpb = (m + target_grid - 1) / target_grid;
-    dpb = (dpb + waves - 1) / waves * waves;
-    if (dpb < waves) dpb = waves;
-    g.draws_per_block = dpb;
-    g.grid = (m + dpb - 1) / dpb;
-    if (g.grid < 1) g.grid = 1;
-    g.lds_bytes = table;
-    return g;
-  }
-  // worthwhile once the batch's non-zeros outnumber the table ~48x: below that the fixed
-  // cost of writing and re-reading one table per workgroup exceeds the atomics it saves
-  if (d.R > 0 && d.bins && !d.force_global && force != 2 && m <= (1 << 20)) {
-    g.binned = true;
-    g.draws_per_block = kBinDraws;
-    g.grid = (m + kBinDraws - 1) / kBinDraws;
-    if (g.grid < 1) g.grid = 1;
-    g.lds_bytes = sizeof(BinEntry) * (size_t)kBinEntCap + sizeof(unsigned) * (3 * (size_t)d.R + 1) +
-                  ((sizeof(unsigned short) * ((size_t)d.n_coarse + 1) + 15) & ~size_t(15));
-    return g;
-  }
-  const bool pays = (double)m * (double)d.avg_nnz >= 48.0 * (double)d.K * (double)d.p;
-  g.lds = d.slab != nullptr && !d.force_global && fits && force != 2 && (force == 1 || pays);
-  if (g.lds) {
-    int dpb = (m + target_grid - 1) / target_grid;
-    const int per_round = kLdsBlock / kGroup;
-    if (dpb < per_round) dpb = per_round;
-    g.draws_per_block = dpb;
-    g.grid = (m + dpb - 1) / dpb;
-    g.lds_bytes = table;
-    static const bool w_lds_on = exp_env_int("SGDNET_W_LDS", 1) != 0;
-    g.w_lds = d.K == 1 && w_lds_on && 2 * table + kLdsStaticReserve <= kLdsPerCu;
-    if (g.w_lds) g.lds_bytes = 2 * table + 16;   // + alignment slack of the second table
-  } else {
-    g.draws_per_block = kBlock / kGroup;
-    g.grid = (m + g.draws_per_block - 1) / g.draws_per_block;
-  }
-  if (g.grid < 1) g.grid = 1;
-  return g;
+static size_t table_bytes(const SagaDev& d) { return sizeof(double) * (size_t)d.K * (size_t)d.p; }
+
+// Function attributes are per device (one process may drive several GPUs: cv_sgdnet fan-out): the limit is raised
+// once per device and kernel, a launch after that makes no HIP call for it but hipGetDevice.
+int allow_dynamic_lds(const void* kernel, int bytes) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count({kernel, dev})) return SGDNET_OK;
+  SGD_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done.insert({kernel, dev});
+  return SGDNET_OK;
 }
 
-int batch_gather_blocks(const SagaDev& d, int m) { return plan_gather(d, m).grid; }
-bool binned_active(const SagaDev& d, int m) { return !d.xd && plan_gather(d, m).binned; }
+// The class width of the kernel instances for K classes: 1, 4, 16 or 64 (17..64 classes: binned and class-lane forms).
+static int class_width(int K) { return K == 1 ? 1 : K <= 4 ? 4 : K <= 16 ? 16 : 64; }
 
-// Doubles of slab storage the LDS-privatised gather needs for batches of m draws (0: the
-// global-atomic form is used).
+// f(std::integral_constant<int, KW>{}) for the instance of class width kw <= 16 (KMAX template parameter)
+template <typename F>
+static int with_class_width(int kw, F&& f) {
+  if (kw == 1) return f(std::integral_constant<int, 1>{});
+  if (kw == 4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 16>{});
+}
+
 // the 8-lane K == 1 form reads two entries per lane: records must hold 16 entries
 static bool lanes8_ok(const SagaDev& d) {
   static const int allow = exp_env_int("SGDNET_LANES8", 1);
@@ -3558,171 +3503,250 @@ int launch_m_move(const SagaDev& d, int to_record, hipStream_t st) {
   SGD_HIP_TRY(hipGetLastError());
   return SGDNET_OK;
 }
+// Binned form (sparse x): K x p tables that fit no LDS, at batches of 4096 draws and more, and 17..64 classes whatever
+// the sizes (the only batched form there).  ensure_binned builds the ranges and sizes the bins when this holds.
+bool wants_binned(const SagaDev& d, int64_t batch) {
+  static const int allow = exp_env_int("SGDNET_BINNED", 1);
+  return allow && !d.xd && d.rec && d.idx && d.K <= 64 && !d.force_global && d.p < (1ll << 31) &&
+         (d.K > 16 || (table_bytes(d) > kLdsTableMax && batch >= 4096));
+}
 
-int64_t batch_gather_slab_doubles(const SagaDev& d, int m) {
-  SagaDev probe = d;
-  probe.slab = reinterpret_cast<double*>(1);
-  const GatherPlan g = plan_gather(probe, m);
-  return g.lds ? (int64_t)g.grid * d.K * d.p : 0;
+// Dense x whose gather hands the batch's gradient changes to an accumulate pass (d.gcb, sized by ensure_dense_tiled):
+// K x p tables beyond the LDS, and 17..64 classes whatever the table (the class-lane gather).
+bool wants_tiles(const SagaDev& d) { return d.xd && d.K <= 64 && (d.K > 16 || table_bytes(d) > kLdsTableMax); }
+
+// Virtual shards need an LDS gather form: K == 1 with w staged in LDS (sparse or dense x), or 2..16 classes of sparse x
+// whose K x p accumulator fits (round 3; the replica of w is read through L2), or dense x (1..16 classes) whose
+// accumulator fits.
+bool vs_eligible(const SagaDev& d) {
+  if (d.V < 2 || d.K < 1 || d.K > 16 || (d.standardize && !(d.vcw && d.c)) || d.force_global || !d.vw) return false;
+  const size_t table = table_bytes(d);
+  if (d.xd) return table <= kLdsTableMax;                        // only the accumulator is staged
+  if (d.K > 1) return d.rec && table <= kLdsTableMax;
+  return 2 * table + 16 + kLdsStaticReserve <= kLdsPerCu;     // accumulator + coefficient snapshot in LDS
+}
+
+static int vs_grid(const SagaDev& d) { return d.v_bps * d.V; }
+
+// ---- the fused epoch of the virtual shards (saga_vs_epoch_kernel) ----
+static int64_t fused_slice(const SagaDev& d) { return 2 * ((d.p + 2 * (int64_t)d.v_bps - 1) / (2 * (int64_t)d.v_bps)); }
+static size_t fused_lds_bytes(const SagaDev& d) {
+  const int64_t part = (int64_t)(kLdsBlock / 64) * fused_slice(d);     // the slice sweep's per-wavefront partial sums
+  return sizeof(double) * (size_t)(d.p + (part > d.p ? part : d.p)) + 16;
+}
+size_t vs_fused_sync_words() { return (size_t)(kSyncLines + 2) * kSyncLine; }
+size_t vs_fused_sync_sticky_word() { return (size_t)kSyncSticky * kSyncLine; }
+size_t vs_fused_col_words() { return (size_t)kFusedMaxBps * kSyncLine; }
+// local: V reference copies [g_sum | w | g_sum_b | b] + V x 128 c.w partials; published: 2 parities x V slices
+size_t vs_fused_exchange_doubles(const SagaDev& d, int n_shards) {
+  return (size_t)n_shards * (size_t)(2 * d.p + 2) + (size_t)n_shards * kFusedMaxBps;
+}
+size_t vs_fused_publish_doubles(const SagaDev& d, int n_shards) { return (size_t)2 * n_shards * (size_t)(2 * d.p + 2); }
+
+// sparse x, one response, compact records, an even number of features, slices of at most 384 features
+bool vs_fused_eligible(const SagaDev& d) {
+  if (!vs_eligible(d) || d.K != 1 || d.xd || !d.cP || !lanes8_ok(d) || (d.p & 1) || !d.vsync || !d.vx || !d.vcol || !d.vpub) return false;
+  if (d.v_bps < 1 || d.v_bps > kFusedMaxBps || d.V * d.v_bps > 1024) return false;
+  if (fused_slice(d) > 2 * 64 * kFusedChunks) return false;
+  if ((int64_t)d.V * d.v_bps * d.p * 8 >= (1ll << 31)) return false;
+  return fused_lds_bytes(d) + kLdsStaticReserve <= kLdsPerCu;
+}
+
+// workgroups added to the launch for the sample-order generators (one per reserved CU)
+static int vs_fused_rng_workgroups(const SagaDev& d) { return d.rngdev ? d.cu_reserve : 0; }
+
+// How a batch of m draws is launched: the batched iteration's one rule.  The binned form is chosen for the epoch's full
+// batch (in.batch), and its tail batch follows.
+BatchPlan plan_batch(const SagaDev& d, int m, const PlanInputs& in) {
+  BatchPlan g{};
+  g.kw = class_width(d.K);
+  const size_t table = table_bytes(d);
+  if (d.V > 1 && vs_eligible(d)) {      // virtual shards: one launch covers the same batch of all V shards
+    const int rng_wgs = vs_fused_rng_workgroups(d);
+    g.slab_doubles = (int64_t)vs_grid(d) * d.K * d.p;
+    if (in.fused && vs_fused_eligible(d) && vs_grid(d) + rng_wgs <= in.cus) {
+      g.form = BatchForm::kFusedEpoch;
+      g.grid = vs_grid(d) + rng_wgs;
+      g.lds_bytes = fused_lds_bytes(d);
+      if (rng_wgs > 0 && g.lds_bytes < kJumpLds) g.lds_bytes = kJumpLds;
+      return g;
+    }
+    g.form = BatchForm::kShards;
+    g.grid = vs_grid(d);
+    int dpb = (m + d.v_bps - 1) / d.v_bps;
+    g.lds_bytes = table;
+    if (d.xd) {
+      const int waves = (d.K > 1 ? kDenseBlock : kDenseVsBlock) / 64;
+      dpb = (dpb + waves - 1) / waves * waves;
+    } else {
+      const int per_round = kLdsBlock / kGroup;
+      if (dpb < per_round) dpb = per_round;
+      if (d.K == 1) {
+        g.w_lds = true;
+        g.lanes8 = lanes8_ok(d);
+        g.lds_bytes = 2 * table + 16;
+      }
+    }
+    g.draws_per_block = dpb;
+    return g;
+  }
+  static const int force = [] {
+    const char* e = exp_env_str("SGDNET_GATHER");   // "lds" | "global": experiments only
+    return !e ? 0 : (e[0] == 'l' ? 1 : 2);
+  }();
+  const int target_grid = lds_target_grid(d);
+  const bool fits = table <= kLdsTableMax;
+  if (d.xd) {   // dense x: wave per draw; LDS table + slabs, or the tiled form for larger tables
+    const int waves = kDenseBlock / 64;
+    if (wants_tiles(d)) {
+      g.form = d.K > 16 ? BatchForm::kDenseClassLane : BatchForm::kDenseTiled;
+      int dpb = (m + 8191) / 8192;               // a row is >= 5 KB here: one or a few draws per wavefront
+      dpb = (dpb + waves - 1) / waves * waves;
+      if (dpb < waves) dpb = waves;
+      g.draws_per_block = dpb;
+      g.grid = (m + dpb - 1) / dpb;
+      if (g.grid < 1) g.grid = 1;
+      const int64_t tiles = (d.p + kTileF - 1) / kTileF;
+      int64_t chunks = (2048 + tiles - 1) / tiles;   // ~2048 workgroups over the chip
+      const int64_t most = (m + 4 * waves - 1) / (4 * waves);
+      if (chunks > most) chunks = most;
+      if (chunks < 1) chunks = 1;
+      if (chunks > 65535) chunks = 65535;
+      g.draws_per_chunk = (int)((m + chunks - 1) / chunks);
+      g.chunks = (int)((m + g.draws_per_chunk - 1) / g.draws_per_chunk);
+      // (kept from before the plan: 17..64 classes whose table fits size a slab the class-lane form does not use, and
+      //  sgdnet_solver_gather_form answers 1 for them)
+      g.slab_doubles = fits ? (int64_t)g.grid * d.K * d.p : 0;
+      return g;
+    }
+    g.form = BatchForm::kDense;
+    int dpb = (m + target_grid - 1) / target_grid;
+    dpb = (dpb + waves - 1) / waves * waves;
+    if (dpb < waves) dpb = waves;
+    g.draws_per_block = dpb;
+    g.grid = (m + dpb - 1) / dpb;
+    if (g.grid < 1) g.grid = 1;
+    g.lds_bytes = table;
+    // (only more than 64 classes, which no batched launch accepts, leave a table beyond the LDS here)
+    g.slab_doubles = fits ? (int64_t)g.grid * d.K * d.p : 0;
+    return g;
+  }
+  // a tail batch of more than 2^20 draws after full batches of fewer is binned (full batches of more are not)
+  if (wants_binned(d, in.batch) && d.R > 0 && !in.bins_disabled && force != 2 && m <= (1 << 20)) {
+    g.form = BatchForm::kBinned;
+    g.draws_per_block = kBinDraws;
+    g.grid = (m + kBinDraws - 1) / kBinDraws;
+    if (g.grid < 1) g.grid = 1;
+    g.lds_bytes = sizeof(BinEntry) * (size_t)kBinEntCap + sizeof(unsigned) * (3 * (size_t)d.R + 1) +
+                  ((sizeof(unsigned short) * ((size_t)d.n_coarse + 1) + 15) & ~size_t(15));
+    return g;
+  }
+  // worthwhile once the batch's non-zeros outnumber the table ~48x: below that the fixed
+  // cost of writing and re-reading one table per workgroup exceeds the atomics it saves
+  const bool pays = (double)m * (double)d.avg_nnz >= 48.0 * (double)d.K * (double)d.p;
+  if (!d.force_global && fits && force != 2 && (force == 1 || pays)) {
+    g.form = BatchForm::kLds;
+    int dpb = (m + target_grid - 1) / target_grid;
+    const int per_round = kLdsBlock / kGroup;
+    if (dpb < per_round) dpb = per_round;
+    g.draws_per_block = dpb;
+    g.grid = (m + dpb - 1) / dpb;
+    g.lds_bytes = table;
+    static const bool w_lds_on = exp_env_int("SGDNET_W_LDS", 1) != 0;
+    g.w_lds = d.K == 1 && w_lds_on && 2 * table + kLdsStaticReserve <= kLdsPerCu;
+    if (g.w_lds) g.lds_bytes = 2 * table + 16;   // + alignment slack of the second table
+    g.lanes8 = g.w_lds && lanes8_ok(d);
+  } else {
+    g.form = BatchForm::kGlobal;
+    g.draws_per_block = kBlock / kGroup;
+    g.grid = (m + g.draws_per_block - 1) / g.draws_per_block;
+  }
+  if (g.grid < 1) g.grid = 1;
+  if (g.form == BatchForm::kLds) g.slab_doubles = (int64_t)g.grid * d.K * d.p;
+  return g;
 }
 
 // ev0/ev1 (optional): dispatch start/stop timestamps of exactly this kernel
 // (hipExtLaunchKernelGGL), used by the benchmark's per-kernel timing.
-int launch_batch_gather(const SagaDev& d, LamParams* lam, int64_t t0_in_epoch, int m, int tail,
+int launch_batch_gather(const SagaDev& d, const BatchPlan& g, LamParams* lam, int64_t t0_in_epoch, int m,
                         int batch_id_offset, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  (void)tail;
-  const GatherPlan g = plan_gather(d, m);
-  if (d.K > 16 && !g.binned && !g.tiled) {
+  if (d.K > 16 && g.form != BatchForm::kBinned && g.form != BatchForm::kDenseClassLane) {
     set_error("batched mode with more than 16 classes needs the binned form (sparse x) or the class-lane form (dense x), "
               "n_classes <= 64; got %d", d.K);
     return SGDNET_EUNSUPPORTED;
   }
-  if (g.tiled && d.K > 16) {
+  // accumulate pass of the tiled forms: feature tiles x draw chunks x groups of 16 classes
+  const dim3 agrid((unsigned)((d.p + kTileF - 1) / kTileF), (unsigned)g.chunks, (unsigned)((d.K + 15) / 16));
+  switch (g.form) {
+  case BatchForm::kDenseClassLane:
     hipExtLaunchKernelGGL(saga_dense_cl_gather_kernel, dim3(g.grid), dim3(kDenseBlock), 0, st, ev0, nullptr, 0, d, lam,
                           t0_in_epoch, m, batch_id_offset, g.draws_per_block);
     SGD_HIP_TRY(hipGetLastError());
-    const dim3 agrid((unsigned)((d.p + kTileF - 1) / kTileF), (unsigned)g.chunks, (unsigned)((d.K + 15) / 16));
     hipExtLaunchKernelGGL(saga_dense_tiled_accumulate_kernel<16>, agrid, dim3(kDenseBlock), 0, st, nullptr, ev1, 0, d, lam,
                           t0_in_epoch, m, g.draws_per_chunk);
-    SGD_HIP_TRY(hipGetLastError());
-    return SGDNET_OK;
-  }
-  if (g.tiled) {
-    if (d.K == 1)
-      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<1, kDenseBlock, false, true>), dim3(g.grid), dim3(kDenseBlock),
+    break;
+  case BatchForm::kDenseTiled:
+    return with_class_width(g.kw, [&](auto kw) {
+      constexpr int KW = decltype(kw)::value;
+      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<KW, kDenseBlock, false, true>), dim3(g.grid), dim3(kDenseBlock),
                             0, st, ev0, nullptr, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else if (d.K <= 4)
-      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<4, kDenseBlock, false, true>), dim3(g.grid), dim3(kDenseBlock),
-                            0, st, ev0, nullptr, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else
-      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<16, kDenseBlock, false, true>), dim3(g.grid), dim3(kDenseBlock),
-                            0, st, ev0, nullptr, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    SGD_HIP_TRY(hipGetLastError());
-    const dim3 agrid((unsigned)((d.p + kTileF - 1) / kTileF), (unsigned)g.chunks);
-    if (d.K == 1)
-      hipExtLaunchKernelGGL(saga_dense_tiled_accumulate_kernel<1>, agrid, dim3(kDenseBlock), 0, st, nullptr, ev1, 0, d,
+      SGD_HIP_TRY(hipGetLastError());
+      hipExtLaunchKernelGGL(saga_dense_tiled_accumulate_kernel<KW>, agrid, dim3(kDenseBlock), 0, st, nullptr, ev1, 0, d,
                             lam, t0_in_epoch, m, g.draws_per_chunk);
-    else if (d.K <= 4)
-      hipExtLaunchKernelGGL(saga_dense_tiled_accumulate_kernel<4>, agrid, dim3(kDenseBlock), 0, st, nullptr, ev1, 0, d,
-                            lam, t0_in_epoch, m, g.draws_per_chunk);
-    else
-      hipExtLaunchKernelGGL(saga_dense_tiled_accumulate_kernel<16>, agrid, dim3(kDenseBlock), 0, st, nullptr, ev1, 0, d,
-                            lam, t0_in_epoch, m, g.draws_per_chunk);
-    SGD_HIP_TRY(hipGetLastError());
-    return SGDNET_OK;
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    });
+  case BatchForm::kDense:
+    return with_class_width(g.kw, [&](auto kw) {
+      constexpr int KW = decltype(kw)::value;
+      const int rc = allow_dynamic_lds(saga_batch_gather_dense_kernel<KW>, kLdsCap);
+      if (rc) return rc;
+      hipExtLaunchKernelGGL(saga_batch_gather_dense_kernel<KW>, dim3(g.grid), dim3(kDenseBlock), g.lds_bytes, st,
+                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    });
+  case BatchForm::kBinned: {
+    auto launch = [&](auto kernel) {
+      const int rc = allow_dynamic_lds(kernel, kLdsAll);
+      if (rc) return rc;
+      hipExtLaunchKernelGGL(kernel, dim3(g.grid), dim3(kBinBlock), g.lds_bytes, st, ev0, ev1, 0, d, lam, t0_in_epoch, m,
+                            batch_id_offset);
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    };
+    if (g.kw == 64) return launch(saga_binned_gather_kernel<64>);
+    return d.family == SGDNET_MULTINOMIAL ? launch(saga_binned_gather_kernel<16, true>) : launch(saga_binned_gather_kernel<16>);
   }
-  if (g.dense) {
-    if (!g.lds) {
-      set_error("batched mode on dense x with n_classes * n_features > 10240 needs n_classes <= 16 (tiled form)");
-      return SGDNET_EUNSUPPORTED;
-    }
-    // function attributes are per device: one process may drive several GPUs (cv_sgdnet fan-out)
-    static bool dense_attr_done_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& dense_attr_done = dense_attr_done_dev[cur_dev & 63];
-    if (!dense_attr_done) {
-      const int cap = 96 * 1024;
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_dense_kernel<1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_dense_kernel<4>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_dense_kernel<16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      dense_attr_done = true;
-    }
-    if (d.K == 1)
-      hipExtLaunchKernelGGL(saga_batch_gather_dense_kernel<1>, dim3(g.grid), dim3(kDenseBlock), g.lds_bytes, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else if (d.K <= 4)
-      hipExtLaunchKernelGGL(saga_batch_gather_dense_kernel<4>, dim3(g.grid), dim3(kDenseBlock), g.lds_bytes, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else
-      hipExtLaunchKernelGGL(saga_batch_gather_dense_kernel<16>, dim3(g.grid), dim3(kDenseBlock), g.lds_bytes, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    SGD_HIP_TRY(hipGetLastError());
-    return SGDNET_OK;
+  case BatchForm::kLds: {
+    auto launch = [&](auto kernel, int cap) {
+      const int rc = allow_dynamic_lds(kernel, cap);
+      if (rc) return rc;
+      hipExtLaunchKernelGGL(kernel, dim3(g.grid), dim3(kLdsBlock), g.lds_bytes, st, ev0, ev1, 0, d, lam, t0_in_epoch, m,
+                            batch_id_offset, g.draws_per_block);
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    };
+    if (g.lanes8) return launch(saga_batch_gather_lds_kernel<1, true, false, kLanes8>, kLdsAll);
+    if (g.w_lds) return launch(saga_batch_gather_lds_kernel<1, true>, kLdsAll);
+    if (g.kw == 1) return launch(saga_batch_gather_lds_kernel<1>, kLdsCap);
+    if (g.kw == 4) return launch(saga_batch_gather_lds_kernel<4>, kLdsCap);
+    return launch(saga_batch_gather_cl_kernel<true>, kLdsCap);
   }
-  if (g.binned) {
-    static bool battr_done_dev[64] = {};
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    if (!battr_done_dev[cur & 63]) {
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_gather_kernel<16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_gather_kernel<16, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_gather_kernel<64>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_sweep_kernel<16, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRangeLdsBytes));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_sweep_kernel<16, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRangeLdsBytes));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_sweep_kernel<64, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRangeLdsBytes));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_binned_sweep_kernel<64, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRangeLdsBytes));
-      battr_done_dev[cur & 63] = true;
-    }
-    if (d.K <= 16 && d.family == SGDNET_MULTINOMIAL)
-      hipExtLaunchKernelGGL((saga_binned_gather_kernel<16, true>), dim3(g.grid), dim3(kBinBlock), g.lds_bytes, st, ev0, ev1, 0,
-                            d, lam, t0_in_epoch, m, batch_id_offset);
-    else if (d.K <= 16)
-      hipExtLaunchKernelGGL(saga_binned_gather_kernel<16>, dim3(g.grid), dim3(kBinBlock), g.lds_bytes, st, ev0, ev1, 0,
-                            d, lam, t0_in_epoch, m, batch_id_offset);
-    else
-      hipExtLaunchKernelGGL(saga_binned_gather_kernel<64>, dim3(g.grid), dim3(kBinBlock), g.lds_bytes, st, ev0, ev1, 0,
-                            d, lam, t0_in_epoch, m, batch_id_offset);
-    SGD_HIP_TRY(hipGetLastError());
-    return SGDNET_OK;
-  }
-  if (g.lds) {
-    static bool attr_done_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& attr_done = attr_done_dev[cur_dev & 63];
-    if (!attr_done) {
-      const int cap = 96 * 1024;   // the dense table is limited to 80 KiB (plan_gather)
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<1, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kLdsPerCu - kLdsStaticReserve));
-      SGD_HIP_TRY(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<1, true, false, kLanes8>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<4>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_cl_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      attr_done = true;
-    }
-    if (d.K == 1 && g.w_lds && lanes8_ok(d))
-      hipExtLaunchKernelGGL((saga_batch_gather_lds_kernel<1, true, false, kLanes8>), dim3(g.grid), dim3(kLdsBlock),
-                            g.lds_bytes, st, ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset,
-                            g.draws_per_block);
-    else if (d.K == 1 && g.w_lds)
-      hipExtLaunchKernelGGL((saga_batch_gather_lds_kernel<1, true>), dim3(g.grid), dim3(kLdsBlock), g.lds_bytes,
-                            st, ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else if (d.K == 1)
-      hipExtLaunchKernelGGL(saga_batch_gather_lds_kernel<1>, dim3(g.grid), dim3(kLdsBlock), g.lds_bytes, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else if (d.K <= 4)
-      hipExtLaunchKernelGGL(saga_batch_gather_lds_kernel<4>, dim3(g.grid), dim3(kLdsBlock), g.lds_bytes, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-    else
-      hipExtLaunchKernelGGL(saga_batch_gather_cl_kernel<true>, dim3(g.grid), dim3(kLdsBlock), g.lds_bytes,
-                            st, ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
-  } else {
-    if (d.K == 1)
+  case BatchForm::kGlobal:
+    if (g.kw == 1)
       hipExtLaunchKernelGGL(saga_batch_gather_kernel<1>, dim3(g.grid), dim3(kBlock), 0, st, ev0, ev1, 0, d,
                             lam, t0_in_epoch, m, batch_id_offset);
-    else if (d.K <= 4)
+    else if (g.kw == 4)
       hipExtLaunchKernelGGL(saga_batch_gather_kernel<4>, dim3(g.grid), dim3(kBlock), 0, st, ev0, ev1, 0, d,
                             lam, t0_in_epoch, m, batch_id_offset);
     else
       hipExtLaunchKernelGGL(saga_batch_gather_cl_kernel<false>, dim3(g.grid), dim3(kBlock), 0, st, ev0, ev1,
                             0, d, lam, t0_in_epoch, m, batch_id_offset, g.draws_per_block);
+    break;
+  default:
+    set_error("internal: launch_batch_gather given a virtual-shard plan");
+    return SGDNET_EINVAL;
   }
   SGD_HIP_TRY(hipGetLastError());
   return SGDNET_OK;
@@ -3734,66 +3758,55 @@ int launch_cw_init(const SagaDev& d, const LamParams* lam, hipStream_t st) {
   return SGDNET_OK;
 }
 
-int launch_batch_sweep(const SagaDev& d, LamParams* lam, int penalty, int tail, int m, int batch_id_offset,
+int launch_batch_sweep(const SagaDev& d, const BatchPlan& g, LamParams* lam, int penalty, int tail, int batch_id_offset,
                        hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, double ov_r, double ov_ls, double ov_m) {
-  const GatherPlan g = plan_gather(d, m);
   // synchronous sharded mode (ov_m > 0): the slots were summed across ranks whose gather grids
   // may differ by one workgroup, so all of them are read (unused slots are zero)
   const int n_parts = ov_m > 0.0 ? kD0Slots : (g.grid < kD0Slots ? g.grid : kD0Slots);
   const SweepOverride ov{ov_r, ov_ls, ov_m};
-  if (g.binned) {
-    const size_t lds = sizeof(double) * (size_t)d.K * (size_t)d.range_max;
-    const dim3 grid(d.R + 1), block(kRangeBlock);
-    if (d.K <= 16 && penalty != SGDNET_GROUPLASSO)
-      hipExtLaunchKernelGGL((saga_binned_sweep_kernel<16, false>), grid, block, lds, st, ev0, ev1, 0, d, lam, tail, n_parts,
-                            batch_id_offset);
-    else if (d.K <= 16)
-      hipExtLaunchKernelGGL((saga_binned_sweep_kernel<16, true>), grid, block, lds, st, ev0, ev1, 0, d, lam, tail, n_parts,
-                            batch_id_offset);
-    else if (penalty != SGDNET_GROUPLASSO)
-      hipExtLaunchKernelGGL((saga_binned_sweep_kernel<64, false>), grid, block, lds, st, ev0, ev1, 0, d, lam, tail, n_parts,
-                            batch_id_offset);
-    else
-      hipExtLaunchKernelGGL((saga_binned_sweep_kernel<64, true>), grid, block, lds, st, ev0, ev1, 0, d, lam, tail, n_parts,
-                            batch_id_offset);
-    SGD_HIP_TRY(hipGetLastError());
-    return SGDNET_OK;
+  switch (g.form) {
+  case BatchForm::kBinned: {
+    auto launch = [&](auto kernel) {
+      const int rc = allow_dynamic_lds(kernel, (int)kRangeLdsBytes);
+      if (rc) return rc;
+      hipExtLaunchKernelGGL(kernel, dim3(d.R + 1), dim3(kRangeBlock), sizeof(double) * (size_t)d.K * (size_t)d.range_max,
+                            st, ev0, ev1, 0, d, lam, tail, n_parts, batch_id_offset);
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    };
+    const bool grouped = penalty == SGDNET_GROUPLASSO;
+    if (g.kw == 64)
+      return grouped ? launch(saga_binned_sweep_kernel<64, true>) : launch(saga_binned_sweep_kernel<64, false>);
+    return grouped ? launch(saga_binned_sweep_kernel<16, true>) : launch(saga_binned_sweep_kernel<16, false>);
   }
-  if (g.tiled && d.K > 16) {
+  case BatchForm::kDenseClassLane: {
     const int grid = (int)((d.p + kBlock / 64 - 1) / (kBlock / 64));
     hipExtLaunchKernelGGL(saga_dense_cl_sweep_kernel, dim3(grid < 1 ? 1 : grid), dim3(kBlock), 0, st, ev0, ev1, 0, d, lam,
                           tail, n_parts, batch_id_offset);
-  } else if (g.lds) {
+    break;
+  }
+  case BatchForm::kLds:
+  case BatchForm::kDense: {
     const int F = kSlabElems / d.K;
     const int grid = (int)((d.p + F - 1) / F);
     hipExtLaunchKernelGGL(saga_batch_sweep_slab_kernel, dim3(grid < 1 ? 1 : grid), dim3(kBlock), 0, st, ev0,
                           ev1, 0, d, lam, tail, g.grid, batch_id_offset);
-  } else if (penalty == SGDNET_GROUPLASSO) {
-    const int grid = (int)((d.p + kBlock - 1) / kBlock);
-    hipExtLaunchKernelGGL(saga_batch_sweep_kernel<true>, dim3(grid < 1 ? 1 : grid), dim3(kBlock), 0, st, ev0,
-                          ev1, 0, d, lam, tail, n_parts, batch_id_offset, ov);
-  } else {
-    const int grid = (int)(((int64_t)d.K * d.p + kBlock - 1) / kBlock);
-    hipExtLaunchKernelGGL(saga_batch_sweep_kernel<false>, dim3(grid < 1 ? 1 : grid), dim3(kBlock), 0, st, ev0,
-                          ev1, 0, d, lam, tail, n_parts, batch_id_offset, ov);
+    break;
+  }
+  default:   // the global-atomic gather and the tiled dense form
+    if (penalty == SGDNET_GROUPLASSO) {
+      const int grid = (int)((d.p + kBlock - 1) / kBlock);
+      hipExtLaunchKernelGGL(saga_batch_sweep_kernel<true>, dim3(grid < 1 ? 1 : grid), dim3(kBlock), 0, st, ev0,
+                            ev1, 0, d, lam, tail, n_parts, batch_id_offset, ov);
+    } else {
+      const int grid = (int)(((int64_t)d.K * d.p + kBlock - 1) / kBlock);
+      hipExtLaunchKernelGGL(saga_batch_sweep_kernel<false>, dim3(grid < 1 ? 1 : grid), dim3(kBlock), 0, st, ev0,
+                            ev1, 0, d, lam, tail, n_parts, batch_id_offset, ov);
+    }
   }
   SGD_HIP_TRY(hipGetLastError());
   return SGDNET_OK;
 }
-
-// Virtual shards need the K == 1 LDS gather with w staged in LDS and a grid that splits evenly.
-// Virtual shards need an LDS gather form and a grid that splits evenly: K == 1 with w staged in LDS (sparse or
-// dense x), or 2..16 classes of sparse x whose K x p accumulator fits (round 3; the replica of w is read through L2).
-bool vs_eligible(const SagaDev& d, int m) {
-  (void)m;
-  if (d.V < 2 || d.K < 1 || d.K > 16 || (d.standardize && !(d.vcw && d.c)) || d.force_global || !d.vw) return false;
-  const size_t table = sizeof(double) * (size_t)d.K * (size_t)d.p;
-  if (d.xd) return table <= 80 * 1024;                           // dense x (1..16 classes): only the accumulator is staged
-  if (d.K > 1) return d.rec && table <= 80 * 1024;
-  return 2 * table + 16 + kLdsStaticReserve <= kLdsPerCu;     // accumulator + coefficient snapshot in LDS
-}
-
-static int vs_grid(const SagaDev& d) { return d.v_bps * d.V; }
 
 int launch_vs_broadcast(const SagaDev& d, hipStream_t st) {
   int grid = (int)((2 * (int64_t)d.K * d.p + 2 * d.K + kBlock - 1) / kBlock);
@@ -3818,159 +3831,58 @@ int launch_vs_merge(const SagaDev& d, int final_merge, hipStream_t st, LamParams
   return SGDNET_OK;
 }
 
-int launch_vs_gather(const SagaDev& d, LamParams* lam, int64_t t0_in_epoch, int m, hipStream_t st, hipEvent_t ev0,
-                     hipEvent_t ev1, int batch_index) {
-  const int grid = vs_grid(d);
-  if (grid / d.V != d.v_bps || grid > kD0Slots) {
-    set_error("internal: virtual-shard geometry (%d workgroups, %d per shard)", grid, d.v_bps);
+int launch_vs_gather(const SagaDev& d, const BatchPlan& g, LamParams* lam, int64_t t0_in_epoch, int m, hipStream_t st,
+                     hipEvent_t ev0, hipEvent_t ev1, int batch_index) {
+  if (g.grid / d.V != d.v_bps || g.grid > kD0Slots) {
+    set_error("internal: virtual-shard geometry (%d workgroups, %d per shard)", g.grid, d.v_bps);
     return SGDNET_EINVAL;
   }
-  if (d.xd) {
-    static bool dense_vs_attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    constexpr int kDenseVsBlock = 1024;           // 16 wavefronts share one LDS copy of the accumulator
-    if (!dense_vs_attr_done[dev & 63]) {
-      SGD_HIP_TRY(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(saga_batch_gather_dense_kernel<1, kDenseVsBlock, true>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_dense_kernel<4, kDenseBlock, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_dense_kernel<16, kDenseBlock, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      dense_vs_attr_done[dev & 63] = true;
-    }
-    const int waves = (d.K > 1 ? kDenseBlock : kDenseVsBlock) / 64;
-    int dpb = (m + d.v_bps - 1) / d.v_bps;
-    dpb = (dpb + waves - 1) / waves * waves;
-    const size_t lds = sizeof(double) * (size_t)d.K * (size_t)d.p;
-    if (d.K == 1)
-      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<1, kDenseVsBlock, true>), dim3(grid), dim3(kDenseVsBlock), lds, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, 0, dpb);
-    // 2..16 classes (round 4): four wavefronts per workgroup (a draw holds per-class registers), the first-occurrence
-    // claims of a sample are per batch (batch_id_offset = the batch's index in the epoch)
-    else if (d.K <= 4)
-      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<4, kDenseBlock, true>), dim3(grid), dim3(kDenseBlock), lds, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_index, dpb);
-    else
-      hipExtLaunchKernelGGL((saga_batch_gather_dense_kernel<16, kDenseBlock, true>), dim3(grid), dim3(kDenseBlock), lds, st,
-                            ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_index, dpb);
+  // batch_id_offset: 0 for K == 1; 2..16 classes (round 3 sparse, round 4 dense) take the batch's index in the epoch,
+  // the first-occurrence claims of a sample are per batch
+  auto launch = [&](auto kernel, int block, int cap, int batch_id_offset) {
+    const int rc = allow_dynamic_lds(kernel, cap);
+    if (rc) return rc;
+    hipExtLaunchKernelGGL(kernel, dim3(g.grid), dim3(block), g.lds_bytes, st, ev0, ev1, 0, d, lam, t0_in_epoch, m,
+                          batch_id_offset, g.draws_per_block);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
+  };
+  if (d.xd) {   // 2..16 classes: four wavefronts per workgroup (a draw holds per-class registers)
+    if (g.kw == 1) return launch(saga_batch_gather_dense_kernel<1, kDenseVsBlock, true>, kDenseVsBlock, kLdsCap, 0);
+    if (g.kw == 4) return launch(saga_batch_gather_dense_kernel<4, kDenseBlock, true>, kDenseBlock, kLdsCap, batch_index);
+    return launch(saga_batch_gather_dense_kernel<16, kDenseBlock, true>, kDenseBlock, kLdsCap, batch_index);
   }
-  int dpb = (m + d.v_bps - 1) / d.v_bps;
-  const int per_round = kLdsBlock / kGroup;
-  if (dpb < per_round) dpb = per_round;
-  if (d.K > 1) {
-    // 2..4 classes: the 16-lane draw of the LDS form against the shard's replica (batch_id_offset = the batch's
-    // index in the epoch: the first-occurrence claims of a sample are per batch)
-    static bool k4_attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!k4_attr_done[dev & 63]) {
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<4, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_cl_kernel<true, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      k4_attr_done[dev & 63] = true;
-    }
-    if (d.K <= 4)
-      hipExtLaunchKernelGGL((saga_batch_gather_lds_kernel<4, false, true>), dim3(grid), dim3(kLdsBlock),
-                            sizeof(double) * (size_t)d.K * (size_t)d.p, st, ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_index,
-                            dpb);
-    else        // 5..16 classes: the class-lane form
-      hipExtLaunchKernelGGL((saga_batch_gather_cl_kernel<true, true>), dim3(grid), dim3(kLdsBlock),
-                            sizeof(double) * (size_t)d.K * (size_t)d.p, st, ev0, ev1, 0, d, lam, t0_in_epoch, m, batch_index,
-                            dpb);
-    SGD_HIP_TRY(hipGetLastError());
-    return SGDNET_OK;
-  }
-  const size_t lds = 2 * sizeof(double) * (size_t)d.p + 16;
-  static bool attr_done_dev[64] = {};
-  int cur_dev = 0;
-  (void)hipGetDevice(&cur_dev);
-  if (!attr_done_dev[cur_dev & 63]) {
-    SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<1, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kLdsPerCu - kLdsStaticReserve));
-    SGD_HIP_TRY(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(saga_batch_gather_lds_kernel<1, true, true, kLanes8>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-    attr_done_dev[cur_dev & 63] = true;
-  }
-  if (lanes8_ok(d))
-    hipExtLaunchKernelGGL((saga_batch_gather_lds_kernel<1, true, true, kLanes8>), dim3(grid), dim3(kLdsBlock), lds,
-                          st, ev0, ev1, 0, d, lam, t0_in_epoch, m, 0, dpb);
-  else
-    hipExtLaunchKernelGGL((saga_batch_gather_lds_kernel<1, true, true>), dim3(grid), dim3(kLdsBlock), lds, st, ev0,
-                          ev1, 0, d, lam, t0_in_epoch, m, 0, dpb);
-  SGD_HIP_TRY(hipGetLastError());
-  return SGDNET_OK;
+  // 2..4 classes: the 16-lane draw of the LDS form against the shard's replica; 5..16 classes: the class-lane form
+  if (g.kw == 4) return launch(saga_batch_gather_lds_kernel<4, false, true>, kLdsBlock, kLdsCap, batch_index);
+  if (g.kw == 16) return launch(saga_batch_gather_cl_kernel<true, true>, kLdsBlock, kLdsCap, batch_index);
+  if (g.lanes8) return launch(saga_batch_gather_lds_kernel<1, true, true, kLanes8>, kLdsBlock, kLdsAll, 0);
+  return launch(saga_batch_gather_lds_kernel<1, true, true>, kLdsBlock, kLdsAll, 0);
 }
 
-int launch_vs_sweep(const SagaDev& d, LamParams* lam, int tail, int m, hipStream_t st, hipEvent_t ev0,
+int launch_vs_sweep(const SagaDev& d, const BatchPlan& g, LamParams* lam, int tail, hipStream_t st, hipEvent_t ev0,
                     hipEvent_t ev1) {
-  (void)m;
   const int F = kSlabElems / d.K;            // features per block
   const int nfb = (int)((d.p + F - 1) / F);
-  if (d.K == 1)
-    hipExtLaunchKernelGGL(saga_vs_sweep_kernel<1>, dim3(nfb * d.V), dim3(kBlock), 0, st, ev0, ev1, 0, d, lam, tail, nfb);
-  else if (d.K <= 4)
-    hipExtLaunchKernelGGL(saga_vs_sweep_kernel<4>, dim3(nfb * d.V), dim3(kBlock), 0, st, ev0, ev1, 0, d, lam, tail, nfb);
-  else
-    hipExtLaunchKernelGGL(saga_vs_sweep_kernel<16>, dim3(nfb * d.V), dim3(kBlock), 0, st, ev0, ev1, 0, d, lam, tail, nfb);
-  SGD_HIP_TRY(hipGetLastError());
-  return SGDNET_OK;
+  return with_class_width(g.kw, [&](auto kw) {
+    hipExtLaunchKernelGGL(saga_vs_sweep_kernel<decltype(kw)::value>, dim3(nfb * d.V), dim3(kBlock), 0, st, ev0, ev1, 0, d,
+                          lam, tail, nfb);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  });
 }
 
-// ---- the fused epoch of the virtual shards (saga_vs_epoch_kernel) ----
-static int64_t fused_slice(const SagaDev& d) { return 2 * ((d.p + 2 * (int64_t)d.v_bps - 1) / (2 * (int64_t)d.v_bps)); }
-static size_t fused_lds_bytes(const SagaDev& d) {
-  const int64_t part = (int64_t)(kLdsBlock / 64) * fused_slice(d);     // the slice sweep's per-wavefront partial sums
-  return sizeof(double) * (size_t)(d.p + (part > d.p ? part : d.p)) + 16;
-}
-size_t vs_fused_sync_words() { return (size_t)(kSyncLines + 2) * kSyncLine; }
-size_t vs_fused_sync_sticky_word() { return (size_t)kSyncSticky * kSyncLine; }
-size_t vs_fused_col_words() { return (size_t)kFusedMaxBps * kSyncLine; }
-// local: V reference copies [g_sum | w | g_sum_b | b] + V x 128 c.w partials; published: 2 parities x V slices
-size_t vs_fused_exchange_doubles(const SagaDev& d, int n_shards) {
-  return (size_t)n_shards * (size_t)(2 * d.p + 2) + (size_t)n_shards * kFusedMaxBps;
-}
-size_t vs_fused_publish_doubles(const SagaDev& d, int n_shards) { return (size_t)2 * n_shards * (size_t)(2 * d.p + 2); }
-
-// sparse x, one response, compact records, an even number of features, slices of at most 384 features
-bool vs_fused_eligible(const SagaDev& d) {
-  if (!vs_eligible(d, 0) || d.K != 1 || d.xd || !d.cP || !lanes8_ok(d) || (d.p & 1) || !d.vsync || !d.vx || !d.vcol || !d.vpub) return false;
-  if (d.v_bps < 1 || d.v_bps > kFusedMaxBps || d.V * d.v_bps > 1024) return false;
-  if (fused_slice(d) > 2 * 64 * kFusedChunks) return false;
-  if ((int64_t)d.V * d.v_bps * d.p * 8 >= (1ll << 31)) return false;
-  return fused_lds_bytes(d) + kLdsStaticReserve <= kLdsPerCu;
-}
-
-// workgroups added to the launch for the sample-order generators (one per reserved CU)
-int vs_fused_rng_workgroups(const SagaDev& d) { return d.rngdev ? d.cu_reserve : 0; }
-
-int launch_vs_epoch(const SagaDev& d, LamParams* lam, int nb, int every, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  static bool attr_done_dev[64] = {};
-  int cur_dev = 0;
-  (void)hipGetDevice(&cur_dev);
-  if (!attr_done_dev[cur_dev & 63]) {
-    SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_vs_epoch_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-    SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_vs_epoch_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu - kLdsStaticReserve));
-    attr_done_dev[cur_dev & 63] = true;
-  }
+int launch_vs_epoch(const SagaDev& d, const BatchPlan& g, LamParams* lam, int nb, int every, hipStream_t st,
+                    hipEvent_t ev0, hipEvent_t ev1) {
+  const bool peers = d.n_peers > 1 && d.peers;
+  int rc = peers ? allow_dynamic_lds(saga_vs_epoch_kernel<true>, kLdsAll) : allow_dynamic_lds(saga_vs_epoch_kernel<false>, kLdsAll);
+  if (rc) return rc;
   if (nb < 1 || every < 1) return SGDNET_EINVAL;
-  const int rng_wgs = vs_fused_rng_workgroups(d);
-  size_t lds = fused_lds_bytes(d);
-  if (rng_wgs > 0 && lds < kJumpLds) lds = kJumpLds;
-  if (d.n_peers > 1 && d.peers)
-    hipExtLaunchKernelGGL(saga_vs_epoch_kernel<true>, dim3(vs_grid(d) + rng_wgs), dim3(kLdsBlock), lds, st, ev0, ev1, 0, d,
-                          lam, nb, every);
+  if (peers)
+    hipExtLaunchKernelGGL(saga_vs_epoch_kernel<true>, dim3(g.grid), dim3(kLdsBlock), g.lds_bytes, st, ev0, ev1, 0, d, lam,
+                          nb, every);
   else
-    hipExtLaunchKernelGGL(saga_vs_epoch_kernel<false>, dim3(vs_grid(d) + rng_wgs), dim3(kLdsBlock), lds, st, ev0, ev1, 0, d,
-                          lam, nb, every);
+    hipExtLaunchKernelGGL(saga_vs_epoch_kernel<false>, dim3(g.grid), dim3(kLdsBlock), g.lds_bytes, st, ev0, ev1, 0, d, lam,
+                          nb, every);
   SGD_HIP_TRY(hipGetLastError());
   return SGDNET_OK;
 }

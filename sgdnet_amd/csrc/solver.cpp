@@ -125,6 +125,7 @@ struct sgdnet_solver {
   // fused epoch of the virtual shards (saga_vs_epoch_kernel): switched off for this solver once a launch could not
   // become resident (a GPU shared with another process); the separate launches take over
   bool fused_off = false;
+  int cus = 0;                   // the device's compute units (read once: the fused epoch needs one workgroup per CU)
   bool fused_in_graph = false;   // the captured epochs use it
   int fused_abort_seen = 0;      // LamParams::fused_abort as the last ConvergenceCheck read it
   FusedPeers* peers_dev = nullptr;   // sgdnet_solver_link_peers
@@ -266,12 +267,7 @@ int m_to_array(sgdnet_solver* s) {
 // ids.  Bins and the gradient-change buffer are sized for the batch.
 int ensure_binned(sgdnet_solver* s, int64_t batch) {
   SagaDev& d = s->d;
-  static const int allow = exp_env_int("SGDNET_BINNED", 1);
-  // more than 16 classes: the only batched form there is (a wavefront per draw), whatever the sizes
-  const bool want = allow && !s->bin_disabled && s->sparse && !d.xd && d.rec && d.idx && d.K <= 64 && !d.force_global &&
-                    d.p < (1ll << 31) &&
-                    (d.K > 16 || (sizeof(double) * (size_t)d.K * (size_t)d.p > 80 * 1024 && batch >= 4096));
-  if (!want) {
+  if (s->bin_disabled || !wants_binned(d, batch)) {
     if (d.R > 0 && d.bins) {             // e.g. a tiny batch after a large one: fall back to the atomic form
       d.bins = nullptr;
       drop_graph(s);
@@ -415,9 +411,7 @@ int ensure_binned(sgdnet_solver* s, int64_t batch) {
 // batch's gradient changes in d.gcb and D is formed feature tile by feature tile.
 int ensure_dense_tiled(sgdnet_solver* s, int64_t batch) {
   SagaDev& d = s->d;
-  // the forms that hand the gradient changes of a batch to an accumulate pass: K x p tables beyond the LDS, and 17..64
-  // classes whatever the table (saga_dense_cl_gather_kernel)
-  if (!d.xd || d.K > 64 || (d.K <= 16 && sizeof(double) * (size_t)d.K * (size_t)d.p <= 80 * 1024)) return SGDNET_OK;
+  if (!wants_tiles(d)) return SGDNET_OK;
   if (batch > s->bin_batch || !s->bin_bufs[1]) {
     SGD_HIP_TRY(hipStreamSynchronize(s->st));
     if (s->bin_bufs[1]) (void)hipFree(s->bin_bufs[1]);
@@ -431,45 +425,35 @@ int ensure_dense_tiled(sgdnet_solver* s, int64_t batch) {
   return SGDNET_OK;
 }
 
+// The launches of an epoch in batches of `batch` draws: m = batch for a full batch, the tail's draws for the tail batch.
+static BatchPlan plan(const sgdnet_solver* s, int64_t batch, int64_t m) {
+  return plan_batch(s->d, (int)m, PlanInputs{batch, s->bin_disabled, !s->fused_off && option(kOptFusedEpoch) != 0, s->cus});
+}
+static bool sharded(const BatchPlan& g) { return g.form == BatchForm::kShards || g.form == BatchForm::kFusedEpoch; }
+// (whether the epoch is one fused launch does not depend on the batch)
+static bool fused_epochs(const sgdnet_solver* s) { return plan(s, 1, 1).form == BatchForm::kFusedEpoch; }
+
 int set_batch_shape(sgdnet_solver* s, int64_t batch, int64_t draws) {
   if (batch < 1) batch = 1;
   {
     const int rcm = m_to_record(s);          // batched kernels: the gradient memory rides in the records
     if (rcm) return rcm;
   }
-  if (s->d.V > 1 && vs_eligible(s->d, (int)batch)) {
-    // per-shard batches; the scratch is sized for the launch that carries V of them
-    const int64_t dps = draws / s->d.V;
-    if (batch > dps) batch = dps;
-    s->d.v_dps = dps;
-    const int64_t slab_need = (int64_t)s->d.v_bps * s->d.V * s->d.K * s->d.p;
-    if (slab_need > s->slab_cap) {
-      SGD_HIP_TRY(hipStreamSynchronize(s->st));
-      if (s->d.slab) SGD_HIP_TRY(hipFree(s->d.slab));
-      s->d.slab = nullptr;
-      SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d.slab), sizeof(double) * (size_t)slab_need));
-      s->slab_cap = slab_need;
-      drop_graph(s);
-    }
-    const int64_t tail = dps - (dps / batch) * batch;
-    s->lam.m_full = batch;
-    s->lam.m_tail = tail;
-    batch_factors(s->lam.alpha, s->lam.gamma, batch, &s->lam.r_full, &s->lam.ls_full);
-    batch_factors(s->lam.alpha, s->lam.gamma, tail, &s->lam.r_tail, &s->lam.ls_tail);
-    s->lam.draws_per_epoch = draws;
-    return SGDNET_OK;
-  }
-  if (batch > draws) batch = draws;
-  {
+  const bool shards = sharded(plan(s, batch, batch));
+  const int64_t per_launch = shards ? draws / s->d.V : draws;   // virtual shards: per-shard batches, V in a launch
+  if (shards) s->d.v_dps = per_launch;
+  if (batch > per_launch) batch = per_launch;
+  if (!shards) {
     int rcb = ensure_binned(s, batch);
     if (!rcb) rcb = ensure_dense_tiled(s, batch);
     if (rcb) return rcb;
   }
   // scratch must cover the full batches AND the tail batch, whose launch geometry (and even
   // its gather form) can differ
-  const int64_t tail_m = draws - (draws / batch) * batch;
-  int64_t slab_need = batch_gather_slab_doubles(s->d, (int)batch);
-  if (tail_m > 0) slab_need = std::max(slab_need, batch_gather_slab_doubles(s->d, (int)tail_m));
+  const int64_t full = per_launch / batch;
+  const int64_t tail = per_launch - full * batch;
+  int64_t slab_need = plan(s, batch, batch).slab_doubles;
+  if (tail > 0) slab_need = std::max(slab_need, plan(s, batch, tail).slab_doubles);
   if (slab_need > s->slab_cap) {
     SGD_HIP_TRY(hipStreamSynchronize(s->st));
     if (s->d.slab) SGD_HIP_TRY(hipFree(s->d.slab));
@@ -478,8 +462,6 @@ int set_batch_shape(sgdnet_solver* s, int64_t batch, int64_t draws) {
     s->slab_cap = slab_need;
     drop_graph(s);
   }
-  const int64_t full = draws / batch;
-  const int64_t tail = draws - full * batch;
   s->lam.m_full = batch;
   s->lam.m_tail = tail;
   batch_factors(s->lam.alpha, s->lam.gamma, batch, &s->lam.r_full, &s->lam.ls_full);
@@ -487,9 +469,6 @@ int set_batch_shape(sgdnet_solver* s, int64_t batch, int64_t draws) {
   s->lam.draws_per_epoch = draws;
   return SGDNET_OK;
 }
-
-bool vs_active(const sgdnet_solver* s, int64_t batch);
-bool vs_fused_active(const sgdnet_solver* s);
 
 // The epoch(s) about to be enqueued read the stream at `stream_offset`.  A slot of the sample-order pipeline that was
 // left raw goes to the fused epoch kernel as it is (LamParams::stream_raw; the kernel converts it, so the slot counts
@@ -502,7 +481,7 @@ int prepare_stream_slot(sgdnet_solver* s, int64_t batch, int64_t stream_offset, 
   if (!P.open) return SGDNET_OK;
   const bool one_slot = n_epochs == 1 && draws == P.n && (stream_offset == 0 || stream_offset == P.n);
   const int slot = stream_offset == 0 ? 0 : 1;
-  const bool fused = one_slot && vs_active(s, batch) && vs_fused_active(s);
+  const bool fused = one_slot && plan(s, batch, batch).form == BatchForm::kFusedEpoch;
   // the launch that consumes generation `used` also produces the pending generation used + 1 (its spare workgroups)
   if (fused && s->d.rngdev && P.pending_gen >= 0 && P.pending_gen == P.used + 1 && slot == (int)(P.used & 1)) {
     s->lam.rng_generate = 1;
@@ -536,8 +515,6 @@ int n_batches(int64_t batch, int64_t draws) {
 // `draws` is the epoch's total; every shard does draws / V of them in batches of `batch`, all
 // shards' k-th batch in one gather + one sweep launch; the replicas are averaged every
 // vs_merge_batches batches and at the end of the epoch.
-bool vs_active(const sgdnet_solver* s, int64_t batch) { return s->d.V > 1 && vs_eligible(s->d, (int)batch); }
-
 int vs_merge_batches(const sgdnet_solver* s, int64_t batch) {
   // draws per shard between merges: n / 32 of the job (parallel.py), settable for sharded jobs
   const int64_t period = s->vs_period > 0 ? s->vs_period : s->d.n / 32;
@@ -545,28 +522,22 @@ int vs_merge_batches(const sgdnet_solver* s, int64_t batch) {
   return (int)(b < 1 ? 1 : b);
 }
 
-// The whole epoch in one launch (saga_batched.hip "Fused epoch"): option fused_epoch, the kernel's own limits, a
-// device with at least as many CUs as the launch has workgroups, and no earlier launch of this solver that failed
-// to become resident.
-bool vs_fused_active(const sgdnet_solver* s) {
-  if (s->fused_off || !option(kOptFusedEpoch) || !vs_fused_eligible(s->d)) return false;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess) return false;
-  return s->d.V * s->d.v_bps + vs_fused_rng_workgroups(s->d) <= cus;
-}
-
+// The whole epoch in one launch (saga_batched.hip "Fused epoch", BatchForm::kFusedEpoch): option fused_epoch, the
+// kernel's own limits, a device with at least as many CUs as the launch has workgroups, and no earlier launch of this
+// solver that failed to become resident.
 int enqueue_epoch_kernels_vs(sgdnet_solver* s, int64_t batch, int64_t draws, std::vector<hipEvent_t>* ev) {
   SagaDev& d = s->d;
   const int64_t dps = draws / d.V;
   if (batch > dps) batch = dps;
   const int nb = n_batches(batch, dps);
+  const BatchPlan full = plan(s, batch, batch);
   const int every = vs_merge_batches(s, batch);
-  if (vs_fused_active(s)) {
+  if (full.form == BatchForm::kFusedEpoch) {
     s->d.vs_xcd_local = option(kOptFusedEpoch) == 1 ? 1 : 0;
     if (ev) {
       hipEvent_t e[2];
       for (auto& x : e) SGD_HIP_TRY(hipEventCreate(&x));
-      int rcf = launch_vs_epoch(d, s->lam_dev, nb, every, s->st, e[0], e[1]);
+      int rcf = launch_vs_epoch(d, full, s->lam_dev, nb, every, s->st, e[0], e[1]);
       if (rcf) return rcf;
       hipEvent_t z[2];                          // no separate sweep launches: an empty interval
       for (auto& x : z) SGD_HIP_TRY(hipEventCreate(&x));
@@ -583,10 +554,11 @@ int enqueue_epoch_kernels_vs(sgdnet_solver* s, int64_t batch, int64_t draws, std
       for (auto& x : e) SGD_HIP_TRY(hipEventCreate(&x));
       s->epoch_ev.push_back(e[0]);
       s->epoch_ev.push_back(e[1]);
-      return launch_vs_epoch(d, s->lam_dev, nb, every, s->st, e[0], e[1]);
+      return launch_vs_epoch(d, full, s->lam_dev, nb, every, s->st, e[0], e[1]);
     }
-    return launch_vs_epoch(d, s->lam_dev, nb, every, s->st);
+    return launch_vs_epoch(d, full, s->lam_dev, nb, every, s->st);
   }
+  const BatchPlan tail_plan = plan(s, batch, dps - (int64_t)(nb - 1) * batch);
   int rc = launch_vs_broadcast(d, s->st);
   if (rc) return rc;
   rc = launch_vs_cw(d, s->st);
@@ -595,18 +567,19 @@ int enqueue_epoch_kernels_vs(sgdnet_solver* s, int64_t batch, int64_t draws, std
     const int64_t t0 = (int64_t)k * batch;
     const int64_t m = (dps - t0 < batch) ? dps - t0 : batch;
     const int tail = (m != batch) ? 1 : 0;
+    const BatchPlan& g = tail ? tail_plan : full;
     if (ev) {
       hipEvent_t e[4];
       for (auto& x : e) SGD_HIP_TRY(hipEventCreate(&x));
-      rc = launch_vs_gather(d, s->lam_dev, t0, (int)m, s->st, e[0], e[1], k);
+      rc = launch_vs_gather(d, g, s->lam_dev, t0, (int)m, s->st, e[0], e[1], k);
       if (rc) return rc;
-      rc = launch_vs_sweep(d, s->lam_dev, tail, (int)m, s->st, e[2], e[3]);
+      rc = launch_vs_sweep(d, g, s->lam_dev, tail, s->st, e[2], e[3]);
       if (rc) return rc;
       for (auto x : e) ev->push_back(x);
     } else {
-      rc = launch_vs_gather(d, s->lam_dev, t0, (int)m, s->st, nullptr, nullptr, k);
+      rc = launch_vs_gather(d, g, s->lam_dev, t0, (int)m, s->st, nullptr, nullptr, k);
       if (rc) return rc;
-      rc = launch_vs_sweep(d, s->lam_dev, tail, (int)m, s->st);
+      rc = launch_vs_sweep(d, g, s->lam_dev, tail, s->st);
       if (rc) return rc;
     }
     const bool last = k + 1 == nb;
@@ -625,10 +598,21 @@ int enqueue_epoch_kernels_vs(sgdnet_solver* s, int64_t batch, int64_t draws, std
 // Enqueue the kernels of one batched epoch (eager or under stream capture).
 int enqueue_epoch_kernels(sgdnet_solver* s, int64_t batch, int64_t draws, std::vector<hipEvent_t>* ev) {
   if (batch < 1) batch = 1;
-  if (vs_active(s, batch)) return enqueue_epoch_kernels_vs(s, batch, draws, ev);
+  if (sharded(plan(s, batch, batch))) return enqueue_epoch_kernels_vs(s, batch, draws, ev);
   if (batch > draws) batch = draws;
   const int nb = n_batches(batch, draws);
-  if (binned_active(s->d, (int)batch)) {
+  const BatchPlan full = plan(s, batch, batch);
+  const BatchPlan tail_plan = plan(s, batch, draws - (int64_t)(nb - 1) * batch);
+  // the launch geometry must fit the scratch sized by set_batch_shape (a mismatch would
+  // write past d0_part / slab on the device)
+  for (const BatchPlan* g : {&full, &tail_plan})
+    if (g->slab_doubles > s->slab_cap) {
+      set_error("internal: gather geometry of a batch exceeds its scratch");
+      return SGDNET_EINVAL;
+    }
+  // (as before the plan: the coefficient copy is refreshed when the FULL batches are binned -- a binned tail batch
+  //  after full batches of more than 2^20 draws finds it as the last binned epoch left it)
+  if (full.form == BatchForm::kBinned) {
     const int rcw = launch_wpad_refresh(s->d, s->st);
     if (rcw) return rcw;
   }
@@ -636,25 +620,20 @@ int enqueue_epoch_kernels(sgdnet_solver* s, int64_t batch, int64_t draws, std::v
     const int64_t t0 = (int64_t)k * batch;
     const int64_t m = (draws - t0 < batch) ? draws - t0 : batch;
     const int tail = (m != batch) ? 1 : 0;
-    // the launch geometry must fit the scratch sized by set_batch_shape (a mismatch would
-    // write past d0_part / slab on the device)
-    if (batch_gather_slab_doubles(s->d, (int)m) > s->slab_cap) {
-      set_error("internal: gather geometry of a %lld-draw batch exceeds its scratch", (long long)m);
-      return SGDNET_EINVAL;
-    }
+    const BatchPlan& g = tail ? tail_plan : full;
     if (ev) {
       // dispatch-level start/stop timestamps of each kernel (no host gaps inside the interval)
       hipEvent_t e[4];
       for (auto& x : e) SGD_HIP_TRY(hipEventCreate(&x));
-      int rc = launch_batch_gather(s->d, s->lam_dev, t0, (int)m, tail, k, s->st, e[0], e[1]);
+      int rc = launch_batch_gather(s->d, g, s->lam_dev, t0, (int)m, k, s->st, e[0], e[1]);
       if (rc) return rc;
-      rc = launch_batch_sweep(s->d, s->lam_dev, s->lam.penalty, tail, (int)m, k, s->st, e[2], e[3]);
+      rc = launch_batch_sweep(s->d, g, s->lam_dev, s->lam.penalty, tail, k, s->st, e[2], e[3]);
       if (rc) return rc;
       for (auto x : e) ev->push_back(x);
     } else {
-      int rc = launch_batch_gather(s->d, s->lam_dev, t0, (int)m, tail, k, s->st);
+      int rc = launch_batch_gather(s->d, g, s->lam_dev, t0, (int)m, k, s->st);
       if (rc) return rc;
-      rc = launch_batch_sweep(s->d, s->lam_dev, s->lam.penalty, tail, (int)m, k, s->st);
+      rc = launch_batch_sweep(s->d, g, s->lam_dev, s->lam.penalty, tail, k, s->st);
       if (rc) return rc;
     }
   }
@@ -662,7 +641,7 @@ int enqueue_epoch_kernels(sgdnet_solver* s, int64_t batch, int64_t draws, std::v
 }
 
 int ensure_graph(sgdnet_solver* s, int64_t batch, int64_t draws) {
-  const int fused = (vs_active(s, batch) && vs_fused_active(s)) ? option(kOptFusedEpoch) : 0;
+  const int fused = fused_epochs(s) ? option(kOptFusedEpoch) : 0;
   for (auto& g : s->graphs)
     if (g.batch == batch && g.draws == draws && g.fused == fused) {
       s->gexec = g.exec;
@@ -1013,6 +992,7 @@ static int solver_create_impl(const sgdnet_problem* pb, DeviceSetup* adopt, sgdn
 
   sgdnet_solver* s = new sgdnet_solver();
   s->device = pb->device;
+  (void)hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, s->device);
   s->sparse = adopt ? adopt->xd_t == nullptr : pb->x_dense == nullptr;
   hipError_t e = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
   if (e != hipSuccess) {
@@ -1574,7 +1554,7 @@ int solver_rng_prefetch(sgdnet_solver* s) {
   // (Generators launched beside the epoch kernel raced it for CUs: dispatched together, one epoch workgroup per XCD
   //  found its CU taken and the whole epoch waited for the generators, +215 us; dispatched later, their own
   //  workgroups could stall until the epoch ended -- profiles/r04_rng_placement.txt.)
-  const bool keep_raw = s->d.V > 1 && P.run_len == 0 && vs_fused_active(s);
+  const bool keep_raw = P.run_len == 0 && fused_epochs(s);
   if (keep_raw && P.dev && s->d.rngdev && P.G > 1 && P.gens >= 1 && P.pending_gen < 0) {
     P.pending_gen = P.gens;
     P.raw[P.gens & 1] = true;
@@ -1989,7 +1969,7 @@ int sgdnet_solver_profile_epoch(sgdnet_solver* s, int64_t batch, int64_t stream_
   }
   std::vector<hipEvent_t> ev;
 #ifdef SGDNET_PHASE_TIMING
-  const bool fused_prof = vs_active(s, batch) && vs_fused_active(s);
+  const bool fused_prof = fused_epochs(s);
   if (fused_prof && s->d.dbg) SGD_HIP_TRY(hipMemsetAsync(s->d.dbg, 0, sizeof(unsigned long long) * 16 * 1024, s->st));
 #endif
   rc = enqueue_epoch_kernels(s, batch, draws_per_epoch, &ev);
@@ -2040,7 +2020,7 @@ int sgdnet_solver_profile_epoch(sgdnet_solver* s, int64_t batch, int64_t stream_
       fprintf(stderr, "[phase]   shard %d: mean start %.1f us, mean end %.1f us\n", v, a0 / s->d.v_bps, a1 / s->d.v_bps);
     }
   } else
-  if (s->d.dbg && binned_active(s->d, (int)batch)) {   // binned form: slots 0-5 gather, 6-10 range sweep
+  if (s->d.dbg && plan(s, batch, batch).form == BatchForm::kBinned) {   // binned form: slots 0-5 gather, 6-10 range sweep
     std::vector<unsigned long long> t(16 * 1024);
     SGD_HIP_TRY(hipMemcpy(t.data(), s->d.dbg, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost));
     static const char* nm[10] = {"gather: init", "gather: draw loop", "gather: barrier", "gather: reserve runs",
@@ -2124,9 +2104,16 @@ int sgdnet_solver_profile_epoch(sgdnet_solver* s, int64_t batch, int64_t stream_
 
 int sgdnet_solver_gather_form(const sgdnet_solver* s, int64_t batch) {
   if (!s || batch < 1) return 0;
-  if (vs_active(s, batch) && vs_fused_active(s)) return 3;
-  if (binned_active(s->d, (int)batch)) return 2;
-  return batch_gather_slab_doubles(s->d, (int)batch) > 0 ? 1 : 0;
+  const BatchPlan g = plan(s, batch, batch);
+  if (g.form == BatchForm::kFusedEpoch) return 3;
+  if (g.form == BatchForm::kBinned) return 2;
+  if (g.form == BatchForm::kShards) {
+    // (kept from before the plan: the answer for the same solver without shards, whatever the shards launch)
+    SagaDev d = s->d;
+    d.V = 0;
+    return plan_batch(d, (int)batch, PlanInputs{batch, s->bin_disabled, false, s->cus}).slab_doubles > 0 ? 1 : 0;
+  }
+  return g.slab_doubles > 0 ? 1 : 0;
 }
 
 int sgdnet_solver_deviance(sgdnet_solver* s, double* out) {
@@ -2265,7 +2252,7 @@ int sgdnet_solver_sync_gather(sgdnet_solver* s, int64_t t0_local, int64_t m_loca
   if (!s || !s->d.force_global || t0_local < 0 || m_local < 0) return SGDNET_EINVAL;
   if (m_local == 0) return SGDNET_OK;
   SGD_HIP_TRY(hipSetDevice(s->device));
-  return launch_batch_gather(s->d, s->lam_dev, t0_local, (int)m_local, 0, round, s->st);
+  return launch_batch_gather(s->d, plan(s, m_local, m_local), s->lam_dev, t0_local, (int)m_local, round, s->st);
 }
 
 int sgdnet_solver_sync_sweep(sgdnet_solver* s, int64_t m_global, int64_t m_local, int round) {
@@ -2273,8 +2260,9 @@ int sgdnet_solver_sync_sweep(sgdnet_solver* s, int64_t m_global, int64_t m_local
   SGD_HIP_TRY(hipSetDevice(s->device));
   double r_m, ls_m;
   batch_factors(s->lam.alpha, s->lam.gamma, m_global, &r_m, &ls_m);
-  return launch_batch_sweep(s->d, s->lam_dev, s->lam.penalty, 0, (int)(m_local > 0 ? m_local : 1), round, s->st,
-                            nullptr, nullptr, r_m, ls_m, (double)m_global);
+  const int64_t m = m_local > 0 ? m_local : 1;
+  return launch_batch_sweep(s->d, plan(s, m, m), s->lam_dev, s->lam.penalty, 0, round, s->st, nullptr, nullptr, r_m, ls_m,
+                            (double)m_global);
 }
 
 int sgdnet_solver_sync_end(sgdnet_solver* s, int rounds) {
@@ -2354,7 +2342,7 @@ int sgdnet_solver_set_virtual_shards(sgdnet_solver* s, int n_shards) {
   // shard v owns the samples [v * base + min(v, rem), ...): sgdnet_amd/parallel.py shard_bounds
   const int64_t base = d.n / n_shards, rem = d.n % n_shards;
   for (int v = 0; v < 8; ++v) d.v_size[v] = v < n_shards ? (double)(base + (v < rem ? 1 : 0)) : 0.0;
-  if (!vs_eligible(d, 0)) {   // the gather forms that carry shards keep their tables in LDS
+  if (!vs_eligible(d)) {   // the gather forms that carry shards keep their tables in LDS
     for (void* q : s->vs_owned) (void)hipFree(q);
     s->vs_owned.clear();
     d.V = 0;
