@@ -216,32 +216,35 @@ struct ExactCtl {
   int* out;             // [0] epochs run, [1] converged
 };
 
-// launchers implemented in the .hip files
-int launch_sparse_exact(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                        hipStream_t st);
-int launch_dense_exact(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                       hipStream_t st);
-size_t sparse_exact_lds_bytes(const SagaDev& d, bool stage_state);
-bool sparse_exact_k1_eligible(const SagaDev& d);
-size_t sparse_exact_k1_lds_bytes(const SagaDev& d, int64_t nit, bool allow_stage, int* ls_cache, int* stage_state);
-int launch_sparse_exact_k1(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, hipStream_t st);
-bool sparse_exact_mc_eligible(const SagaDev& d);
-size_t sparse_exact_mc_lds_bytes();
-int sparse_exact_mc_wavefronts();
-int launch_sparse_exact_mc(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, hipStream_t st);
-size_t sparse_exact_k1m_lds_bytes(int64_t nit, int* ls_cache);
-int sparse_exact_k1m_consumers();
-int launch_sparse_exact_k1m(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, hipStream_t st);
-size_t dense_exact_small_lds_bytes(const SagaDev& d, int64_t nit);
-size_t dense_exact_small2_lds_bytes(const SagaDev& d, int penalty, int64_t nit);
-int launch_dense_exact_small2(const SagaDev& d, int penalty, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                              hipStream_t st);
-int dense_exact_wide_threads(const SagaDev& d);
-size_t dense_exact_wide_lds_bytes(const SagaDev& d, bool stage_state);
-int launch_dense_exact_wide(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, hipStream_t st);
-int launch_dense_exact_small(const SagaDev& d, int penalty, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                             hipStream_t st);
-size_t dense_exact_lds_bytes(const SagaDev& d, bool stage_state);
+// ---- which kernel runs the exact iteration (saga_exact.hip plan_exact: the one rule) ----
+enum class ExactForm {
+  kSparse,        // sparse x: the general iteration on one wavefront
+  kSparseK1x,     // sparse x, one response: the drawn row in registers, a producer wavefront
+  kSparseK1m,     // ... with several consumer wavefronts
+  kSparseMc,      // sparse x, up to 64 classes: the general iteration on several wavefronts
+  kDense,         // dense x: the general iteration on one wavefront
+  kDenseSmall,    // dense x, K p <= 64: the coefficients in registers
+  kDenseSmall2,   // ... with a feeder wavefront (one response)
+  kDenseWide,     // dense x, up to 16 classes: a workgroup per iteration
+};
+struct ExactPlan {
+  ExactForm form;
+  int threads;           // the one workgroup's size
+  size_t lds_bytes;      // its dynamic LDS
+  int use_lds;           // general, wide and row-register kernels: w, g_sum (and lag) staged in LDS
+  int ls_cache;          // row-register kernels: lag_scaling entries kept in LDS
+  int penalty;           // small dense kernels: the penalty of the instance
+};
+struct ExactInputs {     // the solver's run-time facts the plan reads besides SagaDev
+  bool sparse;
+  int64_t draws;         // draws per epoch
+  int penalty;
+  double alpha, gamma;   // L2 strength and step size
+  int64_t nnz;           // non-zeros of x (sparse)
+  int row_registers;     // option exact_row_registers
+};
+int plan_exact(const SagaDev& d, const ExactInputs& in, ExactPlan* plan);
+int launch_exact(const SagaDev& d, const ExactPlan& plan, const LamParams* lam, const ExactCtl& ctl, hipStream_t st);
 
 // ---- how the batched iteration launches a batch (saga_batched.hip plan_batch: the one rule) ----
 enum class BatchForm {

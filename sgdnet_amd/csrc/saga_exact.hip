@@ -22,6 +22,8 @@
 // steps; lane k owns class k for the linear predictor / gradient / intercept.
 // w, g_sum and lag are staged in LDS when they fit (160 KiB per CU).
 #define SGDNET_DET_MATH 1   // bit-identical family gradients (include/sgdnet_detmath.h)
+#include <type_traits>
+
 #include "device_math.hpp"
 
 namespace sgdnet {
@@ -3152,150 +3154,79 @@ __global__ __launch_bounds__(2 * kWave) void saga_dense_exact_small2_kernel(Saga
   }
 }
 
+// ---- which kernel runs the exact iteration, and its launch ----
+
+constexpr size_t kExactLdsBudget = 160 * 1024 - 256;   // dynamic LDS of every exact kernel (none declares static LDS)
+constexpr size_t kSmallLdsMax = 150 * 1024;            // the small dense kernels' LDS: x, y, g_memory, the epoch's draws
+static_assert(kK1xFixedLds <= kExactLdsBudget && kK1mFixedLds <= kExactLdsBudget && kMcFixedLds <= kExactLdsBudget,
+              "the fixed LDS of the sparse kernels fits the budget");
+
+static size_t round16(size_t b) { return (b + 15) & ~size_t(15); }
+
 // 0 when the small-problem kernel does not apply
-size_t dense_exact_small_lds_bytes(const SagaDev& d, int64_t nit) {
+static size_t small_lds_bytes(const SagaDev& d, int64_t nit) {
   if (!d.xd || d.K > 16 || (int64_t)d.K * d.p > kWave || d.n > (1 << 20) || nit > (1 << 16)) return 0;
   const size_t b = sizeof(double) * ((size_t)d.K * d.n + (size_t)d.Ky * d.n + 2 * kWave + 32) +
                    sizeof(uint32_t) * ((size_t)nit + kSmallPf);
-  return b <= 150 * 1024 ? ((b + 15) & ~size_t(15)) : 0;
-}
-
-template <int kFamily, int kPenalty, bool kK1>
-static int launch_small_t(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, hipStream_t st) {
-  SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_dense_exact_small_kernel<kFamily, kPenalty, kK1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((saga_dense_exact_small_kernel<kFamily, kPenalty, kK1>), dim3(1), dim3(kWave), lds_bytes, st, d, lam,
-                     ctl);
-  SGD_HIP_TRY(hipGetLastError());
-  return SGDNET_OK;
-}
-
-template <typename Kern>
-static int launch_k1_t(Kern kern, int threads, const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                       hipStream_t st) {
-  SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes));
-  hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds_bytes, st, d, lam, ctl);
-  SGD_HIP_TRY(hipGetLastError());
-  return SGDNET_OK;
+  return b <= kSmallLdsMax ? round16(b) : 0;
 }
 
 // 0 when the feeder form does not apply: one response, gaussian or binomial, ridge or elastic net
-size_t dense_exact_small2_lds_bytes(const SagaDev& d, int penalty, int64_t nit) {
+static size_t small2_lds_bytes(const SagaDev& d, int penalty, int64_t nit) {
   if (!d.xd || d.K != 1 || d.Ky != 1 || d.p > kWave || d.n > (1 << 20) || nit < 64 ||
       (d.family != SGDNET_GAUSSIAN && d.family != SGDNET_BINOMIAL) ||
       (penalty != SGDNET_RIDGE && penalty != SGDNET_ELASTICNET))
     return 0;
   const size_t b = sizeof(double) * 2 * (size_t)d.n + kSmall2FixedLds;
-  return b <= 150 * 1024 ? ((b + 15) & ~size_t(15)) : 0;
+  return b <= kSmallLdsMax ? round16(b) : 0;
 }
 
-int launch_dense_exact_small2(const SagaDev& d, int penalty, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                              hipStream_t st) {
-  if (d.family == SGDNET_GAUSSIAN)
-    return penalty == SGDNET_RIDGE
-               ? launch_k1_t(saga_dense_exact_small2_kernel<SGDNET_GAUSSIAN, SGDNET_RIDGE>, 2 * kWave, d, lam, ctl, lds_bytes, st)
-               : launch_k1_t(saga_dense_exact_small2_kernel<SGDNET_GAUSSIAN, SGDNET_ELASTICNET>, 2 * kWave, d, lam, ctl, lds_bytes, st);
-  return penalty == SGDNET_RIDGE
-             ? launch_k1_t(saga_dense_exact_small2_kernel<SGDNET_BINOMIAL, SGDNET_RIDGE>, 2 * kWave, d, lam, ctl, lds_bytes, st)
-             : launch_k1_t(saga_dense_exact_small2_kernel<SGDNET_BINOMIAL, SGDNET_ELASTICNET>, 2 * kWave, d, lam, ctl, lds_bytes, st);
-}
-
-int launch_dense_exact_small(const SagaDev& d, int penalty, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                             hipStream_t st) {
-#define SGD_SMALL(F, P, K1) return launch_small_t<F, P, K1>(d, lam, ctl, lds_bytes, st)
-  if (d.K == 1) {
-    if (d.family == SGDNET_GAUSSIAN) {
-      if (penalty == SGDNET_RIDGE) SGD_SMALL(SGDNET_GAUSSIAN, SGDNET_RIDGE, true);
-      SGD_SMALL(SGDNET_GAUSSIAN, SGDNET_ELASTICNET, true);
-    }
-    if (d.family == SGDNET_BINOMIAL) {
-      if (penalty == SGDNET_RIDGE) SGD_SMALL(SGDNET_BINOMIAL, SGDNET_RIDGE, true);
-      SGD_SMALL(SGDNET_BINOMIAL, SGDNET_ELASTICNET, true);
-    }
-  }
-  if (d.family == SGDNET_MULTINOMIAL) {
-    if (penalty == SGDNET_RIDGE) SGD_SMALL(SGDNET_MULTINOMIAL, SGDNET_RIDGE, false);
-    if (penalty == SGDNET_ELASTICNET) SGD_SMALL(SGDNET_MULTINOMIAL, SGDNET_ELASTICNET, false);
-    SGD_SMALL(SGDNET_MULTINOMIAL, SGDNET_GROUPLASSO, false);
-  }
-  if (d.family == SGDNET_MGAUSSIAN) {
-    if (penalty == SGDNET_RIDGE) SGD_SMALL(SGDNET_MGAUSSIAN, SGDNET_RIDGE, false);
-    if (penalty == SGDNET_ELASTICNET) SGD_SMALL(SGDNET_MGAUSSIAN, SGDNET_ELASTICNET, false);
-    SGD_SMALL(SGDNET_MGAUSSIAN, SGDNET_GROUPLASSO, false);
-  }
-#undef SGD_SMALL
-  set_error("small dense exact kernel: unsupported family / class count");
-  return SGDNET_EUNSUPPORTED;
-}
-
-size_t sparse_exact_lds_bytes(const SagaDev& d, bool stage_state) {
+static size_t sparse_lds_bytes(const SagaDev& d, bool stage_state) {
   size_t b = sizeof(double) * (4 * (size_t)d.K + kWave + kLsCache) + sizeof(int) * kWave;
   if (stage_state) b += sizeof(double) * 2 * (size_t)d.K * (size_t)d.p + sizeof(unsigned) * (size_t)d.p;
-  return (b + 15) & ~size_t(15);
+  return round16(b);
 }
 
-size_t dense_exact_lds_bytes(const SagaDev& d, bool stage_state) {
+static size_t dense_lds_bytes(const SagaDev& d, bool stage_state) {
   size_t b = sizeof(double) * (4 * (size_t)d.K + (size_t)d.Ky + (size_t)d.p);
   if (stage_state) b += sizeof(double) * 2 * (size_t)d.K * (size_t)d.p;
-  return (b + 15) & ~size_t(15);
+  return round16(b);
 }
 
-// The register-resident kernel: one response, explicit x.  LDS = the lag_scaling cache, plus w, g_sum and lag
-// when they fit beside at least 2048 entries of it; `*ls_cache` / `*stage_state` tell the launch what was chosen.
-bool sparse_exact_k1_eligible(const SagaDev& d) {
+// The register-resident kernels: one response, explicit x.
+static bool k1x_eligible(const SagaDev& d) {
   return d.K == 1 && d.Ky == 1 && !d.standardize && d.family != SGDNET_MULTINOMIAL && d.ptr && d.idx && d.val;
 }
 
-size_t sparse_exact_k1_lds_bytes(const SagaDev& d, int64_t nit, bool allow_stage, int* ls_cache, int* stage_state) {
-  const size_t fixed = kK1xFixedLds;
-  const size_t cap = 160 * 1024 - 256 - fixed;
+// One consumer: LDS = the lag_scaling cache, plus w, g_sum and lag when they fit beside at least 2048 entries of it.
+static void plan_k1x(const SagaDev& d, int64_t nit, bool allow_stage, ExactPlan* pl) {
+  const size_t cap = kExactLdsBudget - kK1xFixedLds;
   const size_t state = (sizeof(double) * 2 + sizeof(unsigned)) * (size_t)d.p;
   const size_t want = (size_t)nit + 1;
   const size_t floor_entries = want < 2048 ? want : 2048;
   const bool stage = allow_stage && state + sizeof(double) * floor_entries <= cap;
   size_t entries = (cap - (stage ? state : 0)) / sizeof(double);
   if (entries > want) entries = want;
-  *ls_cache = (int)entries;
-  *stage_state = stage ? 1 : 0;
-  return (fixed + sizeof(double) * entries + (stage ? state : 0) + 15) & ~size_t(15);
+  pl->form = ExactForm::kSparseK1x;
+  pl->threads = 2 * kWave;
+  pl->lds_bytes = round16(kK1xFixedLds + sizeof(double) * entries + (stage ? state : 0));
+  pl->use_lds = stage ? 1 : 0;
+  pl->ls_cache = (int)entries;
 }
 
-
-int launch_sparse_exact_k1(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, hipStream_t st) {
-  return ctl.use_lds ? launch_k1_t(saga_sparse_exact_k1x_kernel<true>, 2 * kWave, d, lam, ctl, lds_bytes, st)
-                     : launch_k1_t(saga_sparse_exact_k1x_kernel<false>, 2 * kWave, d, lam, ctl, lds_bytes, st);
-}
-
-// The multi-consumer kernel: LDS = its fixed part + the lag_scaling cache (w, g_sum, lag stay in memory).
-size_t sparse_exact_k1m_lds_bytes(int64_t nit, int* ls_cache) {
-  const size_t cap = 160 * 1024 - 256 - kK1mFixedLds;
-  size_t entries = cap / sizeof(double);
+// Several consumers: LDS = the fixed part + the lag_scaling cache (w, g_sum, lag stay in memory).
+static void plan_k1m(int64_t nit, ExactPlan* pl) {
+  size_t entries = (kExactLdsBudget - kK1mFixedLds) / sizeof(double);
   if (entries > (size_t)nit + 1) entries = (size_t)nit + 1;
-  *ls_cache = (int)entries;
-  return (kK1mFixedLds + sizeof(double) * entries + 15) & ~size_t(15);
-}
-
-int sparse_exact_k1m_consumers() { return kCons; }
-
-int launch_sparse_exact_k1m(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, hipStream_t st) {
-  return launch_k1_t(saga_sparse_exact_k1m_kernel, (kCons + kProd) * kWave, d, lam, ctl, lds_bytes, st);
+  pl->form = ExactForm::kSparseK1m;
+  pl->threads = (kCons + kProd) * kWave;
+  pl->lds_bytes = round16(kK1mFixedLds + sizeof(double) * entries);
+  pl->ls_cache = (int)entries;
 }
 
 // The multi-wavefront general kernel: up to 64 classes, explicit x.
-bool sparse_exact_mc_eligible(const SagaDev& d) {
+static bool mc_eligible(const SagaDev& d) {
   return d.K <= kWave && d.Ky <= kWave && !d.standardize && d.ptr && d.idx && d.val;
-}
-size_t sparse_exact_mc_lds_bytes() { return (kMcFixedLds + 15) & ~size_t(15); }
-int sparse_exact_mc_wavefronts() { return kMc; }
-int launch_sparse_exact_mc(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, hipStream_t st) {
-  return launch_k1_t(saga_sparse_exact_mc_kernel, kMc * kWave, d, lam, ctl, sparse_exact_mc_lds_bytes(), st);
-}
-
-int launch_sparse_exact(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                        hipStream_t st) {
-  return ctl.use_lds ? launch_k1_t(saga_sparse_exact_kernel<true>, kWave, d, lam, ctl, lds_bytes, st)
-                     : launch_k1_t(saga_sparse_exact_kernel<false>, kWave, d, lam, ctl, lds_bytes, st);
 }
 
 // Workgroup size and LDS of the wide dense kernel; 0 threads: not eligible (more than 16 classes).
@@ -3304,57 +3235,151 @@ int launch_sparse_exact(const SagaDev& d, const LamParams* lam, const ExactCtl& 
 static int wide_kmax(const SagaDev& d) { return d.K == 1 ? 1 : (d.K <= 4 ? 4 : 16); }
 static int wide_cap(const SagaDev& d) { return d.K <= 4 ? 512 : 256; }
 
-int dense_exact_wide_threads(const SagaDev& d) {
+static int wide_threads(const SagaDev& d) {
   if (!d.xd || d.K > 16) return 0;
   int64_t t = (d.p + kWave - 1) / kWave * kWave;
   if (t > wide_cap(d)) t = wide_cap(d);
   return (int)t;
 }
 
-size_t dense_exact_wide_lds_bytes(const SagaDev& d, bool stage_state) {
+static size_t wide_lds_bytes(const SagaDev& d, bool stage_state) {
   const int kmax = wide_kmax(d), nwmax = wide_cap(d) / kWave;
   size_t b = sizeof(double) * (size_t)(nwmax * kmax + kmax + 3 * nwmax);
   if (stage_state) {   // padded to whole chunks of T features
-    const size_t T = (size_t)dense_exact_wide_threads(d);
+    const size_t T = (size_t)wide_threads(d);
     const size_t ppad = ((size_t)d.p + T - 1) / T * T;
     b += sizeof(double) * 2 * (size_t)d.K * ppad;
   }
-  return (b + 15) & ~size_t(15);
+  return round16(b);
 }
 
-template <int KMAX, int kT, int kU, bool kStage>
-static int launch_wide_t(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes, int T,
-                         hipStream_t st) {
-  SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_dense_exact_wide_kernel<KMAX, kT, kU, kStage>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((saga_dense_exact_wide_kernel<KMAX, kT, kU, kStage>), dim3(1), dim3(T), lds_bytes, st, d, lam, ctl);
-  SGD_HIP_TRY(hipGetLastError());
-  return SGDNET_OK;
-}
-
-int launch_dense_exact_wide(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                            hipStream_t st) {
-  const int T = dense_exact_wide_threads(d);
-  if (T <= 0) {
-    set_error("wide dense exact kernel: more than 16 classes");
+// The exact iteration's one rule: which kernel, with what workgroup and LDS.  Makes no HIP call.
+int plan_exact(const SagaDev& d, const ExactInputs& in, ExactPlan* pl) {
+  // experiment builds: SGDNET_EXACT_SMALL=0 keeps the general dense kernel, SGDNET_EXACT_SMALL2=0 the small one
+  // without its feeder, SGDNET_EXACT_WIDE=0 the one-wavefront kernel for wider rows
+  static const int small_ok = exp_env_int("SGDNET_EXACT_SMALL", 1);
+  static const int small2_ok = exp_env_int("SGDNET_EXACT_SMALL2", 1);
+  static const int wide_ok = exp_env_int("SGDNET_EXACT_WIDE", 1);
+  *pl = ExactPlan{};
+  pl->penalty = in.penalty;
+  // option exact_row_registers (sparse x): 0 the general kernel; 1 the register-resident kernel with w, g_sum and
+  // lag in LDS where they fit, and the multi-wavefront kernels where the rule below expects them to pay; 2 the
+  // register-resident kernel with its state in memory; 3 the multi-wavefront kernels wherever legal; 4 as 1 without them
+  const int opt = in.row_registers;
+  // a multi-wavefront kernel of `waves` wavefronts: w_scale keeps its sign (the one-consumer kernel alone has the
+  // plain soft threshold), whole rounds of draws, and -- under option 1 -- draws in flight seldom share a feature
+  const double avg = (double)in.nnz / (double)d.n;
+  auto multi_pays = [&](int waves, double max_share) {
+    const double upd = 1.0 - in.alpha * in.gamma;
+    const double share = (double)(waves - 1) * avg * avg / (double)d.p;   // P(a draw in flight shares a feature)
+    return (opt == 1 || opt == 3) && upd > 0.0 && in.draws >= 64 && (opt == 3 || share < max_share);
+  };
+  // the general and wide kernels: w and g_sum (and lag) staged in LDS where they fit
+  auto staged = [&](ExactForm form, int threads, size_t with_state, size_t without) {
+    pl->form = form;
+    pl->threads = threads;
+    pl->use_lds = with_state <= kExactLdsBudget ? 1 : 0;
+    pl->lds_bytes = pl->use_lds ? with_state : without;
+  };
+  if (in.sparse) {
+    if (opt != 0 && k1x_eligible(d)) {
+      if (multi_pays(kCons, 6.0))   // (measured: 1.2 against 1.4 us at share 2.5, 1.36 against 1.40 at 4.5)
+        plan_k1m(in.draws, pl);
+      else
+        plan_k1x(d, in.draws, opt == 1 || opt == 4, pl);
+    } else if (mc_eligible(d) && multi_pays(kMc, 1.0)) {   // (measured: 4.04 against 3.90 us at share 3.5)
+      pl->form = ExactForm::kSparseMc;
+      pl->threads = kMc * kWave;
+      pl->lds_bytes = round16(kMcFixedLds);
+    } else {
+      staged(ExactForm::kSparse, kWave, sparse_lds_bytes(d, true), sparse_lds_bytes(d, false));
+    }
+  } else {
+    const size_t small = small_ok ? small_lds_bytes(d, in.draws) : 0;
+    const size_t small2 = small && small2_ok ? small2_lds_bytes(d, in.penalty, in.draws) : 0;
+    if (small) {
+      pl->form = small2 ? ExactForm::kDenseSmall2 : ExactForm::kDenseSmall;
+      pl->threads = small2 ? 2 * kWave : kWave;
+      pl->lds_bytes = small2 ? small2 : small;
+    } else if (wide_ok && wide_threads(d) > 0) {
+      staged(ExactForm::kDenseWide, wide_threads(d), wide_lds_bytes(d, true), wide_lds_bytes(d, false));
+    } else {
+      staged(ExactForm::kDense, kWave, dense_lds_bytes(d, true), dense_lds_bytes(d, false));
+    }
+  }
+  if (pl->lds_bytes > kExactLdsBudget) {   // the general kernels only: sparse x with very many classes, dense x with K > 16
+    set_error("exact mode: per-iteration scratch (%zu bytes) exceeds LDS", pl->lds_bytes);
     return SGDNET_EUNSUPPORTED;
   }
-  const bool stage = ctl.use_lds != 0;
-  if (d.K == 1) return stage ? launch_wide_t<1, 512, 8, true>(d, lam, ctl, lds_bytes, T, st)
-                             : launch_wide_t<1, 512, 8, false>(d, lam, ctl, lds_bytes, T, st);
-  if (d.K <= 4) return stage ? launch_wide_t<4, 512, 2, true>(d, lam, ctl, lds_bytes, T, st)
-                             : launch_wide_t<4, 512, 2, false>(d, lam, ctl, lds_bytes, T, st);
-  return stage ? launch_wide_t<16, 256, 1, true>(d, lam, ctl, lds_bytes, T, st)
-               : launch_wide_t<16, 256, 1, false>(d, lam, ctl, lds_bytes, T, st);
+  return SGDNET_OK;
 }
 
-int launch_dense_exact(const SagaDev& d, const LamParams* lam, const ExactCtl& ctl, size_t lds_bytes,
-                       hipStream_t st) {
-  SGD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(saga_dense_exact_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL(saga_dense_exact_kernel, dim3(1), dim3(kWave), lds_bytes, st, d, lam, ctl);
-  SGD_HIP_TRY(hipGetLastError());
-  return SGDNET_OK;
+template <int v>
+using IntC = std::integral_constant<int, v>;
+
+// f(family, penalty, kK1) as integral constants for the small dense kernels' instance: one response runs the
+// elastic-net instance for every penalty but ridge; several classes have ridge, elastic-net and group-lasso instances
+template <int kFamily, bool kK1, typename F>
+static int with_small_penalty(int penalty, F&& f) {
+  const auto k1 = std::integral_constant<bool, kK1>{};
+  if (penalty == SGDNET_RIDGE) return f(IntC<kFamily>{}, IntC<SGDNET_RIDGE>{}, k1);
+  if constexpr (kK1)
+    return f(IntC<kFamily>{}, IntC<SGDNET_ELASTICNET>{}, k1);
+  else
+    return penalty == SGDNET_ELASTICNET ? f(IntC<kFamily>{}, IntC<SGDNET_ELASTICNET>{}, k1)
+                                        : f(IntC<kFamily>{}, IntC<SGDNET_GROUPLASSO>{}, k1);
+}
+
+template <typename F>
+static int with_small_instance(const SagaDev& d, int penalty, F&& f) {
+  if (d.K == 1 && d.family == SGDNET_GAUSSIAN) return with_small_penalty<SGDNET_GAUSSIAN, true>(penalty, f);
+  if (d.K == 1 && d.family == SGDNET_BINOMIAL) return with_small_penalty<SGDNET_BINOMIAL, true>(penalty, f);
+  if (d.family == SGDNET_MULTINOMIAL) return with_small_penalty<SGDNET_MULTINOMIAL, false>(penalty, f);
+  if (d.family == SGDNET_MGAUSSIAN) return with_small_penalty<SGDNET_MGAUSSIAN, false>(penalty, f);
+  set_error("small dense exact kernel: unsupported family / class count");
+  return SGDNET_EUNSUPPORTED;
+}
+
+int launch_exact(const SagaDev& d, const ExactPlan& pl, const LamParams* lam, const ExactCtl& ctl, hipStream_t st) {
+  auto go = [&](auto kernel) {
+    const int rc = allow_dynamic_lds(kernel, (int)kExactLdsBudget);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(pl.threads), pl.lds_bytes, st, d, lam, ctl);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  };
+  const bool stage = pl.use_lds != 0;
+  switch (pl.form) {
+  case ExactForm::kDenseSmall2: {   // the plan chose it for gaussian or binomial, ridge or elastic net
+    auto feeder = [&](auto fam, auto pen, auto) {
+      return go(saga_dense_exact_small2_kernel<decltype(fam)::value, decltype(pen)::value>);
+    };
+    return d.family == SGDNET_GAUSSIAN ? with_small_penalty<SGDNET_GAUSSIAN, true>(pl.penalty, feeder)
+                                       : with_small_penalty<SGDNET_BINOMIAL, true>(pl.penalty, feeder);
+  }
+  case ExactForm::kDenseSmall:
+    return with_small_instance(d, pl.penalty, [&](auto fam, auto pen, auto k1) {
+      return go(saga_dense_exact_small_kernel<decltype(fam)::value, decltype(pen)::value, decltype(k1)::value>);
+    });
+  case ExactForm::kSparseK1x:
+    return stage ? go(saga_sparse_exact_k1x_kernel<true>) : go(saga_sparse_exact_k1x_kernel<false>);
+  case ExactForm::kSparse:
+    return stage ? go(saga_sparse_exact_kernel<true>) : go(saga_sparse_exact_kernel<false>);
+  case ExactForm::kDenseWide:
+    if (d.K == 1)
+      return stage ? go(saga_dense_exact_wide_kernel<1, 512, 8, true>) : go(saga_dense_exact_wide_kernel<1, 512, 8, false>);
+    if (d.K <= 4)
+      return stage ? go(saga_dense_exact_wide_kernel<4, 512, 2, true>) : go(saga_dense_exact_wide_kernel<4, 512, 2, false>);
+    return stage ? go(saga_dense_exact_wide_kernel<16, 256, 1, true>) : go(saga_dense_exact_wide_kernel<16, 256, 1, false>);
+  case ExactForm::kSparseK1m:
+    return go(saga_sparse_exact_k1m_kernel);
+  case ExactForm::kSparseMc:
+    return go(saga_sparse_exact_mc_kernel);
+  case ExactForm::kDense:
+    return go(saga_dense_exact_kernel);
+  }
+  set_error("exact mode: unknown kernel form");
+  return SGDNET_EINVAL;
 }
 
 }  // namespace sgdnet

@@ -1653,56 +1653,10 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
       rc = ensure_ls_table(s, draws_per_epoch);
       if (rc) return rc;
     }
-    const size_t lds_cap = 160 * 1024 - 256;
-    // small dense problems: the register-resident kernel (saga_exact.hip); SGDNET_EXACT_SMALL=0 keeps the general one
-    static const int small_ok = exp_env_int("SGDNET_EXACT_SMALL", 1);
-    const size_t lds_small = (!s->sparse && small_ok) ? dense_exact_small_lds_bytes(s->d, draws_per_epoch) : 0;
-    // ... with a feeder wavefront where there is one response (SGDNET_EXACT_SMALL2=0 in experiment builds: without)
-    static const int small2_ok = exp_env_int("SGDNET_EXACT_SMALL2", 1);
-    const size_t lds_small2 = (lds_small && small2_ok) ? dense_exact_small2_lds_bytes(s->d, s->lam.penalty, draws_per_epoch) : 0;
-    // wider dense rows (up to 16 classes): the workgroup-per-iteration kernel; SGDNET_EXACT_WIDE=0 keeps the one-wavefront one
-    static const int wide_ok = exp_env_int("SGDNET_EXACT_WIDE", 1);
-    const bool wide = !s->sparse && !lds_small && wide_ok && dense_exact_wide_threads(s->d) > 0;
-    // sparse x, one response, no implicit centring: the register-resident iteration (option exact_row_registers:
-    // 0 keeps the general kernel; 2 keeps w, g_sum and lag out of the LDS even where they fit; 4: as 1 without the
-    // multi-consumer kernel)
-    const int k1_opt = option(kOptExactRowRegisters);
-    const bool k1 = s->sparse && k1_opt != 0 && sparse_exact_k1_eligible(s->d);
-    int k1_cache = 0, k1_stage = 0;
-    size_t k1_lds = k1 ? sparse_exact_k1_lds_bytes(s->d, draws_per_epoch, k1_opt == 1 || k1_opt == 4, &k1_cache, &k1_stage) : 0;
-    // ... and with several consumer wavefronts where draws seldom share a feature (1: where the rule below expects it
-    // to pay; 3: wherever it is legal; 2, 4: never).
-    bool k1m = false;
-    if (k1 && (k1_opt == 1 || k1_opt == 3)) {
-      const double upd = 1.0 - s->lam.alpha * s->lam.gamma;
-      const bool odd_scale = !(upd > 0.0);        // w_scale changing sign: the one-consumer kernel's plain soft threshold
-      const double avg = (double)s->nnz / (double)s->d.n;
-      const double share = (double)(sparse_exact_k1m_consumers() - 1) * avg * avg / (double)s->d.p;   // P(a draw in flight shares a feature)
-      k1m = !odd_scale && draws_per_epoch >= 64 && (k1_opt == 3 || share < 6.0);   // (measured: 1.2 against 1.4 us at share 2.5, 1.36 against 1.40 at 4.5)
-      if (k1m) {
-        k1_lds = sparse_exact_k1m_lds_bytes(draws_per_epoch, &k1_cache);
-        k1_stage = 0;
-      }
-    }
-    // several classes (or one response where the kernels above do not apply): the general iteration on several
-    // wavefronts at once, same options (1: where draws seldom share features, 3: wherever legal)
-    bool mc = false;
-    if (s->sparse && !k1m && !k1 && (k1_opt == 1 || k1_opt == 3) && sparse_exact_mc_eligible(s->d)) {
-      const double upd = 1.0 - s->lam.alpha * s->lam.gamma;
-      const double avg = (double)s->nnz / (double)s->d.n;
-      const double share = (double)(sparse_exact_mc_wavefronts() - 1) * avg * avg / (double)s->d.p;
-      mc = upd > 0.0 && draws_per_epoch >= 64 && (k1_opt == 3 || share < 1.0);   // (measured: 4.04 against 3.90 us at share 3.5)
-    }
-    const size_t lds_full = s->sparse ? sparse_exact_lds_bytes(s->d, true)
-                                      : (wide ? dense_exact_wide_lds_bytes(s->d, true) : dense_exact_lds_bytes(s->d, true));
-    const bool stage = lds_full <= lds_cap;
-    const size_t lds = stage ? lds_full
-                             : (s->sparse ? sparse_exact_lds_bytes(s->d, false)
-                                          : (wide ? dense_exact_wide_lds_bytes(s->d, false) : dense_exact_lds_bytes(s->d, false)));
-    if (lds > lds_cap) {
-      set_error("exact mode: per-iteration scratch (%zu bytes) exceeds LDS", lds);
-      return SGDNET_EUNSUPPORTED;
-    }
+    ExactPlan plan;
+    rc = plan_exact(s->d, ExactInputs{s->sparse, draws_per_epoch, s->lam.penalty, s->lam.alpha, s->lam.gamma, s->nnz,
+                                      option(kOptExactRowRegisters)}, &plan);
+    if (rc) return rc;
     while (done < max_epochs && !converged) {
       const int64_t avail = (s->stream_len - stream_offset) / draws_per_epoch;
       if (avail <= 0) {
@@ -1718,20 +1672,10 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
       ctl.max_epochs = chunk;
       ctl.tol = tol;
       ctl.LS = s->LS_dev;
-      ctl.use_lds = stage ? 1 : 0;
+      ctl.use_lds = plan.use_lds;
+      ctl.ls_cache = plan.ls_cache;
       ctl.out = s->out_dev;
-      if (k1) {
-        ctl.use_lds = k1_stage;
-        ctl.ls_cache = k1_cache;
-      }
-      rc = mc ? launch_sparse_exact_mc(s->d, s->lam_dev, ctl, s->st)
-         : k1m ? launch_sparse_exact_k1m(s->d, s->lam_dev, ctl, k1_lds, s->st)
-         : k1 ? launch_sparse_exact_k1(s->d, s->lam_dev, ctl, k1_lds, s->st)
-         : s->sparse ? launch_sparse_exact(s->d, s->lam_dev, ctl, lds, s->st)
-                     : (lds_small2 ? launch_dense_exact_small2(s->d, s->lam.penalty, s->lam_dev, ctl, lds_small2, s->st)
-                        : lds_small ? launch_dense_exact_small(s->d, s->lam.penalty, s->lam_dev, ctl, lds_small, s->st)
-                        : wide    ? launch_dense_exact_wide(s->d, s->lam_dev, ctl, lds, s->st)
-                                  : launch_dense_exact(s->d, s->lam_dev, ctl, lds, s->st));
+      rc = launch_exact(s->d, plan, s->lam_dev, ctl, s->st);
       if (rc) return rc;
       int out[2] = {0, 0};
       SGD_HIP_TRY(hipMemcpyAsync(out, s->out_dev, sizeof(out), hipMemcpyDeviceToHost, s->st));
@@ -1747,7 +1691,7 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
         losses[done] = sum / (double)s->d.n;
       }
 #ifdef SGDNET_PHASE_TIMING
-      if (lds_small2 && !s->sparse && s->d.dbg && out[0] > 0) {
+      if (plan.form == ExactForm::kDenseSmall2 && s->d.dbg && out[0] > 0) {
         unsigned long long c[5];
         SGD_HIP_TRY(hipMemcpy(c, s->d.dbg + 24, sizeof(c), hipMemcpyDeviceToHost));
         (void)hipMemset(s->d.dbg + 24, 0, sizeof(c));
@@ -1755,7 +1699,7 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
         fprintf(stderr, "[sgdnet] small dense kernel with feeder, consumer cycles per draw: slot+history %.0f, dot %.0f, gradient+store %.0f, "
                         "intercept %.0f, step+penalty+average %.0f\n", c[0] / its, c[1] / its, c[2] / its, c[3] / its, c[4] / its);
       }
-      if (k1m && s->d.dbg && out[0] > 0) {
+      if (plan.form == ExactForm::kSparseK1m && s->d.dbg && out[0] > 0) {
         (void)hipDeviceSynchronize();
         unsigned long long c[5];
         SGD_HIP_TRY(hipMemcpy(c, s->d.dbg + 16, sizeof(c), hipMemcpyDeviceToHost));
@@ -1763,7 +1707,7 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
         const double its = (double)out[0] * (double)draws_per_epoch;
         fprintf(stderr, "[sgdnet] multi-consumer sparse kernel, polls per draw: slot %.2f, registration %.2f, dependency %.2f, chain %.2f, barrier %.3f\n",
                 c[0] / its, c[1] / its, c[2] / its, c[3] / its, c[4] / its);
-      } else if (k1 && s->d.dbg && out[0] > 0) {
+      } else if (plan.form == ExactForm::kSparseK1x && s->d.dbg && out[0] > 0) {
         (void)hipDeviceSynchronize();
         unsigned long long c[12];
         SGD_HIP_TRY(hipMemcpy(c, s->d.dbg, sizeof(c), hipMemcpyDeviceToHost));
@@ -1774,7 +1718,7 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
         fprintf(stderr, "[sgdnet]   consumer cycles per draw: slot+requests %.0f, catch-up+sum %.0f, gradient %.0f, scale+intercept+early threshold %.0f, "
                         "step+stores %.0f, forward %.0f\n", c[0] / its, c[1] / its, c[2] / its, c[3] / its, c[4] / its, c[5] / its);
       }
-      if (wide && s->d.dbg && out[0] > 0) {   // development aid: shader-clock cycles of thread 0 per phase of the wide kernel
+      if (plan.form == ExactForm::kDenseWide && s->d.dbg && out[0] > 0) {   // development aid: shader-clock cycles of thread 0 per phase of the wide kernel
         unsigned long long ph[6];
         SGD_HIP_TRY(hipMemcpy(ph, s->d.dbg, sizeof(ph), hipMemcpyDeviceToHost));
         (void)hipMemset(s->d.dbg, 0, sizeof(ph));
