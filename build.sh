@@ -14,7 +14,7 @@ if [ ! -f build/.flags ] || [ "$(cat build/.flags)" != "$FLAGS" ]; then rm -f bu
 pids=()
 for f in saga_exact.hip saga_batched.hip r_rng_device.hip setup_device.hip score.hip solver.cpp driver.cpp r_rng.cpp mt_jump.cpp; do
   o=build/${f%.*}.o
-  if [ ! -f "$o" ] || [ "$SRC/$f" -nt "$o" ] || [ "$SRC/common.hpp" -nt "$o" ] || [ "$SRC/device_math.hpp" -nt "$o" ] || [ "$SRC/setup_device.hpp" -nt "$o" ] || [ include/sgdnet_hip.h -nt "$o" ] || [ include/sgdnet_detmath.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$SRC/$f" -nt "$o" ] || [ "$SRC/common.hpp" -nt "$o" ] || [ "$SRC/device_math.hpp" -nt "$o" ] || [ "$SRC/setup_device.hpp" -nt "$o" ] || [ "$SRC/fit_plan.hpp" -nt "$o" ] || [ include/sgdnet_hip.h -nt "$o" ] || [ include/sgdnet_detmath.h -nt "$o" ]; then
     $HIPCC $FLAGS -x hip -c "$SRC/$f" -o "$o" &
     pids+=($!)
   fi
