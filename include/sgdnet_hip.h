@@ -34,10 +34,11 @@ extern "C" {
 
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
- * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  A caller compiled against
+ * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
+ * _dense (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
-#define SGDNET_ABI_VERSION 4
+#define SGDNET_ABI_VERSION 5
 
 /* error codes */
 #define SGDNET_OK          0
@@ -454,6 +455,23 @@ int sgdnet_predict_sparse(int64_t n, int64_t p, const int64_t* rowptr, const int
                           int n_lambda, int device, double* link);
 int sgdnet_predict_dense(const double* x, int64_t n, int64_t p, int n_classes, const double* a0, const double* beta,
                          int n_lambda, int device, double* link);
+
+/* ---- the averaged loss gradient along a fitted path (ABI 5): what an optimality (KKT) check needs from the data ----
+ * G[k, j, l] = (1/n) sum_i x_ij * r_ik(l)   (K x p x n_lambda, K fastest, the layout of sgdnet_result.beta)
+ * G0[k, l]   = (1/n) sum_i r_ik(l)          (K x n_lambda,     the layout of sgdnet_result.a0)
+ * r_i(l) = the family's Gradient (sgdnet_amd/csrc/device_math.hpp; reference src/families.h) at the linear predictor
+ * a0[:, l] + beta[:, :, l]' x_i, on the ORIGINAL x and y: no centring, no scaling, no penalty term.
+ * x and y are exactly what sgdnet_fit_sparse / sgdnet_fit_dense take (dgCMatrix slots or a column-major matrix; y is
+ * n x y_cols column-major, class codes for binomial / multinomial), a0 and beta as sgdnet_result holds them.
+ * f64 throughout, no floating-point atomics: the same input gives the same bits (sgdnet_amd/csrc/gradient.hip).
+ * SGDNET_EINVAL: null pointers, non-positive sizes, a class code outside the family's classes; SGDNET_EUNSUPPORTED:
+ * more classes than sgdnet_score_* take.  sgdnet_amd/kkt.py turns (G, G0) into the optimality residual of a fit. */
+int sgdnet_gradient_sparse(const sgdnet_csc* x, const double* y, int y_cols, int family, int n_classes,
+                           const double* a0, const double* beta, int n_lambda, int device,
+                           double* G, double* G0);
+int sgdnet_gradient_dense(const double* x, int64_t n, int64_t p, const double* y, int y_cols, int family,
+                          int n_classes, const double* a0, const double* beta, int n_lambda, int device,
+                          double* G, double* G0);
 
 /* Default staleness window of the batched mode: about 2 * L_max / L_F, where L_max is the
  * largest squared sample norm and L_F is bounded below by the largest mean squared feature

@@ -5,8 +5,8 @@ warm-started 100-point lambda path (lambda.min.ratio 1e-4, alpha 0.5) on ONE MI3
 
     python scripts/c5_path.py [--n 50000000] [--nlambda 100] [--thresh 1e-3] [--out profiles/r04_c5_path.json]
 
-Records wall time, epochs per lambda, return codes, monotonicity of dev.ratio and the multinomial
-elastic-net KKT residual at the last lambda (tests/test_gpu_c5.py: _multinomial_kkt).
+Records wall time, epochs per lambda, return codes, monotonicity of dev.ratio and (--kkt) the optimality
+certificate of every lambda (sa.kkt: the loss gradient along the path on the device, sgdnet_amd/kkt.py).
 """
 import argparse
 import json
@@ -22,7 +22,8 @@ sys.path.insert(0, ROOT)
 
 def multinomial_kkt(X, y, K, w, b, a_l2, b_l1, chunk=2_000_000):
     """Largest violation of the optimality conditions of (1/n) sum_i -log p_i,y_i + a/2 |w|^2 + b |w|_1
-    (R/sgdnet.R:37-48, src/families.h:235-260), in sample chunks.  X: (p, n) CSC, sample i = column i."""
+    (R/sgdnet.R:37-48, src/families.h:235-260), in sample chunks.  X: (p, n) CSC, sample i = column i.
+    The host pass sa.kkt replaced here; tests/test_gpu_c5.py still checks the fit against it."""
     p, n = X.shape
     g = np.zeros((K, p))
     icpt = np.zeros(K)
@@ -49,7 +50,7 @@ def main():
     ap.add_argument("--first", type=int, default=0, help="run only the first FIRST lambdas of the path (0: all)")
     ap.add_argument("--thresh", type=float, default=1e-3)
     ap.add_argument("--maxit", type=int, default=1000)
-    ap.add_argument("--kkt", action="store_true", help="KKT residual of the last lambda (a host pass over the matrix)")
+    ap.add_argument("--kkt", action="store_true", help="optimality certificate of the path (sa.kkt, on the device)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -96,13 +97,13 @@ def main():
         "epochs_per_lambda_mean": float(fit.npasses) / max(1, len(fit.lambda_)),
     }
     if args.kkt:
-        lam_last = float(fit.lambda_[-1])
-        w = beta[:, :, -1]
-        b = np.asarray(fit.a0)[:, -1]
         tk = time.time()
-        kkt, icpt = multinomial_kkt(X, y, K, w, b, 0.5 * lam_last, 0.5 * lam_last)
-        rec["kkt_last"] = {"lambda": lam_last, "residual": kkt, "residual_over_lambda": kkt / lam_last,
-                           "intercept_residual": icpt, "seconds": time.time() - tk}
+        cert = sa.kkt(fit, xs, y, standardize=False)
+        rec["kkt"] = {"ratio": [float(v) for v in cert["ratio"]], "intercept": [float(v) for v in cert["intercept"]],
+                      "seconds": time.time() - tk}
+        rec["kkt_last"] = {"lambda": float(fit.lambda_[-1]), "residual": float(cert["coef"][-1]),
+                           "residual_over_lambda": float(cert["ratio"][-1]),
+                           "intercept_residual": float(cert["intercept"][-1])}
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:

@@ -1,5 +1,6 @@
 """KKT residual of the C4 bench configuration vs epochs (GPU box)."""
 import sys, os, time
+from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -27,13 +28,16 @@ if V > 1: S.set_virtual_shards(V)
 rng = sa.RRng(seed + 1000)
 draws = V * (n // V) if V > 1 else n
 
+xs = Xt.tocsc()               # samples in rows, as sa.kkt takes it
+
+
 def kkt():
-    w = S.get("w")[0]; b = S.get("intercept")[0]
-    lp = Xt @ w + b
-    r = 1.0 / (1.0 + np.exp(-lp)) - y
-    g = (X @ r) / n + a_l2 * w
-    res = np.where(w == 0, np.maximum(np.abs(g) - b_l1, 0.0), np.abs(g + b_l1 * np.sign(w)))
-    return res.max() / lam, abs(r.sum()) / n / lam, int((w != 0).sum())
+    # the solver's state as a one-lambda fit without preprocessing: the certificate of the problem being iterated
+    w = S.get("w")[0]
+    fit = SimpleNamespace(family="binomial", a0=S.get("intercept")[:1], beta=w[:, None], lambda_=np.array([lam]), alpha=0.5)
+    c = sa.kkt(fit, xs, y, standardize=False)
+    return c["ratio"][0], c["intercept"][0] / lam, int((w != 0).sum())
+
 
 S.convergence(0.0)
 t0 = time.time(); ep = 0

@@ -7,9 +7,12 @@ R front-end for the fit path plus benchmark/multi-GPU plumbing.
 from ._lib import LIB_PATH, SgdnetError, load  # noqa: F401
 from .api import SgdnetFit, sgdnet  # noqa: F401
 from .cv import CvSgdnet, cv_sgdnet  # noqa: F401
+from .kkt import (evaluation_intercepts, feature_moments, kkt, kkt_from_gradient, path_gradient,  # noqa: F401
+                  response_moments)
 from .predict import coef, predict  # noqa: F401
 from .score import score  # noqa: F401
 from .solver import RRng, SagaSolver, auto_batch, get_option, link_peers, option, set_option, shard_window  # noqa: F401
 
 __all__ = ["sgdnet", "SgdnetFit", "SagaSolver", "RRng", "auto_batch", "SgdnetError", "load", "LIB_PATH",
-           "cv_sgdnet", "CvSgdnet", "predict", "coef", "score", "set_option", "get_option", "option"]
+           "cv_sgdnet", "CvSgdnet", "predict", "coef", "score", "set_option", "get_option", "option",
+           "path_gradient", "kkt_from_gradient", "kkt", "feature_moments", "response_moments", "evaluation_intercepts"]

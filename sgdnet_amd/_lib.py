@@ -33,8 +33,9 @@ EXPORTS = [
     "sgdnet_solver_link_peers", "sgdnet_solver_set_cu_budget", "sgdnet_solver_epoch_timing",
     "sgdnet_solver_peer_info_bytes", "sgdnet_solver_peer_info", "sgdnet_solver_link_ipc",
     "sgdnet_solver_rng_layout", "sgdnet_solver_rng_open", "sgdnet_solver_rng_next", "sgdnet_solver_rng_done", "sgdnet_solver_rng_close",
+    "sgdnet_gradient_sparse", "sgdnet_gradient_dense",
 ]
-ABI_VERSION = 4   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
+ABI_VERSION = 5   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
 
 FAMILIES = {"gaussian": 0, "binomial": 1, "multinomial": 2, "mgaussian": 3}
@@ -190,6 +191,10 @@ def load():
     L.sgdnet_rng_jump_poly.argtypes = [C.c_uint64, C.POINTER(C.c_uint32)]
     L.sgdnet_rng_jump.argtypes = [C.POINTER(Rng), C.POINTER(C.c_uint32), C.POINTER(Rng)]
     L.sgdnet_rng_jump.restype = None
+    _grad_tail = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                  C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sgdnet_gradient_sparse.argtypes = [C.POINTER(Csc)] + _grad_tail
+    L.sgdnet_gradient_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _grad_tail
     _lib = L
     return L
 

@@ -14,13 +14,12 @@
 
 #include "common.hpp"
 #include "device_math.hpp"
+#include "path_pairs.hpp"
 
 namespace sgdnet {
 namespace {
 
 constexpr int kScoreBlock = 256;           // 4 wavefronts, one sample each at a time
-constexpr int kMaxPairs = 1024;            // (lambda, class) pairs per call (LDS: 4 x 8 KB)
-constexpr int kMaxLambda = 256;            // lambdas per call (4 running sums per lane)
 constexpr double kProbMin = 1e-05;         // R/score.R:88, 133
 
 struct ScoreArgs {
@@ -36,18 +35,6 @@ struct ScoreArgs {
   double* link;            // n x L x K or nullptr
   double* out;             // L sums or nullptr
 };
-
-// beta[k + K * (j + p * l)]  ->  B[(j * L + l) * K + k]
-__global__ __launch_bounds__(256) void relayout_beta_kernel(const double* beta, int64_t p, int K, int L, double* B) {
-  const int64_t total = p * (int64_t)L * K;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-    const int k = (int)(t % K);
-    const int64_t jl = t / K;
-    const int l = (int)(jl % L);
-    const int64_t j = jl / L;
-    B[t] = beta[k + (int64_t)K * (j + p * l)];
-  }
-}
 
 // one (sample, lambda) loss from the K linear predictors lp[0..K)
 __device__ __forceinline__ double sample_loss(const ScoreArgs& a, const double* lp, const double* ys) {

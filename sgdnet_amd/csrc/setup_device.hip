@@ -335,12 +335,10 @@ int device_gram_lmax(const DeviceSetup& S, int standardize, hipStream_t st, doub
   return SGDNET_OK;
 }
 
-// Feature-major -> sample-major, row norms, packed records.  Frees the feature-major copy.
-int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int standardize, int rec_align,
-                        hipStream_t st, double* max_sqnorm) {
+// Feature-major -> sample-major: a stable sort of the (row, entry) pairs by row.  S.colptr / rowidx / val stay.
+int device_transpose(DeviceSetup& S, hipStream_t st) {
   const int64_t n = S.n, p = S.p, nnz = S.nnz;
   int rc;
-  // ---- transpose: stable sort of (row, entry) pairs by row ----
   int32_t *colof = nullptr, *entry = nullptr, *rows_sorted = nullptr, *perm = nullptr;
   unsigned long long* counts = nullptr;
   if ((rc = dmalloc(&colof, (size_t)nnz)) || (rc = dmalloc(&entry, (size_t)nnz)) ||
@@ -370,9 +368,17 @@ int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int st
                      S.sval);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  for (void* q : {(void*)colof, (void*)entry, (void*)rows_sorted, (void*)perm, (void*)S.colptr, (void*)S.rowidx,
-                  (void*)S.val})
-    (void)hipFree(q);
+  for (void* q : {(void*)colof, (void*)entry, (void*)rows_sorted, (void*)perm, (void*)counts, tmp}) (void)hipFree(q);
+  return SGDNET_OK;
+}
+
+// Feature-major -> sample-major, row norms, packed records.  Frees the feature-major copy.
+int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int standardize, int rec_align,
+                        hipStream_t st, double* max_sqnorm) {
+  const int64_t n = S.n, p = S.p, nnz = S.nnz;
+  int rc;
+  if ((rc = device_transpose(S, st))) return rc;
+  for (void* q : {(void*)S.colptr, (void*)S.rowidx, (void*)S.val}) (void)hipFree(q);
   S.colptr = S.rowidx = nullptr;
   S.val = nullptr;
 
@@ -418,6 +424,10 @@ int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int st
   if ((rc = dmalloc(&ocnt, (size_t)n + 1)) || (rc = dmalloc(&ooff, (size_t)n + 1))) return rc;
   SGD_HIP_TRY(hipMemsetAsync(ocnt, 0, sizeof(long long) * ((size_t)n + 1), st));
   hipLaunchKernelGGL(ovf_count_kernel, dim3(grid_for(n)), dim3(kTB), 0, st, S.sptr, n, cap, kOvfCap, ocnt);
+  size_t scan_bytes = 0;
+  SGD_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, ocnt, ooff, (int)(n + 1), st));
+  void* tmp = nullptr;
+  SGD_HIP_TRY(hipMalloc(&tmp, scan_bytes ? scan_bytes : 1));
   SGD_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, ocnt, ooff, (int)(n + 1), st));
   long long n_ovf = 0;
   SGD_HIP_TRY(hipMemcpyAsync(&n_ovf, ooff + n, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -433,7 +443,7 @@ int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int st
                      y_rows == 1 ? 1 : 0, ooff, n, stride, cap, S.rec_val_off, kOvfStride, kOvfCap, S.rec, S.ovf);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  for (void* q : {(void*)tmp, (void*)counts, (void*)stats, (void*)ocnt, (void*)ooff, (void*)y_dev})
+  for (void* q : {(void*)tmp, (void*)stats, (void*)ocnt, (void*)ooff, (void*)y_dev})
     if (q) (void)hipFree(q);
   return SGDNET_OK;
 }

@@ -45,6 +45,9 @@ int device_setup_begin(DeviceSetup& S, const sgdnet_csc* x, int standardize, hip
                        std::vector<double>& x_center, std::vector<double>& x_scale, double* max_mean_sq);
 int device_xt_times(const DeviceSetup& S, const double* ymap_host, int cols, double* xty_host, hipStream_t st);
 int device_gram_lmax(const DeviceSetup& S, int standardize, hipStream_t st, double* lmax);
+// the transpose alone: S.colptr / rowidx / val (n, p, nnz set) -> S.sptr / sidx / sval; the feature-major copy stays
+// (device_setup_finish runs it and then frees that copy; gradient.hip keeps both)
+int device_transpose(DeviceSetup& S, hipStream_t st);
 int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int standardize, int rec_align,
                         hipStream_t st, double* max_sqnorm);
 
