@@ -195,7 +195,8 @@ struct LamParams {
   int batch_seq;         // running batch id (claims)
   int rng_generate;      // fused epoch kernel: this launch also produces the next generation of the sample order (SagaDev::rngdev)
   int stream_raw;        // the epoch's slot of the sample-order pipeline holds the generators' raw words: the fused epoch
-                         // kernel turns them into draws itself (round 4; every other consumer gets a converted slot)
+                         // kernel turns a word into a draw where it reads it and writes nothing back (every other
+                         // consumer gets a converted slot)
   // ConvergenceCheck scratch: bit patterns of max|dw| and max|w|
   unsigned long long max_change_bits;
   unsigned long long max_size_bits;

@@ -180,7 +180,8 @@ static RngShards make_shards(int n_shards, const double* shard_size, int64_t cou
 }
 
 // raw words -> draws, in place (the second half of launch_rng_fill; also run on its own on a slot of the sample-order
-// pipeline that was left raw for the fused epoch kernel and is consumed by other kernels after all)
+// pipeline that was left raw for the fused epoch kernel and is read by anything else, before or after that kernel).
+// NOT idempotent: the caller knows what the slot holds (solver.cpp slot_to_draws)
 int launch_rng_convert(uint32_t* out, int64_t count, uint32_t n_samples, hipStream_t st, int n_shards,
                        const double* shard_size, int64_t run_len, int narrow_cus) {
   const RngShards sh = make_shards(n_shards, shard_size, count, run_len);
@@ -199,7 +200,8 @@ int launch_rng_convert(uint32_t* out, int64_t count, uint32_t n_samples, hipStre
 
 // state_in -> state_out (may alias); raw words then draws into out[0, count)
 // convert: 1 the wide conversion kernel, 2 the narrow one (narrow_cus CUs), 0 none: the slot keeps the raw words (the
-// fused epoch kernel of the virtual shards converts its own shares, saga_batched.hip)
+// fused epoch kernel of the virtual shards turns a word into a draw where it reads it and leaves the slot raw,
+// saga_batched.hip K1CompactT; solver.cpp keeps the record and converts the slot once for any other reader)
 int launch_rng_fill(const uint32_t* state_in, uint32_t* state_out, uint32_t n_samples, uint32_t* out,
                     int64_t count, hipStream_t st, int n_shards, const double* shard_size, int gens, int64_t run_len,
                     int convert, int narrow_cus, int wgs) {

@@ -663,7 +663,12 @@ struct TicketSource {
 // before the staging, tag_first() (the first pass's cmeta bits) behind it, run() after the workgroup's barrier.
 // (Also requesting the first pass's records before the barrier, with the loop's record loads moved to its end,
 // carries one pass's registers across the back edge: 128 VGPRs and 112 bytes of scratch.)
-struct K1Compact {
+// kRawStream: sp[] may hold the generators' raw words instead of draws (`raw`, wave-uniform; the fused epoch kernel
+// over a slot of the sample-order pipeline).  A word becomes a sample id where it is first needed as one, right in
+// front of tagged(): in tag_first() for the first pass, one pass ahead in run() for all others.  The stream is only
+// read.  Without kRawStream the struct is what it was.
+template <bool kRawStream>
+struct K1CompactT {
   typedef double dpair_t __attribute__((ext_vector_type(2)));
   static constexpr int U = 4;
   // lane geometry
@@ -677,6 +682,14 @@ struct K1Compact {
   TicketSource tk;
   int b_cur, b_nxt;
   uint32_t s_cur, s_nxt;      // s_cur: tagged (long row, response); s_nxt: as read from the stream
+  bool raw = false;           // kRawStream: the stream holds raw words
+  const double* par = nullptr;  // kRawStream: (n_v, lo_v) of the shard, in LDS: read where a word is converted, not carried
+
+  // a word as read from the stream -> sample id (the expression of rng_convert_kernel, r_rng_device.hip)
+  __device__ __forceinline__ uint32_t sample_id(uint32_t x) const {
+    if (kRawStream && raw) x = (uint32_t)par[1] + word_to_draw(x, par[0]);
+    return x;
+  }
 
   __device__ __forceinline__ int own_pos(int base) const { return base + U * g + q < m ? base + U * g + q : base; }
   __device__ __forceinline__ uint32_t tagged(uint32_t sid) const {
@@ -731,7 +744,7 @@ struct K1Compact {
   }
 
   __device__ __forceinline__ void tag_first() {
-    if (b_cur < m) s_cur = tagged(s_cur);
+    if (b_cur < m) s_cur = tagged(sample_id(s_cur));
   }
 
   // all passes of this wavefront; returns the sum of the gradient changes of the draws this lane owns
@@ -764,7 +777,7 @@ struct K1Compact {
       const int b_nn = b_nxt < m ? tk.next() : m;
       uint32_t s_nn = 0u;
       if (b_nn < m) s_nn = sp[own_pos(b_nn)];
-      if (b_nxt < m) s_nxt = tagged(s_nxt);
+      if (b_nxt < m) s_nxt = tagged(sample_id(s_nxt));   // (s_nn stays as read: it is in flight)
       if (half) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -827,6 +840,7 @@ struct K1Compact {
     return gct;
   }
 };
+typedef K1CompactT<false> K1Compact;
 
 template <int U>
 struct K1IdsOnly {
@@ -2355,7 +2369,7 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
   }
   const int64_t m_full = lamp->m_full;
   const int64_t sbase = lamp->stream_base;
-  const bool raw_words = lamp->stream_raw != 0;   // the stream holds the generators' raw words: every workgroup turns its own share into draws
+  const bool raw_words = lamp->stream_raw != 0;   // the stream holds the generators' raw words: a word becomes a draw where it is read (K1CompactT)
   const int64_t dps = d.v_dps;
   const bool std_x = d.standardize != 0;
   const int64_t L = 2 * p + 2;                  // [g_sum | w | g_sum_intercept | intercept]
@@ -2366,39 +2380,10 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
   unsigned* sync = d.vsync;
   const __amdgpu_buffer_rsrc_t rs_slab = fused_rsrc(d.slab, (int64_t)V * S * p * 8);
   const __amdgpu_buffer_rsrc_t rs_w = fused_rsrc(vwv, p * 8);
-  // this workgroup's share of a shard-batch of m draws (the ranges K1Compact::begin hands out): [lo, hi)
-  uint32_t* const stream_v = const_cast<uint32_t*>(d.stream) + sbase + (int64_t)v * dps;
-  // raw words -> draws from shard v's sample range, in place, in two steps: the words of this workgroup's share
-  // are requested early (conv_load), converted and stored a phase later (conv_store) -- no round trip is waited for
-  constexpr int kC = 8;                         // words per thread: shares of up to 8192 draws
-  auto conv_range = [&](int m, int& lo, int& hi) {
-    const int share = ((m + S - 1) / S + kTicket - 1) / kTicket * kTicket;
-    lo = wi * share;
-    hi = lo + share < m ? lo + share : m;
-  };
-  auto conv_load = [&](int64_t t0, int m, uint32_t (&x)[kC]) {
-    int lo, hi;
-    conv_range(m, lo, hi);
-    const uint32_t* q = stream_v + t0;
-#pragma unroll
-    for (int c = 0; c < kC; ++c) {
-      const int i = lo + (int)threadIdx.x + c * kLdsBlock;
-      x[c] = i < hi ? q[i] : 0u;
-    }
-  };
-  auto conv_store = [&](int64_t t0, int m, const uint32_t (&x)[kC]) {
-    int lo, hi;
-    conv_range(m, lo, hi);
-    uint32_t* q = stream_v + t0;
-    const double n_d = sh_par[6], lo_v = sh_par[7];
-#pragma unroll
-    for (int c = 0; c < kC; ++c) {
-      const int i = lo + (int)threadIdx.x + c * kLdsBlock;
-      if (i < hi) q[i] = (uint32_t)lo_v + word_to_draw(x[c], n_d);
-    }
-    for (int i = lo + (int)threadIdx.x + kC * kLdsBlock; i < hi; i += kLdsBlock)   // longer shares: one word at a time
-      q[i] = (uint32_t)lo_v + word_to_draw(q[i], n_d);
-  };
+  // shard v's region of the sample order: draws, or the generators' raw words (raw_words); never written here
+  const uint32_t* const stream_v = d.stream + sbase + (int64_t)v * dps;
+  typedef K1CompactT<true> K1Epoch;
+  const double* const draw_par = sh_par + 6;    // (n_v, lo_v)
 
 #ifdef SGDNET_PHASE_TIMING
   // thread 0's time per phase, summed over the rounds: dbg[workgroup * 16 + phase]; slots 14 / 15: first and last stamp
@@ -2445,14 +2430,7 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
   uint32_t s_first = 0u, s_second = 0u;
   if (alive) {
     const int m0 = (int)(dps < m_full ? dps : m_full);
-    if (raw_words) {
-      uint32_t x0[kC];
-      conv_load(0, m0, x0);
-      conv_store(0, m0, x0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();                          // the ids below are read by other waves than the ones that wrote them
-    }
-    K1Compact nx;
+    K1Epoch nx;
     nx.begin(d, stream_v, m0, wi, S, &ticket_counter);
     s_first = nx.s_cur;
     s_second = nx.s_nxt;
@@ -2465,9 +2443,11 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     const bool merge_due = last || (r + 1) % every == 0;
 
     // ---- stage: long-row bits of the first draws (their ids were requested a phase ago), w, intercept --------
-    if (tid == 0) ticket_counter = K1Compact::static_tickets();
-    K1Compact cg;
+    if (tid == 0) ticket_counter = K1Epoch::static_tickets();
+    K1Epoch cg;
     cg.init(d, stream_v + t0, m, wi, S, &ticket_counter);
+    cg.raw = raw_words;
+    cg.par = draw_par;
     cg.s_cur = s_first;
     cg.s_nxt = s_second;
     cg.tag_first();
@@ -2522,8 +2502,6 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     const int lane = tq & 63, wave = tq >> 6;
     const int64_t t0n = t0 + m_full;
     const int mn = (int)(dps - t0n < m_full ? dps - t0n : m_full);
-    uint32_t xraw[kC];
-    const bool conv_next = !last && raw_words;
 
     // ---- publish the slab (write-through) and the sum of the gradient changes -----------------------
     {
@@ -2543,11 +2521,8 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     }
     fused_arrive(sync, kSyncCnt1 + v);
     FPH(2);
-    // the next round's share of the sample order: requested behind the arrival (in front of it the arrival's drain
-    // waited for these loads: +3 us per round for every workgroup), converted and stored behind the poll below
-    if (conv_next) conv_load(t0n, mn, xraw);
     // behind the arrival, while the rest of the shard finishes: this workgroup's own coefficients (nobody else
-    // writes them), and the next round's share of the sample order.
+    // writes them).
     // A thread owns one PAIR (A, B) of the replicated state: (g_sum_j, w_j) of its feature j, or -- the first thread
     // past the slice in the shard's workgroup 0 -- (g_sum_intercept, intercept): sweep and merge treat both alike
     // (fewer values in flight than two code paths: the phases of this kernel compete with the draw loop for registers)
@@ -2574,7 +2549,6 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     __syncthreads();
     if (!sh_ok) break;
     FPH(3);
-    if (conv_next) conv_store(t0n, mn, xraw);   // (the words arrived while the counter was polled)
 
     // ---- sweep of this workgroup's feature slice ------------------------------------------------
     {
@@ -2723,9 +2697,9 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     }
     fused_arrive(sync, kSyncCnt2 + v);
     FPH(6);
-    // the next round's first sample ids, requested before the wait (converted by this workgroup a phase ago)
+    // the next round's first sample ids (or raw words), requested before the wait
     {
-      K1Compact nx;
+      K1Epoch nx;
       nx.begin(d, stream_v + t0n, mn, wi, S, &ticket_counter);
       s_first = nx.s_cur;
       s_second = nx.s_nxt;

@@ -84,7 +84,9 @@ struct sgdnet_solver {
     uint32_t* poly_n = nullptr;
     uint32_t* ends = nullptr;
     int64_t run_len = 0;   // virtual shards: draws per run of the layout (0: one run = the epoch)
-    // the slot holds the generators' raw words (left to the fused epoch kernel, which converts its own shares)
+    // what the slot's memory holds (in stream order): the generators' raw words, or draws.  Raw slots are left to the
+    // fused epoch kernel, which turns a word into a draw where it reads it and writes nothing back: a slot it has
+    // consumed is still raw.  Every other reader goes through slot_to_draws() first, the ONLY place that clears this.
     bool raw[2] = {false, false};
     // generators inside the fused epoch kernel (SagaDev::rngdev): the generation that the next fused launch is to
     // produce, or -1; a generation still pending when its draws are asked for is produced on the side stream after all
@@ -470,10 +472,35 @@ int set_batch_shape(sgdnet_solver* s, int64_t batch, int64_t draws) {
   return SGDNET_OK;
 }
 
+// Slot q of the sample-order pipeline: raw words -> draws, in place, on the solver's stream, if it holds raw words.
+// The conversion is not idempotent; the slot's flag is tested and cleared here and nowhere else.
+static int slot_to_draws(sgdnet_solver* s, int q) {
+  auto& P = s->pipe;
+  if (!P.raw[q]) return SGDNET_OK;
+  SGD_HIP_TRY(hipStreamWaitEvent(s->st, P.ready[q], 0));        // a generation on the side stream (none: no wait)
+  int rc = launch_rng_convert(s->stream_dev + (int64_t)q * P.n, P.n, (uint32_t)s->d.n, s->st, s->d.V, s->d.v_size,
+                              P.run_len);
+  if (rc) return rc;
+  P.raw[q] = false;
+  return SGDNET_OK;
+}
+
+// entries [offset, offset + count) of the stream are about to be read as draws by something that is not the fused
+// epoch kernel
+static int stream_to_draws(sgdnet_solver* s, int64_t offset, int64_t count) {
+  auto& P = s->pipe;
+  if (!P.open || !(P.raw[0] || P.raw[1])) return SGDNET_OK;
+  for (int q = 0; q < 2; ++q) {
+    if (offset >= (int64_t)(q + 1) * P.n || offset + count <= (int64_t)q * P.n) continue;
+    int rc = slot_to_draws(s, q);
+    if (rc) return rc;
+  }
+  return SGDNET_OK;
+}
+
 // The epoch(s) about to be enqueued read the stream at `stream_offset`.  A slot of the sample-order pipeline that was
-// left raw goes to the fused epoch kernel as it is (LamParams::stream_raw; the kernel converts it, so the slot counts
-// as converted from here on); for any other consumer it is converted now, on the solver's stream (which has waited
-// for the generators: solver_rng_acquire).
+// left raw goes to the fused epoch kernel as it is (LamParams::stream_raw) and stays raw: the kernel only reads it.
+// For any other consumer it is converted now, on the solver's stream.
 int prepare_stream_slot(sgdnet_solver* s, int64_t batch, int64_t stream_offset, int64_t draws, int n_epochs) {
   auto& P = s->pipe;
   s->lam.stream_raw = 0;
@@ -485,22 +512,19 @@ int prepare_stream_slot(sgdnet_solver* s, int64_t batch, int64_t stream_offset, 
   // the launch that consumes generation `used` also produces the pending generation used + 1 (its spare workgroups)
   if (fused && s->d.rngdev && P.pending_gen >= 0 && P.pending_gen == P.used + 1 && slot == (int)(P.used & 1)) {
     s->lam.rng_generate = 1;
+    P.raw[P.pending_gen & 1] = true;            // (the other slot: raw words from this launch on)
     P.pending_gen = -1;
   }
   if (!(P.raw[0] || P.raw[1])) return SGDNET_OK;
   if (fused && P.raw[slot]) {
     s->lam.stream_raw = 1;
-    P.raw[slot] = false;
     return SGDNET_OK;
   }
   for (int q = 0; q < 2; ++q) {
     if (!P.raw[q] || (one_slot && q != slot)) continue;
-    if (P.pending_gen >= 0 && (int)(P.pending_gen & 1) == q) continue;   // not produced yet (solver_rng_acquire will)
     if (!one_slot) SGD_HIP_TRY(hipStreamSynchronize(P.st));      // a slot that may still be generated
-    int rc = launch_rng_convert(s->stream_dev + (int64_t)q * P.n, P.n, (uint32_t)s->d.n, s->st, s->d.V, s->d.v_size,
-                                P.run_len);
+    int rc = slot_to_draws(s, q);
     if (rc) return rc;
-    P.raw[q] = false;
   }
   return SGDNET_OK;
 }
@@ -757,9 +781,8 @@ int fused_recover(sgdnet_solver* s, int code, int64_t draws, int batches, bool* 
     q->stream_base = sb;
     q->batch_seq -= batches;
   }
-  if (s->lam.stream_raw) {                      // the launch was to convert its slot of the sample order and did not
-    const int64_t sb = s->lam.stream_base;
-    int rc = launch_rng_convert(s->stream_dev + sb, s->pipe.n, (uint32_t)s->d.n, s->st, s->d.V, s->d.v_size, s->pipe.run_len);
+  if (s->lam.stream_raw) {                      // the slot holds raw words: the separate launches read draws
+    int rc = stream_to_draws(s, s->lam.stream_base, s->pipe.n);
     if (rc) return rc;
     s->lam.stream_raw = 0;
   }
@@ -1332,6 +1355,8 @@ int sgdnet_solver_get_stream(sgdnet_solver* s, uint32_t* host, int64_t offset, i
     return SGDNET_EINVAL;
   }
   SGD_HIP_TRY(hipSetDevice(s->device));
+  int rc = stream_to_draws(s, offset, count);   // a slot left raw (also one a fused epoch has consumed) reads back as draws
+  if (rc) return rc;
   SGD_HIP_TRY(hipMemcpyAsync(host, s->stream_dev + offset, sizeof(uint32_t) * (size_t)count,
                              hipMemcpyDeviceToHost, s->st));
   SGD_HIP_TRY(hipStreamSynchronize(s->st));
@@ -1548,16 +1573,15 @@ int solver_rng_prefetch(sgdnet_solver* s) {
   if (!P.open || P.gens > P.used + 1) return SGDNET_EINVAL;
   SGD_HIP_TRY(hipSetDevice(s->device));
   // Virtual shards with the fused epoch kernel: that kernel holds every CU for a whole epoch, so its own spare
-  // workgroups produce the next generation (raw words: every workgroup of the NEXT epoch's launch converts the share
-  // it reads), and nothing is launched here: the generation is pending until the launch that carries it is enqueued
+  // workgroups produce the next generation (raw words: the NEXT epoch's launch turns them into draws as it reads
+  // them), and nothing is launched here: the generation is pending until the launch that carries it is enqueued
   // (prepare_stream_slot), or until its draws are asked for without such a launch (solver_rng_acquire).
   // (Generators launched beside the epoch kernel raced it for CUs: dispatched together, one epoch workgroup per XCD
   //  found its CU taken and the whole epoch waited for the generators, +215 us; dispatched later, their own
   //  workgroups could stall until the epoch ended -- profiles/r04_rng_placement.txt.)
   const bool keep_raw = P.run_len == 0 && fused_epochs(s);
   if (keep_raw && P.dev && s->d.rngdev && P.G > 1 && P.gens >= 1 && P.pending_gen < 0) {
-    P.pending_gen = P.gens;
-    P.raw[P.gens & 1] = true;
+    P.pending_gen = P.gens;                     // (its slot keeps what it holds, and its flag, until then)
     ++P.gens;
     return SGDNET_OK;
   }
@@ -1576,7 +1600,7 @@ int solver_rng_acquire(sgdnet_solver* s, int64_t* offset) {
     const int64_t g = P.pending_gen;
     P.pending_gen = -1;
     SGD_HIP_TRY(hipEventRecord(P.freed[slot], s->st));       // after everything enqueued so far
-    int rc = rng_side_generate(s, g, P.raw[slot]);
+    int rc = rng_side_generate(s, g, true);     // (a generation is only ever pending as raw words)
     if (rc) return rc;
   }
   SGD_HIP_TRY(hipStreamWaitEvent(s->st, P.ready[slot], 0));
@@ -1598,18 +1622,15 @@ int solver_rng_close(sgdnet_solver* s, sgdnet_rng* rng) {
   if (!P.open) return SGDNET_OK;
   SGD_HIP_TRY(hipSetDevice(s->device));
   if (P.pending_gen >= 0) {                     // a generation nobody produced: it does not exist (the state below is
-    P.raw[P.pending_gen & 1] = false;           // the one after `used` epochs either way)
-    --P.gens;
+    --P.gens;                                   // the one after `used` epochs either way)
     P.pending_gen = -1;
   }
   SGD_HIP_TRY(hipStreamSynchronize(P.st));
   SGD_HIP_TRY(hipStreamSynchronize(s->st));
   SGD_HIP_TRY(hipMemcpy(rng, P.state[P.used & 1], sizeof(sgdnet_rng), hipMemcpyDeviceToHost));
-  for (int q = 0; q < 2; ++q) {                 // a slot generated ahead for the fused epoch kernel and never consumed
-    if (!P.raw[q]) continue;
-    int rcq = launch_rng_convert(s->stream_dev + (int64_t)q * P.n, P.n, (uint32_t)s->d.n, s->st, s->d.V, s->d.v_size, P.run_len);
+  for (int q = 0; q < 2; ++q) {                 // slots the fused epoch kernel consumed, or never got to: draws from here on
+    int rcq = slot_to_draws(s, q);
     if (rcq) return rcq;
-    P.raw[q] = false;
   }
   P.open = false;
   if (s->d.rngdev) {
@@ -1648,6 +1669,8 @@ int sgdnet_solver_run(sgdnet_solver* s, int mode, int64_t batch, int64_t stream_
 
   if (mode == SGDNET_MODE_EXACT) {
     rc = m_to_array(s);                       // the exact kernels read the K x n gradient memory
+    if (rc) return rc;
+    rc = stream_to_draws(s, stream_offset, s->stream_len - stream_offset);
     if (rc) return rc;
     if (s->sparse) {
       rc = ensure_ls_table(s, draws_per_epoch);
