@@ -35,10 +35,10 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
-#define SGDNET_ABI_VERSION 5
+#define SGDNET_ABI_VERSION 6
 
 /* error codes */
 #define SGDNET_OK          0
@@ -67,6 +67,17 @@ extern "C" {
                                   fall back to the exact iteration outside that */
 #define SGDNET_MODE_AUTO    2  /* sgdnet_fit_* only: batched wherever it is implemented (see above), exact otherwise.  Same optimum, not the reference's
                                   iteration order; SGDNET_MODE_EXACT stays the default. */
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it): the gaussian path of one response solved
+ * to its optimum from the centred cross-products X'X and X'y, which one pass over x leaves on the device; cyclic
+ * coordinate descent on that p x p problem in one workgroup (sgdnet_amd/csrc/covariance.hip).  Needs family =
+ * gaussian, n_classes = 1, n_features <= sgdnet_covariance_max_features(), n_gpus <= 1 and debug = 0; anything else
+ * returns SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition -- there is no fall back to SAGA.
+ * The fit draws no samples: sample_stream, unif, seed and rng_state are accepted and ignored, rng_state is left
+ * untouched bit for bit and result.draws_used = 0.  result.npasses = the coordinate sweeps summed over the path,
+ * max_iter bounds the sweeps of one lambda, tol is the reference's ConvergenceCheck applied per sweep
+ * (max|dw| / max|w| <= tol), and return_codes[l] = 1 when lambda l used all max_iter sweeps without meeting tol.
+ * lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are defined as in the other modes. */
+#define SGDNET_MODE_COVARIANCE 3
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -156,6 +167,8 @@ typedef struct sgdnet_result {
 int sgdnet_abi_version(void);
 const char* sgdnet_last_error(void);
 int sgdnet_device_count(void);
+/* the largest n_features SGDNET_MODE_COVARIANCE takes (198: what one gfx950 workgroup's LDS holds; at least 64) */
+int sgdnet_covariance_max_features(void);
 
 /* ------------------------------------------------------------------------ */
 /* Process-wide backend options.  These are the ONLY switches that change    */

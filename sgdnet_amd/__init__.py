@@ -11,8 +11,10 @@ from .kkt import (evaluation_intercepts, feature_moments, kkt, kkt_from_gradient
                   response_moments)
 from .predict import coef, predict  # noqa: F401
 from .score import score  # noqa: F401
-from .solver import RRng, SagaSolver, auto_batch, get_option, link_peers, option, set_option, shard_window  # noqa: F401
+from .solver import (RRng, SagaSolver, auto_batch, covariance_max_features, get_option, link_peers, option, set_option,  # noqa: F401
+                     shard_window)
 
 __all__ = ["sgdnet", "SgdnetFit", "SagaSolver", "RRng", "auto_batch", "SgdnetError", "load", "LIB_PATH",
            "cv_sgdnet", "CvSgdnet", "predict", "coef", "score", "set_option", "get_option", "option",
-           "path_gradient", "kkt_from_gradient", "kkt", "feature_moments", "response_moments", "evaluation_intercepts"]
+           "path_gradient", "kkt_from_gradient", "kkt", "feature_moments", "response_moments", "evaluation_intercepts",
+           "covariance_max_features"]

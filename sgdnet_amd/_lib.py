@@ -33,14 +33,14 @@ EXPORTS = [
     "sgdnet_solver_link_peers", "sgdnet_solver_set_cu_budget", "sgdnet_solver_epoch_timing",
     "sgdnet_solver_peer_info_bytes", "sgdnet_solver_peer_info", "sgdnet_solver_link_ipc",
     "sgdnet_solver_rng_layout", "sgdnet_solver_rng_open", "sgdnet_solver_rng_next", "sgdnet_solver_rng_done", "sgdnet_solver_rng_close",
-    "sgdnet_gradient_sparse", "sgdnet_gradient_dense",
+    "sgdnet_gradient_sparse", "sgdnet_gradient_dense", "sgdnet_covariance_max_features",
 ]
-ABI_VERSION = 5   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
+ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
 
 FAMILIES = {"gaussian": 0, "binomial": 1, "multinomial": 2, "mgaussian": 3}
 PENALTIES = {"ridge": 0, "elasticnet": 1, "grouplasso": 2}
-MODES = {"exact": 0, "batched": 1, "auto": 2}
+MODES = {"exact": 0, "batched": 1, "auto": 2, "covariance": 3}
 
 UNIF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
 LOSSES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)

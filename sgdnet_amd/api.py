@@ -70,7 +70,10 @@ def sgdnet(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min_ratio=None,
     sgdnet.default (lambda.min.ratio -> lambda_min_ratio, lambda -> lambda_).  Keyword-only
     extensions: debug (options(sgdnet.debug)), seed (set.seed) or rng (an RRng whose state is
     advanced like R's .Random.seed), sample_stream / unif (explicit sample order), mode /
-    batch / device (backend).
+    batch / device (backend).  mode: "exact" (the reference's iteration, the default), "batched", "auto", or
+    "covariance": the gaussian path of one response solved to its optimum by coordinate descent on the device's
+    X'X and X'y (at most covariance_max_features() features; draws no samples, so seed / rng / sample_stream / unif
+    are ignored, npasses counts coordinate sweeps and maxit bounds the sweeps per lambda).
     """
     import scipy.sparse as sp
 
@@ -193,6 +196,8 @@ def sgdnet(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min_ratio=None,
     ctl.seed = int(seed) & 0xFFFFFFFF
     if rng is not None:
         ctl.rng_state = C.pointer(rng.state)
+    if mode not in MODES:
+        _stop("mode must be one of " + ", ".join(f"'{m}'" for m in MODES))
     ctl.mode = MODES[mode]
     ctl.batch = int(batch)
     ctl.device = int(device)

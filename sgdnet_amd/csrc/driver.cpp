@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "covariance.hpp"
 #include "fit_plan.hpp"
 #include "setup_device.hpp"
 
@@ -61,6 +62,9 @@ struct Features {
   hipStream_t st = nullptr;
   double dev_max_mean_sq = 0.0;
   bool dense_dev = false;       // dense x prepared by dense_setup_* (large matrices)
+  // x as it came (covariance mode takes its moments from it): the column-major matrix, or the dgCMatrix values
+  const double* raw_dense = nullptr;
+  const double* raw_values = nullptr;
 };
 
 // math.h:66-79 Mean / :114-130 StandardDeviation (population sd, 0 -> 1)
@@ -924,14 +928,11 @@ int deviance_all_ranks(Ranks& ranks, double* dev) {
 }
 
 // Rescale (utils.h:352-378): the coefficients of lambda li on the scale of the data as it came
-int rescale_into(sgdnet_solver* S, const Features& X, const Response& R, const sgdnet_control* ctl, int li, std::vector<double>& w,
-                 std::vector<double>& b, sgdnet_result* out) {
+// w (K x p) and b (K): the coefficients and intercepts of the preprocessed problem
+void rescale_values(const Features& X, const Response& R, const sgdnet_control* ctl, int li, const double* w, const double* b,
+                    sgdnet_result* out) {
   const int K = ctl->n_classes;
   const int64_t p = X.p;
-  int rc = sgdnet_solver_get_state(S, 0, w.data());
-  if (rc) return rc;
-  rc = sgdnet_solver_get_state(S, 1, b.data());
-  if (rc) return rc;
   double* bo = out->beta + (size_t)li * (size_t)(K * p);
   double* ao = out->a0 + (size_t)li * (size_t)K;
   std::vector<double> xbb((size_t)K, 0.0);
@@ -944,6 +945,79 @@ int rescale_into(sgdnet_solver* S, const Features& X, const Response& R, const s
   for (int k = 0; k < K; ++k)
     ao[k] = ctl->intercept != 0 ? b[(size_t)k] * R.y_scale[(size_t)k] + R.y_center[(size_t)k] - xbb[(size_t)k]
                                 : b[(size_t)k];
+}
+
+int rescale_into(sgdnet_solver* S, const Features& X, const Response& R, const sgdnet_control* ctl, int li, std::vector<double>& w,
+                 std::vector<double>& b, sgdnet_result* out) {
+  int rc = sgdnet_solver_get_state(S, 0, w.data());
+  if (rc) return rc;
+  rc = sgdnet_solver_get_state(S, 1, b.data());
+  if (rc) return rc;
+  rescale_values(X, R, ctl, li, w.data(), b.data(), out);
+  return SGDNET_OK;
+}
+
+// ---- covariance mode (SGDNET_MODE_COVARIANCE, covariance.hip): the stage behind the plan ----
+// The preprocessed problem is the one every mode fits: features (x_j - x_center_j) / x_scale_j (x_center = 0, x_scale = 1
+// without standardize), the response of prepare_response, the penalties of regularization_path.  With an intercept the
+// optimum only sees deviations from the column means, standardised or not; without one the intercept stays at the null
+// model's value and the features are taken as the preprocessing left them: deviations from x_center.
+int fit_covariance(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl,
+                   sgdnet_result* out, PhaseTimer& pt) {
+  const int64_t n = X.n, p = X.p;
+  const int L = ctl->n_lambda;
+  CovarianceProblem pb;
+  pb.n = n;
+  pb.p = p;
+  if (X.sparse) {
+    pb.colptr = X.colptr;
+    pb.rowidx = X.rowidx;
+    pb.values = X.raw_values;
+  } else {
+    pb.x_dense = X.raw_dense;
+  }
+  pb.y = R.y.data();
+  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
+  pb.scale = X.x_scale.data();
+  pb.device = plan.rank_dev[0];
+  pb.n_lambda = L;
+  pb.alpha = path.alpha.data();
+  pb.beta = path.beta.data();
+  pb.ridge = plan.penalty == SGDNET_RIDGE;
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  CovarianceResult cr;
+  int rc = covariance_run(pb, &cr);
+  if (rc) return rc;
+  if (pt.on) fprintf(stderr, "[sgdnet]   covariance: moments %.3f ms, path kernel %.3f ms\n", cr.moments_ms, cr.path_ms);
+
+  // deviance from the quadratic form: |y~ - X~ w|^2 = y~'y~ - n (2 c~'w - w'S w), and w'S w = w'(g + c~) with the path
+  // kernel's gradient g = S w - c~: the explained part is n sum_j w_j (c~_j - g_j), each term w_j c~_j + alpha w_j^2 +
+  // beta |w_j| at the optimum
+  double yy = 0.0;
+  for (int64_t i = 0; i < n; ++i) yy += R.y[(size_t)i] * R.y[(size_t)i];
+  double n_sweeps = 0.0;
+  for (int li = 0; li < L; ++li) {
+    const double* w = cr.w.data() + (size_t)li * (size_t)p;
+    const double* g = cr.g.data() + (size_t)li * (size_t)p;
+    double explained = 0.0, shift = 0.0;
+    for (int64_t j = 0; j < p; ++j) {
+      explained += w[j] * (cr.c[(size_t)j] - g[j]);
+      shift += (cr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j] * w[j];
+    }
+    const double dev = std::max(0.0, yy - (double)n * explained);
+    // (a constant response has a null deviance of 0 and nothing to explain: the ratio is 0, not 0 / 0)
+    out->dev_ratio[li] = R.null_dev_scaled > 0.0 ? 1.0 - dev / R.null_dev_scaled : 0.0;
+    out->lambda[li] = path.lambda[(size_t)li];
+    out->return_codes[li] = cr.unconverged[(size_t)li] ? 1.0 : 0.0;
+    n_sweeps += (double)cr.sweeps[(size_t)li];
+    // the intercept of the preprocessed problem: the response's mean there (R.b0) less the features' means times w
+    const double b = ctl->intercept != 0 ? R.b0[0] - shift : R.b0[0];
+    rescale_values(X, R, ctl, li, w, &b, out);
+  }
+  out->npasses = n_sweeps;
+  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
+  pt.mark("covariance (moments + path)");
   return SGDNET_OK;
 }
 
@@ -967,6 +1041,19 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   Path path;
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
+  if (ctl->mode == SGDNET_MODE_COVARIANCE) {   // plan_fit says whether it may run; it needs none of the SAGA setup below
+    facts.ctl = ctl;
+    facts.sparse = X.sparse;
+    facts.on_device = X.dev != nullptr;
+    facts.n = n;
+    facts.p = p;
+    const FitPlan plan = plan_fit(facts);
+    if (plan.rc) {
+      set_error("%s", plan.error.c_str());
+      return plan.rc;
+    }
+    return fit_covariance(X, R, path, plan, ctl, out, pt);
+  }
   double norm_max = 0.0;
   rc = row_norm_max(X, ctl, R, Ky, trace, &norm_max);
   if (rc) return rc;
@@ -1138,6 +1225,7 @@ int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdn
   X.p = x->n_cols;
   X.colptr = x->colptr;
   X.rowidx = x->rowidx;
+  X.raw_values = x->values;
   const int64_t n = X.n, p = X.p, nnz = x->colptr[p];
   if (x->colptr[0] != 0) {
     set_error("colptr[0] must be 0");
@@ -1217,6 +1305,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
   X.sparse = false;
   X.n = n;
   X.p = p;
+  X.raw_dense = x;
   if (n * p >= kDenseDeviceSetupElems && !option(kOptHostSetup)) {
     // large dense x: statistics, standardisation, lambda_max products, transpose and row norms on the
     // device (dense_setup_*), no host pass over the n * p doubles beyond the one upload
@@ -1235,8 +1324,10 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     col_mean_sd(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
-  X.xt.resize((size_t)(n * p));                               // utils.h:283-288
-  transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
+  if (ctl->mode != SGDNET_MODE_COVARIANCE) {                  // (covariance mode reads x column-major, as it came)
+    X.xt.resize((size_t)(n * p));                             // utils.h:283-288
+    transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
+  }
   return fit_common(X, y, y_cols, ctl, out, batched_gave_up);
 }
 

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "covariance.hpp"
 #include "sgdnet_hip.h"
 
 namespace sgdnet {
@@ -69,7 +70,7 @@ struct FitFacts {
 // SGDNET_MODE_BATCHED means "batched where it is implemented": more than 64 classes run the exact
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
-// An unknown mode comes back as it is (plan_fit refuses it).
+// An unknown mode comes back as it is (plan_fit refuses it), and so does SGDNET_MODE_COVARIANCE: no other mode resolves to it.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -123,6 +124,27 @@ inline FitPlan plan_fit(const FitFacts& f) {
   if (c.elasticnet_mix == 0.0) P.penalty = SGDNET_RIDGE;
   else if (family == SGDNET_MGAUSSIAN || (family == SGDNET_MULTINOMIAL && c.type_multinomial == 1))
     P.penalty = SGDNET_GROUPLASSO;
+
+  // ---- covariance mode: only where it was asked for (mode = auto must not move existing results), and only for
+  // the problem its path kernel holds in one workgroup's LDS (covariance.hpp); no silent fall back ----
+  if (c.mode == SGDNET_MODE_COVARIANCE) {
+    const char* what = nullptr;
+    if (family != SGDNET_GAUSSIAN) what = "family = gaussian";
+    else if (K != 1) what = "one response (n_classes = 1)";
+    else if (f.p > kCovMaxFeatures) what = "no more features than sgdnet_covariance_max_features()";
+    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+    if (what) {
+      P.rc = SGDNET_EUNSUPPORTED;
+      P.error = plan_text("mode = covariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what,
+                          family, K, (long long)f.p, kCovMaxFeatures, c.n_gpus, c.debug);
+      return P;
+    }
+    P.mode = SGDNET_MODE_COVARIANCE;
+    P.rank_dev.assign(1, c.device);
+    P.rank_lo = {0, n};
+    return P;                          // no window, no shards, no draws
+  }
 
   P.mode = resolved_mode(c.mode, K);
   P.window = c.batch;

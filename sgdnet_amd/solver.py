@@ -115,6 +115,11 @@ def shard_window(window, draws_per_shard):
     return int(_lib.load().sgdnet_shard_window(int(window), int(draws_per_shard)))
 
 
+def covariance_max_features():
+    """Largest number of features sgdnet(..., mode="covariance") takes (sgdnet_covariance_max_features of the C ABI)."""
+    return int(_lib.load().sgdnet_covariance_max_features())
+
+
 class SagaSolver:
     """One problem resident in HBM: sample-major x, y and the five SAGA state arrays
     (reference src/sgdnet.cpp:187-198).
