@@ -11,16 +11,23 @@ mkdir -p "$OUT" build
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Iinclude -I$SRC -Wall -Wno-unused-function ${EXTRA_FLAGS:-}"
 # objects are rebuilt when the flags change (e.g. EXTRA_FLAGS=-DSGDNET_PHASE_TIMING experiments)
 if [ ! -f build/.flags ] || [ "$(cat build/.flags)" != "$FLAGS" ]; then rm -f build/*.o; echo "$FLAGS" > build/.flags; fi
+# every source of the library, compiled and linked from this one list
+SOURCES="saga_exact.hip saga_batched.hip r_rng_device.hip setup_device.hip score.hip gradient.hip covariance.hip solver.cpp solver_epoch.cpp solver_rng.cpp solver_shards.cpp phase_report.cpp driver.cpp r_rng.cpp mt_jump.cpp"
+# an object is rebuilt when its source or any header ($SRC/*.hpp, include/*.h) is newer
+newest_header=include/sgdnet_hip.h
+for h in "$SRC"/*.hpp include/*.h; do [ "$h" -nt "$newest_header" ] && newest_header=$h; done
 pids=()
-for f in saga_exact.hip saga_batched.hip r_rng_device.hip setup_device.hip score.hip gradient.hip covariance.hip solver.cpp driver.cpp r_rng.cpp mt_jump.cpp; do
+objs=()
+for f in $SOURCES; do
   o=build/${f%.*}.o
-  if [ ! -f "$o" ] || [ "$SRC/$f" -nt "$o" ] || [ "$SRC/common.hpp" -nt "$o" ] || [ "$SRC/device_math.hpp" -nt "$o" ] || [ "$SRC/setup_device.hpp" -nt "$o" ] || [ "$SRC/fit_plan.hpp" -nt "$o" ] || [ "$SRC/path_pairs.hpp" -nt "$o" ] || [ "$SRC/covariance.hpp" -nt "$o" ] || [ include/sgdnet_hip.h -nt "$o" ] || [ include/sgdnet_detmath.h -nt "$o" ]; then
+  objs+=("$o")
+  if [ ! -f "$o" ] || [ "$SRC/$f" -nt "$o" ] || [ "$newest_header" -nt "$o" ]; then
     $HIPCC $FLAGS -x hip -c "$SRC/$f" -o "$o" &
     pids+=($!)
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsgdnet_hip.so" build/saga_exact.o build/saga_batched.o build/r_rng_device.o build/setup_device.o build/score.o build/gradient.o build/covariance.o build/solver.o build/driver.o build/r_rng.o build/mt_jump.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsgdnet_hip.so" "${objs[@]}"
 make -s -C oracle liboracle.so liboracle_det.so
 # the .Call shim (shim/sgdnet_shim.c) compiled as it will be inside the R package, against the
 # mock of the R C API under tests/rmock (no R in this image): test infrastructure

@@ -29,7 +29,7 @@ __device__ __forceinline__ uint32_t mt_twist(uint32_t a, uint32_t b) {
 constexpr int kRngBlock = 256;      // threads that carry one generator
 constexpr int kGenPerWg = 4;        // generators per workgroup (they step in lock-step: one barrier per block serves all)
 
-// Several generators on ONE R stream (batched mode, solver.cpp: solver_rng_open): generator g (state g of
+// Several generators on ONE R stream (batched mode, solver_rng.cpp: solver_rng_open): generator g (state g of
 // st_in / st_out) fills the g-th segment of `seg` words.  A generator is latency-bound (one barrier per 624
 // words, 227 busy lanes), so kGenPerWg of them share a workgroup -- and with it a CU: the sample order of a C4
 // epoch then holds 8 CUs instead of 32 for the same ~0.18 ms (the LDS gather forms give their workgroups'

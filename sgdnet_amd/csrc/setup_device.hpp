@@ -57,8 +57,8 @@ int solver_create_adopting(const sgdnet_problem* pb, DeviceSetup& S, sgdnet_solv
 
 }  // namespace sgdnet
 
-// solver.cpp: sample-order pipeline of the fit driver (the next epoch's draws are generated on a
-// side stream while the current epoch runs)
+// solver_rng.cpp: sample-order pipeline of the fit driver (the next epoch's draws are generated on a
+// side stream while the current epoch runs); solver.cpp / solver_epoch.cpp: the rest
 int solver_rng_open(sgdnet_solver* s, sgdnet_rng* rng, int64_t n, int generators = 1, int64_t jump_draws = 0);
 int solver_reset_state(sgdnet_solver* s, const double* b0);
 bool solver_bin_overflowed(const sgdnet_solver* s);
