@@ -55,7 +55,7 @@ int option(Option o);
 // src/constants.h:22 of the reference: 100 * DBL_EPSILON
 constexpr double kSmall = 100.0 * 2.220446049250313e-16;
 
-// The sample-order generators as the fused epoch kernel of the virtual shards runs them (saga_batched.hip): its
+// The sample-order generators as the fused epoch kernel of the virtual shards runs them (batched_shards.hip): its
 // spare workgroups produce the NEXT epoch's raw words and jump the generators' start states while the epoch runs.
 // Lives in device memory (the captured launch reads it; `gen` is advanced by the kernel itself).
 struct RngDev {
@@ -69,7 +69,7 @@ struct RngDev {
   unsigned gen;           // the generation the next producing launch makes
 };
 
-// Solvers linked for the replica average across GPUs (the fused epoch kernel's merge, saga_batched.hip): what every
+// Solvers linked for the replica average across GPUs (the fused epoch kernel's merge, batched_shards.hip): what every
 // rank's kernel needs to reach the others -- their exchange buffers and barrier counters (peer pointers, or
 // hipIpc mappings of them) and their shard sizes.  Lives in device memory.
 struct FusedPeers {
@@ -129,13 +129,13 @@ struct SagaDev {
   const double* xd;   // dense p x n
   const double* c;    // x_center_scaled (p) or nullptr
   const double* y;    // Ky x n
-  // packed per-sample records for the batched gather (saga_batched.hip)
+  // packed per-sample records for the batched gather (batched_device.hpp)
   const char* rec;    // n records of rec_stride bytes
   const char* ovf;    // overflow records (256 B each)
   int rec_stride;
   int rec_cap;        // entries held by the main record
   int rec_val_off;    // byte offset of val[] inside a record
-  // compact two-plane records of the K == 1 LDS gather (saga_batched.hip) or nullptr
+  // compact two-plane records of the K == 1 LDS gather (batched_k1.hpp) or nullptr
   char* cP;           // n x 128 B: first cE entries (16-bit feature ids), response, gradient memory
   const char* cQ;     // n x 128 B: entries cE .. cE + 11 of the rows that have them
   const uint32_t* cmeta;  // 2 bits per sample: row longer than cE entries, response != 0 (binomial)
@@ -159,7 +159,7 @@ struct SagaDev {
   double* cw;       // 2 x 16 x K  slots of c.w (implicit centring in batched mode)
   int* claim;     // n     first-occurrence claims (K > 1)
   const uint32_t* stream;
-  // binned form of the batched iteration (saga_batched.hip "binned"): K x p tables that fit no
+  // binned form of the batched iteration (batched_binned.hip): K x p tables that fit no
   // LDS are split into R feature ranges; the gather bins every non-zero of the batch by range
   // and one workgroup per range accumulates its slice of D in LDS and sweeps it.  R == 0: off.
   int R;
@@ -247,7 +247,7 @@ struct ExactInputs {     // the solver's run-time facts the plan reads besides S
 int plan_exact(const SagaDev& d, const ExactInputs& in, ExactPlan* plan);
 int launch_exact(const SagaDev& d, const ExactPlan& plan, const LamParams* lam, const ExactCtl& ctl, hipStream_t st);
 
-// ---- how the batched iteration launches a batch (saga_batched.hip plan_batch: the one rule) ----
+// ---- how the batched iteration launches a batch (batched_plan.cpp plan_batch: the one rule) ----
 enum class BatchForm {
   kGlobal,          // global-atomic gather + element sweep
   kLds,             // sparse x: LDS-privatised gather (three K == 1 variants, K <= 4, class-lane) + slab sweep

@@ -1,5 +1,5 @@
 // R's Mersenne-Twister on the device: the bodies of the state and jump-ahead kernels (r_rng_device.hip), shared
-// with the fused epoch kernel of the virtual shards (saga_batched.hip), whose spare workgroups produce the NEXT
+// with the fused epoch kernel of the virtual shards (batched_shards.hip), whose spare workgroups produce the NEXT
 // epoch's sample order while the epoch runs (round 4).
 #pragma once
 

@@ -201,7 +201,7 @@ int launch_rng_convert(uint32_t* out, int64_t count, uint32_t n_samples, hipStre
 // state_in -> state_out (may alias); raw words then draws into out[0, count)
 // convert: 1 the wide conversion kernel, 2 the narrow one (narrow_cus CUs), 0 none: the slot keeps the raw words (the
 // fused epoch kernel of the virtual shards turns a word into a draw where it reads it and leaves the slot raw,
-// saga_batched.hip K1CompactT; solver.cpp keeps the record and converts the slot once for any other reader)
+// batched_k1.hpp K1CompactT; solver.cpp keeps the record and converts the slot once for any other reader)
 int launch_rng_fill(const uint32_t* state_in, uint32_t* state_out, uint32_t n_samples, uint32_t* out,
                     int64_t count, hipStream_t st, int n_shards, const double* shard_size, int gens, int64_t run_len,
                     int convert, int narrow_cus, int wgs) {

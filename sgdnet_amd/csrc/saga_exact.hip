@@ -8,7 +8,7 @@
 //   saga_dense_exact_kernel   <-  Saga(), src/saga-dense.h:99-224
 // The chain through `intercept` makes every pair of consecutive iterations
 // dependent, so these kernels are latency-bound by construction;
-// the throughput path is saga_batched.hip.  Sparse x with one response has two
+// the throughput path is saga_batched.hip and batched_*.hip.  Sparse x with one response has two
 // faster forms of the same iteration, bit for bit (round 3):
 //   saga_sparse_exact_k1x_kernel  one producer + one consumer wavefront, the drawn
 //                                 row held in registers for the whole draw

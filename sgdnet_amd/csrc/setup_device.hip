@@ -8,7 +8,7 @@
 //                        as a STABLE radix sort of the entries by sample id, so feature ids stay
 //                        ascending inside a sample (the order the exact kernel's dot product uses)
 //   row_norm_kernel      ColNormsMax                                      utils.h:60-77
-//   pack_records_kernel  the batched gather's packed records (saga_batched.hip)
+//   pack_records_kernel  the batched gather's packed records (batched_device.hpp)
 // All of it is streaming / segmented-reduction work bound by HBM bandwidth; none of it is on
 // the per-epoch path.
 #include <cmath>

@@ -84,7 +84,7 @@ int m_to_array(sgdnet_solver* s) {
   return SGDNET_OK;
 }
 
-// Binned form of the batched iteration for K x p tables that fit no LDS (saga_batched.hip
+// Binned form of the batched iteration for K x p tables that fit no LDS (batched_binned.hip
 // "Binned form").  Ranges: contiguous features of equal non-zero mass, at most
 // binned_max_range_features(K) wide; built once per solver from a device histogram of the feature
 // ids.  Bins and the gradient-change buffer are sized for the batch.
@@ -230,7 +230,7 @@ int ensure_binned(sgdnet_solver* s, int64_t batch) {
   return SGDNET_OK;
 }
 
-// Dense x whose K x p accumulator fits no LDS (saga_batched.hip "tiled"): the gather leaves the
+// Dense x whose K x p accumulator fits no LDS (batched_dense.hip "tiled"): the gather leaves the
 // batch's gradient changes in d.gcb and D is formed feature tile by feature tile.
 int ensure_dense_tiled(sgdnet_solver* s, int64_t batch) {
   SagaDev& d = s->d;
@@ -249,7 +249,7 @@ int ensure_dense_tiled(sgdnet_solver* s, int64_t batch) {
 }
 
 // Packs the sample-major CSR rows into fixed-stride records for the batched gather
-// (layout: saga_batched.hip "Packed sample records").
+// (layout: batched_device.hpp "Packed sample records").
 constexpr int kOvfStride = 256;
 constexpr int kOvfCap = 20;
 
@@ -558,7 +558,7 @@ static int solver_create_impl(const sgdnet_problem* pb, DeviceSetup* adopt, sgdn
   TRY(dev_alloc(s, &d.lag, p, true));
   TRY(dev_alloc(s, &d.D, K * p, true));
   TRY(dev_alloc(s, &d.claim, n, false));
-  TRY(dev_alloc(s, &d.d0_part, 2 * 256 * K, true));   // two parity sets of 256 slots (saga_batched.hip)
+  TRY(dev_alloc(s, &d.d0_part, 2 * 256 * K, true));   // two parity sets of 256 slots (batched_geometry.hpp: kD0Slots)
   TRY(dev_alloc(s, &d.cw, 2 * 16 * K, true));
   TRY(dev_alloc(s, &s->ref, 2 * K * p + 2 * K, true));
   TRY(dev_alloc(s, &s->out_dev, 4, true));

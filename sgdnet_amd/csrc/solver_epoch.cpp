@@ -32,7 +32,7 @@ static bool lam_on_device(const sgdnet_solver* s) {
          a.rng_generate == b.rng_generate;
 }
 
-// host mirror of end_epoch (saga_batched.hip)
+// host mirror of end_epoch (batched_device.hpp)
 static void lam_advance(sgdnet_solver* s, int64_t draws, int batches) {
   for (LamParams* q : {&s->lam, &s->lam_dev_mirror}) {
     int64_t sb = q->stream_base + draws;
@@ -157,7 +157,7 @@ static int timing_pair(std::vector<hipEvent_t>* owner, hipEvent_t* e0, hipEvent_
   return SGDNET_OK;
 }
 
-// The whole epoch in one launch (saga_batched.hip "Fused epoch", BatchForm::kFusedEpoch): option fused_epoch, the
+// The whole epoch in one launch (batched_shards.hip "Fused epoch", BatchForm::kFusedEpoch): option fused_epoch, the
 // kernel's own limits, a device with at least as many CUs as the launch has workgroups, and no earlier launch of this
 // solver that failed to become resident.
 // `ev` (sgdnet_solver_profile_epoch) receives four events per gather + sweep pair; for the fused launch its pair and an
@@ -341,7 +341,7 @@ static int read_convergence(sgdnet_solver* s, double tol, int* converged) {
   return SGDNET_OK;
 }
 
-// A fused epoch launch that gave up (saga_batched.hip "Fused epoch").  *rerun: the launch changed nothing, the
+// A fused epoch launch that gave up (batched_shards.hip "Fused epoch").  *rerun: the launch changed nothing, the
 // caller runs the epoch again (the solver has switched to separate launches).
 static int fused_recover(sgdnet_solver* s, int code, int64_t draws, int batches, bool* rerun) {
   *rerun = false;

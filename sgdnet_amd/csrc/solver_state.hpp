@@ -86,7 +86,7 @@ struct sgdnet_solver {
   std::vector<void*> vs_owned;  // virtual-shard replicas
   int64_t vs_period = 0;        // draws per shard between device-side merges (0: n / 32)
   double* own_d0 = nullptr;
-  // binned form (saga_batched.hip): ranges built once, bins sized for the current batch
+  // binned form (batched_binned.hip): ranges built once, bins sized for the current batch
   bool bin_ranges_ready = false;
   int64_t bin_batch = 0;        // the batch the bins and gcb were sized for
   void* bin_bufs[3] = {nullptr, nullptr, nullptr};   // bins, gcb, bin_off
@@ -96,7 +96,7 @@ struct sgdnet_solver {
   bool bin_disabled = false;     // a bin kept overflowing: the solver runs the atomic form (K <= 16) from now on
   bool bin_overflowed = false;   // the last sync found an overflow (the epochs since the previous sync are void)
   // one-response sparse fits with compact records: the batched kernels keep the gradient memory inside the
-  // records (saga_batched.hip "Compact records"), everything else (exact mode, the host) sees the K x n array
+  // records (batched_k1.hpp "Compact records"), everything else (exact mode, the host) sees the K x n array
   bool m_in_rec = false;
   // fused epoch of the virtual shards (saga_vs_epoch_kernel): switched off for this solver once a launch could not
   // become resident (a GPU shared with another process); the separate launches take over
