@@ -501,6 +501,50 @@ int64_t sgdnet_auto_batch(double max_sample_sqnorm, double max_feature_mean_sq);
  * window (the rule of sgdnet_auto_batch keeps a factor 3 to the unstable regime; 1/8 of it is spent here). */
 int64_t sgdnet_shard_window(int64_t window, int64_t draws_per_shard);
 
+/* ------------------------------------------------------------------------ */
+/* Diagnostics (additions only; the ABI version stays): what the device      */
+/* setup passes of a fit (sgdnet_amd/csrc/setup_device.hip) leave behind,     */
+/* copied back pass by pass.  The probes call the functions sgdnet_fit_* call,*/
+/* in the order a fit calls them, on the caller's data; tests compare every   */
+/* output with an exact reference (tests/test_gpu_setup_passes.py).           */
+/* Every pointer is a caller-allocated HOST buffer.  The two sizes the caller */
+/* cannot know in advance are capacities: rec_bytes_cap >= n * rec_stride and */
+/* ovf_bytes_cap >= 256 * n_ovf, else SGDNET_EINVAL (the scalar outputs,      */
+/* n_ovf among them, are filled in all the same, so a second call can size    */
+/* them).  Safe upper bounds: rec_stride <= 6400 (a cap of 512 entries at     */
+/* rec_align <= 256), n_ovf <= nnz / 20 + n.                                  */
+/* ------------------------------------------------------------------------ */
+typedef struct sgdnet_setup_probe {
+  /* both probes */
+  double*  center;         /* p: column means (0 without standardize)                      */
+  double*  scale;          /* p: population sds, 0 -> 1 (1 without standardize)            */
+  double*  xty;            /* p x cols: x' ymap of the prepared x                           */
+  double   max_mean_sq;    /* max_j mean_i x_ij^2 of the prepared x (sparse: scaled, not centred) */
+  double   max_sqnorm;     /* largest squared row norm of the prepared (sparse: centred) x */
+  /* sparse probe: the sample-major matrix, the packed records and their geometry, L_F */
+  int64_t* sptr;           /* n + 1 */
+  int32_t* sidx;           /* nnz   */
+  double*  sval;           /* nnz   */
+  char*    rec;            /* n * rec_stride raw record bytes   */
+  int64_t  rec_bytes_cap;
+  char*    ovf;            /* 256 * n_ovf raw overflow bytes    */
+  int64_t  ovf_bytes_cap;
+  int      rec_stride, rec_cap, rec_val_off;
+  int64_t  n_ovf;
+  double   l_f;            /* device_gram_lmax: largest eigenvalue of X'X/n by power iteration */
+  /* dense probe */
+  double*  xt;             /* p x n column-major: the sample-major standardised matrix */
+  double*  sample;         /* sample_m x p column-major: rows r * sample_stride, r < sample_m (NULL / 0: skipped) */
+} sgdnet_setup_probe;
+
+/* x as sgdnet_fit_sparse takes it; ymap n x cols column-major (what lambda_max multiplies by); y is y_rows x n as the
+ * solvers read it (it rides in the records when y_rows == 1); rec_align: a positive multiple of 64 (a fit uses 128). */
+int sgdnet_setup_probe_sparse(const sgdnet_csc* x, int standardize, const double* ymap, int cols, const double* y,
+                              int y_rows, int rec_align, int device, sgdnet_setup_probe* out);
+/* x n x p column-major as sgdnet_fit_dense takes it (any size: the probe does not apply the 4e6-element threshold). */
+int sgdnet_setup_probe_dense(const double* x, int64_t n, int64_t p, int standardize, const double* ymap, int cols,
+                             int64_t sample_stride, int64_t sample_m, int device, sgdnet_setup_probe* out);
+
 #ifdef __cplusplus
 }
 #endif

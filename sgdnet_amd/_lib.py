@@ -34,6 +34,7 @@ EXPORTS = [
     "sgdnet_solver_peer_info_bytes", "sgdnet_solver_peer_info", "sgdnet_solver_link_ipc",
     "sgdnet_solver_rng_layout", "sgdnet_solver_rng_open", "sgdnet_solver_rng_next", "sgdnet_solver_rng_done", "sgdnet_solver_rng_close",
     "sgdnet_gradient_sparse", "sgdnet_gradient_dense", "sgdnet_covariance_max_features",
+    "sgdnet_setup_probe_sparse", "sgdnet_setup_probe_dense",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -88,6 +89,17 @@ class Problem(C.Structure):
                 ("values", C.POINTER(C.c_double)), ("x_dense", C.POINTER(C.c_double)),
                 ("x_center_scaled", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)),
                 ("y_rows", C.c_int), ("device", C.c_int)]
+
+
+class SetupProbe(C.Structure):
+    """sgdnet_setup_probe (diagnostics): caller-allocated host buffers and the scalars the setup passes leave."""
+    _fields_ = [("center", C.POINTER(C.c_double)), ("scale", C.POINTER(C.c_double)), ("xty", C.POINTER(C.c_double)),
+                ("max_mean_sq", C.c_double), ("max_sqnorm", C.c_double),
+                ("sptr", C.POINTER(C.c_int64)), ("sidx", C.POINTER(C.c_int32)), ("sval", C.POINTER(C.c_double)),
+                ("rec", C.c_void_p), ("rec_bytes_cap", C.c_int64), ("ovf", C.c_void_p), ("ovf_bytes_cap", C.c_int64),
+                ("rec_stride", C.c_int), ("rec_cap", C.c_int), ("rec_val_off", C.c_int), ("n_ovf", C.c_int64),
+                ("l_f", C.c_double),
+                ("xt", C.POINTER(C.c_double)), ("sample", C.POINTER(C.c_double))]
 
 
 class SgdnetError(RuntimeError):
@@ -195,6 +207,10 @@ def load():
                   C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgdnet_gradient_sparse.argtypes = [C.POINTER(Csc)] + _grad_tail
     L.sgdnet_gradient_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _grad_tail
+    L.sgdnet_setup_probe_sparse.argtypes = [C.POINTER(Csc), C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                            C.c_int, C.c_int, C.c_int, C.POINTER(SetupProbe)]
+    L.sgdnet_setup_probe_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                           C.c_int64, C.c_int64, C.c_int, C.POINTER(SetupProbe)]
     _lib = L
     return L
 

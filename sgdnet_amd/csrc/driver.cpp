@@ -1211,6 +1211,32 @@ int with_device_setup(const sgdnet_control* ctl, Features& X, F body) {
   return rc;
 }
 
+// what the device passes index with: checked before anything is uploaded
+int validate_colptr(const sgdnet_csc* x) {
+  if (x->colptr[0] != 0) {
+    set_error("colptr[0] must be 0");
+    return SGDNET_EINVAL;
+  }
+  for (int64_t j = 0; j < x->n_cols; ++j)
+    if (x->colptr[j + 1] < x->colptr[j]) {
+      set_error("colptr is not non-decreasing at column %lld", (long long)j);
+      return SGDNET_EINVAL;
+    }
+  return SGDNET_OK;
+}
+
+int validate_rowidx(const sgdnet_csc* x) {
+  const int64_t nnz = x->colptr[x->n_cols];
+  for (int64_t q = 0; q < nnz; ++q) {
+    const int32_t r = x->rowidx[q];
+    if (r < 0 || r >= x->n_rows) {
+      set_error("row index %d out of range at position %lld", r, (long long)q);
+      return SGDNET_EINVAL;
+    }
+  }
+  return SGDNET_OK;
+}
+
 int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdnet_control* ctl, sgdnet_result* out,
                     bool* batched_gave_up) {
   int rc = validate(ctl, out, y_cols);
@@ -1227,24 +1253,7 @@ int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdn
   X.rowidx = x->rowidx;
   X.raw_values = x->values;
   const int64_t n = X.n, p = X.p, nnz = x->colptr[p];
-  if (x->colptr[0] != 0) {
-    set_error("colptr[0] must be 0");
-    return SGDNET_EINVAL;
-  }
-  for (int64_t j = 0; j < p; ++j)
-    if (x->colptr[j + 1] < x->colptr[j]) {
-      set_error("colptr is not non-decreasing at column %lld", (long long)j);
-      return SGDNET_EINVAL;
-    }
-  rc = validate_response(ctl, y, n);
-  if (rc) return rc;
-  for (int64_t q = 0; q < nnz; ++q) {
-    const int32_t r = x->rowidx[q];
-    if (r < 0 || r >= n) {
-      set_error("row index %d out of range at position %lld", r, (long long)q);
-      return SGDNET_EINVAL;
-    }
-  }
+  if ((rc = validate_colptr(x)) || (rc = validate_response(ctl, y, n)) || (rc = validate_rowidx(x))) return rc;
   if (!option(kOptHostSetup) && !(ctl->n_gpus > 1)) {   // (a fit sharded over several GPUs cuts the host copy into the ranks' ranges)
     // default: the per-fit O(nnz) passes run on the device (setup_device.hip)
     return with_device_setup(ctl, X, [&](DeviceSetup& dev, hipStream_t st) {
@@ -1359,6 +1368,77 @@ int sgdnet_fit_sparse(const sgdnet_csc* x, const double* y, int y_cols, const sg
 int sgdnet_fit_dense(const double* x, int64_t n, int64_t p, const double* y, int y_cols,
                      const sgdnet_control* ctl, sgdnet_result* out) {
   return with_exact_fallback(ctl, [&](const sgdnet_control* c, bool* gave_up) { return fit_dense_impl(x, n, p, y, y_cols, c, out, gave_up); });
+}
+
+// ---- diagnostics (include/sgdnet_hip.h): the setup passes of a fit, run as a fit runs them, everything copied back ----
+
+int sgdnet_setup_probe_sparse(const sgdnet_csc* x, int standardize, const double* ymap, int cols, const double* y, int y_rows,
+                              int rec_align, int device, sgdnet_setup_probe* out) {
+  if (!x || !out || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values || !ymap || cols < 1 ||
+      y_rows < 1 || !y || rec_align < 64 || rec_align % 64 || !out->center || !out->scale || !out->xty || !out->sptr ||
+      !out->sidx || !out->sval || !out->rec || !out->ovf) {
+    set_error("sgdnet_setup_probe_sparse: invalid argument");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  sgdnet_control ctl{};
+  ctl.device = device;
+  Features X;
+  return with_device_setup(&ctl, X, [&](DeviceSetup& dev, hipStream_t st) {
+    std::vector<double> center, scale;
+    int r;
+    if ((r = device_setup_begin(dev, x, standardize ? 1 : 0, st, center, scale, &out->max_mean_sq)) ||
+        (r = device_xt_times(dev, ymap, cols, out->xty, st)) ||
+        (r = device_setup_finish(dev, y, y_rows, standardize ? 1 : 0, rec_align, st, &out->max_sqnorm)) ||
+        (r = device_gram_lmax(dev, standardize ? 1 : 0, st, &out->l_f)))
+      return r;
+    std::copy(center.begin(), center.end(), out->center);
+    std::copy(scale.begin(), scale.end(), out->scale);
+    out->rec_stride = dev.rec_stride;
+    out->rec_cap = dev.rec_cap;
+    out->rec_val_off = dev.rec_val_off;
+    out->n_ovf = dev.n_ovf;
+    const size_t rec_bytes = (size_t)dev.n * (size_t)dev.rec_stride, ovf_bytes = (size_t)dev.n_ovf * 256;
+    if ((size_t)out->rec_bytes_cap < rec_bytes || (size_t)out->ovf_bytes_cap < ovf_bytes) {
+      set_error("sgdnet_setup_probe_sparse: %zu record bytes and %zu overflow bytes, the capacities are %lld and %lld", rec_bytes,
+                ovf_bytes, (long long)out->rec_bytes_cap, (long long)out->ovf_bytes_cap);
+      return SGDNET_EINVAL;
+    }
+    SGD_HIP_TRY(hipMemcpy(out->sptr, dev.sptr, sizeof(int64_t) * ((size_t)dev.n + 1), hipMemcpyDeviceToHost));
+    if (dev.nnz) {
+      SGD_HIP_TRY(hipMemcpy(out->sidx, dev.sidx, sizeof(int32_t) * (size_t)dev.nnz, hipMemcpyDeviceToHost));
+      SGD_HIP_TRY(hipMemcpy(out->sval, dev.sval, sizeof(double) * (size_t)dev.nnz, hipMemcpyDeviceToHost));
+    }
+    SGD_HIP_TRY(hipMemcpy(out->rec, dev.rec, rec_bytes, hipMemcpyDeviceToHost));
+    if (ovf_bytes) SGD_HIP_TRY(hipMemcpy(out->ovf, dev.ovf, ovf_bytes, hipMemcpyDeviceToHost));
+    return (int)SGDNET_OK;
+  });
+}
+
+int sgdnet_setup_probe_dense(const double* x, int64_t n, int64_t p, int standardize, const double* ymap, int cols,
+                             int64_t sample_stride, int64_t sample_m, int device, sgdnet_setup_probe* out) {
+  if (!x || !out || n <= 0 || p <= 0 || !ymap || cols < 1 || !out->center || !out->scale || !out->xty || !out->xt ||
+      sample_m < 0 || (sample_m > 0 && (!out->sample || sample_stride < 1 || (sample_m - 1) * sample_stride >= n))) {
+    set_error("sgdnet_setup_probe_dense: invalid argument");
+    return SGDNET_EINVAL;
+  }
+  sgdnet_control ctl{};
+  ctl.device = device;
+  Features X;
+  return with_device_setup(&ctl, X, [&](DeviceSetup& dev, hipStream_t st) {
+    std::vector<double> center, scale;
+    int r;
+    if ((r = dense_setup_begin(dev, x, n, p, standardize ? 1 : 0, st, center, scale, &out->max_mean_sq)) ||
+        (r = dense_xt_times(dev, ymap, cols, out->xty, st)) ||
+        (sample_m > 0 && (r = dense_sample_rows(dev, sample_stride, sample_m, out->sample, st))) ||
+        (r = dense_setup_finish(dev, st, &out->max_sqnorm)))
+      return r;
+    std::copy(center.begin(), center.end(), out->center);
+    std::copy(scale.begin(), scale.end(), out->scale);
+    SGD_HIP_TRY(hipMemcpy(out->xt, dev.xd_t, sizeof(double) * (size_t)n * (size_t)p, hipMemcpyDeviceToHost));
+    return (int)SGDNET_OK;
+  });
 }
 
 }  // extern "C"

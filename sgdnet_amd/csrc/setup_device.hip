@@ -138,6 +138,10 @@ __global__ __launch_bounds__(kTB) void row_norm_kernel(const int64_t* sptr, cons
     atomicAdd(hist + (z < 64 ? z : 64), 1ull);
   }
   best = wave_max(best);
+  for (int off = 32; off > 0; off >>= 1) {   // the wave's longest row, not lane 0's
+    const unsigned long long o = __shfl_xor(zm, off, 64);
+    zm = o > zm ? o : zm;
+  }
   if ((threadIdx.x & 63) == 0) {
     atomicMax(max_bits, (unsigned long long)__double_as_longlong(best));
     atomicMax(zmax, zm);
@@ -432,6 +436,7 @@ int device_setup_finish(DeviceSetup& S, const double* y_host, int y_rows, int st
   long long n_ovf = 0;
   SGD_HIP_TRY(hipMemcpyAsync(&n_ovf, ooff + n, sizeof(long long), hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
+  S.n_ovf = n_ovf;
   if ((rc = dmalloc(&S.rec, (size_t)n * stride)) || (rc = dmalloc(&S.ovf, (size_t)(n_ovf ? n_ovf : 1) * kOvfStride)))
     return rc;
   double* y_dev = nullptr;

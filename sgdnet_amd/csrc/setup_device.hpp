@@ -21,6 +21,7 @@ struct DeviceSetup {
   char* rec = nullptr;
   char* ovf = nullptr;
   int rec_stride = 0, rec_cap = 0, rec_val_off = 0;
+  int64_t n_ovf = 0;            // 256-B overflow records behind ovf (rows longer than rec_cap)
   float avg_nnz = 0.f;
   // dense x (large problems only, dense_setup_*): column-major copy (freed after the transpose) and
   // the sample-major p x n matrix the solver adopts

@@ -1,0 +1,70 @@
+"""Diagnostics of the device setup passes (include/sgdnet_hip.h "Diagnostics", sgdnet_amd/csrc/setup_device.hip):
+what a fit's once-per-fit passes leave on the device, copied back pass by pass.  Used by the tests; a fit never
+calls these."""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, dptr
+
+OVF_STRIDE = 256      # bytes of one overflow record (batched_device.hpp)
+MAX_REC_STRIDE = 6400  # a cap of 512 entries at rec_align <= 256
+
+
+def setup_probe_sparse(x, ymap, y, standardize=True, rec_align=128, device=0):
+    """x: scipy.sparse matrix, n x p (converted to CSC as sgdnet() does); ymap: (n, cols); y: (y_rows, n) as the solvers
+    read it.  Returns center, scale, max_mean_sq, xty (p, cols), sptr, sidx, sval, max_sqnorm, rec_stride, rec_cap,
+    rec_val_off, n_ovf, rec (uint8, n * rec_stride), ovf (uint8, 256 * n_ovf), l_f."""
+    x = x.tocsc()
+    n, p = x.shape
+    colptr = np.ascontiguousarray(x.indptr, dtype=np.int32)
+    rowidx = np.ascontiguousarray(x.indices, dtype=np.int32)
+    vals = np.ascontiguousarray(x.data, dtype=np.float64)
+    nnz = int(colptr[-1])
+    ymap = np.asfortranarray(np.asarray(ymap, dtype=np.float64).reshape(n, -1))
+    y = np.asfortranarray(np.asarray(y, dtype=np.float64).reshape(-1, n))
+    cols, y_rows = ymap.shape[1], y.shape[0]
+    csc = _lib.Csc()
+    csc.n_rows, csc.n_cols = n, p
+    csc.colptr = colptr.ctypes.data_as(C.POINTER(C.c_int32))
+    csc.rowidx = rowidx.ctypes.data_as(C.POINTER(C.c_int32))
+    csc.values = dptr(vals)
+    o = SimpleNamespace(center=np.empty(p), scale=np.empty(p), xty=np.empty((p, cols), order="F"),
+                        sptr=np.empty(n + 1, dtype=np.int64), sidx=np.empty(max(nnz, 1), dtype=np.int32),
+                        sval=np.empty(max(nnz, 1)), rec=np.empty(n * MAX_REC_STRIDE, dtype=np.uint8),
+                        ovf=np.empty((nnz // 20 + n) * OVF_STRIDE, dtype=np.uint8))
+    pr = _lib.SetupProbe()
+    pr.center, pr.scale, pr.xty, pr.sval = dptr(o.center), dptr(o.scale), dptr(o.xty), dptr(o.sval)
+    pr.sptr = o.sptr.ctypes.data_as(C.POINTER(C.c_int64))
+    pr.sidx = o.sidx.ctypes.data_as(C.POINTER(C.c_int32))
+    pr.rec, pr.rec_bytes_cap = o.rec.ctypes.data, o.rec.size
+    pr.ovf, pr.ovf_bytes_cap = o.ovf.ctypes.data, o.ovf.size
+    check(_lib.load().sgdnet_setup_probe_sparse(C.byref(csc), int(bool(standardize)), dptr(ymap), cols, dptr(y), y_rows,
+                                                int(rec_align), int(device), C.byref(pr)))
+    for name in ("max_mean_sq", "max_sqnorm", "rec_stride", "rec_cap", "rec_val_off", "n_ovf", "l_f"):
+        setattr(o, name, getattr(pr, name))
+    o.sidx, o.sval = o.sidx[:nnz], o.sval[:nnz]
+    o.rec = o.rec[:n * o.rec_stride].copy()
+    o.ovf = o.ovf[:o.n_ovf * OVF_STRIDE].copy()
+    return o
+
+
+def setup_probe_dense(x, ymap, standardize=True, sample_stride=1, sample_m=0, device=0):
+    """x: (n, p) array; ymap: (n, cols).  Returns center, scale, max_mean_sq, xty (p, cols), xt (n, p): the
+    standardised matrix as the device holds it sample-major, max_sqnorm, sample (sample_m, p): dense_sample_rows."""
+    x = np.asfortranarray(np.asarray(x, dtype=np.float64))
+    n, p = x.shape
+    ymap = np.asfortranarray(np.asarray(ymap, dtype=np.float64).reshape(n, -1))
+    cols = ymap.shape[1]
+    o = SimpleNamespace(center=np.empty(p), scale=np.empty(p), xty=np.empty((p, cols), order="F"),
+                        xt=np.empty((n, p)), sample=np.empty((sample_m, p), order="F"))
+    pr = _lib.SetupProbe()
+    pr.center, pr.scale, pr.xty, pr.xt = dptr(o.center), dptr(o.scale), dptr(o.xty), dptr(o.xt)
+    if sample_m:
+        pr.sample = dptr(o.sample)
+    check(_lib.load().sgdnet_setup_probe_dense(dptr(x), n, p, int(bool(standardize)), dptr(ymap), cols, int(sample_stride),
+                                               int(sample_m), int(device), C.byref(pr)))
+    o.max_mean_sq, o.max_sqnorm = pr.max_mean_sq, pr.max_sqnorm
+    return o

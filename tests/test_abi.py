@@ -75,6 +75,37 @@ def test_auto_batch_rule():
     assert sa.auto_batch(50.0, 1e-9) == 131072
     assert sa.auto_batch(1.0, 1.0) == 64
     assert sa.auto_batch(0.0, 0.0) == 64
+    # L_F == 0 (all-zero x: the power iteration of the setup passes stops at 0) gives a finite window, not a division
+    assert sa.auto_batch(50.0, 0.0) == 64
+
+
+def test_window_rule_with_a_zero_l_f_stays_finite(tmp_path):
+    """fit_plan.hpp window_rule is the driver's own form of the rule (floor 8 instead of 64) and a pure function: with
+    L_F == 0, what device_gram_lmax returns for an all-zero x, or a zero row norm, the raw window is 64 draws -- never
+    a division by zero, never the 131072 cap."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "a host C++ compiler builds the rest of the tests' helpers too"
+    src = tmp_path / "window_rule.cpp"
+    src.write_text('''#include "fit_plan.hpp"
+#include <cstdio>
+int main() {
+  const double cases[][2] = {{50.0, 0.0}, {0.0, 0.0}, {0.0, 1.0}, {50.0, 1.0}, {50.0, 1e-9}, {1.0, 1.0}};
+  for (auto& c : cases) {
+    double raw = -1.0;
+    const long long w = sgdnet::window_rule(c[0], c[1], &raw);
+    printf("%lld %.17g\\n", w, raw);
+  }
+  return 0;
+}
+''')
+    exe = tmp_path / "window_rule"
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sgdnet_amd", "csrc"),
+                           str(src), "-o", str(exe)])
+    out = subprocess.check_output([str(exe)], text=True).split("\n")
+    got = [(int(line.split()[0]), float(line.split()[1])) for line in out if line]
+    assert got == [(64, 64.0), (64, 64.0), (64, 64.0), (100, 100.0), (131072, 1e11), (8, 2.0)]
 
 
 def test_shard_window_saves_a_short_last_round():

@@ -293,6 +293,54 @@ def test_large_dense_x_is_prepared_on_the_device(sa, monkeypatch, family, mode):
     assert np.allclose(dev.dev_ratio, host.dev_ratio, atol=1e-7)
 
 
+@pytest.mark.parametrize("standardize", [True, False])
+@pytest.mark.parametrize("family", ["binomial", "gaussian"])
+def test_sparse_x_is_prepared_on_the_device(sa, family, standardize):
+    """Sparse x is standardised, multiplied for lambda_max, transposed, normed and packed on the device
+    (device_setup_*) by default; the host loops (option host_setup = 1) are a second implementation
+    of the same passes and must give the same fit.  Exact mode, same seed; an empty column and an empty row."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(9)
+    n, p = 300, 40
+    x = rng.standard_normal((n, p)) * np.linspace(0.5, 3.0, p) + np.linspace(-1, 1, p)
+    x *= rng.random((n, p)) < 0.2
+    x[:, 7] = 0.0
+    x[11, :] = 0.0
+    b = rng.standard_normal(p) * (rng.random(p) < 0.3)
+    lp = x @ b
+    y = (rng.random(n) < 1 / (1 + np.exp(-lp))).astype(int) if family == "binomial" else lp + rng.standard_normal(n)
+    xs = sp.csc_matrix(x)
+    kw = dict(family=family, alpha=0.5, nlambda=4, lambda_min_ratio=0.2, thresh=1e-7, maxit=400, seed=2, mode="exact",
+              standardize=standardize)
+    dev = sa.sgdnet(xs, y, **kw)
+    with sa.option("host_setup", 1):
+        host = sa.sgdnet(xs, y, **kw)
+    assert np.allclose(dev.lambda_, host.lambda_, rtol=1e-11) and dev.nulldev == pytest.approx(host.nulldev, rel=1e-12)
+    assert np.array_equal(dev.return_codes, host.return_codes) and dev.npasses == host.npasses
+    assert np.abs(dev.beta - host.beta).max() <= 1e-6 * np.abs(host.beta).max()
+    assert np.allclose(dev.dev_ratio, host.dev_ratio, atol=1e-7)
+
+
+@pytest.mark.parametrize("standardize", [True, False])
+@pytest.mark.parametrize("family", ["gaussian", "binomial", "multinomial", "mgaussian"])
+def test_lambda_max_of_the_device_path(sa, family, standardize):
+    """The first lambda of an automatic path is lambda_max / max(alpha, 0.001), and lambda_max comes from the device's
+    x'y (device_xt_times) with the device's column sds: against the numpy definition, inside the x'y rounding bound
+    divided by n (setup_reference.lambda_max_bound has the derivation)."""
+    import kkt_reference as KR
+    import setup_reference as R
+    x, y = KR.problem(family, seed=21, sparse=True)
+    alpha = 0.5
+    fit = sa.sgdnet(x, y, family=family, alpha=alpha, nlambda=3, lambda_min_ratio=0.5, thresh=1e-3, maxit=20, seed=1,
+                    standardize=standardize)
+    got = fit.lambda_[0] * max(alpha, 0.001)
+    want = KR.lambda_max(family, x, y, standardize)
+    bound = R.lambda_max_bound(x, y, family, standardize, fit.lambda_[0])
+    print(f"{family} standardize={standardize}: lambda_max {got:.17g} vs {want:.17g}, |diff| {abs(got - want):.3e}, bound {bound:.3e}")
+    assert bound < 1e-10 * want                  # a rounding bound, not a tolerance
+    assert abs(got - want) <= bound
+
+
 def test_multinomial_fit_on_virtual_shards_reaches_the_unsharded_optimum(sa):
     """Round 3: the fit driver runs 2..4-class fits of sparse x on virtual shards too (250 000 x 300, K = 3: four
     replicas).  Same path, same optimum as the unsharded batched fit at a tight thresh."""
