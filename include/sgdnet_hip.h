@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_* (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -544,6 +544,45 @@ int sgdnet_setup_probe_sparse(const sgdnet_csc* x, int standardize, const double
 /* x n x p column-major as sgdnet_fit_dense takes it (any size: the probe does not apply the 4e6-element threshold). */
 int sgdnet_setup_probe_dense(const double* x, int64_t n, int64_t p, int standardize, const double* ymap, int cols,
                              int64_t sample_stride, int64_t sample_m, int device, sgdnet_setup_probe* out);
+
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in covariance mode (additions only; the ABI version      */
+/* stays): every fold fit of every elastic-net mix in ONE call.  Rows carry a */
+/* group id fold[i] in [0, n_groups); one pass over x leaves the moments of   */
+/* every group on the device, the moments of a training set are pooled from   */
+/* them, and all n_alpha * n_groups paths run side by side, one workgroup     */
+/* each (sgdnet_amd/csrc/covariance.hip).  Job (alpha a, group g) is by        */
+/* definition sgdnet_fit_*(x[T], y[T]) in SGDNET_MODE_COVARIANCE with          */
+/* elasticnet_mix = alphas[a] and the user lambdas lambdas[a][.]; T = the rows */
+/* of group g (train_on_rest = 0: the reference's convention,                  */
+/* R/cv_sgdnet.R:182) or of every other group (train_on_rest = 1).             */
+/* control supplies intercept, standardize, max_iter, tol, n_lambda and        */
+/* device; family must be gaussian; elasticnet_mix and lambda are ignored in   */
+/* favour of the arrays.  No sample is drawn.                                  */
+/* SGDNET_EUNSUPPORTED ("mode = covariance needs ..."): more than              */
+/* sgdnet_covariance_max_features() features, n_gpus > 1, debug, more than     */
+/* 65 535 groups (dense x: row chunks), or group moments -- n_groups x         */
+/* (n_features + 2)^2 doubles -- above 64 MiB (which still holds a             */
+/* leave-one-out CV of 209 rows at 198 features, of 524 288 rows at 2).        */
+/* SGDNET_EINVAL: a fold id outside [0, n_groups), an empty group, a negative  */
+/* lambda, a mix outside [0, 1], train_on_rest with one group.                 */
+/* ------------------------------------------------------------------------ */
+typedef struct sgdnet_cv_cov_result {   /* caller-allocated; job = alpha_index * n_groups + group, L = control.n_lambda */
+  double* a0;            /* jobs x L                                                         */
+  double* beta;          /* jobs x L x n_features: per job the layout of sgdnet_result.beta  */
+  double* dev_ratio;     /* jobs x L                                                         */
+  double* return_codes;  /* jobs x L, 0 converged / 1 max_iter sweeps without meeting tol    */
+  double* nulldev;       /* jobs: the null deviance of y[T]                                  */
+  double* npasses;       /* jobs: coordinate sweeps summed over the path                     */
+} sgdnet_cv_cov_result;
+
+/* x n x p column-major, y and fold n; lambdas n_alpha x control.n_lambda, a row per alpha */
+int sgdnet_cv_covariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                               int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                               const double* lambdas, sgdnet_cv_cov_result* out);
+int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                sgdnet_cv_cov_result* out);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,7 @@ EXPORTS = [
     "sgdnet_solver_rng_layout", "sgdnet_solver_rng_open", "sgdnet_solver_rng_next", "sgdnet_solver_rng_done", "sgdnet_solver_rng_close",
     "sgdnet_gradient_sparse", "sgdnet_gradient_dense", "sgdnet_covariance_max_features",
     "sgdnet_setup_probe_sparse", "sgdnet_setup_probe_dense",
+    "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -100,6 +101,12 @@ class SetupProbe(C.Structure):
                 ("rec_stride", C.c_int), ("rec_cap", C.c_int), ("rec_val_off", C.c_int), ("n_ovf", C.c_int64),
                 ("l_f", C.c_double),
                 ("xt", C.POINTER(C.c_double)), ("sample", C.POINTER(C.c_double))]
+
+
+class CvCovResult(C.Structure):
+    """sgdnet_cv_cov_result: caller-allocated outputs of sgdnet_cv_covariance_*, job-major (job = alpha * n_groups + group)."""
+    _fields_ = [("a0", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)), ("dev_ratio", C.POINTER(C.c_double)),
+                ("return_codes", C.POINTER(C.c_double)), ("nulldev", C.POINTER(C.c_double)), ("npasses", C.POINTER(C.c_double))]
 
 
 class SgdnetError(RuntimeError):
@@ -211,6 +218,10 @@ def load():
                                             C.c_int, C.c_int, C.c_int, C.POINTER(SetupProbe)]
     L.sgdnet_setup_probe_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int,
                                            C.c_int64, C.c_int64, C.c_int, C.POINTER(SetupProbe)]
+    _cv_tail = [C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Control), C.c_int, C.POINTER(C.c_double),
+                C.POINTER(C.c_double), C.POINTER(CvCovResult)]
+    L.sgdnet_cv_covariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
+    L.sgdnet_cv_covariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     _lib = L
     return L
 

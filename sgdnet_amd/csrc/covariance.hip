@@ -24,7 +24,18 @@
 //              beta = mix lambda / sd(y), none for the ridge functor.  A sweep ends with the reference's
 //              ConvergenceCheck (max|dw| / max|w| <= tol; all zero counts as converged: solver.cpp read_convergence).
 //
-// No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz): the same input gives the
+//   folds      covariance_cv_run: every (training set, mix) path of a cross-validation in one launch.  Rows carry a
+//              group id; the same kernels leave one moment matrix per group of the augmented rows [x - a | y - a_y | 1]
+//              about ONE centre a (the whole-data means), so that the last column holds the group's sums of deviations
+//              and its corner n_g.  dense x: the rows are sorted by group (a stable counting sort on the host) and no
+//              row chunk straddles a group; sparse x: the pair kernel's third grid dimension is the group and stored
+//              entries of other groups' rows are skipped.  cov_assemble_kernel pools the groups of a training set T
+//              (one group, or the total -- summed in group order -- minus one) and re-centres to T's own means t,
+//              d = t - a:   M^T_jk = C^T_jk - d_j s^T_k - d_k s^T_j + n_T d_j d_k   (s^T / n_T is of the
+//              order of the columns' sd, not of their mean, so nothing cancels), then writes what cov_path_kernel reads;
+//              the path kernel takes its job (mix, T) from blockIdx.x: one wavefront, one CU's LDS, per job.
+//
+// No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
 #include <algorithm>
 #include <numeric>
@@ -52,7 +63,8 @@ __device__ double block_sum(double v, double* sh) {
   return sh[0];
 }
 
-// blockIdx.x = column j < p: mu[j] = mean of the column (sparse: over all n samples); column p: mu[p] = sum of y
+// blockIdx.x = column j < p: mu[j] = mean of the column (sparse: over all n samples); column p: mu[p] = sum of y and
+// mu[p + 1] = mean of y (the centre of the response of the group moments)
 template <bool kSparse>
 __global__ __launch_bounds__(kBlock) void cov_sum_kernel(const double* __restrict__ x, const int32_t* __restrict__ colptr,
                                                           const double* __restrict__ y, int64_t n, int p, int centre,
@@ -71,16 +83,22 @@ __global__ __launch_bounds__(kBlock) void cov_sum_kernel(const double* __restric
     for (int64_t i = threadIdx.x; i < n; i += kBlock) s += col[i];
   }
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) mu[j] = j == p ? s : s / (double)n;
+  if (threadIdx.x == 0) {
+    mu[j] = j == p ? s : s / (double)n;
+    if (j == p) mu[p + 1] = s / (double)n;
+  }
 }
 
-// blockIdx.x: the pair (tj <= tk) of column tiles of the augmented matrix [x - mu | y], blockIdx.y: the chunk of rows
+// blockIdx.x: the pair (tj <= tk) of column tiles of the augmented matrix, blockIdx.y: the chunk of rows.
+// One fit: ncols = p + 1, the matrix is [x - mu | y] (y as the driver preprocessed it), chunk c is rows [c rows_per_chunk, ...).
+// Group moments: ncols = p + 2, [x - mu | y - mean(y) | 1], chunk c is the sorted rows perm[chunk_begin[c] .. chunk_begin[c + 1]).
 __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __restrict__ x, const double* __restrict__ y,
-                                                                 const double* __restrict__ mu, int64_t n, int p,
-                                                                 int64_t rows_per_chunk, double* __restrict__ part) {
+                                                                 const double* __restrict__ mu, int64_t n, int p, int ncols,
+                                                                 int64_t rows_per_chunk, const int64_t* __restrict__ perm,
+                                                                 const int64_t* __restrict__ chunk_begin, double* __restrict__ part) {
   __shared__ double A[kTileCols][kTileRows + 1], B[kTileCols][kTileRows + 1];
   const int tid = threadIdx.x;
-  const int T = (p + 1 + kTileCols - 1) / kTileCols;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
   int pair = blockIdx.x, tj = 0;
   while (pair >= T - tj) {
     pair -= T - tj;
@@ -88,10 +106,22 @@ __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __
   }
   const int tk = tj + pair;
   const int ta = tid & (kTileCols - 1), tb = tid / kTileCols;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk, r1 = r0 + rows_per_chunk < n ? r0 + rows_per_chunk : n;
+  int64_t r0, r1;
+  if (chunk_begin) {
+    r0 = chunk_begin[blockIdx.y];
+    r1 = chunk_begin[blockIdx.y + 1];
+  } else {
+    r0 = (int64_t)blockIdx.y * rows_per_chunk;
+    r1 = r0 + rows_per_chunk < n ? r0 + rows_per_chunk : n;
+  }
+  const bool grouped = perm != nullptr;
+  const double y_centre = grouped ? mu[p + 1] : 0.0;
   auto dev = [&](int a, int64_t i) -> double {
-    if (i >= r1 || a > p) return 0.0;
-    return a < p ? x[i + (int64_t)a * n] - mu[a] : y[i];
+    if (i >= r1 || a >= ncols) return 0.0;
+    if (a > p) return 1.0;
+    const int64_t r = grouped ? perm[i] : i;
+    if (a < p) return x[r + (int64_t)a * n] - mu[a];
+    return grouped ? y[r] - y_centre : y[r];
   };
   double acc = 0.0;
   for (int64_t base = r0; base < r1; base += kTileRows) {
@@ -107,11 +137,12 @@ __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __
   part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kBlock + tid] = acc;
 }
 
-// the chunks' partial tiles added in chunk order; M is the symmetric (p + 1) x (p + 1) matrix of [x - mu | y]
-__global__ __launch_bounds__(kBlock) void cov_reduce_kernel(const double* __restrict__ part, int chunks, int p,
-                                                             double* __restrict__ M) {
-  const int tid = threadIdx.x, P1 = p + 1;
-  const int T = (P1 + kTileCols - 1) / kTileCols;
+// the chunks' partial tiles added in chunk order; M is the symmetric ncols x ncols matrix of the augmented rows.
+// blockIdx.y = group: its chunks are [group_chunk[g], group_chunk[g + 1]) and its matrix is M[g] (one fit: all chunks, M[0])
+__global__ __launch_bounds__(kBlock) void cov_reduce_kernel(const double* __restrict__ part, int chunks,
+                                                             const int32_t* __restrict__ group_chunk, int ncols, double* __restrict__ M) {
+  const int tid = threadIdx.x;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
   int pair = blockIdx.x, tj = 0;
   while (pair >= T - tj) {
     pair -= T - tj;
@@ -119,11 +150,13 @@ __global__ __launch_bounds__(kBlock) void cov_reduce_kernel(const double* __rest
   }
   const int tk = tj + pair;
   const int a = tj * kTileCols + (tid & (kTileCols - 1)), b = tk * kTileCols + tid / kTileCols;
-  if (a >= P1 || b >= P1) return;
+  if (a >= ncols || b >= ncols) return;
+  const int c0 = group_chunk ? group_chunk[blockIdx.y] : 0, c1 = group_chunk ? group_chunk[blockIdx.y + 1] : chunks;
+  M += (size_t)blockIdx.y * (size_t)ncols * (size_t)ncols;
   double s = 0.0;
-  for (int c = 0; c < chunks; ++c) s += part[((size_t)c * gridDim.x + blockIdx.x) * kBlock + tid];
-  M[(size_t)a * P1 + b] = s;
-  if (tj != tk) M[(size_t)b * P1 + a] = s;
+  for (int c = c0; c < c1; ++c) s += part[((size_t)c * gridDim.x + blockIdx.x) * kBlock + tid];
+  M[(size_t)a * ncols + b] = s;
+  if (tj != tk) M[(size_t)b * ncols + a] = s;
 }
 
 // first position in rowidx[lo, hi) whose row is >= r
@@ -136,38 +169,94 @@ __device__ int lower_bound_row(const int32_t* __restrict__ rowidx, int lo, int h
   return lo;
 }
 
-// blockIdx.x = column j < p, blockIdx.y = column k in [j, p]; k == p is the response
+// Group moments of the response (sparse x; the dense tile kernel has them as columns p and p + 1): blockIdx.x = group g,
+// M[g] gets sum (y - a_y)^2 at (p, p), sum (y - a_y) at (p, p + 1) and n_g at (p + 1, p + 1), each over the rows of g in row order
+__global__ __launch_bounds__(kBlock) void cov_group_response_kernel(const double* __restrict__ y, const int32_t* __restrict__ fold,
+                                                                     const double* __restrict__ mu, int64_t n, int p,
+                                                                     double* __restrict__ M) {
+  __shared__ double sh[kBlock];
+  const int g = blockIdx.x, Pa = p + 2;
+  const double ay = mu[p + 1];
+  double s = 0.0, q = 0.0, c = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += kBlock)
+    if (fold[i] == g) {
+      const double d = y[i] - ay;
+      s += d;
+      q += d * d;
+      c += 1.0;
+    }
+  s = block_sum(s, sh);
+  q = block_sum(q, sh);
+  c = block_sum(c, sh);
+  if (threadIdx.x == 0) {
+    double* Mg = M + (size_t)g * Pa * Pa;
+    Mg[(size_t)p * Pa + p] = q;
+    Mg[(size_t)p * Pa + p + 1] = s;
+    Mg[(size_t)(p + 1) * Pa + p] = s;
+    Mg[(size_t)(p + 1) * Pa + p + 1] = c;
+  }
+}
+
+// blockIdx.x = column j < p, blockIdx.y = column k in [j, p]; k == p is the response.
+// kGrouped: blockIdx.z = group g, only the stored entries whose row is in g count, n becomes n_g, the response is
+// y - a_y, k runs to p + 1 (the column of ones: the group's sum of deviations) and M[g] is (p + 2) x (p + 2) with the
+// response's own entries already in place (cov_group_response_kernel).
+template <bool kGrouped>
 __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* __restrict__ colptr, const int32_t* __restrict__ rowidx,
                                                                   const double* __restrict__ val, const double* __restrict__ y,
                                                                   const double* __restrict__ mu, int64_t n, int p,
-                                                                  double* __restrict__ M) {
+                                                                  const int32_t* __restrict__ fold, double* __restrict__ M) {
   __shared__ double sh[kBlock];
-  const int j = blockIdx.x, k = blockIdx.y, P1 = p + 1, tid = threadIdx.x;
+  const int j = blockIdx.x, k = blockIdx.y, nc = kGrouped ? p + 2 : p + 1, tid = threadIdx.x;
+  const int g = kGrouped ? (int)blockIdx.z : 0;
   if (k < j) return;
+  if (kGrouped) M += (size_t)g * nc * nc;
+  auto mine = [&](int32_t r) -> bool { return !kGrouped || fold[r] == g; };
   const int q0 = colptr[j], q1 = colptr[j + 1];
   const double mj = mu[j];
   if (k == p) {
+    const double ay = kGrouped ? mu[p + 1] : 0.0;
     double a = 0.0, ys = 0.0;
     for (int q = q0 + tid; q < q1; q += kBlock) {
-      const double yi = y[rowidx[q]];
+      if (!mine(rowidx[q])) continue;
+      const double yi = kGrouped ? y[rowidx[q]] - ay : y[rowidx[q]];
       a += (val[q] - mj) * yi;
       ys += yi;
     }
     a = block_sum(a, sh);
     ys = block_sum(ys, sh);
     if (tid == 0) {
-      const double rest = (int64_t)(q1 - q0) == n ? 0.0 : mu[p] - ys;     // the response over the samples NOT stored: none, or all - stored
+      // the response over the samples NOT stored: none, or all - stored
+      const double rest = kGrouped ? M[(size_t)p * nc + p + 1] - ys : ((int64_t)(q1 - q0) == n ? 0.0 : mu[p] - ys);
       const double c = a - mj * rest;
-      M[(size_t)j * P1 + p] = c;
-      M[(size_t)p * P1 + j] = c;
+      M[(size_t)j * nc + p] = c;
+      M[(size_t)p * nc + j] = c;
+    }
+    return;
+  }
+  if (kGrouped && k == p + 1) {          // the sum of the group's deviations: stored entries, then the implicit -mj
+    double a = 0.0, cnt = 0.0;
+    for (int q = q0 + tid; q < q1; q += kBlock)
+      if (mine(rowidx[q])) {
+        a += val[q] - mj;
+        cnt += 1.0;
+      }
+    a = block_sum(a, sh);
+    cnt = block_sum(cnt, sh);
+    if (tid == 0) {
+      const double c = a - (M[(size_t)(p + 1) * nc + p + 1] - cnt) * mj;
+      M[(size_t)j * nc + p + 1] = c;
+      M[(size_t)(p + 1) * nc + j] = c;
     }
     return;
   }
   const int s0 = colptr[k], s1 = colptr[k + 1];
   const double mk = mu[k];
-  double both = 0.0, only_j = 0.0, only_k = 0.0, cnt = 0.0;
+  double both = 0.0, only_j = 0.0, only_k = 0.0, cnt = 0.0, cnt_j = 0.0, cnt_k = 0.0;
   for (int q = q0 + tid; q < q1; q += kBlock) {
     const int32_t r = rowidx[q];
+    if (!mine(r)) continue;
+    cnt_j += 1.0;
     const double d = val[q] - mj;
     const int pos = j == k ? q : lower_bound_row(rowidx, s0, s1, r);
     if (pos < s1 && rowidx[pos] == r) {
@@ -180,6 +269,8 @@ __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* 
   if (j != k)
     for (int s = s0 + tid; s < s1; s += kBlock) {
       const int32_t r = rowidx[s];
+      if (!mine(r)) continue;
+      cnt_k += 1.0;
       const int pos = lower_bound_row(rowidx, q0, q1, r);
       if (!(pos < q1 && rowidx[pos] == r)) only_k += val[s] - mk;
     }
@@ -187,11 +278,81 @@ __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* 
   only_j = block_sum(only_j, sh);
   only_k = block_sum(only_k, sh);
   cnt = block_sum(cnt, sh);
+  if (kGrouped) {
+    cnt_j = block_sum(cnt_j, sh);
+    cnt_k = j == k ? cnt_j : block_sum(cnt_k, sh);
+  }
   if (tid == 0) {
-    const double in_neither = (double)n - ((double)(q1 - q0) + (double)(s1 - s0) - cnt);
+    const double in_neither = kGrouped ? M[(size_t)(p + 1) * nc + p + 1] - (cnt_j + cnt_k - cnt)
+                                       : (double)n - ((double)(q1 - q0) + (double)(s1 - s0) - cnt);
     const double c = both - mk * only_j - mj * only_k + in_neither * mj * mk;
-    M[(size_t)j * P1 + k] = c;
-    M[(size_t)k * P1 + j] = c;
+    M[(size_t)j * nc + k] = c;
+    M[(size_t)k * nc + j] = c;
+  }
+}
+
+// total[e] = sum_g M[g][e], in group order
+__global__ __launch_bounds__(kBlock) void cov_total_kernel(const double* __restrict__ M, int n_groups, int elems, double* __restrict__ total) {
+  const int e = blockIdx.x * kBlock + threadIdx.x;
+  if (e >= elems) return;
+  double s = 0.0;
+  for (int g = 0; g < n_groups; ++g) s += M[(size_t)g * elems + e];
+  total[e] = s;
+}
+
+// blockIdx.x = training set T: group T alone, or (rest) the total less group T.  From the (p + 2) x (p + 2) moments about the
+// common centre a to what cov_path_kernel reads for x[T], y[T] as fit_covariance / prepare_response (driver.cpp) would
+// prepare them: the cross-products about T's own means t = a + d, the y column divided by sd_T(y), the features' sd over T,
+// n_T, and the penalties of every mix in the units of the preprocessed response.
+//   Mt     G x (p + 1) x (p + 1)      scale  G x p      mean  G x (p + 1): t (0 where the features are not centred), mean_T(y)
+//   tstat  3 x G: n_T | sd_T(y) (0 -> 1) | y~'y~         alpha, beta  jobs x n_lambda, job = mix * G + T      ridge  jobs
+__global__ __launch_bounds__(kBlock) void cov_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
+                                                               const double* __restrict__ mu, int n_groups, int p, int rest, int centre,
+                                                               int standardize, const double* __restrict__ mix,
+                                                               const double* __restrict__ lambda, int n_mix, int n_lambda,
+                                                               double* __restrict__ Mt, double* __restrict__ scale, double* __restrict__ mean,
+                                                               double* __restrict__ tstat, double* __restrict__ alpha,
+                                                               double* __restrict__ beta, int32_t* __restrict__ ridge) {
+  __shared__ double s[kCovMaxFeatures + 1], d[kCovMaxFeatures + 1];
+  const int t = blockIdx.x, tid = threadIdx.x, P1 = p + 1, Pa = p + 2;
+  const double* Ct = Mg + (size_t)t * Pa * Pa;
+  auto C = [&](int j, int k) -> double {
+    const double v = Ct[(size_t)j * Pa + k];
+    return rest ? total[(size_t)j * Pa + k] - v : v;
+  };
+  const double nT = C(p + 1, p + 1);
+  for (int j = tid; j < P1; j += kBlock) {
+    s[j] = C(j, p + 1);
+    d[j] = (j == p || centre) ? s[j] / nT : 0.0;
+  }
+  __syncthreads();
+  auto recentred = [&](int j, int k) -> double { return C(j, k) - d[j] * s[k] - d[k] * s[j] + nT * d[j] * d[k]; };
+  const double var_y = recentred(p, p) / nT;
+  const double sd_y = var_y > 0.0 ? sqrt(var_y) : 1.0;
+  for (int e = tid; e < P1 * P1; e += kBlock) {
+    const int j = e / P1, k = e - j * P1;
+    double m = recentred(j, k);
+    if (j == p) m /= sd_y;
+    if (k == p) m /= sd_y;
+    Mt[(size_t)t * P1 * P1 + e] = m;
+  }
+  for (int j = tid; j < p; j += kBlock) {
+    const double v = recentred(j, j) / nT;
+    scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+    mean[(size_t)t * P1 + j] = centre ? mu[j] + d[j] : 0.0;
+  }
+  if (tid == 0) {
+    mean[(size_t)t * P1 + p] = mu[p + 1] + d[p];
+    tstat[t] = nT;
+    tstat[n_groups + t] = sd_y;
+    tstat[2 * n_groups + t] = recentred(p, p) / sd_y / sd_y;
+  }
+  for (int e = tid; e < n_mix * n_lambda; e += kBlock) {
+    const int a = e / n_lambda, l = e - a * n_lambda;
+    const size_t at = ((size_t)a * n_groups + t) * n_lambda + l;
+    alpha[at] = (1.0 - mix[a]) * lambda[e] / sd_y;
+    beta[at] = mix[a] * lambda[e] / sd_y;
+    if (l == 0) ridge[(size_t)a * n_groups + t] = mix[a] == 0.0 ? 1 : 0;
   }
 }
 
@@ -200,13 +361,28 @@ __device__ __forceinline__ int tri(int j, int k) { return k * (k + 1) / 2 + j; }
 
 // One wavefront, the whole path.  Every lane computes the sweep's scalars (the new coefficient, the sweep's
 // max|dw| and max|w|) from the same LDS words, so branches on them are uniform and nothing has to be broadcast.
-__global__ __launch_bounds__(64) void cov_path_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, double dn,
+// blockIdx.x = job; its training set is job % n_sets (M, scale and n per set), its penalties and outputs are the job's
+// own.  One fit is a grid of 1 with n_sets = 1: n and the functor come as scalars (dn_sets = ridge_jobs = null).
+__global__ __launch_bounds__(64) void cov_path_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int n_sets,
+                                                       double dn_one, const double* __restrict__ dn_sets,
                                                        const double* __restrict__ alpha, const double* __restrict__ beta, int n_lambda,
-                                                       int ridge, unsigned max_iter, double tol, double* __restrict__ W,
-                                                       double* __restrict__ G, double* __restrict__ c_out, int32_t* __restrict__ sweeps_out,
-                                                       int32_t* __restrict__ unconverged) {
+                                                       int ridge_one, const int32_t* __restrict__ ridge_jobs, unsigned max_iter, double tol,
+                                                       double* __restrict__ W, double* __restrict__ G, double* __restrict__ c_out,
+                                                       int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
   __shared__ double lds[cov_state_doubles(kCovMaxFeatures)];
   const int lane = threadIdx.x, P1 = p + 1;
+  const size_t job = blockIdx.x, set = job % (size_t)n_sets;
+  M += set * (size_t)P1 * (size_t)P1;
+  scale += set * (size_t)p;
+  const double dn = dn_sets ? dn_sets[set] : dn_one;
+  const int ridge = ridge_jobs ? ridge_jobs[job] : ridge_one;
+  alpha += job * (size_t)n_lambda;
+  beta += job * (size_t)n_lambda;
+  W += job * (size_t)n_lambda * (size_t)p;
+  G += job * (size_t)n_lambda * (size_t)p;
+  c_out += job * (size_t)p;
+  sweeps_out += job * (size_t)n_lambda;
+  unconverged += job * (size_t)n_lambda;
   double* S = lds;
   double* c = S + p * (p + 1) / 2;
   double* w = c + p;
@@ -284,7 +460,7 @@ struct Arena {
 };
 
 struct Events {
-  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;
   ~Events() {
     for (hipEvent_t v : e)
@@ -292,6 +468,47 @@ struct Events {
     if (st) (void)hipStreamDestroy(st);
   }
 };
+
+// the pair kernel looks rows up by binary search: columns whose row indices do not ascend are sorted in a copy
+struct AscendingColumns {
+  const int32_t* rowidx;
+  const double* values;
+  std::vector<int32_t> rows_sorted;
+  std::vector<double> vals_sorted;
+  AscendingColumns(const int32_t* colptr, const int32_t* rowidx_in, const double* values_in, int p) : rowidx(rowidx_in), values(values_in) {
+    const int64_t nnz = p > 0 ? colptr[p] : 0;
+    bool ascending = true;
+    for (int j = 0; j < p && ascending; ++j)
+      for (int64_t q = (int64_t)colptr[j] + 1; q < colptr[j + 1]; ++q)
+        if (rowidx[q] <= rowidx[q - 1]) {
+          ascending = false;
+          break;
+        }
+    if (ascending) return;
+    rows_sorted.assign(rowidx, rowidx + nnz);
+    vals_sorted.assign(values, values + nnz);
+    std::vector<int64_t> order;
+    for (int j = 0; j < p; ++j) {
+      const int64_t q0 = colptr[j], q1 = colptr[j + 1];
+      order.resize((size_t)(q1 - q0));
+      std::iota(order.begin(), order.end(), q0);
+      std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return rowidx[a] < rowidx[b]; });
+      for (int64_t q = q0; q < q1; ++q) {
+        rows_sorted[(size_t)q] = rowidx[order[(size_t)(q - q0)]];
+        vals_sorted[(size_t)q] = values[order[(size_t)(q - q0)]];
+      }
+    }
+    rowidx = rows_sorted.data();
+    values = vals_sorted.data();
+  }
+};
+
+// dense x: the rows one chunk of the moments pass takes (a function of n and the number of tile pairs alone)
+int64_t dense_rows_per_chunk(int64_t n, int pairs) {
+  const int64_t chunk_cap = std::max<int64_t>(16, std::min<int64_t>(256, 1024 / pairs));
+  const int64_t chunks = std::min<int64_t>(chunk_cap, (n + 255) / 256);
+  return ((n + chunks - 1) / chunks + kTileRows - 1) / kTileRows * kTileRows;
+}
 
 }  // namespace
 
@@ -305,52 +522,23 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
 
-  // the pair kernel looks rows up by binary search: columns whose row indices do not ascend are sorted in a copy
   const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* rowidx = pb.rowidx;
-  const double* values = pb.values;
-  std::vector<int32_t> rows_sorted;
-  std::vector<double> vals_sorted;
-  if (sparse) {
-    bool ascending = true;
-    for (int j = 0; j < p && ascending; ++j)
-      for (int64_t q = (int64_t)pb.colptr[j] + 1; q < pb.colptr[j + 1]; ++q)
-        if (rowidx[q] <= rowidx[q - 1]) {
-          ascending = false;
-          break;
-        }
-    if (!ascending) {
-      rows_sorted.assign(rowidx, rowidx + nnz);
-      vals_sorted.assign(values, values + nnz);
-      std::vector<int64_t> order;
-      for (int j = 0; j < p; ++j) {
-        const int64_t q0 = pb.colptr[j], q1 = pb.colptr[j + 1];
-        order.resize((size_t)(q1 - q0));
-        std::iota(order.begin(), order.end(), q0);
-        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return rowidx[a] < rowidx[b]; });
-        for (int64_t q = q0; q < q1; ++q) {
-          rows_sorted[(size_t)q] = rowidx[order[(size_t)(q - q0)]];
-          vals_sorted[(size_t)q] = values[order[(size_t)(q - q0)]];
-        }
-      }
-      rowidx = rows_sorted.data();
-      values = vals_sorted.data();
-    }
-  }
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+  const int32_t* rowidx = cols.rowidx;
+  const double* values = cols.values;
 
   // dense x: the tile pairs and the row chunks (a function of n and p alone)
   const int T = (P1 + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t chunk_cap = std::max<int64_t>(16, std::min<int64_t>(256, 1024 / pairs));
-  int64_t chunks = std::min<int64_t>(chunk_cap, (n + 255) / 256);
-  const int64_t rows_per_chunk = ((n + chunks - 1) / chunks + kTileRows - 1) / kTileRows * kTileRows;
-  chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+  const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+  const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
 
   Arena A;
   const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
   const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P1 : 0);
   const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
   const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)P1);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(P1 + 1));     // (the last entry: mean of y, for the group moments)
   const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
   const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
   const size_t o_M = A.reserve(sizeof(double) * (size_t)P1 * (size_t)P1);
@@ -390,20 +578,21 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
   if (sparse) {
     hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel, dim3((unsigned)p, (unsigned)P1), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_y,
-                       d_mu, n, p, d_M);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<false>, dim3((unsigned)p, (unsigned)P1), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_y,
+                       d_mu, n, p, (const int32_t*)nullptr, d_M);
   } else {
     hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
                        pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p,
-                       rows_per_chunk, A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks, p, d_M);
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, P1,
+                       rows_per_chunk, (const int64_t*)nullptr, (const int64_t*)nullptr, A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       (const int32_t*)nullptr, P1, d_M);
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  hipLaunchKernelGGL(cov_path_kernel, dim3(1), dim3(64), 0, st, d_M, A.at<double>(o_scale), p, (double)n, A.at<double>(o_alpha),
-                     A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G),
-                     A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  hipLaunchKernelGGL(cov_path_kernel, dim3(1), dim3(64), 0, st, d_M, A.at<double>(o_scale), p, 1, (double)n, (const double*)nullptr,
+                     A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr, pb.max_iter, pb.tol,
+                     A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
 
@@ -423,6 +612,170 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   out->mean.resize((size_t)p);     // (entry p was the response's sum)
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  return SGDNET_OK;
+}
+
+
+int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
+  const int64_t n = pb.n;
+  const int p = (int)pb.p, P1 = p + 1, Pa = p + 2, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
+  const bool sparse = pb.x_dense == nullptr;
+  if (n <= 0 || p <= 0 || p > kCovMaxFeatures || L <= 0 || G <= 0 || A_mix <= 0 || !pb.fold || !pb.y || !pb.mix || !pb.lambda ||
+      (pb.train_on_rest && G < 2) || (size_t)G * Pa * Pa * sizeof(double) > kCovGroupMomentBytes ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("covariance_cv_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+  const size_t jobs = (size_t)A_mix * (size_t)G;
+
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+
+  // dense x: the rows sorted by group (stable: a group's rows stay in row order) and cut into chunks of the size one
+  // fit of n rows would use, none across a group's end: the summation order is a function of (n, p, fold) alone
+  const int T = (Pa + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
+  std::vector<int64_t> perm, chunk_begin;
+  std::vector<int32_t> group_chunk;
+  if (!sparse) {
+    std::vector<int64_t> start((size_t)G + 1, 0);
+    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
+    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
+    perm.resize((size_t)n);
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
+    const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+    group_chunk.assign((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
+      if (chunk_begin.size() > (size_t)kCovMaxRowChunks) {
+        set_error("mode = covariance needs the rows of the groups in at most %d chunks: %d groups of %lld rows", kCovMaxRowChunks, G,
+                  (long long)n);
+        return SGDNET_EUNSUPPORTED;
+      }
+      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
+    }
+    chunk_begin.push_back(n);
+  }
+  if (sparse && G > kCovMaxRowChunks) {       // (the pair kernel's gridDim.z)
+    set_error("mode = covariance needs at most %d groups of sparse rows: %d groups", kCovMaxRowChunks, G);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
+  const size_t Melems = (size_t)Pa * (size_t)Pa;
+
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P1 : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
+  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
+  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
+  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)Pa);
+  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
+  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
+  const size_t o_total = A.reserve(sizeof(double) * Melems);
+  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
+  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  const size_t o_Mt = A.reserve(sizeof(double) * (size_t)G * (size_t)P1 * (size_t)P1);
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
+  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
+  const size_t o_alpha = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_beta = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
+  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
+  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
+  const size_t o_c = A.reserve(sizeof(double) * jobs * (size_t)p);
+  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Events ev;
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
+  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  hipStream_t st = ev.st;
+  double* d_x = A.at<double>(o_x);
+  double* d_y = A.at<double>(o_y);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_Mg = A.at<double>(o_Mg);
+  double* d_tstat = A.at<double>(o_tstat);
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)P1, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
+
+  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
+  if (sparse) {
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_group_response_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_y, A.at<int32_t>(o_fold), d_mu, n, p, d_Mg);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
+                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, A.at<int32_t>(o_fold), d_Mg);
+  } else {
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, Pa,
+                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
+  }
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  if (pb.train_on_rest)
+    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
+                       A.at<double>(o_total));
+  hipLaunchKernelGGL(cov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p,
+                     pb.train_on_rest ? 1 : 0, pb.centre ? 1 : 0, pb.standardize ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda),
+                     A_mix, L, A.at<double>(o_Mt), A.at<double>(o_scale), A.at<double>(o_mean), d_tstat, A.at<double>(o_alpha),
+                     A.at<double>(o_beta), A.at<int32_t>(o_ridge));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  hipLaunchKernelGGL(cov_path_kernel, dim3((unsigned)jobs), dim3(64), 0, st, A.at<double>(o_Mt), A.at<double>(o_scale), p, G, 0.0,
+                     d_tstat, A.at<double>(o_alpha), A.at<double>(o_beta), L, 0, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol,
+                     A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+
+  std::vector<double> tstat(3 * (size_t)G);
+  out->mean.resize((size_t)G * (size_t)P1);
+  out->scale.resize((size_t)G * (size_t)p);
+  out->c.resize(jobs * (size_t)p);
+  out->w.resize(jobs * (size_t)L * (size_t)p);
+  out->g.resize(jobs * (size_t)L * (size_t)p);
+  out->sweeps.resize(jobs * (size_t)L);
+  out->unconverged.resize(jobs * (size_t)L);
+  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
+  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
+  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
+  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
+  SGD_HIP_TRY(fetch(out->c.data(), o_c, sizeof(double) * out->c.size()));
+  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
+  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
+  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
+  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  out->n_train.assign(tstat.begin(), tstat.begin() + G);
+  out->y_scale.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
+  out->yy.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
   return SGDNET_OK;
 }
 

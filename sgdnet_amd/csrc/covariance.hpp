@@ -57,4 +57,52 @@ struct CovarianceResult {
 // Moments pass + path kernel (covariance.hip).  p <= kCovMaxFeatures is the caller's business (plan_fit).
 int covariance_run(const CovarianceProblem& pb, CovarianceResult* out);
 
+// ---- cross-validation: every (training set, elastic-net mix) path of one x in one launch ----
+// Rows carry a group id fold[i] in [0, G).  One pass leaves, per group and about ONE centre a (the whole-data column
+// means, or 0 where centre is false; mean(y) for the response), the (p + 2) x (p + 2) moment matrix of the augmented
+// rows [x - a | y - a_y | 1]: the cross-products C^g, the sums of deviations s^g (last column) and n_g (last entry).
+// A training set T is one group or all groups but one; cov_assemble_kernel pools its groups and re-centres to T's own
+// means into what cov_path_kernel reads.  A job is (mix, T): job = mix_index * G + T.
+//
+// The budget of the group moments: G (p + 2)^2 doubles.  64 MiB holds nfolds = n for every n up to 209 at p = 198 and
+// up to 524 288 at p = 2; a 10-fold CV at p = 198 takes 3.2 MB of it.
+constexpr size_t kCovGroupMomentBytes = (size_t)64 << 20;
+constexpr int kCovMaxRowChunks = 65535;   // the dense moments pass puts its row chunks (at least one per group) on gridDim.y
+
+struct CovarianceCvProblem {
+  int64_t n = 0, p = 0;
+  const double* x_dense = nullptr;     // as CovarianceProblem: x and y in host memory, as they came
+  const int32_t* colptr = nullptr;
+  const int32_t* rowidx = nullptr;
+  const double* values = nullptr;
+  const double* y = nullptr;           // n: the response as it came (NOT preprocessed: every training set has its own centre)
+  const int32_t* fold = nullptr;       // n: group ids in [0, n_groups), no group empty (the caller's business)
+  int n_groups = 0;
+  bool train_on_rest = false;          // T = all groups but one (false: T = one group)
+  bool centre = true, standardize = true;
+  int device = 0;
+  int n_mix = 0, n_lambda = 0;
+  const double* mix = nullptr;         // n_mix
+  const double* lambda = nullptr;      // n_mix x n_lambda, a row per mix
+  unsigned max_iter = 0;
+  double tol = 0.0;
+};
+
+struct CovarianceCvResult {
+  // per training set T (n_groups of them)
+  std::vector<double> n_train;         // G
+  std::vector<double> mean;            // G x (p + 1): the means of x (0 where centre is false) and of y over T
+  std::vector<double> scale;           // G x p: the sd feature j is standardised with (1 without standardize)
+  std::vector<double> y_scale, yy;     // G: sd of y over T (0 -> 1); y~'y~ of the preprocessed response
+  // per job
+  std::vector<double> c;               // jobs x p
+  std::vector<double> w, g;            // jobs x n_lambda x p
+  std::vector<int32_t> sweeps, unconverged;   // jobs x n_lambda
+  float moments_ms = 0.f, assemble_ms = 0.f, path_ms = 0.f;
+};
+
+// Group moments + assembly + path kernel over the jobs.  p <= kCovMaxFeatures, the budget above and valid fold ids are
+// the caller's business (driver.cpp: fit_cv_covariance).
+int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out);
+
 }  // namespace sgdnet

@@ -1356,9 +1356,168 @@ int with_exact_fallback(const sgdnet_control* ctl, F fit) {
   return rc;
 }
 
+
+// ---- cross-validation in covariance mode (covariance.hip: covariance_cv_run): the stage behind sgdnet_cv_covariance_* ----
+// Every job (mix, training set T) is fit_covariance on x[T], y[T] by definition: the response centred and scaled by its
+// moments over T (prepare_response), the features centred (and scaled) by theirs, the penalties of regularization_path
+// in the units of that response.  The device assembles all of it from the group moments; what is left for the host is
+// the way back to the scale of the data (rescale_values) and the deviance from the quadratic form, per job.
+int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
+                      int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_cov_result* out) {
+  const int64_t n = pb.n, p = pb.p;
+  if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !pb.y ||
+      !fold || !alphas || !lambdas) {
+    set_error("sgdnet_cv_covariance: null pointer");
+    return SGDNET_EINVAL;
+  }
+  if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
+      (train_on_rest && n_groups < 2)) {
+    set_error("sgdnet_cv_covariance: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    return SGDNET_EINVAL;
+  }
+  const int L = ctl->n_lambda;
+  const char* what = nullptr;
+  if (ctl->family != SGDNET_GAUSSIAN) what = "family = gaussian";
+  else if (p > kCovMaxFeatures) what = "no more features than sgdnet_covariance_max_features()";
+  else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+  else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
+  if (what) {
+    set_error("mode = covariance needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)p,
+              kCovMaxFeatures, ctl->n_gpus, ctl->debug);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const size_t moment_bytes = (size_t)n_groups * (size_t)(p + 2) * (size_t)(p + 2) * sizeof(double);
+  if (moment_bytes > kCovGroupMomentBytes) {
+    set_error("mode = covariance needs the group moments within %zu bytes: %d groups x (%lld + 2)^2 doubles are %zu bytes",
+              kCovGroupMomentBytes, n_groups, (long long)p, moment_bytes);
+    return SGDNET_EUNSUPPORTED;
+  }
+  std::vector<int64_t> count((size_t)n_groups, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    if (fold[i] < 0 || fold[i] >= n_groups) {
+      set_error("fold[%lld] = %d is not a group id in 0..%d", (long long)i, fold[i], n_groups - 1);
+      return SGDNET_EINVAL;
+    }
+    ++count[(size_t)fold[i]];
+  }
+  for (int g = 0; g < n_groups; ++g)
+    if (count[(size_t)g] == 0) {
+      set_error("group %d of %d is empty", g, n_groups);
+      return SGDNET_EINVAL;
+    }
+  for (int a = 0; a < n_alpha; ++a) {
+    if (!(alphas[a] >= 0.0 && alphas[a] <= 1.0)) {
+      set_error("alphas[%d] = %g is not an elastic-net mix in [0, 1]", a, alphas[a]);
+      return SGDNET_EINVAL;
+    }
+    for (int l = 0; l < L; ++l)
+      if (!(lambdas[(size_t)a * L + l] >= 0.0)) {
+        set_error("lambdas[%d][%d] = %g is negative", a, l, lambdas[(size_t)a * L + l]);
+        return SGDNET_EINVAL;
+      }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error("no HIP device available: the SAGA backend has no CPU fallback");
+    return SGDNET_ENODEVICE;
+  }
+  if (ctl->device < 0 || ctl->device >= ndev) {
+    set_error("device %d out of range (%d devices)", ctl->device, ndev);
+    return SGDNET_EINVAL;
+  }
+  PhaseTimer pt;
+  const bool intercept = ctl->intercept != 0;
+  pb.fold = fold;
+  pb.n_groups = n_groups;
+  pb.train_on_rest = train_on_rest != 0;
+  pb.centre = intercept || ctl->standardize != 0;
+  pb.standardize = ctl->standardize != 0;
+  pb.device = ctl->device;
+  pb.n_mix = n_alpha;
+  pb.n_lambda = L;
+  pb.mix = alphas;
+  pb.lambda = lambdas;
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  CovarianceCvResult cr;
+  const int rc = covariance_cv_run(pb, &cr);
+  if (rc) return rc;
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   cv covariance: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", cr.moments_ms,
+            cr.assemble_ms, n_alpha * n_groups, cr.path_ms);
+
+  const size_t P = (size_t)p, P1 = P + 1;
+  for (int a = 0; a < n_alpha; ++a)
+    for (int t = 0; t < n_groups; ++t) {
+      const size_t job = (size_t)a * (size_t)n_groups + (size_t)t;
+      const double nT = cr.n_train[(size_t)t], ys = cr.y_scale[(size_t)t], yy = cr.yy[(size_t)t];
+      const double* mean = cr.mean.data() + (size_t)t * P1;
+      const double* scale = cr.scale.data() + (size_t)t * P;
+      const double* c = cr.c.data() + job * P;
+      double n_sweeps = 0.0;
+      for (int li = 0; li < L; ++li) {
+        const size_t at = job * (size_t)L + (size_t)li;
+        const double* w = cr.w.data() + at * P;
+        const double* g = cr.g.data() + at * P;
+        double* bo = out->beta + at * P;
+        // fit_covariance: the explained part of the deviance is n sum_j w_j (c~_j - g_j); the intercept is the response's
+        // mean over T less the features' means times the coefficients, on the scale of the data
+        double explained = 0.0, xbb = 0.0;
+        for (size_t j = 0; j < P; ++j) {
+          explained += w[j] * (c[j] - g[j]);
+          bo[j] = w[j] * (ys / scale[j]);
+          xbb += mean[j] * bo[j];
+        }
+        const double dev = std::max(0.0, yy - nT * explained);
+        out->dev_ratio[at] = yy > 0.0 ? 1.0 - dev / yy : 0.0;
+        out->a0[at] = intercept ? mean[P] - xbb : 0.0;
+        out->return_codes[at] = cr.unconverged[at] ? 1.0 : 0.0;
+        n_sweeps += (double)cr.sweeps[at];
+      }
+      out->nulldev[job] = yy * ys * ys;
+      out->npasses[job] = n_sweeps;
+    }
+  pt.mark("cv covariance (all folds)");
+  return SGDNET_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sgdnet_cv_covariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                               int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                               sgdnet_cv_cov_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_covariance_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  CovarianceCvProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  pb.y = y;
+  return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                sgdnet_cv_cov_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_covariance_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  CovarianceCvProblem pb;
+  pb.n = x->n_rows;
+  pb.p = x->n_cols;
+  pb.colptr = x->colptr;
+  pb.rowidx = x->rowidx;
+  pb.values = x->values;
+  pb.y = y;
+  return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
 
 int sgdnet_fit_sparse(const sgdnet_csc* x, const double* y, int y_cols, const sgdnet_control* ctl,
                       sgdnet_result* out) {

@@ -13,13 +13,21 @@ Two behaviours of the reference are kept because results depend on them, and fla
     (a 10M x 10k matrix cannot be densified) -- same optimum, different standardisation path.
 With one device and an `rng`, fits consume R's generator in the reference's order (full fits,
 sample() for the fold ids, fold fits); with several devices every fit gets its own seed.
+
+fold_fits="batched" (mode="covariance" only): the n_alpha * nfolds fold fits are ONE native call
+(cv_covariance_fits -> sgdnet_cv_covariance_*): one pass over x leaves the moments of every fold on the
+device, every training set's moments are pooled from them and all paths run side by side, one workgroup each.
+The full fits, the fold ids, the scoring and the result are those of the default fold_fits="separate".
 """
+import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 
 import numpy as np
 
-from .api import sgdnet
+from . import _lib
+from ._lib import FAMILIES, MODES, check, dptr
+from .api import SgdnetFit, sgdnet
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -74,9 +82,111 @@ def find_optimum(summary):
     return dict(alpha_min=summary[i, 0], lambda_min=lam[i], lambda_1se=lam[within].max(), error_min=mean[i])
 
 
-def cv_sgdnet(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, family="gaussian",
-              devices=None, rng=None, seed=0, train_on="fold", densify=False, **fit_args):
+def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                       thresh=0.001, device=0):
+    """Every fold fit of a gaussian cross-validation in covariance mode from one native call.
+
+    foldid: one label per sample (any values; the folds are np.unique(foldid), in that order).  alpha: one mix or a
+    sequence.  lambda_: the penalty strengths, one array per alpha (a single array when alpha is a single number), all
+    of one length.  train_on: "fold" (fit on the fold's own rows, the reference's convention) or "rest".
+    Returns a list of SgdnetFit, alpha-major: entry a * nfolds + j is sgdnet(x[T], y[T], alpha=alpha[a],
+    lambda_=lambda_[a], mode="covariance") for the training set T of fold j."""
     import scipy.sparse as sp
+
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    if not all(isinstance(v, (bool, np.bool_)) for v in (intercept, standardize)):
+        raise ValueError("intercept and standardize must be logical")
+    alphas = np.atleast_1d(np.asarray(alpha, dtype=np.float64))
+    if np.ndim(alpha) == 0:
+        lambda_ = [lambda_]
+    rows = [np.asarray(l, dtype=np.float64).reshape(-1) for l in lambda_]
+    if len(rows) != alphas.size or rows[0].size == 0 or any(r.size != rows[0].size for r in rows):
+        raise ValueError("lambda_ needs one array per alpha, all of one positive length")
+    lam = np.ascontiguousarray(rows)
+    if np.any(alphas < 0) or np.any(alphas > 1):
+        raise ValueError("elastic net mixing parameter (alpha) must be in [0, 1].")
+    if np.any(lam < 0):
+        raise ValueError("penalty strengths (lambdas) must be positive.")
+    if thresh < 0:
+        raise ValueError("threshold for stopping criteria cannot be negative.")
+    if maxit <= 0:
+        raise ValueError("maximum number of iterations cannot be negative or zero.")
+    n, p = x.shape
+    y_enc = np.ascontiguousarray(np.asarray(y), dtype=np.float64).reshape(-1)
+    foldid = np.asarray(foldid).reshape(-1)
+    if y_enc.size != n or foldid.size != n:
+        raise ValueError("the number of samples in 'x', 'y' and 'foldid' must match")
+    values, fold = np.unique(foldid, return_inverse=True)
+    fold = np.ascontiguousarray(fold, dtype=np.int32)
+    G, A, nl = values.size, alphas.size, lam.shape[1]
+
+    ctl = _lib.Control()
+    ctl.family = FAMILIES["gaussian"]
+    ctl.intercept, ctl.standardize = int(intercept), int(standardize)
+    ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, 1
+    ctl.mode, ctl.device = MODES["covariance"], int(device)
+    jobs = A * G
+    a0 = np.zeros((jobs, nl))
+    beta = np.zeros((jobs, nl, p))
+    dev_ratio = np.zeros((jobs, nl))
+    rcodes = np.zeros((jobs, nl))
+    nulldev = np.zeros(jobs)
+    npasses = np.zeros(jobs)
+    res = _lib.CvCovResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses))
+    tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
+            dptr(lam), C.byref(res))
+    L = _lib.load()
+    if sp.issparse(x):
+        xs = sp.csc_matrix(x, dtype=np.float64)
+        xs.sort_indices()
+        colptr = np.ascontiguousarray(xs.indptr, dtype=np.int32)
+        rowidx = np.ascontiguousarray(xs.indices, dtype=np.int32)
+        vals = np.ascontiguousarray(xs.data, dtype=np.float64)
+        csc = _lib.Csc()
+        csc.n_rows, csc.n_cols = n, p
+        csc.colptr = colptr.ctypes.data_as(C.POINTER(C.c_int32))
+        csc.rowidx = rowidx.ctypes.data_as(C.POINTER(C.c_int32))
+        csc.values = dptr(vals)
+        check(L.sgdnet_cv_covariance_sparse(C.byref(csc), *tail))
+    else:
+        xd = np.asfortranarray(np.asarray(x, dtype=np.float64).reshape(n, p))
+        check(L.sgdnet_cv_covariance_dense(dptr(xd), n, p, *tail))
+
+    counts = np.bincount(fold, minlength=G)
+    fits = []
+    for a in range(A):
+        for j in range(G):
+            job = a * G + j
+            b = beta[job].T.copy()                                # (p, n_lambda)
+            fits.append(SgdnetFit(a0=a0[job].copy(), beta=b, lambda_=lam[a].copy(), dev_ratio=dev_ratio[job].copy(),
+                                  df=(b != 0).sum(axis=0), nulldev=float(nulldev[job]), npasses=float(npasses[job]),
+                                  alpha=float(alphas[a]), offset=False, classnames=None, grouped=False,
+                                  nobs=int(n - counts[j] if train_on == "rest" else counts[j]), family="gaussian",
+                                  return_codes=rcodes[job].copy(), draws_used=0))
+    return fits
+
+
+_BATCHED_FIT_ARGS = ("maxit", "standardize", "intercept", "thresh", "mode", "nlambda", "lambda_min_ratio")
+
+
+def cv_sgdnet(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, family="gaussian",
+              devices=None, rng=None, seed=0, train_on="fold", densify=False, fold_fits="separate", **fit_args):
+    import scipy.sparse as sp
+
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if fold_fits == "batched":
+        # one native call covers gaussian fold fits in covariance mode on one device, and nothing else: no silent fallback
+        if fit_args.get("mode") != "covariance":
+            raise ValueError("fold_fits='batched' needs mode='covariance' (got mode=%r)" % (fit_args.get("mode", "exact"),))
+        if family != "gaussian":
+            raise ValueError("fold_fits='batched' needs family='gaussian' (got family=%r)" % (family,))
+        if devices and len(devices) > 1:
+            raise ValueError("fold_fits='batched' needs one device (got devices=%r)" % (list(devices),))
+        extra = sorted(set(fit_args) - set(_BATCHED_FIT_ARGS))
+        if extra:
+            raise ValueError("fold_fits='batched' does not cover the fit argument(s) " + ", ".join(extra))
 
     alpha = np.atleast_1d(np.asarray(alpha, dtype=np.float64))
     if not (nfolds > 2 and alpha.size > 0):
@@ -146,7 +256,19 @@ def cv_sgdnet(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure=
     jobs = [(i, j, (i * nfolds + j) % len(devices), seed + 1000 + i * nfolds + j)
             for i in range(alpha.size) for j in range(nfolds)]               # (alpha, fold, worker, seed)
     cv_raw = [np.full((nfolds, lam[i].size), np.nan) for i in range(alpha.size)]
-    if sequential:
+    if fold_fits == "batched":
+        # the groups of the native call in the order of fold_values (np.unique sorts, and so does np.arange(1, nfolds + 1))
+        kw = {k: fit_args[k] for k in ("maxit", "standardize", "intercept", "thresh") if k in fit_args}
+        fold_fit = cv_covariance_fits(x, y, foldid, alpha, lam, train_on=train_on, device=devices[0], **kw)
+        if len(fold_fit) != alpha.size * nfolds:
+            raise ValueError("fold_fits='batched' needs every fold to hold a sample")
+
+        def score_job(job):
+            i, j = job[0], job[1]
+            test = (foldid == fold_values[j]) != (train_on == "fold")
+            return i, j, score(fold_fit[i * nfolds + j], x[test], y[test], type_measure, device=devices[0])
+        results = map(score_job, jobs)
+    elif sequential:
         results = map(fold_job, jobs)
     else:
         # one worker per entry of `devices` (list a device twice to run two fits on it at a time)
