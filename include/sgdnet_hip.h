@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_* (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON and sgdnet_newton_max_features (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -78,6 +78,21 @@ extern "C" {
  * (max|dw| / max|w| <= tol), and return_codes[l] = 1 when lambda l used all max_iter sweeps without meeting tol.
  * lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are defined as in the other modes. */
 #define SGDNET_MODE_COVARIANCE 3
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): the binomial path of
+ * one response solved to its optimum by proximal Newton steps (IRLS).  An outer step is one pass over x that leaves
+ * mu_i, v_i = mu_i (1 - mu_i) and the mean loss at the iterate, one pass that leaves the weighted Gram matrix
+ * H = Z'VZ / n of the centred features and the column of ones and the gradient q = Z'(y - mu) / n, and cyclic
+ * coordinate descent on the penalised quadratic model in one wavefront, the intercept an unpenalised last
+ * coordinate (sgdnet_amd/csrc/newton.hip).  A step after which the penalised objective rose is halved.  Needs family =
+ * binomial, n_features <= sgdnet_newton_max_features(), n_gpus <= 1 and debug = 0; anything else returns
+ * SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition ("mode = newton needs ...") -- no fall back to SAGA.
+ * The fit draws no samples: sample_stream, unif, seed and rng_state are accepted and ignored, rng_state is left
+ * untouched bit for bit and result.draws_used = 0.  lambda is done when an outer step moves the coefficients and the
+ * intercept by max|du| / max|u| <= tol (all zero counts as converged); max_iter bounds the outer steps of one lambda
+ * and return_codes[l] = 1 when lambda l used them all; result.npasses = the passes over x that evaluated an iterate,
+ * summed over the path.  lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are defined as in the other
+ * modes. */
+#define SGDNET_MODE_NEWTON 4
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -169,6 +184,8 @@ const char* sgdnet_last_error(void);
 int sgdnet_device_count(void);
 /* the largest n_features SGDNET_MODE_COVARIANCE takes (198: what one gfx950 workgroup's LDS holds; at least 64) */
 int sgdnet_covariance_max_features(void);
+/* the largest n_features SGDNET_MODE_NEWTON takes (198: the intercept is one more coordinate of the LDS-resident model) */
+int sgdnet_newton_max_features(void);
 
 /* ------------------------------------------------------------------------ */
 /* Process-wide backend options.  These are the ONLY switches that change    */

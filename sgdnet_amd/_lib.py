@@ -35,7 +35,7 @@ EXPORTS = [
     "sgdnet_solver_rng_layout", "sgdnet_solver_rng_open", "sgdnet_solver_rng_next", "sgdnet_solver_rng_done", "sgdnet_solver_rng_close",
     "sgdnet_gradient_sparse", "sgdnet_gradient_dense", "sgdnet_covariance_max_features",
     "sgdnet_setup_probe_sparse", "sgdnet_setup_probe_dense",
-    "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse",
+    "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse", "sgdnet_newton_max_features",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -43,6 +43,7 @@ MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
 FAMILIES = {"gaussian": 0, "binomial": 1, "multinomial": 2, "mgaussian": 3}
 PENALTIES = {"ridge": 0, "elasticnet": 1, "grouplasso": 2}
 MODES = {"exact": 0, "batched": 1, "auto": 2, "covariance": 3}
+MODE_NEWTON = 4   # SGDNET_MODE_NEWTON: reached through sgdnet_newton(), not through sgdnet(mode=...)
 
 UNIF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
 LOSSES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)

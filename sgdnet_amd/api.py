@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODES, check, dptr
+from ._lib import FAMILIES, MODE_NEWTON, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -75,6 +75,29 @@ def sgdnet(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min_ratio=None,
     X'X and X'y (at most covariance_max_features() features; draws no samples, so seed / rng / sample_stream / unif
     are ignored, npasses counts coordinate sweeps and maxit bounds the sweeps per lambda).
     """
+    return _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
+                standardize_response, debug=debug, seed=seed, rng=rng, sample_stream=sample_stream, unif=unif, mode=mode,
+                modes=MODES, batch=batch, device=device, devices=devices)
+
+
+def sgdnet_newton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
+                  intercept=True, thresh=0.001, *, device=0):
+    """The binomial path of sgdnet(x, y, family="binomial", ...) solved to its optimum by proximal Newton steps on the
+    device (SGDNET_MODE_NEWTON, csrc/newton.hip): per step one pass over x for the weighted Gram matrix X'VX and the
+    gradient, then coordinate descent on the penalised quadratic model, the intercept an unpenalised coordinate.  At
+    most newton_max_features() features.  The arguments, their validation, the response encoding and the returned
+    SgdnetFit are sgdnet()'s; lambda_ and nulldev are those of the other modes bit for bit.  It draws no samples
+    (draws_used = 0); maxit bounds the Newton steps per lambda, thresh is the largest relative change of the
+    coefficients and the intercept a last step may make, npasses counts the passes that evaluated an iterate."""
+    return _fit(x, y, "binomial", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh, False,
+                debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="newton", modes={"newton": MODE_NEWTON},
+                batch=0, device=device, devices=None)
+
+
+def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
+         standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices):
+    """Validation, response encoding, the native call and the post-processing behind sgdnet() and sgdnet_newton();
+    modes: the mode strings the caller accepts and their SGDNET_MODE_* codes."""
     import scipy.sparse as sp
 
     n_samples = x.shape[0]
@@ -196,9 +219,9 @@ def sgdnet(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min_ratio=None,
     ctl.seed = int(seed) & 0xFFFFFFFF
     if rng is not None:
         ctl.rng_state = C.pointer(rng.state)
-    if mode not in MODES:
-        _stop("mode must be one of " + ", ".join(f"'{m}'" for m in MODES))
-    ctl.mode = MODES[mode]
+    if mode not in modes:
+        _stop("mode must be one of " + ", ".join(f"'{m}'" for m in modes))
+    ctl.mode = modes[mode]
     ctl.batch = int(batch)
     ctl.device = int(device)
     if devices is not None and len(devices) > 1:          # the fit sharded over several GPUs (control.n_gpus, ABI 4)

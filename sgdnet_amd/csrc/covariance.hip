@@ -43,51 +43,10 @@
 
 #include "common.hpp"
 #include "covariance.hpp"
+#include "moments_device.hpp"
 
 namespace sgdnet {
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kTileCols = 16;     // columns per tile: 16 x 16 threads own a tile pair
-constexpr int kTileRows = 64;     // rows staged per step
-
-// the sum of v over the workgroup, in a fixed tree order; every thread gets it
-__device__ double block_sum(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
-// blockIdx.x = column j < p: mu[j] = mean of the column (sparse: over all n samples); column p: mu[p] = sum of y and
-// mu[p + 1] = mean of y (the centre of the response of the group moments)
-template <bool kSparse>
-__global__ __launch_bounds__(kBlock) void cov_sum_kernel(const double* __restrict__ x, const int32_t* __restrict__ colptr,
-                                                          const double* __restrict__ y, int64_t n, int p, int centre,
-                                                          double* __restrict__ mu) {
-  __shared__ double sh[kBlock];
-  const int j = blockIdx.x;
-  double s = 0.0;
-  if (j == p) {
-    for (int64_t i = threadIdx.x; i < n; i += kBlock) s += y[i];
-  } else if (!centre) {
-    // deviations from 0
-  } else if (kSparse) {
-    for (int64_t q = (int64_t)colptr[j] + threadIdx.x; q < colptr[j + 1]; q += kBlock) s += x[q];
-  } else {
-    const double* col = x + (int64_t)j * n;
-    for (int64_t i = threadIdx.x; i < n; i += kBlock) s += col[i];
-  }
-  s = block_sum(s, sh);
-  if (threadIdx.x == 0) {
-    mu[j] = j == p ? s : s / (double)n;
-    if (j == p) mu[p + 1] = s / (double)n;
-  }
-}
 
 // blockIdx.x: the pair (tj <= tk) of column tiles of the augmented matrix, blockIdx.y: the chunk of rows.
 // One fit: ncols = p + 1, the matrix is [x - mu | y] (y as the driver preprocessed it), chunk c is rows [c rows_per_chunk, ...).
@@ -135,38 +94,6 @@ __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __
     __syncthreads();
   }
   part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kBlock + tid] = acc;
-}
-
-// the chunks' partial tiles added in chunk order; M is the symmetric ncols x ncols matrix of the augmented rows.
-// blockIdx.y = group: its chunks are [group_chunk[g], group_chunk[g + 1]) and its matrix is M[g] (one fit: all chunks, M[0])
-__global__ __launch_bounds__(kBlock) void cov_reduce_kernel(const double* __restrict__ part, int chunks,
-                                                             const int32_t* __restrict__ group_chunk, int ncols, double* __restrict__ M) {
-  const int tid = threadIdx.x;
-  const int T = (ncols + kTileCols - 1) / kTileCols;
-  int pair = blockIdx.x, tj = 0;
-  while (pair >= T - tj) {
-    pair -= T - tj;
-    ++tj;
-  }
-  const int tk = tj + pair;
-  const int a = tj * kTileCols + (tid & (kTileCols - 1)), b = tk * kTileCols + tid / kTileCols;
-  if (a >= ncols || b >= ncols) return;
-  const int c0 = group_chunk ? group_chunk[blockIdx.y] : 0, c1 = group_chunk ? group_chunk[blockIdx.y + 1] : chunks;
-  M += (size_t)blockIdx.y * (size_t)ncols * (size_t)ncols;
-  double s = 0.0;
-  for (int c = c0; c < c1; ++c) s += part[((size_t)c * gridDim.x + blockIdx.x) * kBlock + tid];
-  M[(size_t)a * ncols + b] = s;
-  if (tj != tk) M[(size_t)b * ncols + a] = s;
-}
-
-// first position in rowidx[lo, hi) whose row is >= r
-__device__ int lower_bound_row(const int32_t* __restrict__ rowidx, int lo, int hi, int32_t r) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (rowidx[mid] < r) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // Group moments of the response (sparse x; the dense tile kernel has them as columns p and p + 1): blockIdx.x = group g,
@@ -356,9 +283,6 @@ __global__ __launch_bounds__(kBlock) void cov_assemble_kernel(const double* __re
   }
 }
 
-// S(j, k) of the packed triangle, j <= k
-__device__ __forceinline__ int tri(int j, int k) { return k * (k + 1) / 2 + j; }
-
 // One wavefront, the whole path.  Every lane computes the sweep's scalars (the new coefficient, the sweep's
 // max|dw| and max|w|) from the same LDS words, so branches on them are uniform and nothing has to be broadcast.
 // blockIdx.x = job; its training set is job % n_sets (M, scale and n per set), its penalties and outputs are the job's
@@ -443,22 +367,6 @@ __global__ __launch_bounds__(64) void cov_path_kernel(const double* __restrict__
   }
 }
 
-// one device allocation cut into aligned pieces
-struct Arena {
-  char* base = nullptr;
-  size_t used = 0;
-  ~Arena() {
-    if (base) (void)hipFree(base);
-  }
-  size_t reserve(size_t bytes) {
-    const size_t at = used;
-    used += (bytes + 255) & ~(size_t)255;
-    return at;
-  }
-  template <class T>
-  T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
-};
-
 struct Events {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;
@@ -468,47 +376,6 @@ struct Events {
     if (st) (void)hipStreamDestroy(st);
   }
 };
-
-// the pair kernel looks rows up by binary search: columns whose row indices do not ascend are sorted in a copy
-struct AscendingColumns {
-  const int32_t* rowidx;
-  const double* values;
-  std::vector<int32_t> rows_sorted;
-  std::vector<double> vals_sorted;
-  AscendingColumns(const int32_t* colptr, const int32_t* rowidx_in, const double* values_in, int p) : rowidx(rowidx_in), values(values_in) {
-    const int64_t nnz = p > 0 ? colptr[p] : 0;
-    bool ascending = true;
-    for (int j = 0; j < p && ascending; ++j)
-      for (int64_t q = (int64_t)colptr[j] + 1; q < colptr[j + 1]; ++q)
-        if (rowidx[q] <= rowidx[q - 1]) {
-          ascending = false;
-          break;
-        }
-    if (ascending) return;
-    rows_sorted.assign(rowidx, rowidx + nnz);
-    vals_sorted.assign(values, values + nnz);
-    std::vector<int64_t> order;
-    for (int j = 0; j < p; ++j) {
-      const int64_t q0 = colptr[j], q1 = colptr[j + 1];
-      order.resize((size_t)(q1 - q0));
-      std::iota(order.begin(), order.end(), q0);
-      std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return rowidx[a] < rowidx[b]; });
-      for (int64_t q = q0; q < q1; ++q) {
-        rows_sorted[(size_t)q] = rowidx[order[(size_t)(q - q0)]];
-        vals_sorted[(size_t)q] = values[order[(size_t)(q - q0)]];
-      }
-    }
-    rowidx = rows_sorted.data();
-    values = vals_sorted.data();
-  }
-};
-
-// dense x: the rows one chunk of the moments pass takes (a function of n and the number of tile pairs alone)
-int64_t dense_rows_per_chunk(int64_t n, int pairs) {
-  const int64_t chunk_cap = std::max<int64_t>(16, std::min<int64_t>(256, 1024 / pairs));
-  const int64_t chunks = std::min<int64_t>(chunk_cap, (n + 255) / 256);
-  return ((n + chunks - 1) / chunks + kTileRows - 1) / kTileRows * kTileRows;
-}
 
 }  // namespace
 

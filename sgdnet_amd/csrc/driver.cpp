@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "covariance.hpp"
 #include "fit_plan.hpp"
+#include "newton.hpp"
 #include "setup_device.hpp"
 
 using namespace sgdnet;
@@ -62,7 +63,7 @@ struct Features {
   hipStream_t st = nullptr;
   double dev_max_mean_sq = 0.0;
   bool dense_dev = false;       // dense x prepared by dense_setup_* (large matrices)
-  // x as it came (covariance mode takes its moments from it): the column-major matrix, or the dgCMatrix values
+  // x as it came (covariance and Newton mode take their moments from it): the column-major matrix, or the dgCMatrix values
   const double* raw_dense = nullptr;
   const double* raw_values = nullptr;
 };
@@ -1021,6 +1022,62 @@ int fit_covariance(const Features& X, const Response& R, const Path& path, const
   return SGDNET_OK;
 }
 
+// ---- Newton mode (SGDNET_MODE_NEWTON, newton.hip): the stage behind the plan ----
+// The same preprocessed problem as above, for a binomial response: the features centred where fit_covariance centres
+// them, the class codes as they came, the intercept an unpenalised coordinate that starts at the null model's value
+// (and stays there without an intercept).
+int fit_newton(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl, sgdnet_result* out,
+               PhaseTimer& pt) {
+  const int64_t n = X.n, p = X.p;
+  const int L = ctl->n_lambda;
+  NewtonProblem pb;
+  pb.n = n;
+  pb.p = p;
+  if (X.sparse) {
+    pb.colptr = X.colptr;
+    pb.rowidx = X.rowidx;
+    pb.values = X.raw_values;
+  } else {
+    pb.x_dense = X.raw_dense;
+  }
+  pb.y = R.y.data();
+  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
+  pb.scale = X.x_scale.data();
+  pb.fit_intercept = ctl->intercept != 0;
+  pb.b0 = R.b0[0];
+  pb.device = plan.rank_dev[0];
+  pb.n_lambda = L;
+  pb.alpha = path.alpha.data();
+  pb.beta = path.beta.data();
+  pb.ridge = plan.penalty == SGDNET_RIDGE;
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  NewtonResult nr;
+  const int rc = newton_run(pb, pt.on, &nr);
+  if (rc) return rc;
+  double n_steps = 0.0;
+  for (int li = 0; li < L; ++li) {
+    const double* u = nr.u.data() + (size_t)li * (size_t)(p + 1);
+    double shift = 0.0;
+    for (int64_t j = 0; j < p; ++j) shift += (nr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j] * u[j];
+    // Family::Loss summed over the samples, doubled (families.h; saga_loss_kernel): the state pass left its mean
+    out->dev_ratio[li] = 1.0 - 2.0 * (double)n * nr.loss[(size_t)li] / R.null_dev_scaled;
+    out->lambda[li] = path.lambda[(size_t)li];
+    out->return_codes[li] = nr.unconverged[(size_t)li] ? 1.0 : 0.0;
+    n_steps += (double)nr.steps[(size_t)li];
+    // the intercept of the preprocessed problem: the one at the centres less the centres' distance from x_center times w
+    const double b = ctl->intercept != 0 ? u[p] - shift : R.b0[0];
+    rescale_values(X, R, ctl, li, u, &b, out);
+  }
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   newton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
+            "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);
+  out->npasses = nr.passes;
+  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
+  pt.mark("newton (state + moments + cd)");
+  return SGDNET_OK;
+}
+
 // *batched_gave_up: the batched iteration gave up on this fit (mode = auto then runs it again in exact mode)
 int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ctl, sgdnet_result* out, bool* batched_gave_up) {
   const int K = ctl->n_classes;
@@ -1041,7 +1098,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   Path path;
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
-  if (ctl->mode == SGDNET_MODE_COVARIANCE) {   // plan_fit says whether it may run; it needs none of the SAGA setup below
+  if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON) {   // plan_fit says whether they may run; they need none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1052,7 +1109,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
       set_error("%s", plan.error.c_str());
       return plan.rc;
     }
-    return fit_covariance(X, R, path, plan, ctl, out, pt);
+    return ctl->mode == SGDNET_MODE_NEWTON ? fit_newton(X, R, path, plan, ctl, out, pt) : fit_covariance(X, R, path, plan, ctl, out, pt);
   }
   double norm_max = 0.0;
   rc = row_norm_max(X, ctl, R, Ky, trace, &norm_max);
@@ -1333,7 +1390,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     col_mean_sd(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
-  if (ctl->mode != SGDNET_MODE_COVARIANCE) {                  // (covariance mode reads x column-major, as it came)
+  if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON) {   // (those modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "covariance.hpp"
+#include "newton.hpp"
 #include "sgdnet_hip.h"
 
 namespace sgdnet {
@@ -70,7 +71,7 @@ struct FitFacts {
 // SGDNET_MODE_BATCHED means "batched where it is implemented": more than 64 classes run the exact
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
-// An unknown mode comes back as it is (plan_fit refuses it), and so does SGDNET_MODE_COVARIANCE: no other mode resolves to it.
+// An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE and SGDNET_MODE_NEWTON: no other mode resolves to them.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -141,6 +142,27 @@ inline FitPlan plan_fit(const FitFacts& f) {
       return P;
     }
     P.mode = SGDNET_MODE_COVARIANCE;
+    P.rank_dev.assign(1, c.device);
+    P.rank_lo = {0, n};
+    return P;                          // no window, no shards, no draws
+  }
+
+  // ---- Newton mode: likewise only where it was asked for (it draws nothing and stops elsewhere than SAGA does), and
+  // only for the problem its inner solve holds in one workgroup's LDS (newton.hpp); no silent fall back ----
+  if (c.mode == SGDNET_MODE_NEWTON) {
+    const char* what = nullptr;
+    if (family != SGDNET_BINOMIAL) what = "family = binomial";
+    else if (K != 1) what = "one response (n_classes = 1)";
+    else if (f.p > kNewtonMaxFeatures) what = "no more features than sgdnet_newton_max_features()";
+    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+    if (what) {
+      P.rc = SGDNET_EUNSUPPORTED;
+      P.error = plan_text("mode = newton needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, family,
+                          (long long)f.p, kNewtonMaxFeatures, c.n_gpus, c.debug);
+      return P;
+    }
+    P.mode = SGDNET_MODE_NEWTON;
     P.rank_dev.assign(1, c.device);
     P.rank_lo = {0, n};
     return P;                          // no window, no shards, no draws

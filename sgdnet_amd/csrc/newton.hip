@@ -1,0 +1,543 @@
+// Newton mode (SGDNET_MODE_NEWTON): the binomial elastic-net path of one response by proximal Newton steps (IRLS).
+//
+// The problem is the one every mode fits (sgdnet_amd/kkt.py): features z_j = (x_j - m_j) / s_j, u = (w, b),
+//     F(u) = (1/n) sum_i [log(1 + e^eta_i) - y_i eta_i] + alpha/2 |w|^2 + beta |w|_1,     eta_i = b + z_i'w,
+// b unpenalised (or frozen at the null model's value), alpha and beta the driver's (regularization_path).  m are the
+// fixed, unweighted column means of cov_sum_kernel (0 where the fit centres nothing): the optimum does not depend on
+// them, the conditioning of the quadratic model does.  One outer step from the iterate u0, warm-started lambda to lambda:
+//
+//   state      newton_state_kernel: eta_i, t_i = 1 / (1 + e^eta_i), v_i = t_i (1 - t_i), r_i = y_i - mu_i and the loss,
+//              a thread per sample; exp / log are the plain-IEEE ones of include/sgdnet_detmath.h.  Deviations are
+//              formed BEFORE they are multiplied: (x_ij - m_j) (w_j / s_j).  Dense x is read column-major; sparse x
+//              is read from the sample-major copy of device_transpose, whose rows hold their columns in ascending
+//              order: one walk over j = 0 .. p - 1 takes the stored value or 0 (no m'w subtracted from a sum afterwards).
+//              newton_finish_kernel adds the workgroups' sums of loss, v and r in workgroup order.
+//   moments    H = (1/n) sum_i v_i [x_i - m | 1][x_i - m | 1]',  q = (1/n) sum_i r_i [x_i - m | 1]   (f64; the 1/n and the
+//              driver's s_j are applied when the inner solve loads them), as an upper triangle of (p + 2)^2: column p
+//              is the ones, column p + 1 is q.
+//              dense x   newton_dense_tile_kernel: cov_dense_tile_kernel with the rows of the second tile weighted at
+//                        staging (v_i; the q column is staged as r_i); cov_reduce_kernel adds the chunks in chunk order.
+//              sparse x  newton_sparse_pair_kernel: a workgroup owns a pair of columns, centred implicitly with weights:
+//                          H_jk = sum_{J and K} v d_j d_k - m_k sum_{J \ K} v d_j - m_j sum_{K \ J} v d_k
+//                                 + (V - sum_{J or K} v) m_j m_k,      d = stored value - mean,  V = sum_i v_i,
+//                        the ones column  sum_J v d_j - m_j (V - sum_J v)  and q_j = sum_J r d_j - m_j (R - sum_J r),
+//                        R = sum_i r_i; a column that stores every row leaves nothing outside it (an exact 0).
+//   inner      newton_cd_kernel: ONE wavefront keeps H (packed triangle), u and g = H (u - u0) - q in LDS (newton.hpp:
+//              the budget behind sgdnet_newton_max_features) and runs cyclic coordinate descent with the update rule
+//              and the uniform-scalar style of cov_path_kernel; the last coordinate, the intercept, has no penalty
+//              and no threshold.  A sweep ends with the reference's ConvergenceCheck over all of u.
+//   accept     the state pass at the candidate gives its objective; the host halves a step after which it rose
+//              (newton_blend_kernel) and evaluates again, at most kNewtonMaxHalvings times.  The accepted candidate's
+//              state pass is the next step's: it costs no extra pass.
+//
+// The outer loop is the host's (newton_run): separate launches on one stream and one small record read back per state
+// pass.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz): the same input gives
+// the same bits.
+#define SGDNET_DET_MATH
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "common.hpp"
+#include "device_math.hpp"
+#include "moments_device.hpp"
+#include "newton.hpp"
+#include "setup_device.hpp"
+
+namespace sgdnet {
+namespace {
+
+constexpr int kStateMaxBlocks = 1024;   // workgroups of the state pass: each leaves three sums
+
+// the record of a candidate, in device memory; the host reads it after every state pass
+enum Rec { kRecLoss = 0, kRecHalfSq, kRecAbs, kRecChange, kRecSize, kRecSweeps, kRecInnerConverged, kRecNegligible, kRecLen };
+
+// a[j] = w_j / s_j (j < p), a[p] = b: the candidate as the state pass multiplies it.  Workgroup b leaves its sums of
+// the loss, v and r in partial[3 b ..].
+template <bool kSparse>
+__global__ __launch_bounds__(kBlock) void newton_state_kernel(const double* __restrict__ x, const int64_t* __restrict__ sptr,
+                                                               const int32_t* __restrict__ sidx, const double* __restrict__ y,
+                                                               const double* __restrict__ mu, const double* __restrict__ a, int64_t n,
+                                                               int p, int centre, double* __restrict__ v, double* __restrict__ r,
+                                                               double* __restrict__ partial) {
+  __shared__ double sh[kBlock];
+  double loss = 0.0, vs = 0.0, rs = 0.0;
+  const double b = a[p];
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    double eta = 0.0;
+    if (kSparse) {
+      int64_t q = sptr[i];
+      const int64_t q1 = sptr[i + 1];
+      if (centre) {
+        for (int j = 0; j < p; ++j) {
+          double d = -mu[j];
+          if (q < q1 && sidx[q] == j) d = x[q++] - mu[j];
+          eta += d * a[j];
+        }
+      } else {
+        for (; q < q1; ++q) eta += x[q] * a[sidx[q]];
+      }
+    } else {
+      for (int j = 0; j < p; ++j) eta += (x[i + (int64_t)j * n] - mu[j]) * a[j];
+    }
+    eta += b;
+    const double yi = y[i];
+    const double e = SGD_EXP(eta);
+    const double t = 1.0 / (1.0 + e);
+    const double vi = t * (1.0 - t), ri = t - (1.0 - yi);     // y - mu, mu = 1 - t (families.h: Gradient = 1 - y - t)
+    v[i] = vi;
+    r[i] = ri;
+    loss += SGD_LOG(1.0 + e) - yi * eta;
+    vs += vi;
+    rs += ri;
+  }
+  loss = block_sum(loss, sh);
+  vs = block_sum(vs, sh);
+  rs = block_sum(rs, sh);
+  if (threadIdx.x == 0) {
+    partial[3 * blockIdx.x] = loss;
+    partial[3 * blockIdx.x + 1] = vs;
+    partial[3 * blockIdx.x + 2] = rs;
+  }
+}
+
+// one workgroup: the sums of the state pass added in workgroup order; rec gets the mean loss, sums = (V, R)
+__global__ __launch_bounds__(kBlock) void newton_finish_kernel(const double* __restrict__ partial, int blocks, int64_t n,
+                                                                double* __restrict__ sums, double* __restrict__ rec) {
+  __shared__ double sh[kBlock];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < blocks; b += kBlock)
+    for (int c = 0; c < 3; ++c) s[c] += partial[3 * b + c];
+  for (int c = 0; c < 3; ++c) s[c] = block_sum(s[c], sh);
+  if (threadIdx.x == 0) {
+    rec[kRecLoss] = s[0] / (double)n;
+    sums[0] = s[1];
+    sums[1] = s[2];
+  }
+}
+
+// cov_dense_tile_kernel for the rows [x - mu | 1 | r] with the second tile's rows weighted: entry (a, b), a <= b, of the
+// (p + 2)^2 matrix is sum_i A_ia B_ib with A = [x - mu | 1 | 0] and B = [v (x - mu) | v | r].
+__global__ __launch_bounds__(kBlock) void newton_dense_tile_kernel(const double* __restrict__ x, const double* __restrict__ v,
+                                                                    const double* __restrict__ r, const double* __restrict__ mu,
+                                                                    int64_t n, int p, int64_t rows_per_chunk, double* __restrict__ part) {
+  __shared__ double A[kTileCols][kTileRows + 1], B[kTileCols][kTileRows + 1];
+  const int tid = threadIdx.x, ncols = p + 2;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  const int ta = tid & (kTileCols - 1), tb = tid / kTileCols;
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+  const int64_t r1 = r0 + rows_per_chunk < n ? r0 + rows_per_chunk : n;
+  auto dev = [&](int a, int64_t i) -> double {          // column a of [x - mu | 1], 0 outside it
+    if (i >= r1 || a > p) return 0.0;
+    return a < p ? x[i + (int64_t)a * n] - mu[a] : 1.0;
+  };
+  double acc = 0.0;
+  for (int64_t base = r0; base < r1; base += kTileRows) {
+    for (int e = tid; e < kTileCols * kTileRows; e += kBlock) {
+      const int row = e & (kTileRows - 1), col = e / kTileRows;
+      const int64_t i = base + row;
+      const int b = tk * kTileCols + col;
+      A[col][row] = dev(tj * kTileCols + col, i);
+      B[col][row] = i >= r1 ? 0.0 : (b == p + 1 ? r[i] : v[i] * dev(b, i));
+    }
+    __syncthreads();
+    for (int i = 0; i < kTileRows; ++i) acc += A[ta][i] * B[tb][i];
+    __syncthreads();
+  }
+  part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kBlock + tid] = acc;
+}
+
+// blockIdx.x = column j < p, blockIdx.y = column k in [j, p + 1]; k == p is the ones, k == p + 1 is q.  sums = (V, R).
+// The workgroup (0, p) also leaves the corner (ones, ones) = V and (0, p + 1) leaves q of the ones, R.
+__global__ __launch_bounds__(kBlock) void newton_sparse_pair_kernel(const int32_t* __restrict__ colptr, const int32_t* __restrict__ rowidx,
+                                                                     const double* __restrict__ val, const double* __restrict__ v,
+                                                                     const double* __restrict__ r, const double* __restrict__ mu,
+                                                                     const double* __restrict__ sums, int64_t n, int p,
+                                                                     double* __restrict__ M) {
+  __shared__ double sh[kBlock];
+  const int j = blockIdx.x, k = blockIdx.y, nc = p + 2, tid = threadIdx.x;
+  if (k < j) return;
+  const int q0 = colptr[j], q1 = colptr[j + 1];
+  const double mj = mu[j];
+  const bool j_full = (int64_t)(q1 - q0) == n;
+  if (k >= p) {                                  // against the ones (weights v) or q (weights r)
+    const double* wt = k == p ? v : r;
+    double a = 0.0, ws = 0.0;
+    for (int q = q0 + tid; q < q1; q += kBlock) {
+      const double wi = wt[rowidx[q]];
+      a += wi * (val[q] - mj);
+      ws += wi;
+    }
+    a = block_sum(a, sh);
+    ws = block_sum(ws, sh);
+    if (tid == 0) {
+      const double total = sums[k - p];
+      M[(size_t)j * nc + k] = a - mj * (j_full ? 0.0 : total - ws);
+      if (j == 0) M[(size_t)p * nc + k] = total;
+    }
+    return;
+  }
+  const int s0 = colptr[k], s1 = colptr[k + 1];
+  const double mk = mu[k];
+  double both = 0.0, only_j = 0.0, only_k = 0.0, v_union = 0.0;
+  for (int q = q0 + tid; q < q1; q += kBlock) {
+    const int32_t row = rowidx[q];
+    const double vi = v[row], d = val[q] - mj;
+    v_union += vi;
+    const int pos = j == k ? q : lower_bound_row(rowidx, s0, s1, row);
+    if (pos < s1 && rowidx[pos] == row) both += vi * d * (val[pos] - mk);
+    else only_j += vi * d;
+  }
+  if (j != k)
+    for (int s = s0 + tid; s < s1; s += kBlock) {
+      const int32_t row = rowidx[s];
+      const int pos = lower_bound_row(rowidx, q0, q1, row);
+      if (!(pos < q1 && rowidx[pos] == row)) {
+        const double vi = v[row];
+        only_k += vi * (val[s] - mk);
+        v_union += vi;
+      }
+    }
+  both = block_sum(both, sh);
+  only_j = block_sum(only_j, sh);
+  only_k = block_sum(only_k, sh);
+  v_union = block_sum(v_union, sh);
+  if (tid == 0) {
+    const bool full = j_full || (int64_t)(s1 - s0) == n;
+    const double in_neither = full ? 0.0 : sums[0] - v_union;
+    M[(size_t)j * nc + k] = both - mk * only_j - mj * only_k + in_neither * mj * mk;
+  }
+}
+
+// What a candidate un[0 .. P) leaves behind, by one wavefront: itself and its state-pass form a (w_j / s_j, b) in
+// memory, and in the record its penalty terms |w|^2 / 2 and |w|_1, its distance from the iterate max|un - u_cur| and
+// its size max|un|.  Lane l takes the coordinates l, l + 64, ... in order; the lanes are joined by a butterfly.
+template <class UP>
+__device__ __forceinline__ void publish_candidate(UP un, const double* __restrict__ u_cur, const double* __restrict__ scale, int p,
+                                                  double* __restrict__ u_cand, double* __restrict__ a_cand, double* __restrict__ rec) {
+  const int lane = threadIdx.x;
+  double sq = 0.0, ab = 0.0, ch = 0.0, sz = 0.0;
+  for (int k = lane; k <= p; k += 64) {
+    const double uk = un[k];
+    ch = fmax(ch, fabs(uk - u_cur[k]));
+    sz = fmax(sz, fabs(uk));
+    if (k < p) {
+      sq += uk * uk;
+      ab += fabs(uk);
+    }
+    u_cand[k] = uk;
+    a_cand[k] = k < p ? uk / scale[k] : uk;
+  }
+  sq = wave_sum(sq);
+  ab = wave_sum(ab);
+  ch = wave_max(ch);
+  sz = wave_max(sz);
+  if (lane == 0) {
+    rec[kRecHalfSq] = 0.5 * sq;
+    rec[kRecAbs] = ab;
+    rec[kRecChange] = ch;
+    rec[kRecSize] = sz;
+  }
+}
+
+// u_cand <- u_cur + t (u_cand - u_cur)   (t = 1: the candidate as it is; the path's start is published this way)
+__global__ __launch_bounds__(64) void newton_blend_kernel(const double* __restrict__ u_cur, const double* __restrict__ scale, int p,
+                                                           double t, double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                           double* __restrict__ rec) {
+  __shared__ double un[kNewtonMaxFeatures + 1];
+  for (int k = threadIdx.x; k <= p; k += 64) un[k] = t == 1.0 ? u_cand[k] : u_cur[k] + t * (u_cand[k] - u_cur[k]);
+  __syncthreads();
+  publish_candidate(un, u_cur, scale, p, u_cand, a_cand, rec);
+}
+
+// One wavefront, one inner solve.  Every lane computes the sweep's scalars (the new coordinate, the sweep's max|du| and
+// max|u|) from the same LDS words, so branches on them are uniform and nothing has to be broadcast (cov_path_kernel).
+// M: the (p + 2)^2 moments (upper triangle), dn = n; the quadratic model about u_cur is
+//   (u - u_cur)'H (u - u_cur) / 2 - q'(u - u_cur) + al/2 |w|^2 + be |w|_1,     its smooth gradient g = H (u - u_cur) - q.
+__global__ __launch_bounds__(64) void newton_cd_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, double dn,
+                                                        const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                        int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                        double* __restrict__ a_cand, double* __restrict__ rec) {
+  __shared__ double lds[newton_state_doubles(kNewtonMaxFeatures)];
+  const int lane = threadIdx.x, P = p + 1, nc = p + 2;
+  double* H = lds;
+  double* u = H + P * (P + 1) / 2;
+  double* g = u + P;
+  for (int k = 0; k < P; ++k) {
+    const double sk = k < p ? scale[k] : 1.0;
+    for (int j = lane; j <= k; j += 64) H[tri(j, k)] = M[(size_t)j * nc + k] / dn / ((j < p ? scale[j] : 1.0) * sk);
+  }
+  for (int k = lane; k < P; k += 64) {
+    g[k] = -(M[(size_t)k * nc + p + 1] / dn / (k < p ? scale[k] : 1.0));
+    u[k] = u_cur[k];
+  }
+  __syncthreads();
+  const int n_coord = fit_intercept ? P : p;     // (the frozen intercept is never visited: it stays at u_cur[p])
+  unsigned sweeps = 0;
+  bool converged = false, negligible = false;
+  while (sweeps < max_sweeps && !converged) {
+    double max_change = 0.0, max_size = 0.0, max_eta_sq = 0.0;
+    for (int j = 0; j < n_coord; ++j) {
+      const bool penalised = j < p;
+      const double uj = u[j], hjj = H[tri(j, j)];
+      const double z = hjj * uj - g[j], denom = penalised ? hjj + al : hjj;
+      double nu = z;
+      if (penalised && !ridge) nu = z > be ? z - be : (z < -be ? z + be : 0.0);
+      // a constant column without an l2 term: H_jj = q_j = 0; every weight underflowed: the intercept stays
+      nu = denom > 0.0 ? nu / denom : (penalised ? 0.0 : uj);
+      const double d = nu - uj;
+      max_change = fmax(max_change, fabs(d));
+      max_size = fmax(max_size, fabs(nu));
+      max_eta_sq = fmax(max_eta_sq, nu * nu * hjj);
+      if (d != 0.0) {
+        __syncthreads();                         // every lane has read u[j] and g[j]
+        if (lane == 0) u[j] = nu;
+        for (int k = lane; k < P; k += 64) g[k] += H[k <= j ? tri(k, j) : tri(j, k)] * d;
+        __syncthreads();
+      }
+    }
+    ++sweeps;
+    const bool all_zero = max_size == 0.0 && max_change == 0.0;
+    const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+    negligible = max_eta_sq <= kNewtonNegligible * kNewtonNegligible;      // zero to rounding (newton.hpp)
+    converged = all_zero || no_change || negligible;
+  }
+  __syncthreads();
+  publish_candidate(u, u_cur, scale, p, u_cand, a_cand, rec);
+  if (lane == 0) {
+    rec[kRecSweeps] = (double)sweeps;
+    rec[kRecInnerConverged] = converged ? 1.0 : 0.0;
+    rec[kRecNegligible] = negligible ? 1.0 : 0.0;
+  }
+}
+
+struct Stream {
+  hipStream_t st = nullptr;
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* rec_host = nullptr;          // pinned: the record of a state pass
+  DeviceSetup S;                       // sparse x: the sample-major copy (the feature-major one lives in the arena)
+  ~Stream() {
+    S.release();
+    for (hipEvent_t v : e)
+      if (v) (void)hipEventDestroy(v);
+    if (rec_host) (void)hipHostFree(rec_host);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+}  // namespace
+
+int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
+  const int64_t n = pb.n;
+  const int p = (int)pb.p, P = p + 1, nc = p + 2, L = pb.n_lambda;
+  const bool sparse = pb.x_dense == nullptr;
+  if (n <= 0 || pb.p <= 0 || pb.p > kNewtonMaxFeatures || L <= 0 || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("newton_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+
+  // dense x: the tile pairs and the row chunks (a function of n and p alone)
+  const int T = (nc + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
+  const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+  const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+  const int state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
+
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_v = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_r = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)nc);          // cov_sum_kernel: the means, then the sum and the mean of y
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
+  const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
+  const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
+  const size_t o_partial = A.reserve(sizeof(double) * 3 * (size_t)state_blocks);
+  const size_t o_sums = A.reserve(sizeof(double) * 2);
+  const size_t o_rec = A.reserve(sizeof(double) * kRecLen);
+  const size_t o_u0 = A.reserve(sizeof(double) * (size_t)P);
+  const size_t o_u1 = A.reserve(sizeof(double) * (size_t)P);
+  const size_t o_a = A.reserve(sizeof(double) * (size_t)P);
+  const size_t o_U = A.reserve(sizeof(double) * (size_t)L * (size_t)P);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Stream sx;
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
+  SGD_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sx.rec_host), sizeof(double) * kRecLen, hipHostMallocDefault));
+  if (timed)
+    for (hipEvent_t& e : sx.e) SGD_HIP_TRY(hipEventCreate(&e));
+  hipStream_t st = sx.st;
+  double* d_x = A.at<double>(o_x);
+  int32_t* d_colptr = A.at<int32_t>(o_colptr);
+  int32_t* d_rowidx = A.at<int32_t>(o_rowidx);
+  double* d_y = A.at<double>(o_y);
+  double* d_v = A.at<double>(o_v);
+  double* d_r = A.at<double>(o_r);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_scale = A.at<double>(o_scale);
+  double* d_M = A.at<double>(o_M);
+  double* d_partial = A.at<double>(o_partial);
+  double* d_sums = A.at<double>(o_sums);
+  double* d_rec = A.at<double>(o_rec);
+  double* d_a = A.at<double>(o_a);
+  double* d_cur = A.at<double>(o_u0);
+  double* d_cand = A.at<double>(o_u1);
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
+    DeviceSetup& S = sx.S;
+    S.n = n;
+    S.p = p;
+    S.nnz = nnz;
+    if (nnz > 0) {
+      S.colptr = d_colptr;
+      S.rowidx = d_rowidx;
+      S.val = d_x;
+      const int rc = device_transpose(S, st);
+      S.colptr = S.rowidx = nullptr;               // the arena owns the feature-major copy; S the sample-major one
+      S.val = nullptr;
+      if (rc) return rc;
+    } else {                                       // nothing stored: every row is empty
+      SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.sptr), sizeof(int64_t) * ((size_t)n + 1)));
+      SGD_HIP_TRY(hipMemsetAsync(S.sptr, 0, sizeof(int64_t) * ((size_t)n + 1), st));
+    }
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
+  std::vector<double> start((size_t)P, 0.0);
+  start[(size_t)p] = pb.b0;
+  SGD_HIP_TRY(hipMemcpyAsync(d_cur, start.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_cand, start.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen, st));
+  if (sparse)
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, pb.centre ? 1 : 0, d_mu);
+  else
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
+                       pb.centre ? 1 : 0, d_mu);
+  SGD_HIP_TRY(hipGetLastError());
+
+  out->passes = out->sweeps = out->halvings = 0.0;
+  out->state_ms = out->moments_ms = out->cd_ms = 0.f;
+  const double* rec = sx.rec_host;
+  // the state pass at the candidate and its record; *before: the events around the step's earlier kernels
+  auto evaluate = [&]() -> int {
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
+    if (sparse)
+      hipLaunchKernelGGL(newton_state_kernel<true>, dim3((unsigned)state_blocks), dim3(kBlock), 0, st, sx.S.sval, sx.S.sptr, sx.S.sidx, d_y,
+                         d_mu, d_a, n, p, pb.centre ? 1 : 0, d_v, d_r, d_partial);
+    else
+      hipLaunchKernelGGL(newton_state_kernel<false>, dim3((unsigned)state_blocks), dim3(kBlock), 0, st, d_x, (const int64_t*)nullptr,
+                         (const int32_t*)nullptr, d_y, d_mu, d_a, n, p, 1, d_v, d_r, d_partial);
+    hipLaunchKernelGGL(newton_finish_kernel, dim3(1), dim3(kBlock), 0, st, d_partial, state_blocks, n, d_sums, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[3], st));
+    SGD_HIP_TRY(hipMemcpyAsync(sx.rec_host, d_rec, sizeof(double) * kRecLen, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipStreamSynchronize(st));
+    out->passes += 1.0;
+    if (timed) {
+      float ms = 0.f;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
+      out->state_ms += ms;
+    }
+    return SGDNET_OK;
+  };
+  auto blend = [&](double t) -> int {
+    hipLaunchKernelGGL(newton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, t, d_cand, d_a, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  };
+
+  // the path's start: w = 0, b = b0
+  int rc = blend(1.0);
+  if (!rc) rc = evaluate();
+  if (rc) return rc;
+  double loss = rec[kRecLoss], half_sq = rec[kRecHalfSq], abs1 = rec[kRecAbs];
+
+  out->loss.assign((size_t)L, 0.0);
+  out->steps.assign((size_t)L, 0);
+  out->unconverged.assign((size_t)L, 0);
+  for (int l = 0; l < L; ++l) {
+    const double al = pb.alpha[l], be = pb.ridge ? 0.0 : pb.beta[l];
+    double objective = loss + al * half_sq + be * abs1;
+    unsigned steps = 0;
+    bool converged = false;
+    while (steps < pb.max_iter && !converged) {
+      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
+      if (sparse) {
+        hipLaunchKernelGGL(newton_sparse_pair_kernel, dim3((unsigned)p, (unsigned)nc), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_v,
+                           d_r, d_mu, d_sums, n, p, d_M);
+      } else {
+        hipLaunchKernelGGL(newton_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_v, d_r, d_mu, n,
+                           p, rows_per_chunk, A.at<double>(o_part));
+        hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                           (const int32_t*)nullptr, nc, d_M);
+      }
+      SGD_HIP_TRY(hipGetLastError());
+      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
+      hipLaunchKernelGGL(newton_cd_kernel, dim3(1), dim3(64), 0, st, d_M, d_scale, p, (double)n, d_cur, al, be, pb.ridge ? 1 : 0,
+                         pb.fit_intercept ? 1 : 0, kNewtonMaxSweeps, pb.tol, d_cand, d_a, d_rec);
+      SGD_HIP_TRY(hipGetLastError());
+      if ((rc = evaluate())) return rc;
+      if (timed) {
+        float ms = 0.f;
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[0], sx.e[1]));
+        out->moments_ms += ms;
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[2]));
+        out->cd_ms += ms;
+      }
+      out->sweeps += rec[kRecSweeps];
+      bool negligible = rec[kRecNegligible] != 0.0;
+      double candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
+      // (a candidate whose objective is not a number counts as one that rose)
+      for (int h = 0; h < kNewtonMaxHalvings && rec[kRecChange] > 0.0 && !(candidate <= objective + kNewtonObjectiveSlack * fabs(objective)); ++h) {
+        if ((rc = blend(0.5)) || (rc = evaluate())) return rc;
+        candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
+        out->halvings += 1.0;
+        negligible = false;              // (the inner solve said so of the whole step, not of a part of it)
+      }
+      std::swap(d_cur, d_cand);
+      objective = candidate;
+      loss = rec[kRecLoss];
+      half_sq = rec[kRecHalfSq];
+      abs1 = rec[kRecAbs];
+      ++steps;
+      const double change = rec[kRecChange], size = rec[kRecSize];
+      const bool all_zero = size == 0.0 && change == 0.0;
+      const bool no_change = size != 0.0 && change / size <= pb.tol;
+      converged = rec[kRecInnerConverged] != 0.0 && (all_zero || no_change || negligible);
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_U) + (size_t)l * (size_t)P, d_cur, sizeof(double) * (size_t)P, hipMemcpyDeviceToDevice, st));
+    out->loss[(size_t)l] = loss;
+    out->steps[(size_t)l] = (int32_t)steps;
+    out->unconverged[(size_t)l] = converged ? 0 : 1;
+  }
+
+  out->mean.resize((size_t)p);
+  out->u.resize((size_t)L * (size_t)P);
+  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), d_mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), A.at<double>(o_U), sizeof(double) * (size_t)L * (size_t)P, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  return SGDNET_OK;
+}
+
+}  // namespace sgdnet
+
+extern "C" int sgdnet_newton_max_features(void) { return sgdnet::kNewtonMaxFeatures; }

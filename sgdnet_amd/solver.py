@@ -120,6 +120,11 @@ def covariance_max_features():
     return int(_lib.load().sgdnet_covariance_max_features())
 
 
+def newton_max_features():
+    """Largest number of features sgdnet_newton() takes (sgdnet_newton_max_features of the C ABI)."""
+    return int(_lib.load().sgdnet_newton_max_features())
+
+
 class SagaSolver:
     """One problem resident in HBM: sample-major x, y and the five SAGA state arrays
     (reference src/sgdnet.cpp:187-198).
