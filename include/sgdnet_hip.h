@@ -562,6 +562,45 @@ int sgdnet_setup_probe_sparse(const sgdnet_csc* x, int standardize, const double
 int sgdnet_setup_probe_dense(const double* x, int64_t n, int64_t p, int standardize, const double* ymap, int cols,
                              int64_t sample_stride, int64_t sample_m, int device, sgdnet_setup_probe* out);
 
+/* Newton mode (sgdnet_amd/csrc/newton.hip), one outer step pass by pass.  The probes go through the host steps a fit
+ * goes through (setup and upload, publish / blend, state pass, moments pass, inner solve): the same kernels on the same
+ * grids in the same order, every output copied back; tests compare each with an exact reference
+ * (tests/test_gpu_newton_passes.py).  The candidate u is published as it is (newton_blend_kernel at t = 1); the state
+ * pass is taken there; the moments are those of that state; the inner solve runs on them about u_cur; last, u is
+ * blended with u_cur at t.  Every pointer is a caller-allocated HOST buffer; a NULL output pointer skips that output.
+ * SGDNET_EINVAL: a missing input, n or p < 1, max_sweeps = 0.  SGDNET_EUNSUPPORTED ("mode = newton needs ..."): more
+ * than sgdnet_newton_max_features() features. */
+typedef struct sgdnet_newton_probe {
+  /* inputs */
+  const double* y;         /* n: class codes 0 / 1                                                   */
+  const double* scale;     /* p: the sd feature j is standardised with                               */
+  const double* u_cur;     /* p + 1: the iterate (coefficients of the standardised problem, intercept) */
+  const double* u;         /* p + 1: the candidate the state is taken at                             */
+  double   t;              /* blend factor                                                           */
+  double   l2, l1, tol;    /* the inner solve's penalty strengths and tolerance                      */
+  int      centre, ridge, fit_intercept;
+  unsigned max_sweeps;
+  /* outputs */
+  double*  mean;           /* p: cov_sum_kernel's column means (0 where centre is 0)                 */
+  double*  pub_u;          /* p + 1: u after the publish at t = 1 ...                                */
+  double*  pub_a;          /* p + 1: ... its state-pass form (w_j / s_j, b) ...                      */
+  double   pub_rec[4];     /* ... and its record: |w|^2 / 2, |w|_1, max|u - u_cur|, max|u|            */
+  double*  blend_u;        /* the same three after the blend at t                                    */
+  double*  blend_a;
+  double   blend_rec[4];
+  double*  v;              /* n: the weights t (1 - t) of the state pass                             */
+  double*  r;              /* n: its residuals y - mu                                                */
+  double   loss, V, R;     /* the mean loss, sum v, sum r (newton_finish_kernel)                     */
+  double*  M;              /* (p + 2)^2, row-major: entries (j, k), j <= k, of the moments of [x - m | 1 | q] (column p
+                              the ones, column p + 1 q) and the corners (p, p) = V, (p, p + 1) = R; nothing else is defined */
+  double*  cd_u;           /* p + 1: the inner solve's candidate ...                                 */
+  double*  cd_a;           /* p + 1                                                                  */
+  double   cd_rec[8];      /* ... and the whole record: loss, |w|^2 / 2, |w|_1, change, size, sweeps, converged, negligible */
+} sgdnet_newton_probe;
+
+int sgdnet_newton_probe_dense(const double* x, int64_t n, int64_t p, int device, sgdnet_newton_probe* io);
+int sgdnet_newton_probe_sparse(const sgdnet_csc* x, int device, sgdnet_newton_probe* io);
+
 /* ------------------------------------------------------------------------ */
 /* Cross-validation in covariance mode (additions only; the ABI version      */
 /* stays): every fold fit of every elastic-net mix in ONE call.  Rows carry a */

@@ -36,6 +36,7 @@ EXPORTS = [
     "sgdnet_gradient_sparse", "sgdnet_gradient_dense", "sgdnet_covariance_max_features",
     "sgdnet_setup_probe_sparse", "sgdnet_setup_probe_dense",
     "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse", "sgdnet_newton_max_features",
+    "sgdnet_newton_probe_dense", "sgdnet_newton_probe_sparse",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -102,6 +103,19 @@ class SetupProbe(C.Structure):
                 ("rec_stride", C.c_int), ("rec_cap", C.c_int), ("rec_val_off", C.c_int), ("n_ovf", C.c_int64),
                 ("l_f", C.c_double),
                 ("xt", C.POINTER(C.c_double)), ("sample", C.POINTER(C.c_double))]
+
+
+class NewtonProbe(C.Structure):
+    """sgdnet_newton_probe (diagnostics): the inputs of one outer step of Newton mode and caller-allocated host buffers
+    for what each of its passes leaves."""
+    _D = C.POINTER(C.c_double)
+    _fields_ = [("y", _D), ("scale", _D), ("u_cur", _D), ("u", _D),
+                ("t", C.c_double), ("l2", C.c_double), ("l1", C.c_double), ("tol", C.c_double),
+                ("centre", C.c_int), ("ridge", C.c_int), ("fit_intercept", C.c_int), ("max_sweeps", C.c_uint),
+                ("mean", _D), ("pub_u", _D), ("pub_a", _D), ("pub_rec", C.c_double * 4),
+                ("blend_u", _D), ("blend_a", _D), ("blend_rec", C.c_double * 4),
+                ("v", _D), ("r", _D), ("loss", C.c_double), ("V", C.c_double), ("R", C.c_double),
+                ("M", _D), ("cd_u", _D), ("cd_a", _D), ("cd_rec", C.c_double * 8)]
 
 
 class CvCovResult(C.Structure):
@@ -219,6 +233,8 @@ def load():
                                             C.c_int, C.c_int, C.c_int, C.POINTER(SetupProbe)]
     L.sgdnet_setup_probe_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int,
                                            C.c_int64, C.c_int64, C.c_int, C.POINTER(SetupProbe)]
+    L.sgdnet_newton_probe_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(NewtonProbe)]
+    L.sgdnet_newton_probe_sparse.argtypes = [C.POINTER(Csc), C.c_int, C.POINTER(NewtonProbe)]
     _cv_tail = [C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Control), C.c_int, C.POINTER(C.c_double),
                 C.POINTER(C.c_double), C.POINTER(CvCovResult)]
     L.sgdnet_cv_covariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail

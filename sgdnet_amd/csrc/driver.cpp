@@ -1657,4 +1657,64 @@ int sgdnet_setup_probe_dense(const double* x, int64_t n, int64_t p, int standard
   });
 }
 
+// ---- diagnostics: one outer step of Newton mode (newton.hip: newton_probe) ----
+
+namespace {
+// what both probes check after their matrix; the refusals of the plan (fit_plan.hpp) by the same name
+int newton_probe_checked(NewtonProblem& pb, int device, sgdnet_newton_probe* io, const char* who) {
+  if (!io || !io->y || !io->scale || !io->u_cur || !io->u || io->max_sweeps == 0) {
+    set_error("%s: invalid argument", who);
+    return SGDNET_EINVAL;
+  }
+  if (pb.p > kNewtonMaxFeatures) {
+    set_error("mode = newton needs no more features than sgdnet_newton_max_features(): %lld features (limit %d)", (long long)pb.p,
+              kNewtonMaxFeatures);
+    return SGDNET_EUNSUPPORTED;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error("no HIP device available: the SAGA backend has no CPU fallback");
+    return SGDNET_ENODEVICE;
+  }
+  if (device < 0 || device >= ndev) {
+    set_error("device %d out of range (%d devices)", device, ndev);
+    return SGDNET_EINVAL;
+  }
+  pb.y = io->y;
+  pb.centre = io->centre != 0;
+  pb.scale = io->scale;
+  pb.device = device;
+  pb.n_lambda = 1;
+  return newton_probe(pb, io);
+}
+}  // namespace
+
+int sgdnet_newton_probe_dense(const double* x, int64_t n, int64_t p, int device, sgdnet_newton_probe* io) {
+  if (!x || n <= 0 || p <= 0) {
+    set_error("sgdnet_newton_probe_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  NewtonProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  return newton_probe_checked(pb, device, io, "sgdnet_newton_probe_dense");
+}
+
+int sgdnet_newton_probe_sparse(const sgdnet_csc* x, int device, sgdnet_newton_probe* io) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_newton_probe_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  NewtonProblem pb;
+  pb.n = x->n_rows;
+  pb.p = x->n_cols;
+  pb.colptr = x->colptr;
+  pb.rowidx = x->rowidx;
+  pb.values = x->values;
+  return newton_probe_checked(pb, device, io, "sgdnet_newton_probe_sparse");
+}
+
 }  // extern "C"

@@ -331,118 +331,140 @@ struct Stream {
   }
 };
 
-}  // namespace
-
-int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
-  const int64_t n = pb.n;
-  const int p = (int)pb.p, P = p + 1, nc = p + 2, L = pb.n_lambda;
-  const bool sparse = pb.x_dense == nullptr;
-  if (n <= 0 || pb.p <= 0 || pb.p > kNewtonMaxFeatures || L <= 0 || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
-      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
-    set_error("newton_run: invalid problem");
-    return SGDNET_EINVAL;
-  }
-  SGD_HIP_TRY(hipSetDevice(pb.device));
-
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-
+// What one problem keeps on the device and the launches of an outer step as named host steps.  newton_run (a fit) and
+// newton_probe (diagnostics) both go through these: the same kernels on the same grids in the same order.
+struct NewtonDevice {
+  int64_t n = 0, nnz = 0;
+  int p = 0, P = 0, nc = 0;
+  bool sparse = false, centre = true, timed = false;
   // dense x: the tile pairs and the row chunks (a function of n and p alone)
-  const int T = (nc + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
-  const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  const int state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
-
+  int pairs = 0;
+  int64_t rows_per_chunk = 0, chunks = 0;
+  int state_blocks = 0;
   Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_v = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_r = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)nc);          // cov_sum_kernel: the means, then the sum and the mean of y
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
-  const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
-  const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
-  const size_t o_partial = A.reserve(sizeof(double) * 3 * (size_t)state_blocks);
-  const size_t o_sums = A.reserve(sizeof(double) * 2);
-  const size_t o_rec = A.reserve(sizeof(double) * kRecLen);
-  const size_t o_u0 = A.reserve(sizeof(double) * (size_t)P);
-  const size_t o_u1 = A.reserve(sizeof(double) * (size_t)P);
-  const size_t o_a = A.reserve(sizeof(double) * (size_t)P);
-  const size_t o_U = A.reserve(sizeof(double) * (size_t)L * (size_t)P);
-  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
-
   Stream sx;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
-  SGD_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sx.rec_host), sizeof(double) * kRecLen, hipHostMallocDefault));
-  if (timed)
-    for (hipEvent_t& e : sx.e) SGD_HIP_TRY(hipEventCreate(&e));
-  hipStream_t st = sx.st;
-  double* d_x = A.at<double>(o_x);
-  int32_t* d_colptr = A.at<int32_t>(o_colptr);
-  int32_t* d_rowidx = A.at<int32_t>(o_rowidx);
-  double* d_y = A.at<double>(o_y);
-  double* d_v = A.at<double>(o_v);
-  double* d_r = A.at<double>(o_r);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_scale = A.at<double>(o_scale);
-  double* d_M = A.at<double>(o_M);
-  double* d_partial = A.at<double>(o_partial);
-  double* d_sums = A.at<double>(o_sums);
-  double* d_rec = A.at<double>(o_rec);
-  double* d_a = A.at<double>(o_a);
-  double* d_cur = A.at<double>(o_u0);
-  double* d_cand = A.at<double>(o_u1);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
-    DeviceSetup& S = sx.S;
-    S.n = n;
-    S.p = p;
-    S.nnz = nnz;
-    if (nnz > 0) {
-      S.colptr = d_colptr;
-      S.rowidx = d_rowidx;
-      S.val = d_x;
-      const int rc = device_transpose(S, st);
-      S.colptr = S.rowidx = nullptr;               // the arena owns the feature-major copy; S the sample-major one
-      S.val = nullptr;
-      if (rc) return rc;
-    } else {                                       // nothing stored: every row is empty
-      SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.sptr), sizeof(int64_t) * ((size_t)n + 1)));
-      SGD_HIP_TRY(hipMemsetAsync(S.sptr, 0, sizeof(int64_t) * ((size_t)n + 1), st));
-    }
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
-  std::vector<double> start((size_t)P, 0.0);
-  start[(size_t)p] = pb.b0;
-  SGD_HIP_TRY(hipMemcpyAsync(d_cur, start.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(d_cand, start.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen, st));
-  if (sparse)
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, pb.centre ? 1 : 0, d_mu);
-  else
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
-                       pb.centre ? 1 : 0, d_mu);
-  SGD_HIP_TRY(hipGetLastError());
+  hipStream_t st = nullptr;
+  double *d_x = nullptr, *d_y = nullptr, *d_v = nullptr, *d_r = nullptr, *d_mu = nullptr, *d_scale = nullptr, *d_part = nullptr,
+         *d_M = nullptr, *d_partial = nullptr, *d_sums = nullptr, *d_rec = nullptr, *d_a = nullptr, *d_cur = nullptr, *d_cand = nullptr,
+         *d_U = nullptr;
+  int32_t *d_colptr = nullptr, *d_rowidx = nullptr;
+  const double* rec = nullptr;         // the pinned copy of the record, as of the last state pass
+  double passes = 0.0;
+  float state_ms = 0.f;
 
-  out->passes = out->sweeps = out->halvings = 0.0;
-  out->state_ms = out->moments_ms = out->cd_ms = 0.f;
-  const double* rec = sx.rec_host;
-  // the state pass at the candidate and its record; *before: the events around the step's earlier kernels
-  auto evaluate = [&]() -> int {
+  // setup and upload: x (cols: its columns with ascending rows), y and scale; the iterate and the candidate start as
+  // u_cur0 and u_cand0 (p + 1 values each, host memory that outlives the call); the column means
+  int setup(const NewtonProblem& pb, const AscendingColumns& cols, const double* u_cur0, const double* u_cand0, bool timed_) {
+    n = pb.n;
+    p = (int)pb.p;
+    P = p + 1;
+    nc = p + 2;
+    sparse = pb.x_dense == nullptr;
+    centre = pb.centre;
+    timed = timed_;
+    const int L = pb.n_lambda;
+    SGD_HIP_TRY(hipSetDevice(pb.device));
+    nnz = sparse ? pb.colptr[p] : 0;
+    const int T = (nc + kTileCols - 1) / kTileCols;
+    pairs = T * (T + 1) / 2;
+    rows_per_chunk = dense_rows_per_chunk(n, pairs);
+    chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
+
+    const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+    const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P : 0);
+    const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+    const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+    const size_t o_v = A.reserve(sizeof(double) * (size_t)n);
+    const size_t o_r = A.reserve(sizeof(double) * (size_t)n);
+    const size_t o_mu = A.reserve(sizeof(double) * (size_t)nc);          // cov_sum_kernel: the means, then the sum and the mean of y
+    const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
+    const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
+    const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
+    const size_t o_partial = A.reserve(sizeof(double) * 3 * (size_t)state_blocks);
+    const size_t o_sums = A.reserve(sizeof(double) * 2);
+    const size_t o_rec = A.reserve(sizeof(double) * kRecLen);
+    const size_t o_u0 = A.reserve(sizeof(double) * (size_t)P);
+    const size_t o_u1 = A.reserve(sizeof(double) * (size_t)P);
+    const size_t o_a = A.reserve(sizeof(double) * (size_t)P);
+    const size_t o_U = A.reserve(sizeof(double) * (size_t)L * (size_t)P);
+    SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+    SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
+    SGD_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sx.rec_host), sizeof(double) * kRecLen, hipHostMallocDefault));
+    if (timed)
+      for (hipEvent_t& e : sx.e) SGD_HIP_TRY(hipEventCreate(&e));
+    st = sx.st;
+    rec = sx.rec_host;
+    d_x = A.at<double>(o_x);
+    d_colptr = A.at<int32_t>(o_colptr);
+    d_rowidx = A.at<int32_t>(o_rowidx);
+    d_y = A.at<double>(o_y);
+    d_v = A.at<double>(o_v);
+    d_r = A.at<double>(o_r);
+    d_mu = A.at<double>(o_mu);
+    d_scale = A.at<double>(o_scale);
+    d_part = A.at<double>(o_part);
+    d_M = A.at<double>(o_M);
+    d_partial = A.at<double>(o_partial);
+    d_sums = A.at<double>(o_sums);
+    d_rec = A.at<double>(o_rec);
+    d_a = A.at<double>(o_a);
+    d_cur = A.at<double>(o_u0);
+    d_cand = A.at<double>(o_u1);
+    d_U = A.at<double>(o_U);
+    if (sparse) {
+      if (nnz > 0) {
+        SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      }
+      SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
+      DeviceSetup& S = sx.S;
+      S.n = n;
+      S.p = p;
+      S.nnz = nnz;
+      if (nnz > 0) {
+        S.colptr = d_colptr;
+        S.rowidx = d_rowidx;
+        S.val = d_x;
+        const int rc = device_transpose(S, st);
+        S.colptr = S.rowidx = nullptr;               // the arena owns the feature-major copy; S the sample-major one
+        S.val = nullptr;
+        if (rc) return rc;
+      } else {                                       // nothing stored: every row is empty
+        SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.sptr), sizeof(int64_t) * ((size_t)n + 1)));
+        SGD_HIP_TRY(hipMemsetAsync(S.sptr, 0, sizeof(int64_t) * ((size_t)n + 1), st));
+      }
+    } else {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cur, u_cur0, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cand, u_cand0, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen, st));
+    if (sparse)
+      hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, centre ? 1 : 0, d_mu);
+    else
+      hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
+                         centre ? 1 : 0, d_mu);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+
+  // publish / blend: d_cand <- d_cur + t (d_cand - d_cur), its state-pass form d_a and its record
+  int publish(double t) {
+    hipLaunchKernelGGL(newton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, t, d_cand, d_a, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+
+  // the state pass at the candidate (d_a) and its record, read back into rec
+  int state_pass() {
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
     if (sparse)
       hipLaunchKernelGGL(newton_state_kernel<true>, dim3((unsigned)state_blocks), dim3(kBlock), 0, st, sx.S.sval, sx.S.sptr, sx.S.sidx, d_y,
-                         d_mu, d_a, n, p, pb.centre ? 1 : 0, d_v, d_r, d_partial);
+                         d_mu, d_a, n, p, centre ? 1 : 0, d_v, d_r, d_partial);
     else
       hipLaunchKernelGGL(newton_state_kernel<false>, dim3((unsigned)state_blocks), dim3(kBlock), 0, st, d_x, (const int64_t*)nullptr,
                          (const int32_t*)nullptr, d_y, d_mu, d_a, n, p, 1, d_v, d_r, d_partial);
@@ -451,23 +473,66 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[3], st));
     SGD_HIP_TRY(hipMemcpyAsync(sx.rec_host, d_rec, sizeof(double) * kRecLen, hipMemcpyDeviceToHost, st));
     SGD_HIP_TRY(hipStreamSynchronize(st));
-    out->passes += 1.0;
+    passes += 1.0;
     if (timed) {
       float ms = 0.f;
       SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
-      out->state_ms += ms;
+      state_ms += ms;
     }
     return SGDNET_OK;
-  };
-  auto blend = [&](double t) -> int {
-    hipLaunchKernelGGL(newton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, t, d_cand, d_a, d_rec);
+  }
+
+  // the moments pass: d_M from d_v, d_r and the sums of the last state pass (timed: between the events 0 and 1)
+  int moments() {
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
+    if (sparse) {
+      hipLaunchKernelGGL(newton_sparse_pair_kernel, dim3((unsigned)p, (unsigned)nc), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_v,
+                         d_r, d_mu, d_sums, n, p, d_M);
+    } else {
+      hipLaunchKernelGGL(newton_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_v, d_r, d_mu, n,
+                         p, rows_per_chunk, d_part);
+      hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, d_part, (int)chunks, (const int32_t*)nullptr, nc,
+                         d_M);
+    }
+    SGD_HIP_TRY(hipGetLastError());
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
+    return SGDNET_OK;
+  }
+
+  // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
+  int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
+    hipLaunchKernelGGL(newton_cd_kernel, dim3(1), dim3(64), 0, st, d_M, d_scale, p, (double)n, d_cur, al, be, ridge ? 1 : 0,
+                       fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
-  };
+  }
+};
 
+}  // namespace
+
+int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
+  const int p = (int)pb.p, P = p + 1, L = pb.n_lambda;
+  const bool sparse = pb.x_dense == nullptr;
+  if (pb.n <= 0 || pb.p <= 0 || pb.p > kNewtonMaxFeatures || L <= 0 || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("newton_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+  std::vector<double> start((size_t)P, 0.0);
+  start[(size_t)p] = pb.b0;
+  NewtonDevice D;
+  int rc = D.setup(pb, cols, start.data(), start.data(), timed);
+  if (rc) return rc;
+  hipStream_t st = D.st;
+
+  out->passes = out->sweeps = out->halvings = 0.0;
+  out->state_ms = out->moments_ms = out->cd_ms = 0.f;
+  const double* rec = D.rec;
   // the path's start: w = 0, b = b0
-  int rc = blend(1.0);
-  if (!rc) rc = evaluate();
+  rc = D.publish(1.0);
+  if (!rc) rc = D.state_pass();
   if (rc) return rc;
   double loss = rec[kRecLoss], half_sq = rec[kRecHalfSq], abs1 = rec[kRecAbs];
 
@@ -480,27 +545,13 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
     unsigned steps = 0;
     bool converged = false;
     while (steps < pb.max_iter && !converged) {
-      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
-      if (sparse) {
-        hipLaunchKernelGGL(newton_sparse_pair_kernel, dim3((unsigned)p, (unsigned)nc), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_v,
-                           d_r, d_mu, d_sums, n, p, d_M);
-      } else {
-        hipLaunchKernelGGL(newton_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_v, d_r, d_mu, n,
-                           p, rows_per_chunk, A.at<double>(o_part));
-        hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                           (const int32_t*)nullptr, nc, d_M);
-      }
-      SGD_HIP_TRY(hipGetLastError());
-      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
-      hipLaunchKernelGGL(newton_cd_kernel, dim3(1), dim3(64), 0, st, d_M, d_scale, p, (double)n, d_cur, al, be, pb.ridge ? 1 : 0,
-                         pb.fit_intercept ? 1 : 0, kNewtonMaxSweeps, pb.tol, d_cand, d_a, d_rec);
-      SGD_HIP_TRY(hipGetLastError());
-      if ((rc = evaluate())) return rc;
+      if ((rc = D.moments()) || (rc = D.inner_solve(al, be, pb.ridge, pb.fit_intercept, kNewtonMaxSweeps, pb.tol)) || (rc = D.state_pass()))
+        return rc;
       if (timed) {
         float ms = 0.f;
-        SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[0], sx.e[1]));
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[0], D.sx.e[1]));
         out->moments_ms += ms;
-        SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[2]));
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[1], D.sx.e[2]));
         out->cd_ms += ms;
       }
       out->sweeps += rec[kRecSweeps];
@@ -508,12 +559,12 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
       double candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
       // (a candidate whose objective is not a number counts as one that rose)
       for (int h = 0; h < kNewtonMaxHalvings && rec[kRecChange] > 0.0 && !(candidate <= objective + kNewtonObjectiveSlack * fabs(objective)); ++h) {
-        if ((rc = blend(0.5)) || (rc = evaluate())) return rc;
+        if ((rc = D.publish(0.5)) || (rc = D.state_pass())) return rc;
         candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
         out->halvings += 1.0;
         negligible = false;              // (the inner solve said so of the whole step, not of a part of it)
       }
-      std::swap(d_cur, d_cand);
+      std::swap(D.d_cur, D.d_cand);
       objective = candidate;
       loss = rec[kRecLoss];
       half_sq = rec[kRecHalfSq];
@@ -524,17 +575,62 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
       const bool no_change = size != 0.0 && change / size <= pb.tol;
       converged = rec[kRecInnerConverged] != 0.0 && (all_zero || no_change || negligible);
     }
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_U) + (size_t)l * (size_t)P, d_cur, sizeof(double) * (size_t)P, hipMemcpyDeviceToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(D.d_U + (size_t)l * (size_t)P, D.d_cur, sizeof(double) * (size_t)P, hipMemcpyDeviceToDevice, st));
     out->loss[(size_t)l] = loss;
     out->steps[(size_t)l] = (int32_t)steps;
     out->unconverged[(size_t)l] = converged ? 0 : 1;
   }
+  out->passes = D.passes;
+  out->state_ms = D.state_ms;
 
   out->mean.resize((size_t)p);
   out->u.resize((size_t)L * (size_t)P);
-  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), d_mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), A.at<double>(o_U), sizeof(double) * (size_t)L * (size_t)P, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), D.d_mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), D.d_U, sizeof(double) * (size_t)L * (size_t)P, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
+  return SGDNET_OK;
+}
+
+// Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is
+// taken at the candidate io->u; the moments are those of that state; the inner solve runs on them about io->u_cur.
+int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io) {
+  const int p = (int)pb.p, P = p + 1, nc = p + 2;
+  const int64_t n = pb.n;
+  const bool sparse = pb.x_dense == nullptr;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+  NewtonDevice D;
+  int rc = D.setup(pb, cols, io->u_cur, io->u, false);
+  if (rc) return rc;
+  hipStream_t st = D.st;
+  double rec[kRecLen];
+  // a candidate as it was published: itself, its state-pass form and fields of the record
+  auto fetch = [&](double* u_out, double* a_out, double* rec_out, int rec_from, int rec_len) -> int {
+    if (u_out) SGD_HIP_TRY(hipMemcpyAsync(u_out, D.d_cand, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+    if (a_out) SGD_HIP_TRY(hipMemcpyAsync(a_out, D.d_a, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipMemcpyAsync(rec, D.d_rec, sizeof(double) * kRecLen, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipStreamSynchronize(st));
+    std::copy(rec + rec_from, rec + rec_from + rec_len, rec_out);
+    return SGDNET_OK;
+  };
+  if ((rc = D.publish(1.0)) || (rc = fetch(io->pub_u, io->pub_a, io->pub_rec, kRecHalfSq, 4))) return rc;
+  if (io->mean) SGD_HIP_TRY(hipMemcpyAsync(io->mean, D.d_mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
+  if ((rc = D.state_pass())) return rc;
+  io->loss = D.rec[kRecLoss];
+  double sums[2];
+  SGD_HIP_TRY(hipMemcpyAsync(sums, D.d_sums, sizeof(sums), hipMemcpyDeviceToHost, st));
+  if (io->v) SGD_HIP_TRY(hipMemcpyAsync(io->v, D.d_v, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (io->r) SGD_HIP_TRY(hipMemcpyAsync(io->r, D.d_r, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+  if ((rc = D.moments())) return rc;
+  if (io->M) SGD_HIP_TRY(hipMemcpyAsync(io->M, D.d_M, sizeof(double) * (size_t)nc * (size_t)nc, hipMemcpyDeviceToHost, st));
+  if ((rc = D.inner_solve(io->l2, io->ridge ? 0.0 : io->l1, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol)) ||
+      (rc = fetch(io->cd_u, io->cd_a, io->cd_rec, 0, kRecLen)))
+    return rc;
+  io->V = sums[0];
+  io->R = sums[1];
+  // the candidate again, blended with the iterate at the caller's t
+  SGD_HIP_TRY(hipMemcpyAsync(D.d_cand, io->u, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+  if ((rc = D.publish(io->t)) || (rc = fetch(io->blend_u, io->blend_a, io->blend_rec, kRecHalfSq, 4))) return rc;
   return SGDNET_OK;
 }
 

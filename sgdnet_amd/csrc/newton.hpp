@@ -6,6 +6,8 @@
 
 #include <vector>
 
+#include "sgdnet_hip.h"
+
 namespace sgdnet {
 
 // The inner solve (newton.hip: newton_cd_kernel) is ONE wavefront that keeps, in f64, for one outer step over the
@@ -76,5 +78,9 @@ struct NewtonResult {
 
 // The Newton loop (newton.hip).  p <= kNewtonMaxFeatures is the caller's business (plan_fit).  timed: fill the *_ms fields.
 int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out);
+
+// Diagnostics (include/sgdnet_hip.h: sgdnet_newton_probe_*): one outer step through the host steps newton_run takes, every
+// output copied back.  pb: x, y, centre, scale, device and n_lambda = 1; the rest comes from io.  The caller has checked both.
+int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io);
 
 }  // namespace sgdnet

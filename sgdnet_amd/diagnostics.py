@@ -1,6 +1,6 @@
-"""Diagnostics of the device setup passes (include/sgdnet_hip.h "Diagnostics", sgdnet_amd/csrc/setup_device.hip):
-what a fit's once-per-fit passes leave on the device, copied back pass by pass.  Used by the tests; a fit never
-calls these."""
+"""Diagnostics (include/sgdnet_hip.h "Diagnostics"): what a fit's once-per-fit device setup passes
+(sgdnet_amd/csrc/setup_device.hip) and the passes of one outer step of Newton mode (sgdnet_amd/csrc/newton.hip) leave
+on the device, copied back pass by pass.  Used by the tests; a fit never calls these."""
 import ctypes as C
 from types import SimpleNamespace
 
@@ -67,4 +67,47 @@ def setup_probe_dense(x, ymap, standardize=True, sample_stride=1, sample_m=0, de
     check(_lib.load().sgdnet_setup_probe_dense(dptr(x), n, p, int(bool(standardize)), dptr(ymap), cols, int(sample_stride),
                                                int(sample_m), int(device), C.byref(pr)))
     o.max_mean_sq, o.max_sqnorm = pr.max_mean_sq, pr.max_sqnorm
+    return o
+
+
+NEWTON_REC = ("loss", "half_sq", "abs", "change", "size", "sweeps", "converged", "negligible")
+
+
+def newton_probe(x, y, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0, ridge=False, fit_intercept=True,
+                 max_sweeps=1000, tol=1e-7, device=0):
+    """One outer step of Newton mode, pass by pass (sgdnet_newton_probe_dense, or _sparse for a scipy.sparse x, whose CSC
+    slots go to the library as they are).  scale: (p,); u_cur, u: (p + 1,).  Returns mean; pub_u, pub_a, pub_rec and
+    blend_u, blend_a, blend_rec (u published as it is, and blended with u_cur at t; the records are dicts of half_sq, abs,
+    change, size); v, r, loss, V, R (the state pass at u); M ((p + 2, p + 2), defined for j <= k and at the corners);
+    cd_u, cd_a, cd_rec (the inner solve on M about u_cur; a dict of all eight fields)."""
+    sparse = hasattr(x, "tocsc")
+    if sparse:
+        n, p = x.shape
+        colptr = np.ascontiguousarray(x.indptr, dtype=np.int32)
+        rowidx = np.ascontiguousarray(x.indices, dtype=np.int32)
+        vals = np.ascontiguousarray(x.data, dtype=np.float64)
+        csc = _lib.Csc()
+        csc.n_rows, csc.n_cols = n, p
+        csc.colptr = colptr.ctypes.data_as(C.POINTER(C.c_int32))
+        csc.rowidx = rowidx.ctypes.data_as(C.POINTER(C.c_int32))
+        csc.values = dptr(vals)
+    else:
+        x = np.asfortranarray(np.asarray(x, dtype=np.float64))
+        n, p = x.shape
+    ins = [np.ascontiguousarray(a, dtype=np.float64).reshape(k) for a, k in ((y, n), (scale, p), (u_cur, p + 1), (u, p + 1))]
+    o = SimpleNamespace(mean=np.empty(p), v=np.empty(n), r=np.empty(n), M=np.empty((p + 2, p + 2)),
+                        **{f"{s}_{w}": np.empty(p + 1) for s in ("pub", "blend", "cd") for w in ("u", "a")})
+    pr = _lib.NewtonProbe()
+    pr.y, pr.scale, pr.u_cur, pr.u = (dptr(a) for a in ins)
+    pr.t, pr.l2, pr.l1, pr.tol = float(t), float(l2), float(l1), float(tol)
+    pr.centre, pr.ridge, pr.fit_intercept, pr.max_sweeps = int(bool(centre)), int(bool(ridge)), int(bool(fit_intercept)), int(max_sweeps)
+    for name in ("mean", "v", "r", "M", "pub_u", "pub_a", "blend_u", "blend_a", "cd_u", "cd_a"):
+        setattr(pr, name, dptr(getattr(o, name)))
+    L = _lib.load()
+    check(L.sgdnet_newton_probe_sparse(C.byref(csc), int(device), C.byref(pr)) if sparse else
+          L.sgdnet_newton_probe_dense(dptr(x), n, p, int(device), C.byref(pr)))
+    o.loss, o.V, o.R = pr.loss, pr.V, pr.R
+    o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
+    o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
+    o.cd_rec = dict(zip(NEWTON_REC, pr.cd_rec))
     return o
