@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON and sgdnet_newton_max_features (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_* (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -639,6 +639,55 @@ int sgdnet_cv_covariance_dense(const double* x, int64_t n, int64_t p, const doub
 int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
                                 const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
                                 sgdnet_cv_cov_result* out);
+
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in Newton mode (additions only; the ABI version stays):  */
+/* every fold fit of every elastic-net mix in ONE call, all of them advancing */
+/* in lock-step.  The arguments are those of sgdnet_cv_covariance_*.  Job     */
+/* (alpha a, group g) is by definition sgdnet_fit_*(x[T], y[T]) in            */
+/* SGDNET_MODE_NEWTON with elasticnet_mix = alphas[a] and the user lambdas    */
+/* lambdas[a][.], T as above: the same preprocessed problem (x_center and     */
+/* x_scale over T, the null model of y[T], its null deviance), the same       */
+/* stopping rule, constants and accept / halve rule, return_codes and npasses */
+/* (state passes of that job) meaning what they mean there.  y holds the      */
+/* class codes 0 / 1 of the WHOLE response.  The rows are sorted by group on  */
+/* the host and uploaded once; every kernel of the Newton loop runs over all  */
+/* jobs at once, each job on the rows of its own training set, and per round  */
+/* the host sends one command per job (step / halve / idle, the penalties,    */
+/* which iterate is current, where to store an accepted one) and reads all    */
+/* records back in one copy (sgdnet_amd/csrc/newton.hip: newton_cv_run).      */
+/* control supplies intercept, standardize, max_iter (Newton steps per        */
+/* lambda), tol, n_lambda and device; family must be binomial.  No sample is  */
+/* drawn.  The same input gives the same bits, and a job's bits do not depend */
+/* on which other jobs share the call.                                         */
+/* SGDNET_EUNSUPPORTED ("mode = newton needs ..."): a family other than        */
+/* binomial, more than sgdnet_newton_max_features() features, n_gpus > 1,      */
+/* debug, more than 65 535 jobs, or a workspace -- jobs x (2 n_rows +          */
+/* (n_features + 2)^2 + dense x: row chunks x tile pairs x 256) doubles --     */
+/* above 1 GiB (which still holds 5 mixes x 10 folds of 1.3 million rows at    */
+/* 14 features or of 900 000 rows at 198, and a leave-one-out CV of 300 rows   */
+/* at 198 features for 5 mixes).                                               */
+/* SGDNET_EINVAL: the cases of sgdnet_cv_covariance_*, a response that is not  */
+/* a class code, and a training set that does not hold both classes (the       */
+/* message names its group).                                                   */
+/* ------------------------------------------------------------------------ */
+typedef struct sgdnet_cv_newton_result {   /* caller-allocated; job = alpha_index * n_groups + group, L = control.n_lambda */
+  double* a0;            /* jobs x L                                                         */
+  double* beta;          /* jobs x L x n_features: per job the layout of sgdnet_result.beta  */
+  double* dev_ratio;     /* jobs x L                                                         */
+  double* return_codes;  /* jobs x L, 0 converged / 1 max_iter steps without meeting tol     */
+  double* nulldev;       /* jobs: the null deviance of y[T]                                  */
+  double* npasses;       /* jobs: state passes over the path                                 */
+  double* steps;         /* jobs: Newton steps over the path                                 */
+  double* halvings;      /* jobs: steps halved (each costs one more state pass)              */
+} sgdnet_cv_newton_result;
+
+int sgdnet_cv_newton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                           int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                           const double* lambdas, sgdnet_cv_newton_result* out);
+int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                            const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                            sgdnet_cv_newton_result* out);
 
 #ifdef __cplusplus
 }

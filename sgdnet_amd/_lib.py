@@ -37,6 +37,7 @@ EXPORTS = [
     "sgdnet_setup_probe_sparse", "sgdnet_setup_probe_dense",
     "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse", "sgdnet_newton_max_features",
     "sgdnet_newton_probe_dense", "sgdnet_newton_probe_sparse",
+    "sgdnet_cv_newton_dense", "sgdnet_cv_newton_sparse",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -122,6 +123,13 @@ class CvCovResult(C.Structure):
     """sgdnet_cv_cov_result: caller-allocated outputs of sgdnet_cv_covariance_*, job-major (job = alpha * n_groups + group)."""
     _fields_ = [("a0", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)), ("dev_ratio", C.POINTER(C.c_double)),
                 ("return_codes", C.POINTER(C.c_double)), ("nulldev", C.POINTER(C.c_double)), ("npasses", C.POINTER(C.c_double))]
+
+
+class CvNewtonResult(C.Structure):
+    """sgdnet_cv_newton_result: caller-allocated outputs of sgdnet_cv_newton_*, job-major (job = alpha * n_groups + group)."""
+    _fields_ = [("a0", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)), ("dev_ratio", C.POINTER(C.c_double)),
+                ("return_codes", C.POINTER(C.c_double)), ("nulldev", C.POINTER(C.c_double)), ("npasses", C.POINTER(C.c_double)),
+                ("steps", C.POINTER(C.c_double)), ("halvings", C.POINTER(C.c_double))]
 
 
 class SgdnetError(RuntimeError):
@@ -239,6 +247,9 @@ def load():
                 C.POINTER(C.c_double), C.POINTER(CvCovResult)]
     L.sgdnet_cv_covariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_covariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
+    _cv_tail = _cv_tail[:-1] + [C.POINTER(CvNewtonResult)]
+    L.sgdnet_cv_newton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
+    L.sgdnet_cv_newton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     _lib = L
     return L
 

@@ -1538,6 +1538,304 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
   return SGDNET_OK;
 }
 
+// ---- cross-validation in Newton mode (newton.hip: newton_cv_run): the stage behind sgdnet_cv_newton_* ----
+// Every job (mix, training set T) is fit_newton on x[T], y[T] by definition.  The rows are stably sorted by group here,
+// once, so that T is a range of rows or the complement of one; what fit_newton takes from the preprocessing of x[T],
+// y[T] -- x_center and x_scale over T, the null model's intercept, the null deviance, regularization_path's penalties
+// for the user's lambdas -- is formed here per training set, the features' moments pooled from per-group sums of
+// deviations about the whole-data column means (formed before anything is squared: DESIGN.md 4.6).
+struct CvNewtonMatrix {
+  int64_t n = 0, p = 0;
+  const double* dense = nullptr;
+  const int32_t* colptr = nullptr;
+  const int32_t* rowidx = nullptr;
+  const double* values = nullptr;
+};
+
+int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
+                  int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_newton_result* out) {
+  const int64_t n = X.n, p = X.p;
+  if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !out->steps ||
+      !out->halvings || !y || !fold || !alphas || !lambdas) {
+    set_error("sgdnet_cv_newton: null pointer");
+    return SGDNET_EINVAL;
+  }
+  if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
+      (train_on_rest && n_groups < 2)) {
+    set_error("sgdnet_cv_newton: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    return SGDNET_EINVAL;
+  }
+  const int L = ctl->n_lambda, G = n_groups;
+  const bool sparse = X.dense == nullptr, rest = train_on_rest != 0;
+  const char* what = nullptr;
+  if (ctl->family != SGDNET_BINOMIAL) what = "family = binomial";
+  else if (p > kNewtonMaxFeatures) what = "no more features than sgdnet_newton_max_features()";
+  else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+  else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
+  if (what) {
+    set_error("mode = newton needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)p,
+              kNewtonMaxFeatures, ctl->n_gpus, ctl->debug);
+    return SGDNET_EUNSUPPORTED;
+  }
+  int rc = validate_response(ctl, y, n);
+  if (rc) return rc;
+  std::vector<int64_t> start((size_t)G + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    if (fold[i] < 0 || fold[i] >= G) {
+      set_error("fold[%lld] = %d is not a group id in 0..%d", (long long)i, fold[i], G - 1);
+      return SGDNET_EINVAL;
+    }
+    ++start[(size_t)fold[i] + 1];
+  }
+  for (int g = 0; g < G; ++g) {
+    if (start[(size_t)g + 1] == 0) {
+      set_error("group %d of %d is empty", g, G);
+      return SGDNET_EINVAL;
+    }
+    start[(size_t)g + 1] += start[(size_t)g];
+  }
+  for (int a = 0; a < n_alpha; ++a) {
+    if (!(alphas[a] >= 0.0 && alphas[a] <= 1.0)) {
+      set_error("alphas[%d] = %g is not an elastic-net mix in [0, 1]", a, alphas[a]);
+      return SGDNET_EINVAL;
+    }
+    for (int l = 0; l < L; ++l)
+      if (!(lambdas[(size_t)a * L + l] >= 0.0)) {
+        set_error("lambdas[%d][%d] = %g is negative", a, l, lambdas[(size_t)a * L + l]);
+        return SGDNET_EINVAL;
+      }
+  }
+  // the rows stably sorted by group: row i goes to position to[i]
+  std::vector<int64_t> to((size_t)n);
+  {
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < n; ++i) to[(size_t)i] = fill[(size_t)fold[i]]++;
+  }
+  std::vector<double> ys((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ys[(size_t)to[(size_t)i]] = y[i];
+  // the response of every training set: both classes, the null model and its deviance (fit_null_model, null_deviance)
+  const bool intercept = ctl->intercept != 0;
+  std::vector<int64_t> n_t((size_t)G);
+  std::vector<double> b0((size_t)G), nulldev((size_t)G);
+  {
+    double ones_all = 0.0;
+    std::vector<double> ones((size_t)G, 0.0);
+    for (int g = 0; g < G; ++g) {
+      for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) ones[(size_t)g] += ys[(size_t)i];
+      ones_all += ones[(size_t)g];
+    }
+    for (int g = 0; g < G; ++g) {
+      const int64_t own = start[(size_t)g + 1] - start[(size_t)g];
+      n_t[(size_t)g] = rest ? n - own : own;
+      const double k = rest ? ones_all - ones[(size_t)g] : ones[(size_t)g];
+      if (k <= 0.0 || k >= (double)n_t[(size_t)g]) {
+        set_error("the training set of group %d of %d holds one class only (%lld rows, %lld of class 1)", g, G, (long long)n_t[(size_t)g],
+                  (long long)k);
+        return SGDNET_EINVAL;
+      }
+      b0[(size_t)g] = intercept ? binomial_link(k / (double)n_t[(size_t)g]) : 0.0;
+      // sum over T of log(1 + e^b0) - y b0, its equal terms counted instead of added one by one
+      const double lp = b0[(size_t)g];
+      nulldev[(size_t)g] = 2.0 * ((double)n_t[(size_t)g] * log(1.0 + exp(lp)) - k * lp);
+    }
+  }
+  if ((int64_t)n_alpha * G > kNewtonCvMaxJobs) {
+    set_error("mode = newton needs no more than %lld jobs in one cross-validation call: %d mixes x %d groups", (long long)kNewtonCvMaxJobs,
+              n_alpha, G);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const size_t workspace = newton_cv_workspace_bytes(n, p, sparse, n_t.data(), G, n_alpha);
+  if (workspace > kNewtonCvWorkspaceBytes) {
+    set_error("mode = newton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of (2 x %lld rows + (%lld + 2)^2 moments%s) "
+              "doubles are %zu bytes", kNewtonCvWorkspaceBytes, n_alpha, G, (long long)n, (long long)p, sparse ? "" : " + row-chunk partials",
+              workspace);
+    return SGDNET_EUNSUPPORTED;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error("no HIP device available: the SAGA backend has no CPU fallback");
+    return SGDNET_ENODEVICE;
+  }
+  if (ctl->device < 0 || ctl->device >= ndev) {
+    set_error("device %d out of range (%d devices)", ctl->device, ndev);
+    return SGDNET_EINVAL;
+  }
+  PhaseTimer pt;
+
+  // x with its rows sorted, and per group and column the sums of d = x - a and of d^2 about the whole-data mean a
+  const size_t P = (size_t)p;
+  std::vector<double> xs, abar(P, 0.0), s1((size_t)G * P, 0.0), s2((size_t)G * P, 0.0);
+  std::vector<int32_t> rows, cut;
+  if (sparse) {
+    const int64_t nnz = X.colptr[p];
+    xs.resize((size_t)nnz);
+    rows.resize((size_t)nnz);
+    cut.resize(P * ((size_t)G + 1));
+    std::vector<int64_t> at((size_t)G + 1);
+    for (int64_t j = 0; j < p; ++j) {
+      const int64_t q0 = X.colptr[j], q1 = X.colptr[j + 1];
+      double sum = 0.0;
+      for (int64_t q = q0; q < q1; ++q) sum += X.values[q];
+      const double a = abar[(size_t)j] = sum / (double)n;
+      // a counting pass: the entries of a group keep their order, so the sorted rows ascend within the column
+      std::fill(at.begin(), at.end(), 0);
+      for (int64_t q = q0; q < q1; ++q) ++at[(size_t)fold[X.rowidx[q]] + 1];
+      at[0] = q0;
+      for (int g = 0; g < G; ++g) at[(size_t)g + 1] += at[(size_t)g];
+      int32_t* c = cut.data() + (size_t)j * ((size_t)G + 1);
+      for (int g = 0; g <= G; ++g) c[g] = (int32_t)at[(size_t)g];
+      for (int g = 0; g < G; ++g) {     // the rows of the group that store nothing: d = -a
+        const double zeros = (double)((start[(size_t)g + 1] - start[(size_t)g]) - (at[(size_t)g + 1] - at[(size_t)g]));
+        s1[(size_t)g * P + (size_t)j] = zeros * -a;
+        s2[(size_t)g * P + (size_t)j] = zeros * (a * a);
+      }
+      for (int64_t q = q0; q < q1; ++q) {
+        const int32_t r = X.rowidx[q];
+        const int g = fold[r];
+        const int64_t dst = at[(size_t)g]++;
+        rows[(size_t)dst] = (int32_t)to[(size_t)r];
+        xs[(size_t)dst] = X.values[q];
+        const double d = X.values[q] - a;
+        s1[(size_t)g * P + (size_t)j] += d;
+        s2[(size_t)g * P + (size_t)j] += d * d;
+      }
+      // (the pair kernel looks rows up by binary search: a column that came with its rows out of order is put in order)
+      bool ascending = true;
+      for (int64_t q = q0 + 1; q < q1 && ascending; ++q) ascending = rows[(size_t)q] > rows[(size_t)q - 1];
+      if (!ascending) {
+        std::vector<std::pair<int32_t, double>> e((size_t)(q1 - q0));
+        for (int64_t q = q0; q < q1; ++q) e[(size_t)(q - q0)] = {rows[(size_t)q], xs[(size_t)q]};
+        std::stable_sort(e.begin(), e.end(), [](const std::pair<int32_t, double>& l, const std::pair<int32_t, double>& r) { return l.first < r.first; });
+        for (int64_t q = q0; q < q1; ++q) {
+          rows[(size_t)q] = e[(size_t)(q - q0)].first;
+          xs[(size_t)q] = e[(size_t)(q - q0)].second;
+        }
+      }
+    }
+  } else {
+    xs.resize((size_t)n * P);
+    parallel_for(p, (double)n * (double)p, [&](int64_t j0, int64_t j1) {
+      for (int64_t j = j0; j < j1; ++j) {
+        const double* col = X.dense + j * n;
+        double* dst = xs.data() + j * n;
+        double sum = 0.0;
+        for (int64_t i = 0; i < n; ++i) {
+          dst[to[(size_t)i]] = col[i];
+          sum += col[i];
+        }
+        const double a = abar[(size_t)j] = sum / (double)n;
+        for (int g = 0; g < G; ++g) {
+          double t1 = 0.0, t2 = 0.0;
+          for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) {
+            const double d = dst[i] - a;
+            t1 += d;
+            t2 += d * d;
+          }
+          s1[(size_t)g * P + (size_t)j] = t1;
+          s2[(size_t)g * P + (size_t)j] = t2;
+        }
+      }
+    });
+  }
+  // pooled per training set (the group's own sums, or the total -- added in group order -- less them) and moved to the
+  // set's own mean: mean_T = a + S1 / n_T, var_T = S2 / n_T - (S1 / n_T)^2
+  const bool centre = intercept || ctl->standardize != 0;
+  std::vector<double> mean((size_t)G * P, 0.0), scale((size_t)G * P, 1.0);
+  for (size_t j = 0; j < P; ++j) {
+    const double a = abar[j];
+    double t1 = 0.0, t2 = 0.0;
+    for (int g = 0; g < G; ++g) {
+      t1 += s1[(size_t)g * P + j];
+      t2 += s2[(size_t)g * P + j];
+    }
+    for (int g = 0; g < G; ++g) {
+      const double nT = (double)n_t[(size_t)g];
+      const double d = (rest ? t1 - s1[(size_t)g * P + j] : s1[(size_t)g * P + j]) / nT;
+      const double var = (rest ? t2 - s2[(size_t)g * P + j] : s2[(size_t)g * P + j]) / nT - d * d;
+      if (centre) mean[(size_t)g * P + j] = a + d;
+      if (ctl->standardize) scale[(size_t)g * P + j] = var > 0.0 ? sqrt(var) : 1.0;
+    }
+  }
+  pt.mark("cv newton: rows sorted, moments");
+
+  // regularization_path for user lambdas and a binomial response (its y_scale is 1)
+  std::vector<double> l2((size_t)n_alpha * (size_t)L), l1(l2.size());
+  std::vector<uint8_t> ridge((size_t)n_alpha);
+  for (int a = 0; a < n_alpha; ++a) {
+    ridge[(size_t)a] = alphas[a] == 0.0;
+    for (int l = 0; l < L; ++l) {
+      l2[(size_t)a * L + l] = (1.0 - alphas[a]) * lambdas[(size_t)a * L + l] / 1.0;
+      l1[(size_t)a * L + l] = alphas[a] * lambdas[(size_t)a * L + l] / 1.0;
+    }
+  }
+  NewtonCvProblem pb;
+  pb.n = n;
+  pb.p = p;
+  if (sparse) {
+    pb.colptr = X.colptr;
+    pb.rowidx = rows.data();
+    pb.values = xs.data();
+    pb.cut = cut.data();
+  } else {
+    pb.x_dense = xs.data();
+  }
+  pb.y = ys.data();
+  pb.n_sets = G;
+  pb.start = start.data();
+  pb.train_on_rest = rest;
+  pb.centre = centre;
+  pb.fit_intercept = intercept;
+  pb.mean = mean.data();
+  pb.scale = scale.data();
+  pb.b0 = b0.data();
+  pb.device = ctl->device;
+  pb.n_mix = n_alpha;
+  pb.n_lambda = L;
+  pb.l2 = l2.data();
+  pb.l1 = l1.data();
+  pb.ridge = ridge.data();
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  NewtonCvResult nr;
+  rc = newton_cv_run(pb, pt.on, &nr);
+  if (rc) return rc;
+
+  const size_t P1 = P + 1;
+  double most_steps = 0.0, most_halvings = 0.0;
+  for (int a = 0; a < n_alpha; ++a)
+    for (int t = 0; t < G; ++t) {
+      const size_t job = (size_t)a * (size_t)G + (size_t)t;
+      const double* m = mean.data() + (size_t)t * P;
+      const double* s = scale.data() + (size_t)t * P;
+      for (int li = 0; li < L; ++li) {
+        const size_t at = job * (size_t)L + (size_t)li;
+        const double* u = nr.u.data() + at * P1;
+        double* bo = out->beta + at * P;
+        // fit_newton and rescale_values: the intercept at the centres less the centres times the coefficients
+        double xbb = 0.0;
+        for (size_t j = 0; j < P; ++j) {
+          bo[j] = u[j] / s[j];
+          xbb += m[j] * bo[j];
+        }
+        out->a0[at] = intercept ? u[P] - xbb : b0[(size_t)t];
+        out->dev_ratio[at] = 1.0 - 2.0 * (double)n_t[(size_t)t] * nr.loss[at] / nulldev[(size_t)t];
+        out->return_codes[at] = nr.unconverged[at] ? 1.0 : 0.0;
+      }
+      out->nulldev[job] = nulldev[(size_t)t];
+      out->npasses[job] = nr.passes[job];
+      out->steps[job] = nr.steps[job];
+      out->halvings[job] = nr.halvings[job];
+      most_steps = std::max(most_steps, nr.steps[job] + nr.halvings[job]);
+      most_halvings = std::max(most_halvings, nr.halvings[job]);
+    }
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   cv newton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
+            "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
+            nr.moments_ms, nr.cd_ms, nr.state_ms);
+  pt.mark("cv newton (all folds)");
+  return SGDNET_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1574,6 +1872,38 @@ int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int3
   pb.values = x->values;
   pb.y = y;
   return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_newton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                           const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                           sgdnet_cv_newton_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_newton_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  CvNewtonMatrix X;
+  X.n = n;
+  X.p = p;
+  X.dense = x;
+  return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                            const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                            sgdnet_cv_newton_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_newton_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  CvNewtonMatrix X;
+  X.n = x->n_rows;
+  X.p = x->n_cols;
+  X.colptr = x->colptr;
+  X.rowidx = x->rowidx;
+  X.values = x->values;
+  return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
 }
 
 int sgdnet_fit_sparse(const sgdnet_csc* x, const double* y, int y_cols, const sgdnet_control* ctl,

@@ -33,6 +33,12 @@
 // The outer loop is the host's (newton_run): separate launches on one stream and one small record read back per state
 // pass.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz): the same input gives
 // the same bits.
+//
+// Cross-validation (newton_cv_run, include/sgdnet_hip.h: sgdnet_cv_newton_*): all fold fits of all mixes advance in
+// lock-step.  The rows are sorted by group once, so a training set is a range of rows or the complement of one; the
+// newton_cv_* kernels are the kernels above with a job dimension, each job on its own rows, centres, scales and buffers;
+// the host keeps newton_run's state machine once per job, sends one command per job and round and reads all records
+// back in one copy.
 #define SGDNET_DET_MATH
 #include <algorithm>
 #include <utility>
@@ -260,11 +266,11 @@ __global__ __launch_bounds__(64) void newton_blend_kernel(const double* __restri
 // max|u|) from the same LDS words, so branches on them are uniform and nothing has to be broadcast (cov_path_kernel).
 // M: the (p + 2)^2 moments (upper triangle), dn = n; the quadratic model about u_cur is
 //   (u - u_cur)'H (u - u_cur) / 2 - q'(u - u_cur) + al/2 |w|^2 + be |w|_1,     its smooth gradient g = H (u - u_cur) - q.
-__global__ __launch_bounds__(64) void newton_cd_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, double dn,
-                                                        const double* __restrict__ u_cur, double al, double be, int ridge,
-                                                        int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
-                                                        double* __restrict__ a_cand, double* __restrict__ rec) {
-  __shared__ double lds[newton_state_doubles(kNewtonMaxFeatures)];
+// (the body of newton_cd_kernel and of newton_cv_cd_kernel, which runs it once per job; lds: the workgroup's whole LDS)
+__device__ __forceinline__ void newton_cd_solve(double* lds, const double* __restrict__ M, const double* __restrict__ scale, int p, double dn,
+                                                const double* __restrict__ u_cur, double al, double be, int ridge, int fit_intercept,
+                                                unsigned max_sweeps, double tol, double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                double* __restrict__ rec) {
   const int lane = threadIdx.x, P = p + 1, nc = p + 2;
   double* H = lds;
   double* u = H + P * (P + 1) / 2;
@@ -315,6 +321,336 @@ __global__ __launch_bounds__(64) void newton_cd_kernel(const double* __restrict_
     rec[kRecInnerConverged] = converged ? 1.0 : 0.0;
     rec[kRecNegligible] = negligible ? 1.0 : 0.0;
   }
+}
+
+__global__ __launch_bounds__(64) void newton_cd_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, double dn,
+                                                        const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                        int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                        double* __restrict__ a_cand, double* __restrict__ rec) {
+  __shared__ double lds[newton_state_doubles(kNewtonMaxFeatures)];
+  newton_cd_solve(lds, M, scale, p, dn, u_cur, al, be, ridge, fit_intercept, max_sweeps, tol, u_cand, a_cand, rec);
+}
+
+// ---- cross-validation (newton_cv_run): the kernels above with a job dimension ----
+// A job is one (mix, training set).  x and y hold the rows sorted by group, so the rows of a training set are one range
+// of rows or two: [a0, a1) and [b0, b1) (the second empty when the job trains on its own group).  Row li of the job's
+// problem, li = 0 .. n_t - 1, is row cv_row(J, li) of x; a job visits its own rows only.  Every job has its own a, v, r,
+// sums, moments, record, two iterates and slice of U; its centres and scales are its training set's; its grids (state
+// workgroups, row chunks) are those newton_run would choose for n_t rows, so its arithmetic is the same whichever other
+// jobs share the launch.  The host sends one CvCmd per job and round.
+enum CvAction { kCvIdle = 0, kCvStep, kCvHalve, kCvStart };
+
+struct CvCmd {
+  int32_t action;          // CvAction; kCvStart: publish the path's start and evaluate it
+  int32_t cur;             // which of the job's two iterates is the current one (the other holds the candidate)
+  int32_t slot;            // >= 0: the current iterate is the answer for this lambda: store it into U[slot] first
+  int32_t ridge;
+  double l2, l1;           // this lambda's penalties
+};
+
+struct CvJob {
+  int64_t a0, a1, b0, b1;  // the rows of the training set
+  int64_t n_t;
+  int64_t rows_per_chunk;  // dense x: dense_rows_per_chunk(n_t, pairs)
+  int32_t set;             // the training set: whose centres and scales
+  int32_t state_blocks, chunks, pad;
+};
+
+__device__ __forceinline__ int64_t cv_row(const CvJob& J, int64_t li) {
+  const int64_t la = J.a1 - J.a0;
+  return li < la ? J.a0 + li : J.b0 + (li - la);
+}
+
+// newton_state_kernel for the job blockIdx.y; workgroup b of the job leaves its sums in partial[job][3 b ..]
+template <bool kSparse>
+__global__ __launch_bounds__(kBlock) void newton_cv_state_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                  const double* __restrict__ x, const int64_t* __restrict__ sptr,
+                                                                  const int32_t* __restrict__ sidx, const double* __restrict__ y,
+                                                                  const double* __restrict__ mu_all, const double* __restrict__ a_all,
+                                                                  int64_t n, int p, int centre, double* __restrict__ v_all,
+                                                                  double* __restrict__ r_all, double* __restrict__ partial_all) {
+  __shared__ double sh[kBlock];
+  const int job = blockIdx.y;
+  if (cmd[job].action == kCvIdle) return;
+  const CvJob J = jobs[job];
+  if ((int)blockIdx.x >= J.state_blocks) return;
+  const double* __restrict__ mu = mu_all + (size_t)J.set * (size_t)p;
+  const double* __restrict__ a = a_all + (size_t)job * (size_t)(p + 1);
+  double* __restrict__ v = v_all + (size_t)job * (size_t)n;
+  double* __restrict__ r = r_all + (size_t)job * (size_t)n;
+  double* __restrict__ partial = partial_all + (size_t)job * 3 * kStateMaxBlocks;
+  double loss = 0.0, vs = 0.0, rs = 0.0;
+  const double b = a[p];
+  for (int64_t li = (int64_t)blockIdx.x * kBlock + threadIdx.x; li < J.n_t; li += (int64_t)J.state_blocks * kBlock) {
+    const int64_t i = cv_row(J, li);
+    double eta = 0.0;
+    if (kSparse) {
+      int64_t q = sptr[i];
+      const int64_t q1 = sptr[i + 1];
+      if (centre) {
+        for (int j = 0; j < p; ++j) {
+          double d = -mu[j];
+          if (q < q1 && sidx[q] == j) d = x[q++] - mu[j];
+          eta += d * a[j];
+        }
+      } else {
+        for (; q < q1; ++q) eta += x[q] * a[sidx[q]];
+      }
+    } else {
+      for (int j = 0; j < p; ++j) eta += (x[i + (int64_t)j * n] - mu[j]) * a[j];
+    }
+    eta += b;
+    const double yi = y[i];
+    const double e = SGD_EXP(eta);
+    const double t = 1.0 / (1.0 + e);
+    const double vi = t * (1.0 - t), ri = t - (1.0 - yi);
+    v[i] = vi;
+    r[i] = ri;
+    loss += SGD_LOG(1.0 + e) - yi * eta;
+    vs += vi;
+    rs += ri;
+  }
+  loss = block_sum(loss, sh);
+  vs = block_sum(vs, sh);
+  rs = block_sum(rs, sh);
+  if (threadIdx.x == 0) {
+    partial[3 * blockIdx.x] = loss;
+    partial[3 * blockIdx.x + 1] = vs;
+    partial[3 * blockIdx.x + 2] = rs;
+  }
+}
+
+// newton_finish_kernel for the job blockIdx.x: the mean is over the job's n_t rows
+__global__ __launch_bounds__(kBlock) void newton_cv_finish_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                   const double* __restrict__ partial_all, double* __restrict__ sums_all,
+                                                                   double* __restrict__ rec_all) {
+  __shared__ double sh[kBlock];
+  const int job = blockIdx.x;
+  if (cmd[job].action == kCvIdle) return;
+  const double* __restrict__ partial = partial_all + (size_t)job * 3 * kStateMaxBlocks;
+  const int blocks = jobs[job].state_blocks;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < blocks; b += kBlock)
+    for (int c = 0; c < 3; ++c) s[c] += partial[3 * b + c];
+  for (int c = 0; c < 3; ++c) s[c] = block_sum(s[c], sh);
+  if (threadIdx.x == 0) {
+    rec_all[(size_t)job * kRecLen + kRecLoss] = s[0] / (double)jobs[job].n_t;
+    sums_all[2 * job] = s[1];
+    sums_all[2 * job + 1] = s[2];
+  }
+}
+
+// newton_dense_tile_kernel for the job blockIdx.z: blockIdx.y is a chunk of the JOB's rows.  part[job][chunk][pair][tid].
+__global__ __launch_bounds__(kBlock) void newton_cv_dense_tile_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                       const double* __restrict__ x, const double* __restrict__ v_all,
+                                                                       const double* __restrict__ r_all, const double* __restrict__ mu_all,
+                                                                       int64_t n, int p, int max_chunks, double* __restrict__ part) {
+  __shared__ double A[kTileCols][kTileRows + 1], B[kTileCols][kTileRows + 1];
+  const int job = blockIdx.z;
+  if (cmd[job].action != kCvStep) return;
+  const CvJob J = jobs[job];
+  if ((int)blockIdx.y >= J.chunks) return;
+  const double* __restrict__ mu = mu_all + (size_t)J.set * (size_t)p;
+  const double* __restrict__ v = v_all + (size_t)job * (size_t)n;
+  const double* __restrict__ r = r_all + (size_t)job * (size_t)n;
+  const int tid = threadIdx.x, ncols = p + 2;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  const int ta = tid & (kTileCols - 1), tb = tid / kTileCols;
+  const int64_t r0 = (int64_t)blockIdx.y * J.rows_per_chunk;
+  const int64_t r1 = r0 + J.rows_per_chunk < J.n_t ? r0 + J.rows_per_chunk : J.n_t;
+  double acc = 0.0;
+  for (int64_t base = r0; base < r1; base += kTileRows) {
+    for (int e = tid; e < kTileCols * kTileRows; e += kBlock) {
+      const int row = e & (kTileRows - 1), col = e / kTileRows;
+      const int64_t li = base + row;
+      const int ca = tj * kTileCols + col, cb = tk * kTileCols + col;
+      double da = 0.0, db = 0.0;
+      if (li < r1) {
+        const int64_t i = cv_row(J, li);
+        if (ca <= p) da = ca < p ? x[i + (int64_t)ca * n] - mu[ca] : 1.0;
+        if (cb == p + 1) db = r[i];
+        else if (cb <= p) db = v[i] * (cb < p ? x[i + (int64_t)cb * n] - mu[cb] : 1.0);
+      }
+      A[col][row] = da;
+      B[col][row] = db;
+    }
+    __syncthreads();
+    for (int i = 0; i < kTileRows; ++i) acc += A[ta][i] * B[tb][i];
+    __syncthreads();
+  }
+  part[(((size_t)job * (size_t)max_chunks + blockIdx.y) * gridDim.x + blockIdx.x) * kBlock + tid] = acc;
+}
+
+// cov_reduce_kernel for the job blockIdx.y: its chunks added in chunk order into M[job]
+__global__ __launch_bounds__(kBlock) void newton_cv_reduce_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                   const double* __restrict__ part, int max_chunks, int ncols,
+                                                                   double* __restrict__ M_all) {
+  const int job = blockIdx.y;
+  if (cmd[job].action != kCvStep) return;
+  const int tid = threadIdx.x;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  const int a = tj * kTileCols + (tid & (kTileCols - 1)), b = tk * kTileCols + tid / kTileCols;
+  if (a >= ncols || b >= ncols) return;
+  const int chunks = jobs[job].chunks;
+  double* __restrict__ M = M_all + (size_t)job * (size_t)ncols * (size_t)ncols;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += part[(((size_t)job * (size_t)max_chunks + c) * gridDim.x + blockIdx.x) * kBlock + tid];
+  M[(size_t)a * ncols + b] = s;
+  if (tj != tk) M[(size_t)b * ncols + a] = s;
+}
+
+// The entries of a column in the rows of a training set: two ranges of positions (cut: NewtonCvProblem), entry e of the
+// set at position at(e).  find(row): the position of the entry in that row, or -1.
+struct CvColumn {
+  int a0, a1, b0, b1;
+  __device__ CvColumn(const int32_t* __restrict__ cut, int n_sets, int j, int group, bool rest) {
+    const int32_t* c = cut + (size_t)j * (size_t)(n_sets + 1);
+    if (rest) {
+      a0 = c[0];
+      a1 = c[group];
+      b0 = c[group + 1];
+      b1 = c[n_sets];
+    } else {
+      a0 = c[group];
+      a1 = c[group + 1];
+      b0 = b1 = a1;
+    }
+  }
+  __device__ int count() const { return (a1 - a0) + (b1 - b0); }
+  __device__ int at(int e) const { return e < a1 - a0 ? a0 + e : b0 + (e - (a1 - a0)); }
+  // split: the first row of the second range of rows (rows below it can only sit in the first range of positions)
+  __device__ int find(const int32_t* __restrict__ rowidx, int32_t row, int64_t split) const {
+    const bool first = (int64_t)row < split;
+    const int lo = first ? a0 : b0, hi = first ? a1 : b1;
+    const int pos = lower_bound_row(rowidx, lo, hi, row);
+    return pos < hi && rowidx[pos] == row ? pos : -1;
+  }
+};
+
+// newton_sparse_pair_kernel for the job blockIdx.z over the entries in the rows of its training set
+__global__ __launch_bounds__(kBlock) void newton_cv_sparse_pair_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                        const int32_t* __restrict__ cut, int n_sets, int rest,
+                                                                        const int32_t* __restrict__ rowidx, const double* __restrict__ val,
+                                                                        const double* __restrict__ v_all, const double* __restrict__ r_all,
+                                                                        const double* __restrict__ mu_all, const double* __restrict__ sums_all,
+                                                                        int64_t n, int p, double* __restrict__ M_all) {
+  __shared__ double sh[kBlock];
+  const int job = blockIdx.z;
+  if (cmd[job].action != kCvStep) return;
+  const int j = blockIdx.x, k = blockIdx.y, nc = p + 2, tid = threadIdx.x;
+  if (k < j) return;
+  const CvJob J = jobs[job];
+  const double* __restrict__ mu = mu_all + (size_t)J.set * (size_t)p;
+  const double* __restrict__ v = v_all + (size_t)job * (size_t)n;
+  const double* __restrict__ r = r_all + (size_t)job * (size_t)n;
+  const double* __restrict__ sums = sums_all + 2 * (size_t)job;
+  double* __restrict__ M = M_all + (size_t)job * (size_t)nc * (size_t)nc;
+  const int64_t split = J.b0;           // (training on the own group: b0 = a1, past every row of the set)
+  const CvColumn cj(cut, n_sets, j, J.set, rest != 0);
+  const int nj = cj.count();
+  const double mj = mu[j];
+  const bool j_full = (int64_t)nj == J.n_t;
+  if (k >= p) {                                  // against the ones (weights v) or q (weights r)
+    const double* wt = k == p ? v : r;
+    double a = 0.0, ws = 0.0;
+    for (int e = tid; e < nj; e += kBlock) {
+      const int q = cj.at(e);
+      const double wi = wt[rowidx[q]];
+      a += wi * (val[q] - mj);
+      ws += wi;
+    }
+    a = block_sum(a, sh);
+    ws = block_sum(ws, sh);
+    if (tid == 0) {
+      const double total = sums[k - p];
+      M[(size_t)j * nc + k] = a - mj * (j_full ? 0.0 : total - ws);
+      if (j == 0) M[(size_t)p * nc + k] = total;
+    }
+    return;
+  }
+  const CvColumn ck(cut, n_sets, k, J.set, rest != 0);
+  const int nk = ck.count();
+  const double mk = mu[k];
+  double both = 0.0, only_j = 0.0, only_k = 0.0, v_union = 0.0;
+  for (int e = tid; e < nj; e += kBlock) {
+    const int q = cj.at(e);
+    const int32_t row = rowidx[q];
+    const double vi = v[row], d = val[q] - mj;
+    v_union += vi;
+    const int pos = j == k ? q : ck.find(rowidx, row, split);
+    if (pos >= 0) both += vi * d * (val[pos] - mk);
+    else only_j += vi * d;
+  }
+  if (j != k)
+    for (int e = tid; e < nk; e += kBlock) {
+      const int s = ck.at(e);
+      const int32_t row = rowidx[s];
+      if (cj.find(rowidx, row, split) < 0) {
+        const double vi = v[row];
+        only_k += vi * (val[s] - mk);
+        v_union += vi;
+      }
+    }
+  both = block_sum(both, sh);
+  only_j = block_sum(only_j, sh);
+  only_k = block_sum(only_k, sh);
+  v_union = block_sum(v_union, sh);
+  if (tid == 0) {
+    const bool full = j_full || (int64_t)nk == J.n_t;
+    const double in_neither = full ? 0.0 : sums[0] - v_union;
+    M[(size_t)j * nc + k] = both - mk * only_j - mj * only_k + in_neither * mj * mk;
+  }
+}
+
+// newton_blend_kernel for the job blockIdx.x: a halving (t = 1/2), or the path's start published as it is (t = 1)
+__global__ __launch_bounds__(64) void newton_cv_blend_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                              const double* __restrict__ scale_all, int p, double* __restrict__ u_all,
+                                                              double* __restrict__ a_all, double* __restrict__ rec_all) {
+  __shared__ double un[kNewtonMaxFeatures + 1];
+  const int job = blockIdx.x, P = p + 1;
+  const CvCmd c = cmd[job];
+  if (c.action != kCvHalve && c.action != kCvStart) return;
+  const double* __restrict__ u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)P;
+  double* __restrict__ u_cand = u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)P;
+  const double t = c.action == kCvStart ? 1.0 : 0.5;
+  for (int k = threadIdx.x; k <= p; k += 64) un[k] = t == 1.0 ? u_cand[k] : u_cur[k] + t * (u_cand[k] - u_cur[k]);
+  __syncthreads();
+  publish_candidate(un, u_cur, scale_all + (size_t)jobs[job].set * (size_t)p, p, u_cand, a_all + (size_t)job * (size_t)P,
+                    rec_all + (size_t)job * kRecLen);
+}
+
+// newton_cd_kernel for the job blockIdx.x: one wavefront per job, each declaring the whole LDS, so the jobs spread one
+// per CU.  Before anything else it stores the current iterate into U[slot] where the host says it answers a lambda.
+__global__ __launch_bounds__(64) void newton_cv_cd_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                           const double* __restrict__ M_all, const double* __restrict__ scale_all, int p,
+                                                           int n_lambda, int fit_intercept, unsigned max_sweeps, double tol,
+                                                           double* __restrict__ u_all, double* __restrict__ a_all,
+                                                           double* __restrict__ rec_all, double* __restrict__ U_all) {
+  __shared__ double lds[newton_state_doubles(kNewtonMaxFeatures)];
+  const int job = blockIdx.x, P = p + 1, nc = p + 2;
+  const CvCmd c = cmd[job];
+  const double* __restrict__ u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)P;
+  if (c.slot >= 0) {
+    double* __restrict__ U = U_all + ((size_t)job * (size_t)n_lambda + (size_t)c.slot) * (size_t)P;
+    for (int k = threadIdx.x; k < P; k += 64) U[k] = u_cur[k];
+  }
+  if (c.action != kCvStep) return;
+  newton_cd_solve(lds, M_all + (size_t)job * (size_t)nc * (size_t)nc, scale_all + (size_t)jobs[job].set * (size_t)p, p,
+                  (double)jobs[job].n_t, u_cur, c.l2, c.l1, c.ridge, fit_intercept, max_sweeps, tol,
+                  u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)P, a_all + (size_t)job * (size_t)P,
+                  rec_all + (size_t)job * kRecLen);
 }
 
 struct Stream {
@@ -631,6 +967,319 @@ int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io) {
   // the candidate again, blended with the iterate at the caller's t
   SGD_HIP_TRY(hipMemcpyAsync(D.d_cand, io->u, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
   if ((rc = D.publish(io->t)) || (rc = fetch(io->blend_u, io->blend_a, io->blend_rec, kRecHalfSq, 4))) return rc;
+  return SGDNET_OK;
+}
+
+namespace {
+
+// the geometry of a call's jobs: a function of (n, p, the groups, the number of mixes) alone
+struct CvGeometry {
+  int pairs = 0, max_chunks = 0, max_state_blocks = 0;
+  std::vector<CvJob> jobs;
+  CvGeometry(int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix) {
+    const int nc = (int)p + 2, T = (nc + kTileCols - 1) / kTileCols;
+    pairs = T * (T + 1) / 2;
+    jobs.resize((size_t)n_sets * (size_t)n_mix);
+    for (int a = 0; a < n_mix; ++a)
+      for (int t = 0; t < n_sets; ++t) {
+        CvJob& J = jobs[(size_t)a * (size_t)n_sets + (size_t)t];
+        J = CvJob{};
+        J.n_t = n_t[t];
+        J.set = t;
+        J.rows_per_chunk = dense_rows_per_chunk(J.n_t, pairs);
+        J.chunks = sparse ? 0 : (int32_t)((J.n_t + J.rows_per_chunk - 1) / J.rows_per_chunk);
+        J.state_blocks = (int32_t)std::min<int64_t>(kStateMaxBlocks, (J.n_t + kBlock - 1) / kBlock);
+        max_chunks = std::max(max_chunks, (int)J.chunks);
+        max_state_blocks = std::max(max_state_blocks, (int)J.state_blocks);
+      }
+  }
+  // per job: v, r, the moments and the chunks' partial tiles
+  size_t workspace_doubles(int64_t n, int64_t p) const {
+    return jobs.size() * (2 * (size_t)n + (size_t)(p + 2) * (size_t)(p + 2) + (size_t)max_chunks * (size_t)pairs * kBlock);
+  }
+};
+
+// what the host knows of a job between two rounds: newton_run's local variables
+struct CvJobState {
+  int l = 0, cur = 0, halved = 0, action = kCvStart, slot = -1;
+  unsigned steps = 0;
+  bool negligible = false;
+  double objective = 0.0, candidate = 0.0, loss = 0.0, half_sq = 0.0, abs1 = 0.0;
+};
+
+struct CvPinned {
+  void* p = nullptr;
+  ~CvPinned() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+}  // namespace
+
+size_t newton_cv_workspace_bytes(int64_t n, int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix) {
+  return sizeof(double) * CvGeometry(p, sparse, n_t, n_sets, n_mix).workspace_doubles(n, p);
+}
+
+// The lock-step loop.  A round: the commands go up in one copy, every kernel is launched once over all jobs (a job whose
+// command does not need a kernel leaves it at once), the records come back in one copy, and every job's state machine
+// moves exactly as newton_run moves its one: a step is (moments, inner solve, state pass at the candidate); a candidate
+// after which the objective rose is halved (blend, state pass) in the next round; an accepted candidate becomes the
+// current iterate by flipping `cur`; a lambda that is done names the slot of U its iterate goes to.  The loop ends
+// when every job has finished its last lambda; one last launch stores the iterates still owed.
+int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
+  const int p = (int)pb.p, P = p + 1, nc = p + 2, L = pb.n_lambda, G = pb.n_sets;
+  const int64_t n = pb.n;
+  const bool sparse = pb.x_dense == nullptr;
+  if (n <= 0 || p <= 0 || p > kNewtonMaxFeatures || L <= 0 || G <= 0 || pb.n_mix <= 0 || !pb.y || !pb.start || !pb.mean || !pb.scale ||
+      !pb.b0 || !pb.l2 || !pb.l1 || !pb.ridge || pb.max_iter == 0 || (sparse && (!pb.colptr || !pb.rowidx || !pb.values || !pb.cut)) ||
+      (int64_t)G * pb.n_mix > kNewtonCvMaxJobs) {
+    set_error("newton_cv_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  std::vector<int64_t> n_t((size_t)G);
+  for (int t = 0; t < G; ++t) {
+    const int64_t own = pb.start[t + 1] - pb.start[t];
+    n_t[(size_t)t] = pb.train_on_rest ? n - own : own;
+    if (own <= 0 || n_t[(size_t)t] <= 0) {
+      set_error("newton_cv_run: empty training set %d", t);
+      return SGDNET_EINVAL;
+    }
+  }
+  CvGeometry geo(p, sparse, n_t.data(), G, pb.n_mix);
+  const int jobs = (int)geo.jobs.size();
+  for (int job = 0; job < jobs; ++job) {
+    CvJob& J = geo.jobs[(size_t)job];
+    const int t = J.set;
+    if (pb.train_on_rest) {
+      J.a0 = 0;
+      J.a1 = pb.start[t];
+      J.b0 = pb.start[t + 1];
+      J.b1 = n;
+    } else {
+      J.a0 = pb.start[t];
+      J.a1 = J.b0 = J.b1 = pb.start[t + 1];
+    }
+  }
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_cut = A.reserve(sparse ? sizeof(int32_t) * (size_t)p * (size_t)(G + 1) : 0);
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_jobs = A.reserve(sizeof(CvJob) * (size_t)jobs);
+  const size_t o_cmd = A.reserve(sizeof(CvCmd) * (size_t)jobs);
+  const size_t o_v = A.reserve(sizeof(double) * (size_t)jobs * (size_t)n);
+  const size_t o_r = A.reserve(sizeof(double) * (size_t)jobs * (size_t)n);
+  const size_t o_part = A.reserve(sizeof(double) * (size_t)jobs * (size_t)geo.max_chunks * (size_t)geo.pairs * kBlock);
+  const size_t o_M = A.reserve(sizeof(double) * (size_t)jobs * (size_t)nc * (size_t)nc);
+  const size_t o_partial = A.reserve(sizeof(double) * (size_t)jobs * 3 * kStateMaxBlocks);
+  const size_t o_sums = A.reserve(sizeof(double) * 2 * (size_t)jobs);
+  const size_t o_rec = A.reserve(sizeof(double) * kRecLen * (size_t)jobs);
+  const size_t o_u = A.reserve(sizeof(double) * 2 * (size_t)P * (size_t)jobs);
+  const size_t o_a = A.reserve(sizeof(double) * (size_t)P * (size_t)jobs);
+  const size_t o_U = A.reserve(sizeof(double) * (size_t)jobs * (size_t)L * (size_t)P);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+  double *d_x = A.at<double>(o_x), *d_y = A.at<double>(o_y), *d_mu = A.at<double>(o_mu), *d_scale = A.at<double>(o_scale),
+         *d_v = A.at<double>(o_v), *d_r = A.at<double>(o_r), *d_part = A.at<double>(o_part), *d_M = A.at<double>(o_M),
+         *d_partial = A.at<double>(o_partial), *d_sums = A.at<double>(o_sums), *d_rec = A.at<double>(o_rec), *d_u = A.at<double>(o_u),
+         *d_a = A.at<double>(o_a), *d_U = A.at<double>(o_U);
+  int32_t *d_colptr = A.at<int32_t>(o_colptr), *d_rowidx = A.at<int32_t>(o_rowidx), *d_cut = A.at<int32_t>(o_cut);
+  CvJob* d_jobs = A.at<CvJob>(o_jobs);
+  CvCmd* d_cmd = A.at<CvCmd>(o_cmd);
+
+  Stream sx;                           // (its rec_host is not used here: the records of all jobs come back into `pinned`)
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
+  hipStream_t st = sx.st;
+  if (timed)
+    for (hipEvent_t& e : sx.e) SGD_HIP_TRY(hipEventCreate(&e));
+  CvPinned pinned;                     // the commands of a round, then the records of its state passes
+  SGD_HIP_TRY(hipHostMalloc(&pinned.p, sizeof(CvCmd) * (size_t)jobs + sizeof(double) * kRecLen * (size_t)jobs, hipHostMallocDefault));
+  CvCmd* cmd = static_cast<CvCmd*>(pinned.p);
+  const double* rec_all = reinterpret_cast<const double*>(cmd + jobs);
+
+  // upload: x, y, the training sets' centres and scales, the jobs; both iterates of every job start at (0, b0)
+  std::vector<double> start((size_t)jobs * 2 * (size_t)P, 0.0);
+  for (int job = 0; job < jobs; ++job)
+    for (int b = 0; b < 2; ++b) start[((size_t)job * 2 + (size_t)b) * (size_t)P + (size_t)p] = pb.b0[geo.jobs[(size_t)job].set];
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, pb.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cut, pb.cut, sizeof(int32_t) * (size_t)p * (size_t)(G + 1), hipMemcpyHostToDevice, st));
+    DeviceSetup& S = sx.S;             // the sample-major copy of the state pass (NewtonDevice::setup)
+    S.n = n;
+    S.p = p;
+    S.nnz = nnz;
+    if (nnz > 0) {
+      S.colptr = d_colptr;
+      S.rowidx = d_rowidx;
+      S.val = d_x;
+      const int rc = device_transpose(S, st);
+      S.colptr = S.rowidx = nullptr;
+      S.val = nullptr;
+      if (rc) return rc;
+    } else {
+      SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.sptr), sizeof(int64_t) * ((size_t)n + 1)));
+      SGD_HIP_TRY(hipMemsetAsync(S.sptr, 0, sizeof(int64_t) * ((size_t)n + 1), st));
+    }
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_mu, pb.mean, sizeof(double) * (size_t)G * (size_t)p, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)G * (size_t)p, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_jobs, geo.jobs.data(), sizeof(CvJob) * (size_t)jobs, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_u, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen * (size_t)jobs, st));
+
+  out->loss.assign((size_t)jobs * (size_t)L, 0.0);
+  out->unconverged.assign((size_t)jobs * (size_t)L, 0);
+  out->passes.assign((size_t)jobs, 0.0);
+  out->steps.assign((size_t)jobs, 0.0);
+  out->halvings.assign((size_t)jobs, 0.0);
+  out->sweeps = 0.0;
+  out->rounds = 0;
+  out->moments_ms = out->cd_ms = out->state_ms = 0.f;
+
+  std::vector<CvJobState> state((size_t)jobs);
+  const int centre = pb.centre ? 1 : 0, fit_intercept = pb.fit_intercept ? 1 : 0;
+  auto penalties = [&](int job, int l, double* al, double* be) {
+    const size_t at = (size_t)(job / G) * (size_t)L + (size_t)l;
+    *al = pb.l2[at];
+    *be = pb.ridge[job / G] ? 0.0 : pb.l1[at];
+  };
+  int live = jobs;
+  for (;;) {
+    bool any_step = false, any_blend = false;
+    for (int job = 0; job < jobs; ++job) {
+      const CvJobState& s = state[(size_t)job];
+      CvCmd& c = cmd[job];
+      c.action = s.action;
+      c.cur = s.cur;
+      c.slot = s.slot;
+      c.ridge = pb.ridge[job / G] ? 1 : 0;
+      c.l2 = c.l1 = 0.0;
+      if (s.action == kCvStep) penalties(job, s.l, &c.l2, &c.l1);
+      any_step |= s.action == kCvStep;
+      any_blend |= s.action == kCvHalve || s.action == kCvStart;
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(d_cmd, cmd, sizeof(CvCmd) * (size_t)jobs, hipMemcpyHostToDevice, st));
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
+    if (any_step) {
+      if (sparse) {
+        hipLaunchKernelGGL(newton_cv_sparse_pair_kernel, dim3((unsigned)p, (unsigned)nc, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs,
+                           d_cut, G, pb.train_on_rest ? 1 : 0, d_rowidx, d_x, d_v, d_r, d_mu, d_sums, n, p, d_M);
+      } else {
+        hipLaunchKernelGGL(newton_cv_dense_tile_kernel, dim3((unsigned)geo.pairs, (unsigned)geo.max_chunks, (unsigned)jobs), dim3(kBlock), 0,
+                           st, d_cmd, d_jobs, d_x, d_v, d_r, d_mu, n, p, geo.max_chunks, d_part);
+        hipLaunchKernelGGL(newton_cv_reduce_kernel, dim3((unsigned)geo.pairs, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs, d_part,
+                           geo.max_chunks, nc, d_M);
+      }
+    }
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
+    // (the inner solve's kernel also stores the iterates owed to U: it runs in every round)
+    hipLaunchKernelGGL(newton_cv_cd_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_M, d_scale, p, L, fit_intercept,
+                       kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
+    if (any_blend)
+      hipLaunchKernelGGL(newton_cv_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, d_u, d_a, d_rec);
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
+    if (live > 0) {
+      if (sparse)
+        hipLaunchKernelGGL(newton_cv_state_kernel<true>, dim3((unsigned)geo.max_state_blocks, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd,
+                           d_jobs, sx.S.sval, sx.S.sptr, sx.S.sidx, d_y, d_mu, d_a, n, p, centre, d_v, d_r, d_partial);
+      else
+        hipLaunchKernelGGL(newton_cv_state_kernel<false>, dim3((unsigned)geo.max_state_blocks, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd,
+                           d_jobs, d_x, (const int64_t*)nullptr, (const int32_t*)nullptr, d_y, d_mu, d_a, n, p, 1, d_v, d_r, d_partial);
+      hipLaunchKernelGGL(newton_cv_finish_kernel, dim3((unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs, d_partial, d_sums, d_rec);
+    }
+    SGD_HIP_TRY(hipGetLastError());
+    if (live == 0) break;              // (that was the launch that stores the last iterates)
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[3], st));
+    SGD_HIP_TRY(hipMemcpyAsync(const_cast<double*>(rec_all), d_rec, sizeof(double) * kRecLen * (size_t)jobs, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipStreamSynchronize(st));
+    ++out->rounds;
+    if (timed) {
+      float ms = 0.f;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[0], sx.e[1]));
+      out->moments_ms += ms;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[2]));
+      out->cd_ms += ms;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
+      out->state_ms += ms;
+    }
+
+    for (int job = 0; job < jobs; ++job) {
+      CvJobState& s = state[(size_t)job];
+      const int did = s.action;
+      s.slot = -1;
+      if (did == kCvIdle) continue;
+      const double* rec = rec_all + (size_t)job * kRecLen;
+      out->passes[(size_t)job] += 1.0;
+      double al, be;
+      penalties(job, s.l, &al, &be);
+      if (did == kCvStart) {           // the path's start: w = 0, b = b0
+        s.loss = rec[kRecLoss];
+        s.half_sq = rec[kRecHalfSq];
+        s.abs1 = rec[kRecAbs];
+        s.objective = s.loss + al * s.half_sq + be * s.abs1;
+        s.steps = 0;
+        s.action = kCvStep;
+        continue;
+      }
+      if (did == kCvStep) {
+        out->sweeps += rec[kRecSweeps];
+        s.negligible = rec[kRecNegligible] != 0.0;
+        s.halved = 0;
+      } else {
+        out->halvings[(size_t)job] += 1.0;
+        s.negligible = false;          // (the inner solve said so of the whole step, not of a part of it)
+      }
+      s.candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
+      // (a candidate whose objective is not a number counts as one that rose)
+      if (s.halved < kNewtonMaxHalvings && rec[kRecChange] > 0.0 &&
+          !(s.candidate <= s.objective + kNewtonObjectiveSlack * fabs(s.objective))) {
+        ++s.halved;
+        s.action = kCvHalve;
+        continue;
+      }
+      s.cur ^= 1;                      // accepted: the candidate is the iterate
+      s.objective = s.candidate;
+      s.loss = rec[kRecLoss];
+      s.half_sq = rec[kRecHalfSq];
+      s.abs1 = rec[kRecAbs];
+      ++s.steps;
+      out->steps[(size_t)job] += 1.0;
+      const double change = rec[kRecChange], size = rec[kRecSize];
+      const bool all_zero = size == 0.0 && change == 0.0;
+      const bool no_change = size != 0.0 && change / size <= pb.tol;
+      const bool converged = rec[kRecInnerConverged] != 0.0 && (all_zero || no_change || s.negligible);
+      s.action = kCvStep;
+      if (converged || s.steps >= pb.max_iter) {
+        const size_t at = (size_t)job * (size_t)L + (size_t)s.l;
+        out->loss[at] = s.loss;
+        out->unconverged[at] = converged ? 0 : 1;
+        s.slot = s.l++;
+        s.steps = 0;
+        if (s.l == L) {
+          s.action = kCvIdle;
+          --live;
+        } else {
+          penalties(job, s.l, &al, &be);
+          s.objective = s.loss + al * s.half_sq + be * s.abs1;
+        }
+      }
+    }
+  }
+  out->u.resize((size_t)jobs * (size_t)L * (size_t)P);
+  SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), d_U, sizeof(double) * out->u.size(), hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
   return SGDNET_OK;
 }
 

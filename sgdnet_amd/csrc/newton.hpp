@@ -79,6 +79,61 @@ struct NewtonResult {
 // The Newton loop (newton.hip).  p <= kNewtonMaxFeatures is the caller's business (plan_fit).  timed: fill the *_ms fields.
 int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out);
 
+// ---- cross-validation: every fold fit of every mix through the Newton loop in lock-step (newton.hip: newton_cv_run) ----
+// Job (mix a, training set t) = a * n_sets + t is newton_run on the rows of its training set.  The caller hands x and y
+// over with the rows stably sorted by group, so that a training set is the row range of its group
+// [start[t], start[t + 1]) or the complement of it, and everything newton_run takes per problem per training set.
+//
+// What a call keeps on the device per job, in doubles: v and r (2 n: indexed by row, whichever rows the job trains on),
+// the moments ((p + 2)^2) and, for dense x, the row chunks' partial tiles (chunks x tile pairs x 256; at most 16 x
+// 91 x 256 at p = 198, 256 x 1 x 256 at p <= 14).  Calls whose jobs need more than this are refused.  1 GiB still holds
+// 50 jobs (5 mixes x 10 folds) of 1.3 million rows at p <= 14, 50 jobs of 900 000 rows at p = 198, and a
+// leave-one-out CV of 300 rows at p = 198 for 5 mixes (1500 jobs).
+constexpr size_t kNewtonCvWorkspaceBytes = (size_t)1 << 30;
+// the jobs ride in a grid dimension
+constexpr int64_t kNewtonCvMaxJobs = 65535;
+
+struct NewtonCvProblem {
+  int64_t n = 0, p = 0;
+  // x with its rows sorted by group: one of the two, in host memory
+  const double* x_dense = nullptr;     // column-major n x p
+  const int32_t* colptr = nullptr;     // p + 1; the rows of a column ascend
+  const int32_t* rowidx = nullptr;
+  const double* values = nullptr;
+  const int32_t* cut = nullptr;        // sparse x: p x (n_sets + 1); cut[j][t] = the first entry of column j in a row >= start[t]
+  const double* y = nullptr;           // n: class codes 0 / 1, rows sorted as x's
+  int n_sets = 0;                      // the groups; training set t is group t or everything else
+  const int64_t* start = nullptr;      // n_sets + 1: the first row of each group
+  bool train_on_rest = false;
+  bool centre = true, fit_intercept = true;
+  const double* mean = nullptr;        // n_sets x p: the centres of training set t (its own column means; 0 where centre is false)
+  const double* scale = nullptr;       // n_sets x p: the sd the driver standardises with over the training set (1 where it does not)
+  const double* b0 = nullptr;          // n_sets: the null model's intercept
+  int device = 0;
+  int n_mix = 0, n_lambda = 0;
+  const double* l2 = nullptr;          // n_mix x n_lambda: regularization_path's alpha[l]
+  const double* l1 = nullptr;          // n_mix x n_lambda: regularization_path's beta[l]
+  const uint8_t* ridge = nullptr;      // n_mix: the ridge functor (no threshold)
+  unsigned max_iter = 0;
+  double tol = 0.0;
+};
+
+struct NewtonCvResult {                // job-major
+  std::vector<double> u;               // jobs x n_lambda x (p + 1): as NewtonResult::u, at the centres of the job's training set
+  std::vector<double> loss;            // jobs x n_lambda
+  std::vector<int32_t> unconverged;    // jobs x n_lambda
+  std::vector<double> passes, steps, halvings;   // jobs: state passes, outer steps and halvings over the path
+  double sweeps = 0.0;
+  int rounds = 0;                      // rounds of the lock-step loop: launches shared by all jobs
+  float moments_ms = 0.f, cd_ms = 0.f, state_ms = 0.f;   // (timed only)
+};
+
+// the device memory the jobs of a call need (see above); n_t: the rows of each training set
+size_t newton_cv_workspace_bytes(int64_t n, int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix);
+
+// The lock-step loop.  The caller has checked the sizes, the feature limit, the job count and the workspace.
+int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out);
+
 // Diagnostics (include/sgdnet_hip.h: sgdnet_newton_probe_*): one outer step through the host steps newton_run takes, every
 // output copied back.  pb: x, y, centre, scale, device and n_lambda = 1; the rest comes from io.  The caller has checked both.
 int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io);

@@ -18,6 +18,10 @@ fold_fits="batched" (mode="covariance" only): the n_alpha * nfolds fold fits are
 (cv_covariance_fits -> sgdnet_cv_covariance_*): one pass over x leaves the moments of every fold on the
 device, every training set's moments are pooled from them and all paths run side by side, one workgroup each.
 The full fits, the fold ids, the scoring and the result are those of the default fold_fits="separate".
+
+cv_sgdnet_newton() is the binomial CV whose fits are sgdnet_newton(); its fold_fits="batched" runs all fold fits through
+cv_newton_fits -> sgdnet_cv_newton_*: the Newton loops of all jobs advance in lock-step, every kernel launched once per
+round over all of them (csrc/newton.hip: newton_cv_run).  _cv() is the body both CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -26,8 +30,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODES, check, dptr
-from .api import SgdnetFit, sgdnet
+from ._lib import FAMILIES, MODE_NEWTON, MODES, check, dptr
+from .api import SgdnetFit, _levels, sgdnet, sgdnet_newton
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -91,8 +95,39 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
     of one length.  train_on: "fold" (fit on the fold's own rows, the reference's convention) or "rest".
     Returns a list of SgdnetFit, alpha-major: entry a * nfolds + j is sgdnet(x[T], y[T], alpha=alpha[a],
     lambda_=lambda_[a], mode="covariance") for the training set T of fold j."""
+    y_enc = np.ascontiguousarray(np.asarray(y), dtype=np.float64).reshape(-1)
+    return _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, family="gaussian", classnames=None, maxit=maxit,
+                             standardize=standardize, intercept=intercept, thresh=thresh, device=device)
+
+
+def cv_newton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                   thresh=0.001, device=0):
+    """Every fold fit of a binomial cross-validation in Newton mode from one native call, all of them advancing in lock-step.
+
+    The arguments are cv_covariance_fits's; y holds two classes and is encoded once, over all samples, as sgdnet() encodes
+    a binomial response (so a fold's class codes are the whole data's).  Returns a list of SgdnetFit, alpha-major: entry
+    a * nfolds + j is sgdnet_newton(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a]) for the training set T of fold j;
+    its diagnostics hold the job's Newton steps and halvings over the path ("steps", "halvings")."""
+    y_arr = np.asarray(y)
+    if y_arr.ndim > 1 and y_arr.shape[1] > 1:
+        raise ValueError("response for binomial regression must be one-dimensional.")
+    levels, _, codes = _levels(y_arr)
+    if levels.size > 2:
+        raise ValueError("more than two classes in response. Are you looking for family = 'multinomial'?")
+    if levels.size == 1:
+        raise ValueError("only one class in response.")
+    return _native_fold_fits(x, np.ascontiguousarray(codes), foldid, alpha, lambda_, train_on, family="binomial",
+                             classnames=[str(v) for v in levels], maxit=maxit, standardize=standardize, intercept=intercept,
+                             thresh=thresh, device=device)
+
+
+def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, classnames, maxit, standardize, intercept, thresh,
+                      device):
+    """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*)
+    and cv_newton_fits (binomial: sgdnet_cv_newton_*); y_enc: the response as the backend takes it."""
     import scipy.sparse as sp
 
+    newton = family == "binomial"
     if train_on not in ("fold", "rest"):
         raise ValueError("train_on must be 'fold' or 'rest'")
     if not all(isinstance(v, (bool, np.bool_)) for v in (intercept, standardize)):
@@ -113,7 +148,6 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
     if maxit <= 0:
         raise ValueError("maximum number of iterations cannot be negative or zero.")
     n, p = x.shape
-    y_enc = np.ascontiguousarray(np.asarray(y), dtype=np.float64).reshape(-1)
     foldid = np.asarray(foldid).reshape(-1)
     if y_enc.size != n or foldid.size != n:
         raise ValueError("the number of samples in 'x', 'y' and 'foldid' must match")
@@ -122,10 +156,10 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
     G, A, nl = values.size, alphas.size, lam.shape[1]
 
     ctl = _lib.Control()
-    ctl.family = FAMILIES["gaussian"]
+    ctl.family = FAMILIES[family]
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
     ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, 1
-    ctl.mode, ctl.device = MODES["covariance"], int(device)
+    ctl.mode, ctl.device = (MODE_NEWTON if newton else MODES["covariance"]), int(device)
     jobs = A * G
     a0 = np.zeros((jobs, nl))
     beta = np.zeros((jobs, nl, p))
@@ -133,7 +167,12 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
     rcodes = np.zeros((jobs, nl))
     nulldev = np.zeros(jobs)
     npasses = np.zeros(jobs)
-    res = _lib.CvCovResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses))
+    steps, halvings = np.zeros(jobs), np.zeros(jobs)
+    if newton:
+        res = _lib.CvNewtonResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses), dptr(steps),
+                                  dptr(halvings))
+    else:
+        res = _lib.CvCovResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses))
     tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
             dptr(lam), C.byref(res))
     L = _lib.load()
@@ -148,10 +187,10 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
         csc.colptr = colptr.ctypes.data_as(C.POINTER(C.c_int32))
         csc.rowidx = rowidx.ctypes.data_as(C.POINTER(C.c_int32))
         csc.values = dptr(vals)
-        check(L.sgdnet_cv_covariance_sparse(C.byref(csc), *tail))
+        check((L.sgdnet_cv_newton_sparse if newton else L.sgdnet_cv_covariance_sparse)(C.byref(csc), *tail))
     else:
         xd = np.asfortranarray(np.asarray(x, dtype=np.float64).reshape(n, p))
-        check(L.sgdnet_cv_covariance_dense(dptr(xd), n, p, *tail))
+        check((L.sgdnet_cv_newton_dense if newton else L.sgdnet_cv_covariance_dense)(dptr(xd), n, p, *tail))
 
     counts = np.bincount(fold, minlength=G)
     fits = []
@@ -161,9 +200,10 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
             b = beta[job].T.copy()                                # (p, n_lambda)
             fits.append(SgdnetFit(a0=a0[job].copy(), beta=b, lambda_=lam[a].copy(), dev_ratio=dev_ratio[job].copy(),
                                   df=(b != 0).sum(axis=0), nulldev=float(nulldev[job]), npasses=float(npasses[job]),
-                                  alpha=float(alphas[a]), offset=False, classnames=None, grouped=False,
-                                  nobs=int(n - counts[j] if train_on == "rest" else counts[j]), family="gaussian",
-                                  return_codes=rcodes[job].copy(), draws_used=0))
+                                  alpha=float(alphas[a]), offset=False, classnames=classnames, grouped=False,
+                                  nobs=int(n - counts[j] if train_on == "rest" else counts[j]), family=family,
+                                  return_codes=rcodes[job].copy(), draws_used=0,
+                                  diagnostics=dict(steps=float(steps[job]), halvings=float(halvings[job])) if newton else {}))
     return fits
 
 
@@ -187,6 +227,51 @@ def cv_sgdnet(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure=
         extra = sorted(set(fit_args) - set(_BATCHED_FIT_ARGS))
         if extra:
             raise ValueError("fold_fits='batched' does not cover the fit argument(s) " + ", ".join(extra))
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):
+        kw = dict(fit_args)
+        if sequential:
+            kw["rng"] = rng                       # R's global generator, advanced by every fit
+        else:
+            kw["seed"] = fit_seed
+        return sgdnet(xx, yy, family=family, alpha=float(a), lambda_=lam, device=dev, **kw)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        kw = {k: fit_args[k] for k in ("maxit", "standardize", "intercept", "thresh") if k in fit_args}
+        return cv_covariance_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **kw)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family=family, devices=devices, rng=rng, seed=seed,
+               train_on=train_on, densify=densify, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
+def cv_sgdnet_newton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                     train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                     standardize=True, intercept=True, thresh=0.001):
+    """cv_sgdnet(family="binomial") with every fit a sgdnet_newton(): the fold ids, the scoring, the generator and the
+    returned CvSgdnet are cv_sgdnet's.  fold_fits="separate" (the default) runs one sgdnet_newton per fold;
+    "batched" runs all fold fits of all alphas through ONE native call (cv_newton_fits) with the full fits' lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_newton(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio, device=dev,
+                             **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_newton_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="binomial", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
+def _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, *, family, devices, rng, seed, train_on, densify, fit_one, batched_fits):
+    """The cross-validation behind cv_sgdnet() and cv_sgdnet_newton(): the full fits, the fold ids, the fold fits, the scores
+    and the summary.  fit_one(x, y, lambda, alpha, device, seed, rng, sequential) is a fit; batched_fits(x, y, foldid, alpha,
+    lambdas, device), where given, returns every fold fit from one call (alpha-major), else the folds are fitted one by one."""
+    import scipy.sparse as sp
 
     alpha = np.atleast_1d(np.asarray(alpha, dtype=np.float64))
     if not (nfolds > 2 and alpha.size > 0):
@@ -222,12 +307,7 @@ def cv_sgdnet(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure=
         rng = RRng(seed)
 
     def one_fit(xx, yy, lam, a, dev, fit_seed):
-        kw = dict(fit_args)
-        if sequential:
-            kw["rng"] = rng                       # R's global generator, advanced by every fit
-        else:
-            kw["seed"] = fit_seed
-        return sgdnet(xx, yy, family=family, alpha=float(a), lambda_=lam, device=dev, **kw)
+        return fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential)
 
     fits = [one_fit(x, y, lam_in[i], alpha[i], devices[0], seed + 1 + i) for i in range(alpha.size)]
     lam = [f.lambda_ for f in fits]
@@ -256,17 +336,18 @@ def cv_sgdnet(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure=
     jobs = [(i, j, (i * nfolds + j) % len(devices), seed + 1000 + i * nfolds + j)
             for i in range(alpha.size) for j in range(nfolds)]               # (alpha, fold, worker, seed)
     cv_raw = [np.full((nfolds, lam[i].size), np.nan) for i in range(alpha.size)]
-    if fold_fits == "batched":
+    if batched_fits is not None:
         # the groups of the native call in the order of fold_values (np.unique sorts, and so does np.arange(1, nfolds + 1))
-        kw = {k: fit_args[k] for k in ("maxit", "standardize", "intercept", "thresh") if k in fit_args}
-        fold_fit = cv_covariance_fits(x, y, foldid, alpha, lam, train_on=train_on, device=devices[0], **kw)
+        fold_fit = batched_fits(x, y, foldid, alpha, lam, devices[0])
         if len(fold_fit) != alpha.size * nfolds:
             raise ValueError("fold_fits='batched' needs every fold to hold a sample")
 
         def score_job(job):
             i, j = job[0], job[1]
             test = (foldid == fold_values[j]) != (train_on == "fold")
-            return i, j, score(fold_fit[i * nfolds + j], x[test], y[test], type_measure, device=devices[0])
+            # (the tie-breaking draws of "auc" are taken fold by fold in the order of the separate fits: see fold_job)
+            tie_rng = rng if type_measure == "auc" else None
+            return i, j, score(fold_fit[i * nfolds + j], x[test], y[test], type_measure, device=devices[0], rng=tie_rng)
         results = map(score_job, jobs)
     elif sequential:
         results = map(fold_job, jobs)
