@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_* (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -93,6 +93,20 @@ extern "C" {
  * summed over the path.  lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are defined as in the other
  * modes. */
 #define SGDNET_MODE_NEWTON 4
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): the mgaussian path of
+ * n_classes responses solved to its optimum from the centred cross-products X'X and X'Y, which one pass over x leaves
+ * on the device: the group lasso over the responses of a feature with its l2 part (the ridge functor at
+ * elasticnet_mix = 0), by cyclic block coordinate descent in one workgroup, one Gram matrix serving all responses
+ * (sgdnet_amd/csrc/covariance.hip: cov_group_path_kernel).  For 0 < elasticnet_mix < 1 this is the only mode with an
+ * optimum to return: the reference's group-lasso step has no fixed point there.  Needs family =
+ * mgaussian, n_features <= sgdnet_mcovariance_max_features(n_classes), n_gpus <= 1 and debug = 0; anything else returns
+ * SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition ("mode = mcovariance needs ...") -- no fall back to
+ * SAGA.  The fit draws no samples: sample_stream, unif, seed and rng_state are accepted and ignored, rng_state is left
+ * untouched bit for bit and result.draws_used = 0.  result.npasses = the block sweeps summed over the path, max_iter
+ * bounds the sweeps of one lambda, tol is the reference's ConvergenceCheck over all n_features x n_classes coefficients
+ * per sweep, and return_codes[l] = 1 when lambda l used all max_iter sweeps without meeting tol.  lambda, nulldev,
+ * dev_ratio, standardize_response, intercept = 0 and standardize = 0 are defined as in the other modes. */
+#define SGDNET_MODE_MCOVARIANCE 5
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -186,6 +200,9 @@ int sgdnet_device_count(void);
 int sgdnet_covariance_max_features(void);
 /* the largest n_features SGDNET_MODE_NEWTON takes (198: the intercept is one more coordinate of the LDS-resident model) */
 int sgdnet_newton_max_features(void);
+/* the largest n_features SGDNET_MODE_MCOVARIANCE takes with n_responses responses: the LDS holds p (p + 1) / 2 + 3 p K
+ * doubles (195 at K = 2, 174 at K = 10, 63 at K = 96); 0 where nothing fits or n_responses < 1 */
+int sgdnet_mcovariance_max_features(int n_responses);
 
 /* ------------------------------------------------------------------------ */
 /* Process-wide backend options.  These are the ONLY switches that change    */

@@ -37,7 +37,7 @@ EXPORTS = [
     "sgdnet_setup_probe_sparse", "sgdnet_setup_probe_dense",
     "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse", "sgdnet_newton_max_features",
     "sgdnet_newton_probe_dense", "sgdnet_newton_probe_sparse",
-    "sgdnet_cv_newton_dense", "sgdnet_cv_newton_sparse",
+    "sgdnet_cv_newton_dense", "sgdnet_cv_newton_sparse", "sgdnet_mcovariance_max_features",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -46,6 +46,7 @@ FAMILIES = {"gaussian": 0, "binomial": 1, "multinomial": 2, "mgaussian": 3}
 PENALTIES = {"ridge": 0, "elasticnet": 1, "grouplasso": 2}
 MODES = {"exact": 0, "batched": 1, "auto": 2, "covariance": 3}
 MODE_NEWTON = 4   # SGDNET_MODE_NEWTON: reached through sgdnet_newton(), not through sgdnet(mode=...)
+MODE_MCOVARIANCE = 5   # SGDNET_MODE_MCOVARIANCE: reached through sgdnet_mcovariance(), likewise
 
 UNIF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
 LOSSES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)
@@ -250,6 +251,7 @@ def load():
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvNewtonResult)]
     L.sgdnet_cv_newton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_newton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
+    L.sgdnet_mcovariance_max_features.argtypes = [C.c_int]
     _lib = L
     return L
 

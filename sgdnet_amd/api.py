@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_NEWTON, MODES, check, dptr
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_NEWTON, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -94,9 +94,25 @@ def sgdnet_newton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=Non
                 batch=0, device=device, devices=None)
 
 
+def sgdnet_mcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
+                       intercept=True, thresh=0.001, standardize_response=False, *, device=0):
+    """The multi-response path of sgdnet(x, y, family="mgaussian", ...) solved to its optimum on the device
+    (SGDNET_MODE_MCOVARIANCE, csrc/covariance.hip): one pass over x for the centred X'X and X'Y, then cyclic block
+    coordinate descent over the features, a block the coefficients of one feature for all responses -- the group
+    lasso with its l2 part, or ridge at alpha = 0.  For 0 < alpha < 1 it is the only mode that returns the optimum of
+    the problem kkt.py states (the SAGA group-lasso step has no fixed point there).  At most
+    mcovariance_max_features(y.shape[1]) features.  The arguments, their validation and the returned SgdnetFit are
+    sgdnet()'s; lambda_ and nulldev are those of the other modes bit for bit.  It draws no samples (draws_used = 0);
+    maxit bounds the sweeps per lambda, thresh is the largest relative change a last sweep may make, npasses counts
+    sweeps."""
+    return _fit(x, y, "mgaussian", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
+                standardize_response, debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="mcovariance",
+                modes={"mcovariance": MODE_MCOVARIANCE}, batch=0, device=device, devices=None)
+
+
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
          standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices):
-    """Validation, response encoding, the native call and the post-processing behind sgdnet() and sgdnet_newton();
+    """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton() and sgdnet_mcovariance();
     modes: the mode strings the caller accepts and their SGDNET_MODE_* codes."""
     import scipy.sparse as sp
 

@@ -35,6 +35,11 @@
 //              order of the columns' sd, not of their mean, so nothing cancels), then writes what cov_path_kernel reads;
 //              the path kernel takes its job (mix, T) from blockIdx.x: one wavefront, one CU's LDS, per job.
 //
+//   responses  mcovariance_run (SGDNET_MODE_MCOVARIANCE): K responses of an mgaussian fit share S.  The moment kernels take a
+//              response count (columns p .. p + K - 1 of the augmented matrix; one response is the case above, bit for
+//              bit) and cov_group_path_kernel runs cyclic BLOCK coordinate descent, a block the K coefficients of a
+//              feature: the group lasso with its l2 part, closed form per block (covariance.hpp has the LDS budget).
+//
 // No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
 #include <algorithm>
@@ -49,11 +54,12 @@ namespace sgdnet {
 namespace {
 
 // blockIdx.x: the pair (tj <= tk) of column tiles of the augmented matrix, blockIdx.y: the chunk of rows.
-// One fit: ncols = p + 1, the matrix is [x - mu | y] (y as the driver preprocessed it), chunk c is rows [c rows_per_chunk, ...).
-// Group moments: ncols = p + 2, [x - mu | y - mean(y) | 1], chunk c is the sorted rows perm[chunk_begin[c] .. chunk_begin[c + 1]).
+// One fit: ncols = p + nresp, the matrix is [x - mu | y_1 .. y_nresp] (y as the driver preprocessed it, n x nresp column-major),
+// chunk c is rows [c rows_per_chunk, ...).
+// Group moments: nresp = 1, ncols = p + 2, [x - mu | y - mean(y) | 1], chunk c is the sorted rows perm[chunk_begin[c] .. chunk_begin[c + 1]).
 __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __restrict__ x, const double* __restrict__ y,
-                                                                 const double* __restrict__ mu, int64_t n, int p, int ncols,
-                                                                 int64_t rows_per_chunk, const int64_t* __restrict__ perm,
+                                                                 const double* __restrict__ mu, int64_t n, int p, int nresp,
+                                                                 int ncols, int64_t rows_per_chunk, const int64_t* __restrict__ perm,
                                                                  const int64_t* __restrict__ chunk_begin, double* __restrict__ part) {
   __shared__ double A[kTileCols][kTileRows + 1], B[kTileCols][kTileRows + 1];
   const int tid = threadIdx.x;
@@ -77,10 +83,10 @@ __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __
   const double y_centre = grouped ? mu[p + 1] : 0.0;
   auto dev = [&](int a, int64_t i) -> double {
     if (i >= r1 || a >= ncols) return 0.0;
-    if (a > p) return 1.0;
+    if (a >= p + nresp) return 1.0;
     const int64_t r = grouped ? perm[i] : i;
     if (a < p) return x[r + (int64_t)a * n] - mu[a];
-    return grouped ? y[r] - y_centre : y[r];
+    return grouped ? y[r] - y_centre : y[r + (int64_t)(a - p) * n];
   };
   double acc = 0.0;
   for (int64_t base = r0; base < r1; base += kTileRows) {
@@ -124,29 +130,31 @@ __global__ __launch_bounds__(kBlock) void cov_group_response_kernel(const double
   }
 }
 
-// blockIdx.x = column j < p, blockIdx.y = column k in [j, p]; k == p is the response.
-// kGrouped: blockIdx.z = group g, only the stored entries whose row is in g count, n becomes n_g, the response is
+// blockIdx.x = column j < p, blockIdx.y = column k in [j, p + nresp); k = p + r is response r (y is n x nresp, column-major;
+// mu[p + r] its sum) and M is (p + nresp) x (p + nresp), its response-by-response block left alone.
+// kGrouped: nresp = 1, blockIdx.z = group g, only the stored entries whose row is in g count, n becomes n_g, the response is
 // y - a_y, k runs to p + 1 (the column of ones: the group's sum of deviations) and M[g] is (p + 2) x (p + 2) with the
 // response's own entries already in place (cov_group_response_kernel).
 template <bool kGrouped>
 __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* __restrict__ colptr, const int32_t* __restrict__ rowidx,
                                                                   const double* __restrict__ val, const double* __restrict__ y,
-                                                                  const double* __restrict__ mu, int64_t n, int p,
+                                                                  const double* __restrict__ mu, int64_t n, int p, int nresp,
                                                                   const int32_t* __restrict__ fold, double* __restrict__ M) {
   __shared__ double sh[kBlock];
-  const int j = blockIdx.x, k = blockIdx.y, nc = kGrouped ? p + 2 : p + 1, tid = threadIdx.x;
+  const int j = blockIdx.x, k = blockIdx.y, nc = kGrouped ? p + 2 : p + nresp, tid = threadIdx.x;
   const int g = kGrouped ? (int)blockIdx.z : 0;
   if (k < j) return;
   if (kGrouped) M += (size_t)g * nc * nc;
   auto mine = [&](int32_t r) -> bool { return !kGrouped || fold[r] == g; };
   const int q0 = colptr[j], q1 = colptr[j + 1];
   const double mj = mu[j];
-  if (k == p) {
+  if (kGrouped ? k == p : k >= p) {
     const double ay = kGrouped ? mu[p + 1] : 0.0;
+    const double* yk = y + (int64_t)(k - p) * n;
     double a = 0.0, ys = 0.0;
     for (int q = q0 + tid; q < q1; q += kBlock) {
       if (!mine(rowidx[q])) continue;
-      const double yi = kGrouped ? y[rowidx[q]] - ay : y[rowidx[q]];
+      const double yi = kGrouped ? yk[rowidx[q]] - ay : yk[rowidx[q]];
       a += (val[q] - mj) * yi;
       ys += yi;
     }
@@ -154,10 +162,10 @@ __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* 
     ys = block_sum(ys, sh);
     if (tid == 0) {
       // the response over the samples NOT stored: none, or all - stored
-      const double rest = kGrouped ? M[(size_t)p * nc + p + 1] - ys : ((int64_t)(q1 - q0) == n ? 0.0 : mu[p] - ys);
+      const double rest = kGrouped ? M[(size_t)p * nc + p + 1] - ys : ((int64_t)(q1 - q0) == n ? 0.0 : mu[k] - ys);
       const double c = a - mj * rest;
-      M[(size_t)j * nc + p] = c;
-      M[(size_t)p * nc + j] = c;
+      M[(size_t)j * nc + k] = c;
+      M[(size_t)k * nc + j] = c;
     }
     return;
   }
@@ -367,6 +375,137 @@ __global__ __launch_bounds__(64) void cov_path_kernel(const double* __restrict__
   }
 }
 
+// The block update of feature j of cov_group_path_kernel, for one response: from the stored w_jr and g_jr to the new w_jr.
+// scale = max(0, 1 - l1 / |z|) (1 for the ridge functor), 0 where |z| = 0 or the denominator is 0.  Every caller passes
+// the same words through the same operations, so every lane holds the same bits.
+__device__ __forceinline__ double group_new_w(double sjj, double wjr, double gjr, double shrink, double denom) {
+  return shrink * fma(sjj, wjr, -gjr) / denom;
+}
+
+// Several responses (SGDNET_MODE_MCOVARIANCE): one workgroup of kWidth lanes, the whole path of
+//   min  sum_r |y~_r - X~ w_r|^2 / (2 n) + l2 / 2 sum_jr w_jr^2 + l1 sum_j |w_j.|
+// by cyclic block coordinate descent, a block the K coefficients of a feature.  S is shared by the responses; c~, w and
+// g = S w - c~ are p x K, entry (j, r) at j K + r.  M is the (p + K) x (p + K) matrix of the moments pass.
+// As in cov_path_kernel every lane computes |z|, the block's moves and the sweep's max|dw| and max|w| itself from the
+// same LDS words in the same order (r = 0 .. K - 1): the branches around the barriers are uniform, nothing is broadcast,
+// and a block that does not move costs no LDS write and no barrier.  A moving block: the lanes stride over the entries
+// (k, r), k != j, of g and recompute the move d_r of their response from w_j. and g_j. (still the old ones: there is no
+// room in the budget for K more doubles), then -- a barrier later -- row j of w and g is replaced: two barriers per
+// moving block and one per sweep.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void cov_group_path_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
+                                                                 double dn, const double* __restrict__ alpha,
+                                                                 const double* __restrict__ beta, int n_lambda, int ridge,
+                                                                 unsigned max_iter, double tol, double* __restrict__ W,
+                                                                 double* __restrict__ G, double* __restrict__ c_out,
+                                                                 int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+  __shared__ double lds[kCovLdsDoubles];
+  const int lane = threadIdx.x, nc = p + K, pK = p * K;
+  double* S = lds;
+  double* c = S + p * (p + 1) / 2;
+  double* w = c + pK;
+  double* g = w + pK;
+  for (int k = 0; k < p; ++k) {
+    const double sk = scale[k];
+    for (int j = lane; j <= k; j += kWidth) S[tri(j, k)] = M[(size_t)j * nc + k] / dn / (scale[j] * sk);
+  }
+  for (int e = lane; e < pK; e += kWidth) {
+    const int j = e / K, r = e - j * K;
+    c[e] = M[(size_t)j * nc + p + r] / dn / scale[j];
+    c_out[e] = c[e];
+    w[e] = 0.0;
+  }
+  __syncthreads();
+  // the walk of a lane over the entries e = k K + r in strides of kWidth, without a division per entry
+  const int k_first = lane / K, r_first = lane - k_first * K, k_step = kWidth / K, r_step = kWidth - k_step * K;
+  for (int l = 0; l < n_lambda; ++l) {
+    const double l2 = alpha[l], l1 = beta[l];
+    // the gradient afresh at every lambda, as in cov_path_kernel
+    for (int e = lane, k = k_first, r = r_first; e < pK; e += kWidth) {
+      double s = 0.0;
+      for (int j = 0; j < p; ++j) s += S[j <= k ? tri(j, k) : tri(k, j)] * w[j * K + r];
+      g[e] = s - c[e];
+      k += k_step;
+      r += r_step;
+      if (r >= K) {
+        r -= K;
+        ++k;
+      }
+    }
+    __syncthreads();
+    unsigned sweeps = 0;
+    bool converged = false;
+    while (sweeps < max_iter && !converged) {
+      double max_change = 0.0, max_size = 0.0;
+      for (int j = 0; j < p; ++j) {
+        const double sjj = S[tri(j, j)], denom = sjj + l2;
+        const double* wj = w + j * K;
+        const double* gj = g + j * K;
+        double zz = 0.0;
+        for (int r = 0; r < K; ++r) {
+          const double z = fma(sjj, wj[r], -gj[r]);
+          zz = fma(z, z, zz);
+        }
+        const double nz = sqrt(zz);
+        double shrink = 1.0;
+        if (!ridge) shrink = nz > l1 ? 1.0 - l1 / nz : 0.0;
+        if (!(nz > 0.0) || !(denom > 0.0)) shrink = 0.0;     // (a constant column without an l2 term: S_jj = c~_j. = 0)
+        const double den = denom > 0.0 ? denom : 1.0;
+        bool moved = false;
+        for (int r = 0; r < K; ++r) {
+          const double nw = group_new_w(sjj, wj[r], gj[r], shrink, den), d = nw - wj[r];
+          max_change = fmax(max_change, fabs(d));
+          max_size = fmax(max_size, fabs(nw));
+          moved = moved || d != 0.0;
+        }
+        if (moved) {
+          __syncthreads();                         // every lane has read what the blocks that stayed needed
+          for (int e = lane, k = k_first, r = r_first; e < pK; e += kWidth) {
+            if (k != j) {
+              const double d = group_new_w(sjj, wj[r], gj[r], shrink, den) - wj[r];
+              g[e] = fma(S[k <= j ? tri(k, j) : tri(j, k)], d, g[e]);
+            }
+            k += k_step;
+            r += r_step;
+            if (r >= K) {
+              r -= K;
+              ++k;
+            }
+          }
+          __syncthreads();                         // every lane has read the old w_j. and g_j.
+          for (int r = lane; r < K; r += kWidth) {
+            const double nw = group_new_w(sjj, wj[r], gj[r], shrink, den), d = nw - wj[r];
+            g[j * K + r] = fma(sjj, d, gj[r]);
+            w[j * K + r] = nw;
+          }
+          // (row j is read again by the next sweep, or by the copy out: behind the sweep's barrier.  Until then a later
+          //  block reads its own row, which the loop above finished before the barrier, and writes behind its first one)
+        }
+      }
+      __syncthreads();
+      ++sweeps;
+      const bool all_zero = max_size == 0.0 && max_change == 0.0;
+      const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+      converged = all_zero || no_change;
+    }
+    for (int e = lane; e < pK; e += kWidth) {
+      W[(size_t)l * pK + e] = w[e];
+      G[(size_t)l * pK + e] = g[e];
+    }
+    if (lane == 0) {
+      sweeps_out[l] = (int32_t)sweeps;
+      unconverged[l] = converged ? 0 : 1;
+    }
+  }
+}
+
+// The path kernel's workgroup.  Both widths give the same bits (every entry is updated by one lane from the same words in
+// the same order); profiles/mcovariance_path.txt has their times: at 300 x 174, K = 10 four wavefronts halve the path
+// (284 -> 137 ms), at 4000 x 9, K = 3 (27 entries) three of them would only wait at the barriers (1.30 -> 1.36 ms).
+// So: one wavefront while one stride of it covers all p K entries, four beyond.
+constexpr int kMcovNarrow = 64, kMcovWide = 256;
+constexpr int mcov_path_width(size_t entries) { return entries <= (size_t)kMcovNarrow ? kMcovNarrow : kMcovWide; }
+
 struct Events {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;
@@ -444,13 +583,13 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
 
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
   if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, 1, pb.centre ? 1 : 0, d_mu);
     hipLaunchKernelGGL(cov_sparse_pair_kernel<false>, dim3((unsigned)p, (unsigned)P1), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_y,
-                       d_mu, n, p, (const int32_t*)nullptr, d_M);
+                       d_mu, n, p, 1, (const int32_t*)nullptr, d_M);
   } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
                        pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, P1,
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, 1, P1,
                        rows_per_chunk, (const int64_t*)nullptr, (const int64_t*)nullptr, A.at<double>(o_part));
     hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
                        (const int32_t*)nullptr, P1, d_M);
@@ -477,6 +616,115 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   SGD_HIP_TRY(hipMemcpyAsync(out->unconverged.data(), A.at<int32_t>(o_unconv), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
   out->mean.resize((size_t)p);     // (entry p was the response's sum)
+  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  return SGDNET_OK;
+}
+
+
+int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width) {
+  const int64_t n = pb.n;
+  const int p = (int)pb.p, K = pb.K, nc = p + K, L = pb.n_lambda;
+  const bool sparse = pb.x_dense == nullptr;
+  if (n <= 0 || p <= 0 || K < 1 || pb.p > mcov_max_features(K) || L <= 0 || !pb.y || (width != 0 && width != kMcovNarrow && width != kMcovWide) || (!sparse && pb.colptr) ||
+      (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("mcovariance_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+
+  // dense x: the tile pairs and the row chunks (a function of n, p and K alone)
+  const int T = (nc + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
+  const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+  const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+  const size_t pK = (size_t)p * (size_t)K;
+  if (width == 0) width = mcov_path_width(pK);
+
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(nc + 1));
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
+  const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
+  const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
+  const size_t o_alpha = A.reserve(sizeof(double) * (size_t)L);
+  const size_t o_beta = A.reserve(sizeof(double) * (size_t)L);
+  const size_t o_W = A.reserve(sizeof(double) * (size_t)L * pK);
+  const size_t o_G = A.reserve(sizeof(double) * (size_t)L * pK);
+  const size_t o_c = A.reserve(sizeof(double) * pK);
+  const size_t o_sweeps = A.reserve(sizeof(int32_t) * (size_t)L);
+  const size_t o_unconv = A.reserve(sizeof(int32_t) * (size_t)L);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Events ev;
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
+  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  hipStream_t st = ev.st;
+  double* d_x = A.at<double>(o_x);
+  int32_t* d_colptr = A.at<int32_t>(o_colptr);
+  int32_t* d_rowidx = A.at<int32_t>(o_rowidx);
+  double* d_y = A.at<double>(o_y);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_M = A.at<double>(o_M);
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)(p + 1), hipMemcpyHostToDevice, st));
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n * (size_t)K, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_scale), pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_alpha), pb.alpha, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_beta), pb.beta, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, st));
+
+  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
+  if (sparse) {
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, K, pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<false>, dim3((unsigned)p, (unsigned)nc), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_y,
+                       d_mu, n, p, K, (const int32_t*)nullptr, d_M);
+  } else {
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, K,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, nc,
+                       rows_per_chunk, (const int64_t*)nullptr, (const int64_t*)nullptr, A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       (const int32_t*)nullptr, nc, d_M);
+  }
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  if (width == kMcovNarrow)
+    hipLaunchKernelGGL(cov_group_path_kernel<kMcovNarrow>, dim3(1), dim3(kMcovNarrow), 0, st, d_M, A.at<double>(o_scale), p, K, (double)n, A.at<double>(o_alpha),
+                       A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G),
+                       A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  else
+    hipLaunchKernelGGL(cov_group_path_kernel<kMcovWide>, dim3(1), dim3(kMcovWide), 0, st, d_M, A.at<double>(o_scale), p, K, (double)n, A.at<double>(o_alpha),
+                       A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G),
+                       A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+
+  out->mean.resize((size_t)p);
+  out->c.resize(pK);
+  out->w.resize((size_t)L * pK);
+  out->g.resize((size_t)L * pK);
+  out->sweeps.resize((size_t)L);
+  out->unconverged.resize((size_t)L);
+  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), d_mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->c.data(), A.at<double>(o_c), sizeof(double) * pK, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->w.data(), A.at<double>(o_W), sizeof(double) * (size_t)L * pK, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->g.data(), A.at<double>(o_G), sizeof(double) * (size_t)L * pK, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->sweeps.data(), A.at<int32_t>(o_sweeps), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->unconverged.data(), A.at<int32_t>(o_unconv), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
   return SGDNET_OK;
@@ -589,15 +837,15 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
 
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
   if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p,
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, 1,
                        pb.centre ? 1 : 0, d_mu);
     hipLaunchKernelGGL(cov_group_response_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_y, A.at<int32_t>(o_fold), d_mu, n, p, d_Mg);
     hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
-                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, A.at<int32_t>(o_fold), d_Mg);
+                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, 1, A.at<int32_t>(o_fold), d_Mg);
   } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
                        pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, Pa,
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, 1, Pa,
                        (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
     hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
                        A.at<int32_t>(o_gchunk), Pa, d_Mg);
@@ -649,3 +897,4 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
 }  // namespace sgdnet
 
 extern "C" int sgdnet_covariance_max_features(void) { return sgdnet::kCovMaxFeatures; }
+extern "C" int sgdnet_mcovariance_max_features(int n_responses) { return sgdnet::mcov_max_features(n_responses); }

@@ -57,6 +57,57 @@ struct CovarianceResult {
 // Moments pass + path kernel (covariance.hip).  p <= kCovMaxFeatures is the caller's business (plan_fit).
 int covariance_run(const CovarianceProblem& pb, CovarianceResult* out);
 
+// ---- several responses (SGDNET_MODE_MCOVARIANCE): the mgaussian group-lasso path ----
+// cov_group_path_kernel keeps the same packed triangle S (one Gram matrix serves all K responses) and c~, w and the
+// gradient as p x K each, entry (j, r) at j K + r:
+//   p (p + 1) / 2 + 3 p K doubles
+// One response would give the 198 features above; K = 2 gives 195 (19 110 + 1 170 = 20 280), K = 10 gives 174
+// (15 225 + 5 220 = 20 445), K = 96 gives 63 (2 016 + 18 144 = 20 160).  Nothing fits from K = 6 827 on (a single
+// feature needs 1 + 3 K doubles).
+constexpr int64_t mcov_state_doubles(int64_t p, int64_t K) { return p * (p + 1) / 2 + 3 * p * K; }
+constexpr int mcov_max_features(int K) {
+  if (K < 1 || mcov_state_doubles(1, K) > kCovLdsDoubles) return 0;
+  int p = 1;
+  while (mcov_state_doubles(p + 1, K) <= kCovLdsDoubles) ++p;
+  return p;
+}
+static_assert(mcov_max_features(1) == kCovMaxFeatures, "one response: the budget of cov_path_kernel");
+static_assert(mcov_max_features(2) == 195 && mcov_max_features(3) == 193 && mcov_max_features(5) == 187, "the LDS budget (see above)");
+static_assert(mcov_max_features(10) == 174 && mcov_max_features(16) == 159 && mcov_max_features(32) == 127, "the LDS budget (see above)");
+static_assert(mcov_max_features(64) == 86 && mcov_max_features(95) == 64 && mcov_max_features(96) == 63, "the LDS budget (see above)");
+static_assert(mcov_max_features(0) == 0 && mcov_max_features(6826) == 1 && mcov_max_features(6827) == 0, "where nothing fits");
+
+struct McovarianceProblem {
+  int64_t n = 0, p = 0;
+  int K = 0;                           // responses
+  const double* x_dense = nullptr;     // as CovarianceProblem
+  const int32_t* colptr = nullptr;
+  const int32_t* rowidx = nullptr;
+  const double* values = nullptr;
+  const double* y = nullptr;           // n x K, column-major: the responses less the null model's intercepts
+  bool centre = true;
+  const double* scale = nullptr;       // p
+  int device = 0;
+  int n_lambda = 0;
+  const double* alpha = nullptr;       // l2 strength per lambda
+  const double* beta = nullptr;        // group threshold per lambda
+  bool ridge = false;
+  unsigned max_iter = 0;               // block sweeps per lambda
+  double tol = 0.0;
+};
+
+struct McovarianceResult {
+  std::vector<double> mean;            // p
+  std::vector<double> c;               // p x K, entry (j, r) at j K + r: c~_jr = sum_i x~_ij y~_ir / n
+  std::vector<double> w, g;            // n_lambda x p x K
+  std::vector<int32_t> sweeps, unconverged;   // n_lambda
+  float moments_ms = 0.f, path_ms = 0.f;
+};
+
+// Moments pass + cov_group_path_kernel (covariance.hip).  p <= mcov_max_features(K) is the caller's business (plan_fit).
+// width: lanes of the path kernel's workgroup (64 or 256), 0 = the rule of covariance.hip (mcov_path_width)
+int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0);
+
 // ---- cross-validation: every (training set, elastic-net mix) path of one x in one launch ----
 // Rows carry a group id fold[i] in [0, G).  One pass leaves, per group and about ONE centre a (the whole-data column
 // means, or 0 where centre is false; mean(y) for the response), the (p + 2) x (p + 2) moment matrix of the augmented

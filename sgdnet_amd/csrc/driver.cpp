@@ -1022,6 +1022,82 @@ int fit_covariance(const Features& X, const Response& R, const Path& path, const
   return SGDNET_OK;
 }
 
+// ---- several responses (SGDNET_MODE_MCOVARIANCE, covariance.hip): the stage behind the plan ----
+// The features as fit_covariance takes them; the responses as prepare_response left them (standardised only with
+// standardize_response) less the null model's intercepts R.b0, subtracted here so that the moments pass multiplies
+// deviations.  The intercept of the preprocessed problem stays at R.b0 (less the features' mean shift times w where it
+// is fitted), as it does for one response.
+int fit_mcovariance(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl,
+                    sgdnet_result* out, PhaseTimer& pt) {
+  const int64_t n = X.n, p = X.p;
+  const int L = ctl->n_lambda, K = ctl->n_classes;
+  std::vector<double> yd((size_t)n * (size_t)K);
+  double yy = 0.0;
+  for (int r = 0; r < K; ++r)
+    for (int64_t i = 0; i < n; ++i) {
+      const double d = R.y[(size_t)(i + (int64_t)r * n)] - R.b0[(size_t)r];
+      yd[(size_t)(i + (int64_t)r * n)] = d;
+      yy += d * d;
+    }
+  McovarianceProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.K = K;
+  if (X.sparse) {
+    pb.colptr = X.colptr;
+    pb.rowidx = X.rowidx;
+    pb.values = X.raw_values;
+  } else {
+    pb.x_dense = X.raw_dense;
+  }
+  pb.y = yd.data();
+  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
+  pb.scale = X.x_scale.data();
+  pb.device = plan.rank_dev[0];
+  pb.n_lambda = L;
+  pb.alpha = path.alpha.data();
+  pb.beta = path.beta.data();
+  pb.ridge = plan.penalty == SGDNET_RIDGE;
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  static const int width = exp_env_int("SGDNET_MCOV_WIDTH", 0);     // (64 or 256 lanes: profiles/mcovariance_path.txt)
+  McovarianceResult cr;
+  const int rc = mcovariance_run(pb, &cr, width);
+  if (rc) return rc;
+
+  // deviance from the quadratic form, as in fit_covariance: sum_r |y~_r - X~ w_r|^2 = sum_r y~_r'y~_r - n sum_jr w_jr (c~_jr - g_jr)
+  const size_t pK = (size_t)p * (size_t)K;
+  double n_sweeps = 0.0;
+  std::vector<double> b((size_t)K);
+  for (int li = 0; li < L; ++li) {
+    const double* w = cr.w.data() + (size_t)li * pK;
+    const double* g = cr.g.data() + (size_t)li * pK;
+    double explained = 0.0;
+    std::fill(b.begin(), b.end(), 0.0);
+    for (int64_t j = 0; j < p; ++j) {
+      const double shift = (cr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j];
+      for (int r = 0; r < K; ++r) {
+        const size_t e = (size_t)j * (size_t)K + (size_t)r;
+        explained += w[e] * (cr.c[e] - g[e]);
+        b[(size_t)r] += shift * w[e];
+      }
+    }
+    const double dev = std::max(0.0, yy - (double)n * explained);
+    out->dev_ratio[li] = R.null_dev_scaled > 0.0 ? 1.0 - dev / R.null_dev_scaled : 0.0;
+    out->lambda[li] = path.lambda[(size_t)li];
+    out->return_codes[li] = cr.unconverged[(size_t)li] ? 1.0 : 0.0;
+    n_sweeps += (double)cr.sweeps[(size_t)li];
+    for (int r = 0; r < K; ++r) b[(size_t)r] = ctl->intercept != 0 ? R.b0[(size_t)r] - b[(size_t)r] : R.b0[(size_t)r];
+    rescale_values(X, R, ctl, li, w, b.data(), out);
+  }
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   mcovariance: moments %.3f ms, path kernel %.3f ms, %.0f sweeps\n", cr.moments_ms, cr.path_ms, n_sweeps);
+  out->npasses = n_sweeps;
+  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
+  pt.mark("mcovariance (moments + path)");
+  return SGDNET_OK;
+}
+
 // ---- Newton mode (SGDNET_MODE_NEWTON, newton.hip): the stage behind the plan ----
 // The same preprocessed problem as above, for a binomial response: the features centred where fit_covariance centres
 // them, the class codes as they came, the intercept an unpenalised coordinate that starts at the null model's value
@@ -1098,7 +1174,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   Path path;
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
-  if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON) {   // plan_fit says whether they may run; they need none of the SAGA setup below
+  if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_MCOVARIANCE) {   // plan_fit says whether they may run; they need none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1109,6 +1185,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
       set_error("%s", plan.error.c_str());
       return plan.rc;
     }
+    if (ctl->mode == SGDNET_MODE_MCOVARIANCE) return fit_mcovariance(X, R, path, plan, ctl, out, pt);
     return ctl->mode == SGDNET_MODE_NEWTON ? fit_newton(X, R, path, plan, ctl, out, pt) : fit_covariance(X, R, path, plan, ctl, out, pt);
   }
   double norm_max = 0.0;
@@ -1390,7 +1467,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     col_mean_sd(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
-  if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON) {   // (those modes read x column-major, as it came)
+  if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON && ctl->mode != SGDNET_MODE_MCOVARIANCE) {   // (those modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }

@@ -71,7 +71,8 @@ struct FitFacts {
 // SGDNET_MODE_BATCHED means "batched where it is implemented": more than 64 classes run the exact
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
-// An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE and SGDNET_MODE_NEWTON: no other mode resolves to them.
+// An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE, SGDNET_MODE_NEWTON
+// and SGDNET_MODE_MCOVARIANCE: no other mode resolves to them.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -163,6 +164,27 @@ inline FitPlan plan_fit(const FitFacts& f) {
       return P;
     }
     P.mode = SGDNET_MODE_NEWTON;
+    P.rank_dev.assign(1, c.device);
+    P.rank_lo = {0, n};
+    return P;                          // no window, no shards, no draws
+  }
+
+  // ---- several responses from one Gram matrix: likewise only where it was asked for, and only for the problem its path
+  // kernel holds in one workgroup's LDS (covariance.hpp: mcov_max_features); no silent fall back ----
+  if (c.mode == SGDNET_MODE_MCOVARIANCE) {
+    const int limit = mcov_max_features(K);
+    const char* what = nullptr;
+    if (family != SGDNET_MGAUSSIAN) what = "family = mgaussian";
+    else if (f.p > limit) what = "no more features than sgdnet_mcovariance_max_features(n_classes)";
+    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+    if (what) {
+      P.rc = SGDNET_EUNSUPPORTED;
+      P.error = plan_text("mode = mcovariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what,
+                          family, K, (long long)f.p, limit, c.n_gpus, c.debug);
+      return P;
+    }
+    P.mode = SGDNET_MODE_MCOVARIANCE;
     P.rank_dev.assign(1, c.device);
     P.rank_lo = {0, n};
     return P;                          // no window, no shards, no draws

@@ -29,17 +29,19 @@ __device__ double block_sum(double v, double* sh) {
   return sh[0];
 }
 
-// blockIdx.x = column j < p: mu[j] = mean of the column (sparse: over all n samples); column p: mu[p] = sum of y and
-// mu[p + 1] = mean of y (the centre of the response of the group moments)
+// blockIdx.x = column j < p: mu[j] = mean of the column (sparse: over all n samples); column p + r, r < nresp: mu[p + r] =
+// sum of response r (y is n x nresp, column-major).  One response: mu[p + 1] = mean of y as well (the centre of the
+// response of the group moments)
 template <bool kSparse>
 __global__ __launch_bounds__(kBlock) void cov_sum_kernel(const double* __restrict__ x, const int32_t* __restrict__ colptr,
-                                                          const double* __restrict__ y, int64_t n, int p, int centre,
+                                                          const double* __restrict__ y, int64_t n, int p, int nresp, int centre,
                                                           double* __restrict__ mu) {
   __shared__ double sh[kBlock];
   const int j = blockIdx.x;
   double s = 0.0;
-  if (j == p) {
-    for (int64_t i = threadIdx.x; i < n; i += kBlock) s += y[i];
+  if (j >= p) {
+    const double* col = y + (int64_t)(j - p) * n;
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) s += col[i];
   } else if (!centre) {
     // deviations from 0
   } else if (kSparse) {
@@ -50,8 +52,8 @@ __global__ __launch_bounds__(kBlock) void cov_sum_kernel(const double* __restric
   }
   s = block_sum(s, sh);
   if (threadIdx.x == 0) {
-    mu[j] = j == p ? s : s / (double)n;
-    if (j == p) mu[p + 1] = s / (double)n;
+    mu[j] = j >= p ? s : s / (double)n;
+    if (j == p && nresp == 1) mu[p + 1] = s / (double)n;
   }
 }
 

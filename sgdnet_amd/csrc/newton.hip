@@ -780,10 +780,10 @@ struct NewtonDevice {
     SGD_HIP_TRY(hipMemcpyAsync(d_cand, u_cand0, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
     SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen, st));
     if (sparse)
-      hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, centre ? 1 : 0, d_mu);
+      hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, 1, centre ? 1 : 0, d_mu);
     else
       hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p,
-                         centre ? 1 : 0, d_mu);
+                         1, centre ? 1 : 0, d_mu);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
   }

@@ -125,6 +125,12 @@ def newton_max_features():
     return int(_lib.load().sgdnet_newton_max_features())
 
 
+def mcovariance_max_features(n_responses):
+    """Largest number of features sgdnet_mcovariance() takes with n_responses responses
+    (sgdnet_mcovariance_max_features of the C ABI); 0 where nothing fits."""
+    return int(_lib.load().sgdnet_mcovariance_max_features(int(n_responses)))
+
+
 class SagaSolver:
     """One problem resident in HBM: sample-major x, y and the five SAGA state arrays
     (reference src/sgdnet.cpp:187-198).
