@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -107,6 +107,23 @@ extern "C" {
  * per sweep, and return_codes[l] = 1 when lambda l used all max_iter sweeps without meeting tol.  lambda, nulldev,
  * dev_ratio, standardize_response, intercept = 0 and standardize = 0 are defined as in the other modes. */
 #define SGDNET_MODE_MCOVARIANCE 5
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): the multinomial path
+ * of n_classes classes solved to its optimum by proximal Newton steps on the JOINT Hessian of all n_classes x
+ * (n_features + 1) coordinates.  An outer step is one pass over x that leaves the class probabilities mu_ik and the
+ * mean loss at the iterate, one pass that leaves the n_classes (n_classes + 1) / 2 weighted Gram matrices
+ * H_kl = Z'diag(mu_k (delta_kl - mu_l)) Z / n of the centred features and the column of ones with the gradients
+ * q_k = Z'(y_k - mu_k) / n, and cyclic coordinate descent on the penalised quadratic model in one workgroup, the
+ * intercepts unpenalised coordinates (sgdnet_amd/csrc/mnewton.hip).  A step after which the penalised objective rose is
+ * halved.  Sparse x is expanded to a dense copy first.  Needs family = multinomial with the ungrouped penalty,
+ * 2 <= n_classes <= 99, n_features <= sgdnet_mnewton_max_features(n_classes), n_gpus <= 1, debug = 0 and, for sparse x,
+ * n_samples x n_features x 8 bytes <= 1 GiB; anything else returns SGDNET_EUNSUPPORTED and sgdnet_last_error() names
+ * the condition ("mode = mnewton needs ...") -- no fall back to SAGA.  The fit draws no samples: sample_stream, unif,
+ * seed and rng_state are accepted and ignored, rng_state is left untouched bit for bit and result.draws_used = 0.
+ * Stopping, max_iter, return_codes and npasses are SGDNET_MODE_NEWTON's, the change taken over all coordinates.  The
+ * loss does not see a shift common to all intercepts: a0 comes back with its class mean removed.  At elasticnet_mix = 1
+ * and an even n_classes the optimum need not be unique in the coefficients (its deviance and its optimality
+ * conditions are).  lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are defined as in the other modes. */
+#define SGDNET_MODE_MNEWTON 6
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -203,6 +220,10 @@ int sgdnet_newton_max_features(void);
 /* the largest n_features SGDNET_MODE_MCOVARIANCE takes with n_responses responses: the LDS holds p (p + 1) / 2 + 3 p K
  * doubles (195 at K = 2, 174 at K = 10, 63 at K = 96); 0 where nothing fits or n_responses < 1 */
 int sgdnet_mcovariance_max_features(int n_responses);
+/* the largest n_features SGDNET_MODE_MNEWTON takes with n_classes classes: the LDS holds Q (Q + 1) / 2 + 2 Q doubles,
+ * Q = n_classes (n_features + 1) <= 199: 199 / n_classes - 1 (98 at K = 2, 65 at K = 3, 38 at K = 5, 18 at K = 10,
+ * 1 at K = 99); 0 for n_classes < 2 or >= 100 */
+int sgdnet_mnewton_max_features(int n_classes);
 
 /* ------------------------------------------------------------------------ */
 /* Process-wide backend options.  These are the ONLY switches that change    */

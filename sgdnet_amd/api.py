@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_NEWTON, MODES, check, dptr
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -110,10 +110,30 @@ def sgdnet_mcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda
                 modes={"mcovariance": MODE_MCOVARIANCE}, batch=0, device=device, devices=None)
 
 
+def sgdnet_mnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
+                   intercept=True, thresh=0.001, *, device=0):
+    """The multinomial path of sgdnet(x, y, family="multinomial", ...) solved to its optimum by proximal Newton steps
+    on the joint Hessian of all classes (SGDNET_MODE_MNEWTON, csrc/mnewton.hip): per step one pass over x for the class
+    probabilities, one for the K (K + 1) / 2 weighted Gram matrices and the gradients, then coordinate descent on the
+    penalised quadratic model over all K (p + 1) coordinates, the intercepts unpenalised.  At most
+    mnewton_max_features(K) = 199 // K - 1 features (65 at K = 3, 18 at K = 10), K <= 99; sparse x is expanded to a
+    dense copy first (at most 1 GiB) and gives the dense fit's bits.  The arguments, their validation, the response encoding and the returned
+    SgdnetFit are sgdnet()'s, except that two classes are taken (the softmax form, both classes penalised); lambda_
+    and nulldev are those of the other modes bit for bit.  a0 has its class mean removed, as sgdnet() returns it.  At
+    alpha = 1 and an even number of classes the optimum need not be unique in the coefficients: compare deviances and
+    optimality residuals (kkt()) there, not coefficients.  It draws no samples (draws_used = 0); maxit bounds the
+    Newton steps per lambda, thresh is the largest relative change of all coefficients and intercepts a last step may
+    make, npasses counts the passes that evaluated an iterate."""
+    return _fit(x, y, "multinomial", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh, False,
+                debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="mnewton", modes={"mnewton": MODE_MNEWTON},
+                batch=0, device=device, devices=None, min_classes=2)
+
+
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
-         standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices):
-    """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton() and sgdnet_mcovariance();
-    modes: the mode strings the caller accepts and their SGDNET_MODE_* codes."""
+         standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3):
+    """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton(),
+    sgdnet_mcovariance() and sgdnet_mnewton(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
+    min_classes: the fewest classes a multinomial response may have."""
     import scipy.sparse as sp
 
     n_samples = x.shape[0]
@@ -186,7 +206,7 @@ def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standar
         levels, counts, codes = _levels(y_arr)
         class_names = [str(v) for v in levels]
         n_classes = levels.size
-        if n_classes == 2:
+        if n_classes == 2 and min_classes > 2:
             _stop("only two classes in response. Are you looking for family = 'binomial'?")
         if n_classes == 1:
             _stop("only one class in response.")

@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "covariance.hpp"
 #include "fit_plan.hpp"
+#include "mnewton.hpp"
 #include "newton.hpp"
 #include "setup_device.hpp"
 
@@ -1154,6 +1155,71 @@ int fit_newton(const Features& X, const Response& R, const Path& path, const Fit
   return SGDNET_OK;
 }
 
+// ---- multinomial Newton mode (SGDNET_MODE_MNEWTON, mnewton.hip): the stage behind the plan ----
+// The preprocessed problem of fit_newton with K classes: the class codes as they came, per class an unpenalised intercept
+// that starts at the null model's value (and stays there without an intercept).  The loss does not see a shift common
+// to all intercepts: they are returned with their class mean removed (kkt.py removes the class mean of G0 likewise).
+int fit_mnewton(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl, sgdnet_result* out,
+                PhaseTimer& pt) {
+  const int64_t n = X.n, p = X.p;
+  const int L = ctl->n_lambda, K = ctl->n_classes;
+  MNewtonProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.K = K;
+  pb.x_dense = X.raw_dense;            // (sparse x came here as its dense copy: fit_sparse_impl)
+  pb.y = R.y.data();
+  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
+  pb.scale = X.x_scale.data();
+  pb.fit_intercept = ctl->intercept != 0;
+  pb.b0 = R.b0.data();
+  pb.device = plan.rank_dev[0];
+  pb.n_lambda = L;
+  pb.alpha = path.alpha.data();
+  pb.beta = path.beta.data();
+  pb.ridge = plan.penalty == SGDNET_RIDGE;
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  static const int width = exp_env_int("SGDNET_MNEWTON_WIDTH", 0);  // (64 or 256 lanes: profiles/mnewton_path.txt)
+  MNewtonResult nr;
+  const int rc = mnewton_run(pb, pt.on, &nr, width);
+  if (rc) return rc;
+  const int64_t P = p + 1;
+  double n_steps = 0.0;
+  std::vector<double> w((size_t)K * (size_t)p), b((size_t)K);
+  for (int li = 0; li < L; ++li) {
+    const double* u = nr.u.data() + (size_t)li * (size_t)(K * P);
+    double b_mean = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double* uk = u + (size_t)k * (size_t)P;
+      double shift = 0.0;
+      for (int64_t j = 0; j < p; ++j) {
+        w[(size_t)(k + j * K)] = uk[j];
+        shift += (nr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j] * uk[j];
+      }
+      // the intercept of the preprocessed problem: the one at the centres less the centres' distance from x_center times w
+      b[(size_t)k] = ctl->intercept != 0 ? uk[p] - shift : R.b0[(size_t)k];
+      b_mean += b[(size_t)k];
+    }
+    b_mean /= (double)K;
+    if (ctl->intercept != 0)
+      for (int k = 0; k < K; ++k) b[(size_t)k] -= b_mean;
+    // Family::Loss summed over the samples, doubled (families.h; saga_loss_kernel): the state pass left its mean
+    out->dev_ratio[li] = 1.0 - 2.0 * (double)n * nr.loss[(size_t)li] / R.null_dev_scaled;
+    out->lambda[li] = path.lambda[(size_t)li];
+    out->return_codes[li] = nr.unconverged[(size_t)li] ? 1.0 : 0.0;
+    n_steps += (double)nr.steps[(size_t)li];
+    rescale_values(X, R, ctl, li, w.data(), b.data(), out);
+  }
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   mnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
+            "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);
+  out->npasses = nr.passes;
+  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
+  pt.mark("mnewton (state + moments + cd)");
+  return SGDNET_OK;
+}
+
 // *batched_gave_up: the batched iteration gave up on this fit (mode = auto then runs it again in exact mode)
 int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ctl, sgdnet_result* out, bool* batched_gave_up) {
   const int K = ctl->n_classes;
@@ -1174,7 +1240,8 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   Path path;
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
-  if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_MCOVARIANCE) {   // plan_fit says whether they may run; they need none of the SAGA setup below
+  if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_MCOVARIANCE ||
+      ctl->mode == SGDNET_MODE_MNEWTON) {   // plan_fit says whether they may run; they need none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1186,6 +1253,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
       return plan.rc;
     }
     if (ctl->mode == SGDNET_MODE_MCOVARIANCE) return fit_mcovariance(X, R, path, plan, ctl, out, pt);
+    if (ctl->mode == SGDNET_MODE_MNEWTON) return fit_mnewton(X, R, path, plan, ctl, out, pt);
     return ctl->mode == SGDNET_MODE_NEWTON ? fit_newton(X, R, path, plan, ctl, out, pt) : fit_covariance(X, R, path, plan, ctl, out, pt);
   }
   double norm_max = 0.0;
@@ -1371,6 +1439,9 @@ int validate_rowidx(const sgdnet_csc* x) {
   return SGDNET_OK;
 }
 
+int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y_cols, const sgdnet_control* ctl, sgdnet_result* out,
+                   bool* batched_gave_up);
+
 int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdnet_control* ctl, sgdnet_result* out,
                     bool* batched_gave_up) {
   int rc = validate(ctl, out, y_cols);
@@ -1388,6 +1459,25 @@ int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdn
   X.raw_values = x->values;
   const int64_t n = X.n, p = X.p, nnz = x->colptr[p];
   if ((rc = validate_colptr(x)) || (rc = validate_response(ctl, y, n)) || (rc = validate_rowidx(x))) return rc;
+  if (ctl->mode == SGDNET_MODE_MNEWTON) {
+    // This mode holds at most 98 features and reads x dense.  The copy is made here, before anything is computed from x,
+    // so that the standard deviations, lambda_max and everything after them are the dense fit's of the same matrix, bit
+    // for bit.  The plan's refusals come first: one of them is the size of this copy.  Entries stored twice add up.
+    FitFacts facts;
+    facts.ctl = ctl;
+    facts.sparse = true;
+    facts.n = n;
+    facts.p = p;
+    const FitPlan plan = plan_fit(facts);
+    if (plan.rc) {
+      set_error("%s", plan.error.c_str());
+      return plan.rc;
+    }
+    std::vector<double> xd((size_t)(n * p), 0.0);
+    for (int64_t j = 0; j < p; ++j)
+      for (int64_t q = x->colptr[j]; q < x->colptr[j + 1]; ++q) xd[(size_t)(x->rowidx[q] + j * n)] += x->values[q];
+    return fit_dense_impl(xd.data(), n, p, y, y_cols, ctl, out, batched_gave_up);
+  }
   if (!option(kOptHostSetup) && !(ctl->n_gpus > 1)) {   // (a fit sharded over several GPUs cuts the host copy into the ranks' ranges)
     // default: the per-fit O(nnz) passes run on the device (setup_device.hip)
     return with_device_setup(ctl, X, [&](DeviceSetup& dev, hipStream_t st) {
@@ -1467,7 +1557,8 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     col_mean_sd(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
-  if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON && ctl->mode != SGDNET_MODE_MCOVARIANCE) {   // (those modes read x column-major, as it came)
+  if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON && ctl->mode != SGDNET_MODE_MCOVARIANCE &&
+      ctl->mode != SGDNET_MODE_MNEWTON) {   // (those modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "covariance.hpp"
+#include "mnewton.hpp"
 #include "newton.hpp"
 #include "sgdnet_hip.h"
 
@@ -71,8 +72,8 @@ struct FitFacts {
 // SGDNET_MODE_BATCHED means "batched where it is implemented": more than 64 classes run the exact
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
-// An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE, SGDNET_MODE_NEWTON
-// and SGDNET_MODE_MCOVARIANCE: no other mode resolves to them.
+// An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE, SGDNET_MODE_NEWTON,
+// SGDNET_MODE_MCOVARIANCE and SGDNET_MODE_MNEWTON: no other mode resolves to them.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -185,6 +186,32 @@ inline FitPlan plan_fit(const FitFacts& f) {
       return P;
     }
     P.mode = SGDNET_MODE_MCOVARIANCE;
+    P.rank_dev.assign(1, c.device);
+    P.rank_lo = {0, n};
+    return P;                          // no window, no shards, no draws
+  }
+
+  // ---- multinomial Newton mode: likewise only where it was asked for, and only for the problem whose joint Hessian its
+  // inner solve holds in one workgroup's LDS (mnewton.hpp: mnewton_max_features); sparse x is expanded to a dense copy
+  // by the driver, which has its own bound; no silent fall back ----
+  if (c.mode == SGDNET_MODE_MNEWTON) {
+    const int limit = mnewton_max_features(K);
+    const char* what = nullptr;
+    if (family != SGDNET_MULTINOMIAL) what = "family = multinomial";
+    else if (K < 2 || K >= 100) what = "2 to 99 classes";
+    else if (c.type_multinomial != 0) what = "the ungrouped penalty (type_multinomial = 0)";
+    else if (f.p > limit) what = "no more features than sgdnet_mnewton_max_features(n_classes)";
+    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+    else if (f.sparse && (double)n * (double)f.p * 8.0 > (double)kMNewtonDenseCopyBytes)
+      what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
+    if (what) {
+      P.rc = SGDNET_EUNSUPPORTED;
+      P.error = plan_text("mode = mnewton needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what,
+                          family, K, (long long)n, (long long)f.p, limit, c.n_gpus, c.debug);
+      return P;
+    }
+    P.mode = SGDNET_MODE_MNEWTON;
     P.rank_dev.assign(1, c.device);
     P.rank_lo = {0, n};
     return P;                          // no window, no shards, no draws

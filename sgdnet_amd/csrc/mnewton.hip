@@ -1,0 +1,525 @@
+// Multinomial Newton mode (SGDNET_MODE_MNEWTON): the multinomial elastic-net path by proximal Newton steps on the JOINT
+// Hessian of all classes.
+//
+// The problem is the one every mode fits (sgdnet_amd/kkt.py): features z_j = (x_j - m_j) / s_j, U = (w_k, b_k), k = 1 .. K,
+//     F(U) = (1/n) sum_i [log sum_k e^eta_ik - eta_{i, y_i}] + sum_k (alpha/2 |w_k|^2 + beta |w_k|_1),   eta_ik = b_k + z_i'w_k,
+// the b_k unpenalised (or frozen at the null model's values), alpha and beta the driver's (regularization_path).  The loss
+// is flat along "the same shift for every class": the intercepts are defined up to a constant (the driver returns them
+// with their class mean removed), and with alpha = 0 so are the coefficients of a feature no class of which is at zero
+// -- at an even K the lasso optimum need not be unique.  Coordinate (k, j) lives at k P + j, P = p + 1, j = p the
+// intercept; Q = K P.  One outer step from the iterate U0, warm-started lambda to lambda, as newton.hip takes it:
+//
+//   state      mnewton_state_kernel: eta_ik for all classes, the softmax with the row maximum subtracted (exp / log are
+//              the plain-IEEE ones of include/sgdnet_detmath.h), mu (n x K, a column per class) and the loss, a thread
+//              per sample.  Deviations are formed BEFORE they are multiplied: (x_ij - m_j) (w_kj / s_j).
+//              mnewton_finish_kernel adds the workgroups' sums of the loss in workgroup order.
+//   moments    with z~ = [x - m | 1], for every class pair k <= l
+//                  H_kl = (1/n) sum_i mu_ik (delta_kl - mu_il) z~_i z~_i',      q_k = (1/n) sum_i (y_ik - mu_ik) z~_i
+//              (f64; the 1/n and the driver's s_j are applied when the inner solve loads them): K (K + 1) / 2 weighted Gram
+//              matrices of the same rows.  mnewton_pair_tile_kernel is newton_cv_dense_tile_kernel with the class pair
+//              where that kernel has the job: the pair's weight is formed at staging from the stored mu, the q column is
+//              staged as y_ik - mu_ik for the diagonal pairs (0 elsewhere); mnewton_pair_reduce_kernel adds the row
+//              chunks in chunk order into one (p + 2)^2 matrix per pair.
+//   inner      mnewton_cd_kernel: ONE workgroup keeps the packed triangle of the Q x Q joint Hessian, U and
+//              g = H (U - U0) - q in LDS (mnewton.hpp: the budget behind sgdnet_mnewton_max_features) and runs
+//              newton_cd_kernel's cyclic coordinate descent over all Q coordinates; the K intercepts have no penalty and
+//              no threshold (a frozen intercept is never visited).  A coordinate whose diagonal entry is not positive
+//              and that has no ridge term stays where it is.
+//   accept     the state pass at the candidate gives its objective; the host halves a step after which it rose
+//              (mnewton_blend_kernel), at most kNewtonMaxHalvings times.  The accepted candidate's pass is the next step's.
+//
+// x is dense, column-major: this mode's p is at most 98, and the driver expands sparse x before anything is computed from
+// it (driver.cpp: fit_sparse_impl), so that a sparse fit is the dense fit of the same matrix from the standard deviations
+// and lambda_max on, bit for bit.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K):
+// the same input gives the same bits.
+#define SGDNET_DET_MATH
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "common.hpp"
+#include "device_math.hpp"
+#include "mnewton.hpp"
+#include "moments_device.hpp"
+
+namespace sgdnet {
+namespace {
+
+constexpr int kStateMaxBlocks = 1024;   // workgroups of the state pass: each leaves one sum
+
+// the record of a candidate, in device memory; the host reads it after every state pass (newton.hip)
+enum Rec { kRecLoss = 0, kRecHalfSq, kRecAbs, kRecChange, kRecSize, kRecSweeps, kRecInnerConverged, kRecNegligible, kRecLen };
+
+// a[k P + j] = w_kj / s_j (j < p), a[k P + p] = b_k: the candidate as the state pass multiplies it.  mu[i + k n] holds
+// eta_ik, then e^(eta_ik - max), then mu_ik.  Workgroup b leaves its sum of the loss in partial[b].
+__global__ __launch_bounds__(kBlock) void mnewton_state_kernel(const double* __restrict__ x, const double* __restrict__ y,
+                                                                const double* __restrict__ m, const double* __restrict__ a, int64_t n, int p,
+                                                                int K, double* __restrict__ mu, double* __restrict__ partial) {
+  __shared__ double sh[kBlock];
+  const int P = p + 1;
+  double loss = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const int yi = (int)(y[i] + 0.5);
+    double mx = 0.0, eta_y = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double* __restrict__ ak = a + (size_t)k * (size_t)P;
+      double eta = 0.0;
+      for (int j = 0; j < p; ++j) eta += (x[i + (int64_t)j * n] - m[j]) * ak[j];
+      eta += ak[p];
+      mu[i + (int64_t)k * n] = eta;
+      mx = k == 0 ? eta : fmax(mx, eta);
+      if (k == yi) eta_y = eta;
+    }
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double e = SGD_EXP(mu[i + (int64_t)k * n] - mx);
+      mu[i + (int64_t)k * n] = e;
+      s += e;
+    }
+    for (int k = 0; k < K; ++k) mu[i + (int64_t)k * n] /= s;
+    loss += (SGD_LOG(s) + mx) - eta_y;
+  }
+  loss = block_sum(loss, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = loss;
+}
+
+// one workgroup: the sums of the state pass added in workgroup order; rec gets the mean loss
+__global__ __launch_bounds__(kBlock) void mnewton_finish_kernel(const double* __restrict__ partial, int blocks, int64_t n,
+                                                                 double* __restrict__ rec) {
+  __shared__ double sh[kBlock];
+  double s = 0.0;
+  for (int b = threadIdx.x; b < blocks; b += kBlock) s += partial[b];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) rec[kRecLoss] = s / (double)n;
+}
+
+// class pair c = 0 .. K (K + 1) / 2 - 1 -> (k, l), k <= l, row by row of the upper triangle
+__device__ __forceinline__ void class_pair(int c, int K, int* k, int* l) {
+  int kk = 0;
+  while (c >= K - kk) {
+    c -= K - kk;
+    ++kk;
+  }
+  *k = kk;
+  *l = kk + c;
+}
+__device__ __forceinline__ int class_pair_index(int k, int l, int K) { return k * K - k * (k - 1) / 2 + (l - k); }
+
+// newton_cv_dense_tile_kernel with the class pair blockIdx.z where that kernel has the job: entry (a, b), a <= b, of the
+// pair's (p + 2)^2 matrix is sum_i A_ia B_ib with A = [x - m | 1 | 0] and B = [v (x - m) | v | r], v_i = mu_ik (delta_kl -
+// mu_il) and r_i = y_ik - mu_ik on the diagonal pairs, 0 elsewhere.  part[pair][chunk][tile pair][tid].
+__global__ __launch_bounds__(kBlock) void mnewton_pair_tile_kernel(const double* __restrict__ x, const double* __restrict__ y,
+                                                                    const double* __restrict__ mu, const double* __restrict__ m, int64_t n,
+                                                                    int p, int K, int64_t rows_per_chunk, double* __restrict__ part) {
+  __shared__ double A[kTileCols][kTileRows + 1], B[kTileCols][kTileRows + 1];
+  const int tid = threadIdx.x, ncols = p + 2;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  int ck, cl;
+  class_pair((int)blockIdx.z, K, &ck, &cl);
+  const double* __restrict__ mu_k = mu + (int64_t)ck * n;
+  const double* __restrict__ mu_l = mu + (int64_t)cl * n;
+  const int ta = tid & (kTileCols - 1), tb = tid / kTileCols;
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+  const int64_t r1 = r0 + rows_per_chunk < n ? r0 + rows_per_chunk : n;
+  double acc = 0.0;
+  for (int64_t base = r0; base < r1; base += kTileRows) {
+    for (int e = tid; e < kTileCols * kTileRows; e += kBlock) {
+      const int row = e & (kTileRows - 1), col = e / kTileRows;
+      const int64_t i = base + row;
+      const int ca = tj * kTileCols + col, cb = tk * kTileCols + col;
+      double da = 0.0, db = 0.0;
+      if (i < r1) {
+        if (ca <= p) da = ca < p ? x[i + (int64_t)ca * n] - m[ca] : 1.0;
+        if (cb == p + 1) {
+          if (ck == cl) db = ((int)(y[i] + 0.5) == ck ? 1.0 : 0.0) - mu_k[i];
+        } else if (cb <= p) {
+          const double v = ck == cl ? mu_k[i] * (1.0 - mu_k[i]) : -(mu_k[i] * mu_l[i]);
+          db = v * (cb < p ? x[i + (int64_t)cb * n] - m[cb] : 1.0);
+        }
+      }
+      A[col][row] = da;
+      B[col][row] = db;
+    }
+    __syncthreads();
+    for (int i = 0; i < kTileRows; ++i) acc += A[ta][i] * B[tb][i];
+    __syncthreads();
+  }
+  part[(((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kBlock + tid] = acc;
+}
+
+// newton_cv_reduce_kernel for the class pair blockIdx.y: its chunks added in chunk order into M[pair]
+__global__ __launch_bounds__(kBlock) void mnewton_pair_reduce_kernel(const double* __restrict__ part, int chunks, int ncols,
+                                                                      double* __restrict__ M_all) {
+  const int tid = threadIdx.x;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  const int a = tj * kTileCols + (tid & (kTileCols - 1)), b = tk * kTileCols + tid / kTileCols;
+  if (a >= ncols || b >= ncols) return;
+  double* __restrict__ M = M_all + (size_t)blockIdx.y * (size_t)ncols * (size_t)ncols;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += part[(((size_t)blockIdx.y * (size_t)chunks + c) * gridDim.x + blockIdx.x) * kBlock + tid];
+  M[(size_t)a * ncols + b] = s;
+  if (tj != tk) M[(size_t)b * ncols + a] = s;
+}
+
+// What a candidate un[0 .. Q) leaves behind, by the workgroup's first wavefront (publish_candidate of newton.hip over K
+// classes): itself and its state-pass form in memory, and in the record its penalty terms sum_k |w_k|^2 / 2 and
+// sum_k |w_k|_1, its distance from the iterate max|un - u_cur| and its size max|un|.  Lane l takes the coordinates
+// l, l + 64, ... in order; the lanes are joined by a butterfly.  Whatever the workgroup's width: the same bits.
+template <class UP>
+__device__ __forceinline__ void mnewton_publish(UP un, const double* __restrict__ u_cur, const double* __restrict__ scale, int p, int Q,
+                                                double* __restrict__ u_cand, double* __restrict__ a_cand, double* __restrict__ rec) {
+  const int lane = threadIdx.x, P = p + 1;
+  if (lane >= 64) return;
+  double sq = 0.0, ab = 0.0, ch = 0.0, sz = 0.0;
+  for (int c = lane; c < Q; c += 64) {
+    const int j = c % P;
+    const double uc = un[c];
+    ch = fmax(ch, fabs(uc - u_cur[c]));
+    sz = fmax(sz, fabs(uc));
+    if (j < p) {
+      sq += uc * uc;
+      ab += fabs(uc);
+    }
+    u_cand[c] = uc;
+    a_cand[c] = j < p ? uc / scale[j] : uc;
+  }
+  sq = wave_sum(sq);
+  ab = wave_sum(ab);
+  ch = wave_max(ch);
+  sz = wave_max(sz);
+  if (lane == 0) {
+    rec[kRecHalfSq] = 0.5 * sq;
+    rec[kRecAbs] = ab;
+    rec[kRecChange] = ch;
+    rec[kRecSize] = sz;
+  }
+}
+
+// u_cand <- u_cur + t (u_cand - u_cur)   (t = 1: the candidate as it is; the path's start is published this way)
+__global__ __launch_bounds__(64) void mnewton_blend_kernel(const double* __restrict__ u_cur, const double* __restrict__ scale, int p, int Q,
+                                                            double t, double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                            double* __restrict__ rec) {
+  __shared__ double un[kMNewtonMaxCoordinates];
+  for (int c = threadIdx.x; c < Q; c += 64) un[c] = t == 1.0 ? u_cand[c] : u_cur[c] + t * (u_cand[c] - u_cur[c]);
+  __syncthreads();
+  mnewton_publish(un, u_cur, scale, p, Q, u_cand, a_cand, rec);
+}
+
+// One workgroup of kWidth lanes, one inner solve.  Every lane computes the sweep's scalars (the new coordinate, the
+// sweep's max|du| and max|u|) from the same LDS words, so branches on them are uniform and nothing has to be broadcast
+// (newton_cd_kernel); the width only spreads the update of g, an entry per lane, so both widths give the same bits.
+// M: the K (K + 1) / 2 pair moments, (p + 2)^2 each (upper triangle), dn = n; the quadratic model about u_cur is
+//   (U - U0)'H (U - U0) / 2 - q'(U - U0) + sum_k (al/2 |w_k|^2 + be |w_k|_1),     its smooth gradient g = H (U - U0) - q.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void mnewton_cd_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
+                                                             double dn, const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                             int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                             double* __restrict__ a_cand, double* __restrict__ rec) {
+  __shared__ double lds[mnewton_state_doubles(kMNewtonMaxCoordinates)];
+  const int lane = threadIdx.x, P = p + 1, nc = p + 2, Q = K * P;
+  const size_t block = (size_t)nc * (size_t)nc;
+  double* H = lds;
+  double* u = H + Q * (Q + 1) / 2;
+  double* g = u + Q;
+  for (int c2 = 0; c2 < Q; ++c2) {
+    const int l = c2 / P, b = c2 - l * P;
+    const double sb = b < p ? scale[b] : 1.0;
+    for (int c1 = lane; c1 <= c2; c1 += kWidth) {
+      const int k = c1 / P, a = c1 - k * P;         // k <= l
+      const int lo = a < b ? a : b, hi = a < b ? b : a;
+      H[tri(c1, c2)] = M[(size_t)class_pair_index(k, l, K) * block + (size_t)lo * nc + hi] / dn / ((a < p ? scale[a] : 1.0) * sb);
+    }
+  }
+  for (int c = lane; c < Q; c += kWidth) {
+    const int k = c / P, a = c - k * P;
+    g[c] = -(M[(size_t)class_pair_index(k, k, K) * block + (size_t)a * nc + p + 1] / dn / (a < p ? scale[a] : 1.0));
+    u[c] = u_cur[c];
+  }
+  __syncthreads();
+  unsigned sweeps = 0;
+  bool converged = false, negligible = false;
+  while (sweeps < max_sweeps && !converged) {
+    double max_change = 0.0, max_size = 0.0, max_eta_sq = 0.0;
+    for (int k = 0, j = 0; k < K; ++k) {
+      for (int a = 0; a < P; ++a, ++j) {
+        const bool penalised = a < p;
+        if (!penalised && !fit_intercept) continue;          // (the frozen intercept is never visited: it stays at u_cur)
+        const double uj = u[j], hjj = H[tri(j, j)];
+        const double z = hjj * uj - g[j], denom = penalised ? hjj + al : hjj;
+        double nu = z;
+        if (penalised && !ridge) nu = z > be ? z - be : (z < -be ? z + be : 0.0);
+        // a constant column without an l2 term: H_jj = q_j = 0; every weight underflowed: the coordinate stays
+        nu = denom > 0.0 ? nu / denom : uj;
+        // what the threshold leaves of a coordinate when |z| equals it but for rounding (lambda_max: newton.hpp,
+        // kNewtonNegligible) is an exact zero: a path that starts at lambda_max starts with all coefficients 0.0
+        if (penalised && !ridge && nu * nu * hjj <= kNewtonNegligible * kNewtonNegligible) nu = 0.0;
+        const double d = nu - uj;
+        max_change = fmax(max_change, fabs(d));
+        max_size = fmax(max_size, fabs(nu));
+        max_eta_sq = fmax(max_eta_sq, nu * nu * hjj);
+        if (d != 0.0) {
+          __syncthreads();                         // every lane has read u[j] and g[j]
+          if (lane == 0) u[j] = nu;
+          for (int c = lane; c < Q; c += kWidth) g[c] += H[c <= j ? tri(c, j) : tri(j, c)] * d;
+          __syncthreads();
+        }
+      }
+    }
+    ++sweeps;
+    const bool all_zero = max_size == 0.0 && max_change == 0.0;
+    const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+    negligible = max_eta_sq <= kNewtonNegligible * kNewtonNegligible;      // zero to rounding (newton.hpp)
+    converged = all_zero || no_change || negligible;
+  }
+  __syncthreads();
+  mnewton_publish(u, u_cur, scale, p, Q, u_cand, a_cand, rec);
+  if (lane == 0) {
+    rec[kRecSweeps] = (double)sweeps;
+    rec[kRecInnerConverged] = converged ? 1.0 : 0.0;
+    rec[kRecNegligible] = negligible ? 1.0 : 0.0;
+  }
+}
+
+// One wavefront while one stride of it covers the coordinates; 256 lanes beyond (profiles/mnewton_path.txt).
+int mnewton_cd_width(int Q) { return Q <= 64 ? 64 : 256; }
+
+struct Stream {
+  hipStream_t st = nullptr;
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* rec_host = nullptr;          // pinned: the record of a state pass
+  ~Stream() {
+    for (hipEvent_t v : e)
+      if (v) (void)hipEventDestroy(v);
+    if (rec_host) (void)hipHostFree(rec_host);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+// What one problem keeps on the device and the launches of an outer step as named host steps (NewtonDevice of newton.hip).
+struct MNewtonDevice {
+  int64_t n = 0;
+  int p = 0, P = 0, nc = 0, K = 0, Q = 0, class_pairs = 0, width = 64;
+  bool timed = false;
+  int pairs = 0;                       // the tile pairs and the row chunks (a function of n, p and K alone)
+  int64_t rows_per_chunk = 0, chunks = 0;
+  int state_blocks = 0;
+  Arena A;
+  Stream sx;
+  hipStream_t st = nullptr;
+  double *d_x = nullptr, *d_y = nullptr, *d_mu = nullptr, *d_m = nullptr, *d_scale = nullptr, *d_part = nullptr, *d_M = nullptr,
+         *d_partial = nullptr, *d_rec = nullptr, *d_a = nullptr, *d_cur = nullptr, *d_cand = nullptr, *d_U = nullptr;
+  const double* rec = nullptr;         // the pinned copy of the record, as of the last state pass
+  double passes = 0.0;
+  float state_ms = 0.f;
+
+  int setup(const MNewtonProblem& pb, const double* start, bool timed_, int width_) {
+    n = pb.n;
+    p = (int)pb.p;
+    P = p + 1;
+    nc = p + 2;
+    K = pb.K;
+    Q = K * P;
+    class_pairs = K * (K + 1) / 2;
+    timed = timed_;
+    width = width_ == 64 || width_ == 256 ? width_ : mnewton_cd_width(Q);
+    const int L = pb.n_lambda;
+    SGD_HIP_TRY(hipSetDevice(pb.device));
+    const int T = (nc + kTileCols - 1) / kTileCols;
+    pairs = T * (T + 1) / 2;
+    // (the chunk count shrinks with all the workgroups of a chunk: tile pairs x class pairs)
+    rows_per_chunk = dense_rows_per_chunk(n, pairs * class_pairs);
+    chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
+
+    const size_t o_x = A.reserve(sizeof(double) * (size_t)(n * (int64_t)p));
+    const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+    const size_t o_mu = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
+    const size_t o_m = A.reserve(sizeof(double) * (size_t)nc);           // cov_sum_kernel: the means, then the sum and the mean of y
+    const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
+    const size_t o_part = A.reserve(sizeof(double) * (size_t)class_pairs * (size_t)chunks * (size_t)pairs * kBlock);
+    const size_t o_M = A.reserve(sizeof(double) * (size_t)class_pairs * (size_t)nc * (size_t)nc);
+    const size_t o_partial = A.reserve(sizeof(double) * (size_t)state_blocks);
+    const size_t o_rec = A.reserve(sizeof(double) * kRecLen);
+    const size_t o_u0 = A.reserve(sizeof(double) * (size_t)Q);
+    const size_t o_u1 = A.reserve(sizeof(double) * (size_t)Q);
+    const size_t o_a = A.reserve(sizeof(double) * (size_t)Q);
+    const size_t o_U = A.reserve(sizeof(double) * (size_t)L * (size_t)Q);
+    SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+    SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
+    SGD_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sx.rec_host), sizeof(double) * kRecLen, hipHostMallocDefault));
+    if (timed)
+      for (hipEvent_t& e : sx.e) SGD_HIP_TRY(hipEventCreate(&e));
+    st = sx.st;
+    rec = sx.rec_host;
+    d_x = A.at<double>(o_x);
+    d_y = A.at<double>(o_y);
+    d_mu = A.at<double>(o_mu);
+    d_m = A.at<double>(o_m);
+    d_scale = A.at<double>(o_scale);
+    d_part = A.at<double>(o_part);
+    d_M = A.at<double>(o_M);
+    d_partial = A.at<double>(o_partial);
+    d_rec = A.at<double>(o_rec);
+    d_a = A.at<double>(o_a);
+    d_cur = A.at<double>(o_u0);
+    d_cand = A.at<double>(o_u1);
+    d_U = A.at<double>(o_U);
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cur, start, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cand, start, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen, st));
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
+                       pb.centre ? 1 : 0, d_m);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+
+  // publish / blend: d_cand <- d_cur + t (d_cand - d_cur), its state-pass form d_a and its record
+  int publish(double t) {
+    hipLaunchKernelGGL(mnewton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+
+  // the state pass at the candidate (d_a) and its record, read back into rec
+  int state_pass() {
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
+    hipLaunchKernelGGL(mnewton_state_kernel, dim3((unsigned)state_blocks), dim3(kBlock), 0, st, d_x, d_y, d_m, d_a, n, p, K, d_mu, d_partial);
+    hipLaunchKernelGGL(mnewton_finish_kernel, dim3(1), dim3(kBlock), 0, st, d_partial, state_blocks, n, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[3], st));
+    SGD_HIP_TRY(hipMemcpyAsync(sx.rec_host, d_rec, sizeof(double) * kRecLen, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipStreamSynchronize(st));
+    passes += 1.0;
+    if (timed) {
+      float ms = 0.f;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
+      state_ms += ms;
+    }
+    return SGDNET_OK;
+  }
+
+  // the moments pass: d_M from d_mu of the last state pass (timed: between the events 0 and 1)
+  int moments() {
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
+    hipLaunchKernelGGL(mnewton_pair_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks, (unsigned)class_pairs), dim3(kBlock), 0, st, d_x,
+                       d_y, d_mu, d_m, n, p, K, rows_per_chunk, d_part);
+    hipLaunchKernelGGL(mnewton_pair_reduce_kernel, dim3((unsigned)pairs, (unsigned)class_pairs), dim3(kBlock), 0, st, d_part, (int)chunks,
+                       nc, d_M);
+    SGD_HIP_TRY(hipGetLastError());
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
+    return SGDNET_OK;
+  }
+
+  // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
+  int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
+    if (width == 256)
+      hipLaunchKernelGGL(mnewton_cd_kernel<256>, dim3(1), dim3(256), 0, st, d_M, d_scale, p, K, (double)n, d_cur, al, be, ridge ? 1 : 0,
+                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+    else
+      hipLaunchKernelGGL(mnewton_cd_kernel<64>, dim3(1), dim3(64), 0, st, d_M, d_scale, p, K, (double)n, d_cur, al, be, ridge ? 1 : 0,
+                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+};
+
+}  // namespace
+
+int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width) {
+  const int p = (int)pb.p, P = p + 1, K = pb.K, L = pb.n_lambda;
+  if (pb.n <= 0 || pb.p <= 0 || K < 2 || pb.p > mnewton_max_features(K) || L <= 0 || !pb.x_dense || !pb.y || !pb.scale || !pb.b0 || !pb.alpha ||
+      !pb.beta || pb.max_iter == 0) {
+    set_error("mnewton_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  const int Q = K * P;
+  std::vector<double> start((size_t)Q, 0.0);
+  for (int k = 0; k < K; ++k) start[(size_t)k * (size_t)P + (size_t)p] = pb.b0[k];
+  MNewtonDevice D;
+  int rc = D.setup(pb, start.data(), timed, width);
+  if (rc) return rc;
+  hipStream_t st = D.st;
+
+  out->passes = out->sweeps = out->halvings = 0.0;
+  out->state_ms = out->moments_ms = out->cd_ms = 0.f;
+  const double* rec = D.rec;
+  // the path's start: w = 0, b = b0
+  rc = D.publish(1.0);
+  if (!rc) rc = D.state_pass();
+  if (rc) return rc;
+  double loss = rec[kRecLoss], half_sq = rec[kRecHalfSq], abs1 = rec[kRecAbs];
+
+  out->loss.assign((size_t)L, 0.0);
+  out->steps.assign((size_t)L, 0);
+  out->unconverged.assign((size_t)L, 0);
+  for (int l = 0; l < L; ++l) {
+    const double al = pb.alpha[l], be = pb.ridge ? 0.0 : pb.beta[l];
+    double objective = loss + al * half_sq + be * abs1;
+    unsigned steps = 0;
+    bool converged = false;
+    while (steps < pb.max_iter && !converged) {
+      if ((rc = D.moments()) || (rc = D.inner_solve(al, be, pb.ridge, pb.fit_intercept, kNewtonMaxSweeps, pb.tol)) || (rc = D.state_pass()))
+        return rc;
+      if (timed) {
+        float ms = 0.f;
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[0], D.sx.e[1]));
+        out->moments_ms += ms;
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[1], D.sx.e[2]));
+        out->cd_ms += ms;
+      }
+      out->sweeps += rec[kRecSweeps];
+      bool negligible = rec[kRecNegligible] != 0.0;
+      double candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
+      // (a candidate whose objective is not a number counts as one that rose)
+      for (int h = 0; h < kNewtonMaxHalvings && rec[kRecChange] > 0.0 && !(candidate <= objective + kNewtonObjectiveSlack * fabs(objective)); ++h) {
+        if ((rc = D.publish(0.5)) || (rc = D.state_pass())) return rc;
+        candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
+        out->halvings += 1.0;
+        negligible = false;              // (the inner solve said so of the whole step, not of a part of it)
+      }
+      std::swap(D.d_cur, D.d_cand);
+      objective = candidate;
+      loss = rec[kRecLoss];
+      half_sq = rec[kRecHalfSq];
+      abs1 = rec[kRecAbs];
+      ++steps;
+      const double change = rec[kRecChange], size = rec[kRecSize];
+      const bool all_zero = size == 0.0 && change == 0.0;
+      const bool no_change = size != 0.0 && change / size <= pb.tol;
+      converged = rec[kRecInnerConverged] != 0.0 && (all_zero || no_change || negligible);
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(D.d_U + (size_t)l * (size_t)Q, D.d_cur, sizeof(double) * (size_t)Q, hipMemcpyDeviceToDevice, st));
+    out->loss[(size_t)l] = loss;
+    out->steps[(size_t)l] = (int32_t)steps;
+    out->unconverged[(size_t)l] = converged ? 0 : 1;
+  }
+  out->passes = D.passes;
+  out->state_ms = D.state_ms;
+
+  out->mean.resize((size_t)p);
+  out->u.resize((size_t)L * (size_t)Q);
+  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), D.d_m, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), D.d_U, sizeof(double) * (size_t)L * (size_t)Q, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  return SGDNET_OK;
+}
+
+}  // namespace sgdnet
+
+extern "C" int sgdnet_mnewton_max_features(int n_classes) { return sgdnet::mnewton_max_features(n_classes); }

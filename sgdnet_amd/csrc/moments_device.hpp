@@ -1,6 +1,6 @@
-// What the moment passes of covariance.hip and newton.hip share: the tile geometry, the fixed-order workgroup sum, the
+// What the moment passes of covariance.hip, newton.hip and mnewton.hip share: the tile geometry, the fixed-order workgroup sum, the
 // column means, the chunk reduction, the row lookup of the sparse pair kernels, the packed triangle, and the host
-// helpers around them.  Included by those two units only; everything has internal linkage (each unit gets its own
+// helpers around them.  Included by those three units only; everything has internal linkage (each unit gets its own
 // copy of the kernels, as if they were written in it).
 #pragma once
 
