@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -638,6 +638,50 @@ typedef struct sgdnet_newton_probe {
 
 int sgdnet_newton_probe_dense(const double* x, int64_t n, int64_t p, int device, sgdnet_newton_probe* io);
 int sgdnet_newton_probe_sparse(const sgdnet_csc* x, int device, sgdnet_newton_probe* io);
+
+/* Multinomial Newton mode (sgdnet_amd/csrc/mnewton.hip), one outer step pass by pass (additions only; the ABI version
+ * stays).  Dense x only: a fit in this mode expands sparse x before anything is computed from it.  The probe goes through
+ * the host steps a fit goes through (setup and upload, publish at t = 1, state pass, moments pass, inner solve, blend at
+ * t): the same kernels on the same grids in the same order, every output copied back; tests compare each with an exact
+ * reference (tests/test_gpu_mnewton_passes.py).  Coordinate (k, j) of u_cur, u and of every candidate lives at
+ * k (p + 1) + j, j = p the intercept of class k; Q = K (p + 1).  The candidate u is published as it is; the state pass
+ * is taken there; the moments are those of that state; the inner solve runs on them about u_cur; last, u is blended
+ * with u_cur at t.  Every pointer is a caller-allocated HOST buffer; a NULL output pointer skips that output.
+ * SGDNET_EINVAL: a missing input, n or p < 1, K < 2, max_sweeps = 0, a width other than 0 / 64 / 256.
+ * SGDNET_EUNSUPPORTED ("mode = mnewton needs ..."): more than sgdnet_mnewton_max_features(K) features. */
+typedef struct sgdnet_mnewton_probe_io {
+  /* inputs */
+  const double* y;         /* n: class codes 0 .. K - 1                                              */
+  int      K;              /* classes                                                                */
+  const double* scale;     /* p: the sd feature j is standardised with                               */
+  const double* u_cur;     /* Q: the iterate (per class the coefficients of the standardised problem, then the intercept) */
+  const double* u;         /* Q: the candidate the state is taken at                                 */
+  double   t;              /* blend factor                                                           */
+  double   l2, l1, tol;    /* the inner solve's penalty strengths and tolerance                      */
+  int      centre, ridge, fit_intercept;
+  unsigned max_sweeps;
+  int      width;          /* lanes of the inner solve's workgroup: 64 or 256; 0: the rule a fit follows */
+  /* outputs */
+  double*  mean;           /* p: cov_sum_kernel's column means (0 where centre is 0)                 */
+  double*  pub_u;          /* Q: u after the publish at t = 1 ...                                    */
+  double*  pub_a;          /* Q: ... its state-pass form (w_kj / s_j, b_k) ...                       */
+  double   pub_rec[4];     /* ... and its record: sum_k |w_k|^2 / 2, sum_k |w_k|_1, max|u - u_cur|, max|u| */
+  double*  blend_u;        /* the same three after the blend at t                                    */
+  double*  blend_a;
+  double   blend_rec[4];
+  double*  mu;             /* n x K, a column per class: the softmax of the state pass               */
+  double   loss;           /* the mean loss (mnewton_finish_kernel)                                  */
+  double*  M;              /* K (K + 1) / 2 blocks of (p + 2)^2, row-major; block c is the class pair (k, l), k <= l, in the
+                              order (0, 0), (0, 1), .., (0, K - 1), (1, 1), ..  Defined in a block: entries (a, b), a <= b <= p
+                              (the weighted moments of [x - m | 1], column p the ones), for every pair; entries (a, p + 1),
+                              a <= p (the q column), for the pairs k = l; for the pairs k < l column p + 1 is exactly 0.0.
+                              Nothing else is defined */
+  double*  cd_u;           /* Q: the inner solve's candidate ...                                     */
+  double*  cd_a;           /* Q                                                                      */
+  double   cd_rec[8];      /* ... and the whole record: loss, |w|^2 / 2, |w|_1, change, size, sweeps, converged, negligible */
+} sgdnet_mnewton_probe_io;
+
+int sgdnet_mnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_mnewton_probe_io* io);
 
 /* ------------------------------------------------------------------------ */
 /* Cross-validation in covariance mode (additions only; the ABI version      */

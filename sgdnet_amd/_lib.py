@@ -38,7 +38,7 @@ EXPORTS = [
     "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse", "sgdnet_newton_max_features",
     "sgdnet_newton_probe_dense", "sgdnet_newton_probe_sparse",
     "sgdnet_cv_newton_dense", "sgdnet_cv_newton_sparse", "sgdnet_mcovariance_max_features",
-    "sgdnet_mnewton_max_features",
+    "sgdnet_mnewton_max_features", "sgdnet_mnewton_probe",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -119,6 +119,19 @@ class NewtonProbe(C.Structure):
                 ("mean", _D), ("pub_u", _D), ("pub_a", _D), ("pub_rec", C.c_double * 4),
                 ("blend_u", _D), ("blend_a", _D), ("blend_rec", C.c_double * 4),
                 ("v", _D), ("r", _D), ("loss", C.c_double), ("V", C.c_double), ("R", C.c_double),
+                ("M", _D), ("cd_u", _D), ("cd_a", _D), ("cd_rec", C.c_double * 8)]
+
+
+class MNewtonProbe(C.Structure):
+    """sgdnet_mnewton_probe_io (diagnostics): the inputs of one outer step of multinomial Newton mode and caller-allocated
+    host buffers for what each of its passes leaves."""
+    _D = C.POINTER(C.c_double)
+    _fields_ = [("y", _D), ("K", C.c_int), ("scale", _D), ("u_cur", _D), ("u", _D),
+                ("t", C.c_double), ("l2", C.c_double), ("l1", C.c_double), ("tol", C.c_double),
+                ("centre", C.c_int), ("ridge", C.c_int), ("fit_intercept", C.c_int), ("max_sweeps", C.c_uint), ("width", C.c_int),
+                ("mean", _D), ("pub_u", _D), ("pub_a", _D), ("pub_rec", C.c_double * 4),
+                ("blend_u", _D), ("blend_a", _D), ("blend_rec", C.c_double * 4),
+                ("mu", _D), ("loss", C.c_double),
                 ("M", _D), ("cd_u", _D), ("cd_a", _D), ("cd_rec", C.c_double * 8)]
 
 
@@ -255,6 +268,7 @@ def load():
     L.sgdnet_cv_newton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     L.sgdnet_mcovariance_max_features.argtypes = [C.c_int]
     L.sgdnet_mnewton_max_features.argtypes = [C.c_int]
+    L.sgdnet_mnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(MNewtonProbe)]
     _lib = L
     return L
 

@@ -2215,4 +2215,52 @@ int sgdnet_newton_probe_sparse(const sgdnet_csc* x, int device, sgdnet_newton_pr
   return newton_probe_checked(pb, device, io, "sgdnet_newton_probe_sparse");
 }
 
+// ---- diagnostics: one outer step of multinomial Newton mode (mnewton.hip: mnewton_probe) ----
+
+namespace {
+// the refusals of the plan (fit_plan.hpp) by the same name
+int mnewton_probe_checked(MNewtonProblem& pb, int device, sgdnet_mnewton_probe_io* io, const char* who) {
+  if (!io || !io->y || !io->scale || !io->u_cur || !io->u || io->K < 2 || io->max_sweeps == 0 ||
+      (io->width != 0 && io->width != 64 && io->width != 256)) {
+    set_error("%s: invalid argument", who);
+    return SGDNET_EINVAL;
+  }
+  const int limit = mnewton_max_features(io->K);
+  if (pb.p > limit) {
+    set_error("mode = mnewton needs no more features than sgdnet_mnewton_max_features(n_classes): n_classes %d, %lld features (limit %d)",
+              io->K, (long long)pb.p, limit);
+    return SGDNET_EUNSUPPORTED;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error("no HIP device available: the SAGA backend has no CPU fallback");
+    return SGDNET_ENODEVICE;
+  }
+  if (device < 0 || device >= ndev) {
+    set_error("device %d out of range (%d devices)", device, ndev);
+    return SGDNET_EINVAL;
+  }
+  pb.K = io->K;
+  pb.y = io->y;
+  pb.centre = io->centre != 0;
+  pb.scale = io->scale;
+  pb.fit_intercept = io->fit_intercept != 0;
+  pb.device = device;
+  pb.n_lambda = 1;
+  return mnewton_probe(pb, io);
+}
+}  // namespace
+
+int sgdnet_mnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_mnewton_probe_io* io) {
+  if (!x || n <= 0 || p <= 0) {
+    set_error("sgdnet_mnewton_probe: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  MNewtonProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  return mnewton_probe_checked(pb, device, io, "sgdnet_mnewton_probe");
+}
+
 }  // extern "C"

@@ -32,6 +32,9 @@
 // it (driver.cpp: fit_sparse_impl), so that a sparse fit is the dense fit of the same matrix from the standard deviations
 // and lambda_max on, bit for bit.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K):
 // the same input gives the same bits.
+//
+// sgdnet_mnewton_probe (include/sgdnet_hip.h; mnewton_probe below) runs one outer step through the host steps of
+// MNewtonDevice and copies every pass's output back: tests/test_gpu_mnewton_passes.py checks the passes one by one.
 #define SGDNET_DET_MATH
 #include <algorithm>
 #include <utility>
@@ -263,8 +266,9 @@ __global__ __launch_bounds__(kWidth) void mnewton_cd_kernel(const double* __rest
         // a constant column without an l2 term: H_jj = q_j = 0; every weight underflowed: the coordinate stays
         nu = denom > 0.0 ? nu / denom : uj;
         // what the threshold leaves of a coordinate when |z| equals it but for rounding (lambda_max: newton.hpp,
-        // kNewtonNegligible) is an exact zero: a path that starts at lambda_max starts with all coefficients 0.0
-        if (penalised && !ridge && nu * nu * hjj <= kNewtonNegligible * kNewtonNegligible) nu = 0.0;
+        // kNewtonNegligible) is an exact zero: a path that starts at lambda_max starts with all coefficients 0.0.
+        // (Not for a coordinate that stays: with H_jj = 0 the test holds whatever uj is.)
+        if (penalised && !ridge && denom > 0.0 && nu * nu * hjj <= kNewtonNegligible * kNewtonNegligible) nu = 0.0;
         const double d = nu - uj;
         max_change = fmax(max_change, fabs(d));
         max_size = fmax(max_size, fabs(nu));
@@ -324,7 +328,8 @@ struct MNewtonDevice {
   double passes = 0.0;
   float state_ms = 0.f;
 
-  int setup(const MNewtonProblem& pb, const double* start, bool timed_, int width_) {
+  // u_cur: the iterate; u_cand: the candidate the first publish takes (a fit starts with both at the path's start)
+  int setup(const MNewtonProblem& pb, const double* u_cur, const double* u_cand, bool timed_, int width_) {
     n = pb.n;
     p = (int)pb.p;
     P = p + 1;
@@ -380,8 +385,8 @@ struct MNewtonDevice {
     SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
     SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
     SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(d_cur, start, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(d_cand, start, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cur, u_cur, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(d_cand, u_cand, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
     SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen, st));
     hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
                        pb.centre ? 1 : 0, d_m);
@@ -452,7 +457,7 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
   std::vector<double> start((size_t)Q, 0.0);
   for (int k = 0; k < K; ++k) start[(size_t)k * (size_t)P + (size_t)p] = pb.b0[k];
   MNewtonDevice D;
-  int rc = D.setup(pb, start.data(), timed, width);
+  int rc = D.setup(pb, start.data(), start.data(), timed, width);
   if (rc) return rc;
   hipStream_t st = D.st;
 
@@ -517,6 +522,41 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
   SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), D.d_m, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), D.d_U, sizeof(double) * (size_t)L * (size_t)Q, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
+  return SGDNET_OK;
+}
+
+// Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is
+// taken at the candidate io->u; the moments are those of that state; the inner solve runs on them about io->u_cur.
+int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io) {
+  MNewtonDevice D;
+  int rc = D.setup(pb, io->u_cur, io->u, false, io->width);
+  if (rc) return rc;
+  hipStream_t st = D.st;
+  const size_t Q = (size_t)D.Q;
+  double rec[kRecLen];
+  // a candidate as it was published: itself, its state-pass form and fields of the record
+  auto fetch = [&](double* u_out, double* a_out, double* rec_out, int rec_from, int rec_len) -> int {
+    if (u_out) SGD_HIP_TRY(hipMemcpyAsync(u_out, D.d_cand, sizeof(double) * Q, hipMemcpyDeviceToHost, st));
+    if (a_out) SGD_HIP_TRY(hipMemcpyAsync(a_out, D.d_a, sizeof(double) * Q, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipMemcpyAsync(rec, D.d_rec, sizeof(double) * kRecLen, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipStreamSynchronize(st));
+    std::copy(rec + rec_from, rec + rec_from + rec_len, rec_out);
+    return SGDNET_OK;
+  };
+  if ((rc = D.publish(1.0)) || (rc = fetch(io->pub_u, io->pub_a, io->pub_rec, kRecHalfSq, 4))) return rc;
+  if (io->mean) SGD_HIP_TRY(hipMemcpyAsync(io->mean, D.d_m, sizeof(double) * (size_t)D.p, hipMemcpyDeviceToHost, st));
+  if ((rc = D.state_pass())) return rc;
+  io->loss = D.rec[kRecLoss];
+  if (io->mu) SGD_HIP_TRY(hipMemcpyAsync(io->mu, D.d_mu, sizeof(double) * (size_t)D.n * (size_t)D.K, hipMemcpyDeviceToHost, st));
+  if ((rc = D.moments())) return rc;
+  if (io->M)
+    SGD_HIP_TRY(hipMemcpyAsync(io->M, D.d_M, sizeof(double) * (size_t)D.class_pairs * (size_t)D.nc * (size_t)D.nc, hipMemcpyDeviceToHost, st));
+  if ((rc = D.inner_solve(io->l2, io->ridge ? 0.0 : io->l1, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol)) ||
+      (rc = fetch(io->cd_u, io->cd_a, io->cd_rec, 0, kRecLen)))
+    return rc;
+  // the candidate again, blended with the iterate at the caller's t
+  SGD_HIP_TRY(hipMemcpyAsync(D.d_cand, io->u, sizeof(double) * Q, hipMemcpyHostToDevice, st));
+  if ((rc = D.publish(io->t)) || (rc = fetch(io->blend_u, io->blend_a, io->blend_rec, kRecHalfSq, 4))) return rc;
   return SGDNET_OK;
 }
 

@@ -74,4 +74,8 @@ struct MNewtonResult {
 // timed: fill the *_ms fields.  width: lanes of the inner solve's workgroup (64 or 256), 0 = the rule of mnewton.hip
 int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width = 0);
 
+// Diagnostics (include/sgdnet_hip.h: sgdnet_mnewton_probe): one outer step through the host steps mnewton_run takes, every
+// output copied back.  pb: n, p, K, x_dense, y, centre, scale, device and n_lambda = 1; the rest is read from io.
+int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io);
+
 }  // namespace sgdnet

@@ -1,6 +1,6 @@
 """Diagnostics (include/sgdnet_hip.h "Diagnostics"): what a fit's once-per-fit device setup passes
-(sgdnet_amd/csrc/setup_device.hip) and the passes of one outer step of Newton mode (sgdnet_amd/csrc/newton.hip) leave
-on the device, copied back pass by pass.  Used by the tests; a fit never calls these."""
+(sgdnet_amd/csrc/setup_device.hip) and the passes of one outer step of Newton mode (sgdnet_amd/csrc/newton.hip) and of
+multinomial Newton mode (sgdnet_amd/csrc/mnewton.hip) leave on the device, copied back pass by pass.  Used by the tests; a fit never calls these."""
 import ctypes as C
 from types import SimpleNamespace
 
@@ -107,6 +107,37 @@ def newton_probe(x, y, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0, ridg
     check(L.sgdnet_newton_probe_sparse(C.byref(csc), int(device), C.byref(pr)) if sparse else
           L.sgdnet_newton_probe_dense(dptr(x), n, p, int(device), C.byref(pr)))
     o.loss, o.V, o.R = pr.loss, pr.V, pr.R
+    o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
+    o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
+    o.cd_rec = dict(zip(NEWTON_REC, pr.cd_rec))
+    return o
+
+
+def mnewton_probe(x, y, K, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0, ridge=False, fit_intercept=True,
+                  max_sweeps=1000, tol=1e-7, width=0, device=0):
+    """One outer step of multinomial Newton mode, pass by pass (sgdnet_mnewton_probe; dense x only).  y: n class codes
+    0 .. K - 1; scale: (p,); u_cur, u: (K, p + 1) or flat, coordinate (k, j) at k (p + 1) + j, j = p the intercept.
+    width: lanes of the inner solve, 64 or 256 (0: the rule a fit follows).  Returns mean; pub_u, pub_a, pub_rec and
+    blend_u, blend_a, blend_rec (u published as it is, and blended with u_cur at t; flat, Q = K (p + 1); the records are
+    dicts of half_sq, abs, change, size); mu (n, K) and loss (the state pass at u); M (K (K + 1) / 2, p + 2, p + 2), the
+    class pairs (k, l), k <= l, row by row of the upper triangle (include/sgdnet_hip.h says which entries are defined);
+    cd_u, cd_a, cd_rec (the inner solve on M about u_cur; a dict of all eight fields)."""
+    x = np.asfortranarray(np.asarray(x, dtype=np.float64))
+    n, p = x.shape
+    K = int(K)
+    Q, pairs = max(K, 0) * (p + 1), max(K, 0) * (max(K, 0) + 1) // 2
+    ins = [np.ascontiguousarray(a, dtype=np.float64).reshape(k) for a, k in ((y, n), (scale, p), (u_cur, Q), (u, Q))]
+    o = SimpleNamespace(mean=np.empty(p), mu=np.empty((n, max(K, 0)), order="F"), M=np.empty((pairs, p + 2, p + 2)),
+                        **{f"{s}_{w}": np.empty(Q) for s in ("pub", "blend", "cd") for w in ("u", "a")})
+    pr = _lib.MNewtonProbe()
+    pr.y, pr.scale, pr.u_cur, pr.u = (dptr(a) for a in ins)
+    pr.K, pr.width = K, int(width)
+    pr.t, pr.l2, pr.l1, pr.tol = float(t), float(l2), float(l1), float(tol)
+    pr.centre, pr.ridge, pr.fit_intercept, pr.max_sweeps = int(bool(centre)), int(bool(ridge)), int(bool(fit_intercept)), int(max_sweeps)
+    for name in ("mean", "mu", "M", "pub_u", "pub_a", "blend_u", "blend_a", "cd_u", "cd_a"):
+        setattr(pr, name, dptr(getattr(o, name)))
+    check(_lib.load().sgdnet_mnewton_probe(dptr(x), n, p, int(device), C.byref(pr)))
+    o.loss = pr.loss
     o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
     o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
     o.cd_rec = dict(zip(NEWTON_REC, pr.cd_rec))
