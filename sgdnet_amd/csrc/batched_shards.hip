@@ -344,24 +344,30 @@ __device__ __forceinline__ double fused_block_sum(double a, double* red) {
 __device__ __forceinline__ void fused_leave(const SagaDev& d, LamParams* lamp, int nb, bool epoch_done) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x < 64) {                       // wavefront 0: lane 0 signs out, every lane has a share of the reset
     unsigned* sync = d.vsync;
-    if (epoch_done && blockIdx.x == 0) {
-      end_epoch(lamp, nb);
-      // linked solvers: one more launch whose merges the slice counters have counted (this workgroup says so, not
-      // the last one out: that may be a generators' workgroup, which knows nothing of the epoch)
-      if (d.n_peers > 1) __hip_atomic_fetch_add(sync + kSyncSeq * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned prev = 0u;
+    if (threadIdx.x == 0) {
+      if (epoch_done && blockIdx.x == 0) {
+        end_epoch(lamp, nb);
+        // linked solvers: one more launch whose merges the slice counters have counted (this workgroup says so, not
+        // the last one out: that may be a generators' workgroup, which knows nothing of the epoch)
+        if (d.n_peers > 1) __hip_atomic_fetch_add(sync + kSyncSeq * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      prev = __hip_atomic_fetch_add(sync + kSyncExit * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    const unsigned prev = __hip_atomic_fetch_add(sync + kSyncExit * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    prev = (unsigned)__shfl((int)prev, 0);
     if (prev + 1u == gridDim.x) {
+      // one lane per word: the stores of a pass leave together instead of one behind the other
       // (linked solvers: the other ranks add to this rank's slice counters whenever THEY get there -- those run on
       //  from launch to launch, with the launch count as their base)
-      for (int wd = 0; wd < kSyncLines; ++wd)
+      const int lane = (int)threadIdx.x;
+      for (int wd = lane; wd < kSyncLines; wd += 64)
         __hip_atomic_store(sync + wd * kSyncLine, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (!(d.n_peers > 1))
-        for (int wd = 0; wd < kFusedMaxBps; ++wd)
+        for (int wd = lane; wd < kFusedMaxBps; wd += 64)
           __hip_atomic_store(d.vcol + wd * kSyncLine, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (d.rngdev && lamp->rng_generate) d.rngdev->gen += 1u;
+      if (lane == 0 && d.rngdev && lamp->rng_generate) d.rngdev->gen += 1u;
     }
   }
 }
@@ -375,7 +381,7 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
   __shared__ int ticket_counter;
   __shared__ int sh_ok;
   __shared__ double sh_red[kLdsBlock / 64];
-  __shared__ double sh_val[4];                  // [0] b0 of the round, [1] sum of gc of the shard's batch
+  __shared__ double sh_val[4];                  // [0] b0 of the round, [1] sum of gc of the shard's batch, [2] b as the epoch starts
   const int tid = threadIdx.x;
   const int64_t p = d.p;                        // K == 1, p even
   const int64_t P2 = p >> 1;
@@ -417,12 +423,17 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     sh_par[3] = lamp->ls_full;
     sh_par[4] = lamp->r_tail;
     sh_par[5] = lamp->ls_tail;
-    double tot = 0.0, lo = 0.0;
-    for (int u = 0; u < d.V; ++u) {
-      tot += d.v_size[u];
-      if (u < (int)blockIdx.x % d.V) lo += d.v_size[u];
+    // the eight sizes are read together (constant indices: V <= 8 is the array's length), summed in the shards' order
+    const int vv = (int)blockIdx.x % d.V;
+    double tot = 0.0, lo = 0.0, own = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const double x = d.v_size[u];
+      if (u < d.V) tot += x;
+      if (u < vv) lo += x;
+      if (u == vv) own = x;
     }
-    sh_par[6] = d.v_size[(int)blockIdx.x % d.V];
+    sh_par[6] = own;
     sh_par[7] = lo;
     sh_par[8] = tot;
   }
@@ -459,21 +470,62 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
 #else
 #define FPH(slot) ((void)0)
 #endif
-  // ---- start barrier: before "go" nothing is modified ---------------------------------------------
+  // ---- start barrier: before "go" nothing is modified in global memory ------------------------------------
+  // The workgroup arrives first.  While the others arrive, round 0's cold reads are on their way: the first sample
+  // words, their cmeta bits, b and the coefficients for LDS.  All of them are inputs that the launch before this one
+  // completed; loads and LDS contents commit nothing, so a launch that gives up still leaves global memory as it was.
   if (tid == 0) {
     // which XCD runs this workgroup: the shard's workgroups OR their bits together before they arrive
     const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;        // HW_REG_XCC_ID
     __hip_atomic_fetch_or(sync + (kSyncXcd + v) * kSyncLine, 1u << xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_fetch_add(sync + kSyncStart * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sh_ok = fused_start(sync, lamp, (unsigned)(V * S)) ? 1 : 0;
-    if (sh_ok) {
-      const unsigned mask = sync_load(sync, kSyncXcd + v);
-      sh_ok = (mask & (mask - 1u)) == 0u ? 3 : 1;        // bit 1: the whole shard on one XCD
+  }
+  constexpr int kStage = 8;                     // one round of loads for up to 16 384 coefficients
+  uint32_t s_first = 0u, s_second = 0u;
+  {
+    K1Epoch nx;
+    nx.begin(d, stream_v, (int)(dps < m_full ? dps : m_full), wi, S, &ticket_counter);
+    nx.raw = raw_words;
+    nx.par = draw_par;
+    f64x2_t t[kStage];
+#pragma unroll
+    for (int q = 0; q < kStage; ++q) {
+      const int64_t i = tid + (int64_t)q * kLdsBlock;
+      t[q] = f64x2_t{0.0, 0.0};
+      if (i < P2) t[q] = reinterpret_cast<const f64x2_t*>(d.w)[i];
     }
+    if (tid == 64) sh_val[2] = d.b[0];
+    __syncthreads();                            // sh_par: a raw word becomes a sample id with (n_v, lo_v)
+    nx.tag_first();
+    s_first = nx.s_cur;                         // round 0: tagged already
+    s_second = nx.s_nxt;
+    if (tid == 0) {
+      sh_ok = fused_start(sync, lamp, (unsigned)(V * S)) ? 1 : 0;
+      if (sh_ok) {
+        const unsigned mask = sync_load(sync, kSyncXcd + v);
+        sh_ok = (mask & (mask - 1u)) == 0u ? 3 : 1;        // bit 1: the whole shard on one XCD
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kStage; ++q) {
+      const int64_t i = tid + (int64_t)q * kLdsBlock;
+      if (i < P2) W2[i] = t[q];
+    }
+    for (int64_t i = tid + (int64_t)kStage * kLdsBlock; i < P2; i += kLdsBlock)   // (no shape of today gets here)
+      W2[i] = reinterpret_cast<const f64x2_t*>(d.w)[i];
   }
   for (int64_t i = tid; i < P2; i += kLdsBlock) D2[i] = f64x2_t{0.0, 0.0};
   __syncthreads();
+#ifdef SGDNET_PHASE_TIMING
+  // slots 8 / 9 / 10: "go" seen -> round 0 enters its draw loop; last round's stores issued -> the workgroup is out;
+  // kernel entry -> "go" seen
+  unsigned long long ph_go = 0;
+  if (d.dbg && tid == 0) {
+    ph_go = phase_stamp();
+    d.dbg[(size_t)blockIdx.x * 16 + 10] = ph_go - ph_t;
+  }
+#endif
   bool done = false;
   bool alive = sh_ok != 0;
   unsigned col_base = 0u;                       // linked solvers: merges of the launches before this one
@@ -484,16 +536,9 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
   }
   const bool local = (sh_ok & 2) != 0 && d.vs_xcd_local != 0;
   int mi = 0;                                   // merges so far
-  // the sample ids of a round's first two passes are requested a phase ahead; only they are carried over (the
-  // rest of K1Compact is lane geometry, set up again at the top of the round: fewer registers live across the phases)
-  uint32_t s_first = 0u, s_second = 0u;
-  if (alive) {
-    const int m0 = (int)(dps < m_full ? dps : m_full);
-    K1Epoch nx;
-    nx.begin(d, stream_v, m0, wi, S, &ticket_counter);
-    s_first = nx.s_cur;
-    s_second = nx.s_nxt;
-  }
+  // the sample ids of a round's first two passes are requested a phase ahead (round 0's: before the start barrier);
+  // only they are carried over (the rest of K1Compact is lane geometry, set up again at the top of the round: fewer
+  // registers live across the phases)
   for (int r = 0; alive && r < nb; ++r) {
     const int64_t t0 = (int64_t)r * m_full;
     const int m = (int)(dps - t0 < m_full ? dps - t0 : m_full);
@@ -509,24 +554,23 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     cg.par = draw_par;
     cg.s_cur = s_first;
     cg.s_nxt = s_second;
-    cg.tag_first();
+    if (r > 0) cg.tag_first();
     int ts = threadIdx.x;                       // (opaque, as tq below)
     asm volatile("" : "+v"(ts));
     double cw = 0.0, bv = 0.0;                  // wave 0: requested in front of the staging loads (one round trip for all)
     if ((ts >> 6) == 0) {
       if (std_x && r > 0)
         for (int k = ts & 63; k < S; k += 64) cw += ld_sc1(cwp + v * kFusedMaxBps + k);
-      bv = r == 0 ? d.b[0] : ld_sc1(d.vb + v);
+      bv = r == 0 ? sh_val[2] : ld_sc1(d.vb + v);
     }
-    {
-      constexpr int kStage = 8;                 // one round of loads for up to 16 384 coefficients
+    if (r > 0) {                                // (round 0's coefficients were staged before the start barrier)
       for (int64_t i0 = ts; i0 < P2; i0 += (int64_t)kLdsBlock * kStage) {
         f64x2_t t[kStage];
 #pragma unroll
         for (int q = 0; q < kStage; ++q) {
           const int64_t i = i0 + (int64_t)q * kLdsBlock;
           t[q] = f64x2_t{0.0, 0.0};
-          if (i < P2) t[q] = r == 0 ? reinterpret_cast<const f64x2_t*>(d.w)[i] : ld2_sc1(rs_w, (uint32_t)(i * 16));
+          if (i < P2) t[q] = ld2_sc1(rs_w, (uint32_t)(i * 16));
         }
 #pragma unroll
         for (int q = 0; q < kStage; ++q) {
@@ -549,6 +593,9 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     }
     const double b0 = sh_val[0];
     FPH(0);
+#ifdef SGDNET_PHASE_TIMING
+    if (d.dbg && tid == 0 && r == 0) d.dbg[(size_t)blockIdx.x * 16 + 8] = ph_t - ph_go;
+#endif
 
     // ---- draws ------------------------------------------------------------------------------
     const double gct = cg.run(d, b0, Wl, Dl);
@@ -732,8 +779,13 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
       if (act) {
         a_new = ma;
         b_new = mb;
-        st_sc1(refv + oa, ma);
-        st_sc1(refv + ob, mb);
+        // The reference copy is read at the NEXT merge of this launch; a later launch starts from the solver's own
+        // state (mi == 0) and writes the copy before it reads it.  So the epoch's last merge skips it -- except shard
+        // 0's, kept beside the own state it equals.
+        if (!last || v == 0) {
+          st_sc1(refv + oa, ma);
+          st_sc1(refv + ob, mb);
+        }
         if (last && v == 0) {                     // the solver's own state: what the epoch returns
           *const_cast<double*>(own_a) = ma;
           *const_cast<double*>(own_b) = mb;
@@ -746,7 +798,8 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
       st_shard(rep_a, a_new, local);
       st_shard(rep_b, b_new, local);
     }
-    if (std_x) {                                // c . w of the slice, for the next round's linear predictors
+    if (std_x && !last) {                       // c . w of the slice, for the next round's linear predictors (round 0 of
+                                                // the next launch sums c . w itself: nothing reads the last round's)
       const double a = fused_block_sum(upd ? c_own * b_new : 0.0, sh_red);
       if (tq == 0) st_shard(cwp + v * kFusedMaxBps + wi, a, local);
     }
@@ -769,7 +822,13 @@ __global__ __launch_bounds__(kLdsBlock) void saga_vs_epoch_kernel(SagaDev d, Lam
     FPH(7);
   }
 
+#ifdef SGDNET_PHASE_TIMING
+  if (d.dbg && tid == 0) ph_t = phase_stamp();
+#endif
   fused_leave(d, lamp, nb, done);
+#ifdef SGDNET_PHASE_TIMING
+  if (d.dbg && tid == 0) d.dbg[(size_t)blockIdx.x * 16 + 9] = phase_stamp() - ph_t;
+#endif
 }
 
 // ------------------------------ launchers ---------------------------------

@@ -76,6 +76,17 @@ int phase_report_batched(const sgdnet_solver* s, int64_t batch, bool fused_prof)
       fprintf(stderr, "[phase] %-16s per epoch: mean %7.1f us  min %7.1f  max %7.1f\n", nm[ph], sum / grid, mn, mx);
     }
     fprintf(stderr, "[phase] sum of the means %.1f us\n", tot_mean);
+    // the epoch's boundary, once per launch: slots 10 / 8 / 9
+    static const char* bn[3] = {"entry -> go seen", "go -> draw loop 0", "last stores -> out"};
+    const int bs[3] = {10, 8, 9};
+    for (int k = 0; k < 3; ++k) {
+      double sum = 0, mx = 0, mn = 1e30;
+      for (int b = 0; b < grid; ++b) {
+        const double dt = (double)t[b * 16 + bs[k]] / 100.0;
+        sum += dt; mx = std::max(mx, dt); mn = std::min(mn, dt);
+      }
+      fprintf(stderr, "[phase] %-18s per launch: mean %6.1f us  min %6.1f  max %6.1f\n", bn[k], sum / grid, mn, mx);
+    }
     for (int v = 0; v < s->d.V; ++v) {
       double a0 = 0, a1 = 0;
       for (int b = v * s->d.v_bps; b < (v + 1) * s->d.v_bps; ++b) {

@@ -600,6 +600,7 @@ void sgdnet_solver_destroy(sgdnet_solver* s) {
   drop_graph(s);
   for (void* q : s->ipc_opened) (void)hipIpcCloseMemHandle(q);
   for (hipEvent_t e : s->epoch_ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : s->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->trace_ev)
     if (e) (void)hipEventDestroy(e);
   for (void* p : s->owned) (void)hipFree(p);

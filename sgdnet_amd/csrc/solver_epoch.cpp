@@ -146,13 +146,30 @@ static int vs_merge_batches(const sgdnet_solver* s, int64_t batch) {
 
 // Dispatch-level start / stop events of one launch (no host gaps inside the interval) where somebody asked for its
 // time, nullptrs where nobody did.  The pair belongs to `owner` before the launch it brackets: a launch that fails
-// leaks nothing.
-static int timing_pair(std::vector<hipEvent_t>* owner, hipEvent_t* e0, hipEvent_t* e1) {
+// leaks nothing.  `pool` (optional): events to take before any is created.
+static int timing_pair(std::vector<hipEvent_t>* owner, hipEvent_t* e0, hipEvent_t* e1,
+                       std::vector<hipEvent_t>* pool = nullptr) {
   *e0 = *e1 = nullptr;
   if (!owner) return SGDNET_OK;
   for (hipEvent_t* e : {e0, e1}) {
-    SGD_HIP_TRY(hipEventCreate(e));
+    if (pool && !pool->empty()) {
+      *e = pool->back();
+      pool->pop_back();
+    } else {
+      SGD_HIP_TRY(hipEventCreate(e));
+    }
     owner->push_back(*e);
+  }
+  return SGDNET_OK;
+}
+
+// sgdnet_solver_epoch_timing(enable): the events of the launches to come are made now, not between them
+constexpr size_t kTimedLaunchesAhead = 64;
+static int fill_event_pool(sgdnet_solver* s) {
+  while (s->ev_pool.size() < 2 * kTimedLaunchesAhead) {
+    hipEvent_t e = nullptr;
+    SGD_HIP_TRY(hipEventCreate(&e));
+    s->ev_pool.push_back(e);
   }
   return SGDNET_OK;
 }
@@ -172,7 +189,7 @@ static int enqueue_epoch_kernels_vs(sgdnet_solver* s, int64_t batch, int64_t dra
   if (full.form == BatchForm::kFusedEpoch) {
     s->d.vs_xcd_local = option(kOptFusedEpoch) == 1 ? 1 : 0;
     hipEvent_t e0, e1;
-    int rcf = timing_pair(ev ? ev : s->time_epochs ? &s->epoch_ev : nullptr, &e0, &e1);
+    int rcf = timing_pair(ev ? ev : s->time_epochs ? &s->epoch_ev : nullptr, &e0, &e1, ev ? nullptr : &s->ev_pool);
     if (!rcf) rcf = launch_vs_epoch(d, full, s->lam_dev, nb, every, s->st, e0, e1);
     if (rcf || !ev) return rcf;
     hipEvent_t z0, z1;                          // no separate sweep launches: an empty interval
@@ -268,7 +285,12 @@ static int ensure_graph(sgdnet_solver* s, int64_t batch, int64_t draws) {
   }
   s->fused_in_graph = fused != 0;
   SGD_HIP_TRY(hipStreamBeginCapture(s->st, hipStreamCaptureModeThreadLocal));
+  // (a captured launch does not run: it gets no timing events -- a pair that is never recorded has no interval, and
+  //  the failed hipEventElapsedTime would stay behind as the thread's last error for the next launch to find)
+  const bool timed = s->time_epochs;
+  s->time_epochs = false;
   int rc = enqueue_epoch_kernels(s, batch, draws, nullptr);
+  s->time_epochs = timed;
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(s->st, &g);
   if (rc) {
@@ -731,9 +753,13 @@ int sgdnet_solver_epoch_timing(sgdnet_solver* s, int enable, double* sum_ms, int
       ++cnt;
     }
   }
-  for (hipEvent_t e : s->epoch_ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : s->epoch_ev) s->ev_pool.push_back(e);   // (the stream is idle: every one of them has completed)
   s->epoch_ev.clear();
   s->time_epochs = enable != 0;
+  if (enable) {
+    const int rcp = fill_event_pool(s);
+    if (rcp) return rcp;
+  }
   if (sum_ms) *sum_ms = tot;
   if (launches) *launches = cnt;
   return SGDNET_OK;

@@ -3,7 +3,8 @@
 // current epoch runs (solver_rng_open / prefetch / acquire / release / close and their sgdnet_solver_rng_* wrappers).
 // What a slot of the pipeline holds, raw words or draws (RngPipe::raw[]), and which generation is still owed
 // (RngPipe::pending_gen) are assigned in this file and nowhere else; slot_to_draws() is the one place that converts a
-// slot and clears its flag.
+// slot and clears its flag.  The same holds for the flags that let back-to-back fused epochs go without stream markers
+// (RngPipe::in_kernel / freed_owed / quiet, and the invariant stated beside them).
 #include <algorithm>
 #include <vector>
 
@@ -51,6 +52,7 @@ int prepare_stream_slot(sgdnet_solver* s, int64_t batch, int64_t stream_offset, 
   auto& P = s->pipe;
   s->lam.stream_raw = 0;
   s->lam.rng_generate = 0;
+  P.quiet = false;
   if (!P.open) return SGDNET_OK;
   const bool one_slot = n_epochs == 1 && draws == P.n && (stream_offset == 0 || stream_offset == P.n);
   const int slot = stream_offset == 0 ? 0 : 1;
@@ -59,11 +61,14 @@ int prepare_stream_slot(sgdnet_solver* s, int64_t batch, int64_t stream_offset, 
   if (fused && s->d.rngdev && P.pending_gen >= 0 && P.pending_gen == P.used + 1 && slot == (int)(P.used & 1)) {
     s->lam.rng_generate = 1;
     P.raw[P.pending_gen & 1] = true;            // (the other slot: raw words from this launch on)
+    P.in_kernel[P.pending_gen & 1] = true;
     P.pending_gen = -1;
   }
   if (!(P.raw[0] || P.raw[1])) return SGDNET_OK;
   if (fused && P.raw[slot]) {
     s->lam.stream_raw = 1;
+    // produced by the launch before, the next generation inside this one: the side stream has no part in this epoch
+    P.quiet = s->lam.rng_generate != 0 && P.in_kernel[slot] && P.run_len == 0;
     return SGDNET_OK;
   }
   for (int q = 0; q < 2; ++q) {
@@ -170,6 +175,9 @@ int solver_rng_open(sgdnet_solver* s, sgdnet_rng* rng, int64_t n, int generators
   P.gens = P.used = 0;
   P.pending_gen = -1;
   P.raw[0] = P.raw[1] = false;
+  P.in_kernel[0] = P.in_kernel[1] = false;
+  P.freed_owed[0] = P.freed_owed[1] = false;    // (recorded just above)
+  P.quiet = false;
   // the same generators as the fused epoch kernel of the virtual shards runs them on its spare workgroups
   RngDev* want = nullptr;
   if (generators > 1 && s->d.V > 1 && s->d.vsync) {
@@ -199,9 +207,16 @@ int solver_rng_open(sgdnet_solver* s, sgdnet_rng* rng, int64_t n, int generators
 static int rng_side_generate(sgdnet_solver* s, int64_t g, bool keep_raw) {
   auto& P = s->pipe;
   const int slot = (int)(g & 1);
+  // Launches that went without their record (solver_rng_release) are covered here: behind everything enqueued so far,
+  // which is also behind the fused launch that left the start states state[g & 1] (it precedes the slot's last reader).
+  if (P.freed_owed[slot]) {
+    SGD_HIP_TRY(hipEventRecord(P.freed[slot], s->st));
+    P.freed_owed[slot] = false;
+  }
   SGD_HIP_TRY(hipStreamWaitEvent(P.st, P.freed[slot], 0));
   int rc;
   P.raw[slot] = keep_raw;
+  P.in_kernel[slot] = false;
   if (P.G > 1) {
     rc = launch_rng_fill(P.state[g & 1], P.ends, (uint32_t)s->d.n, s->stream_dev + (int64_t)slot * P.n, P.n,
                          P.st, s->d.V, s->d.v_size, P.G, P.run_len, keep_raw ? 0 : 1, 0, s->d.cu_reserve);
@@ -254,10 +269,12 @@ int solver_rng_acquire(sgdnet_solver* s, int64_t* offset) {
     const int64_t g = P.pending_gen;
     P.pending_gen = -1;
     SGD_HIP_TRY(hipEventRecord(P.freed[slot], s->st));       // after everything enqueued so far
+    P.freed_owed[slot] = false;
     int rc = rng_side_generate(s, g, true);     // (a generation is only ever pending as raw words)
     if (rc) return rc;
   }
-  SGD_HIP_TRY(hipStreamWaitEvent(s->st, P.ready[slot], 0));
+  // a slot that a fused launch filled needs no wait: that launch precedes every reader on the solver's stream
+  if (!P.in_kernel[slot]) SGD_HIP_TRY(hipStreamWaitEvent(s->st, P.ready[slot], 0));
   *offset = (int64_t)slot * P.n;
   return SGDNET_OK;
 }
@@ -265,7 +282,14 @@ int solver_rng_acquire(sgdnet_solver* s, int64_t* offset) {
 // the epoch that consumed the acquired draws has been enqueued on the solver's stream
 int solver_rng_release(sgdnet_solver* s) {
   auto& P = s->pipe;
-  SGD_HIP_TRY(hipEventRecord(P.freed[P.used & 1], s->st));
+  const int slot = (int)(P.used & 1);
+  if (P.quiet) {                                // nothing but the kernel between two fused epochs: the record is owed
+    P.freed_owed[slot] = true;                  // (rng_side_generate makes it before the side stream touches the slot)
+    P.quiet = false;
+  } else {
+    SGD_HIP_TRY(hipEventRecord(P.freed[slot], s->st));
+    P.freed_owed[slot] = false;
+  }
   ++P.used;
   return SGDNET_OK;
 }

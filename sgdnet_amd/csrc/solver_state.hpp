@@ -66,6 +66,17 @@ struct sgdnet_solver {
     // produce, or -1; a generation still pending when its draws are asked for is produced on the side stream after all
     sgdnet::RngDev* dev = nullptr;
     int64_t pending_gen = -1;
+    // Steady state of the fused epochs: the launch of epoch e reads slot e & 1, which the launch of epoch e - 1 filled
+    // (in_kernel[]), and fills the other slot itself.  Producer and consumer are consecutive kernels of the solver's
+    // stream, the side stream is idle, and nothing but the kernel is enqueued: no wait for ready[], no record of
+    // freed[] (`quiet`, decided per launch in prepare_stream_slot).  The record is owed instead (freed_owed[]).
+    // INVARIANT: the side stream never writes a slot, or a generator state, that an enqueued launch still reads.
+    // Every write of the side stream goes through rng_side_generate(), which first waits for freed[slot]; if that
+    // record is owed it is made there, on the solver's stream behind everything enqueued so far.  solver_rng.cpp
+    // stays the only file that assigns raw[], pending_gen and these flags.
+    bool in_kernel[2] = {false, false};         // the slot's content comes from a fused launch on the solver's stream
+    bool freed_owed[2] = {false, false};        // a launch read the slot and no freed[] record stands behind it yet
+    bool quiet = false;                         // the launch being enqueued needs no marker on either side
   } pipe;
   int64_t nnz = 0;
   bool penalty_set = false;
@@ -108,6 +119,7 @@ struct sgdnet_solver {
   // sgdnet_solver_epoch_timing: dispatch start / stop events of every fused epoch launch (the benchmark's timed region)
   bool time_epochs = false;
   std::vector<hipEvent_t> epoch_ev;
+  std::vector<hipEvent_t> ev_pool;   // events of earlier timed regions, reused: none is created while a timed region runs
   std::vector<void*> ipc_opened;   // sgdnet_solver_link_ipc: the peers' buffers as mapped here
   // SGDNET_TRACE: host-side split of this solver's batched epochs (development aid; sgdnet_solver_destroy prints it).
   // The events bracket an epoch's launch on the solver's stream: created on first use, on the solver's device.
