@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -124,6 +124,18 @@ extern "C" {
  * and an even n_classes the optimum need not be unique in the coefficients (its deviance and its optimality
  * conditions are).  lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are defined as in the other modes. */
 #define SGDNET_MODE_MNEWTON 6
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): SGDNET_MODE_COVARIANCE's
+ * problem and method for up to sgdnet_wcovariance_max_features() features.  The scaled Gram matrix stays in global memory
+ * as a full symmetric matrix; one workgroup keeps c~, the coefficients, the gradient, diag S and an ascending list of the
+ * coordinates that can move in its LDS, runs cyclic coordinate descent over that list and reads one column of S per
+ * coordinate that moves; coordinates outside the list are screened with the full gradient and join when they would move
+ * (sgdnet_amd/csrc/covariance.hip: cov_wide_path_kernel).  Takes every n_features from 1 to the limit.  Needs family =
+ * gaussian, n_classes = 1, n_features <= sgdnet_wcovariance_max_features(), n_gpus <= 1 and debug = 0; anything else
+ * returns SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition ("mode = wcovariance needs ...") -- no fall
+ * back to SAGA or to SGDNET_MODE_COVARIANCE.  Draws, rng_state, draws_used, tol, return_codes, lambda, nulldev,
+ * dev_ratio, intercept = 0 and standardize = 0 are SGDNET_MODE_COVARIANCE's; max_iter bounds the sweeps over the list
+ * of one lambda and result.npasses counts those sweeps.  Same optimum as SGDNET_MODE_COVARIANCE, not the same bits. */
+#define SGDNET_MODE_WCOVARIANCE 7
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -215,6 +227,9 @@ const char* sgdnet_last_error(void);
 int sgdnet_device_count(void);
 /* the largest n_features SGDNET_MODE_COVARIANCE takes (198: what one gfx950 workgroup's LDS holds; at least 64) */
 int sgdnet_covariance_max_features(void);
+/* the largest n_features SGDNET_MODE_WCOVARIANCE takes (4531: 4 p doubles, p list words and p bits in one workgroup's
+ * LDS; at least 4096) */
+int sgdnet_wcovariance_max_features(void);
 /* the largest n_features SGDNET_MODE_NEWTON takes (198: the intercept is one more coordinate of the LDS-resident model) */
 int sgdnet_newton_max_features(void);
 /* the largest n_features SGDNET_MODE_MCOVARIANCE takes with n_responses responses: the LDS holds p (p + 1) / 2 + 3 p K
@@ -264,6 +279,11 @@ int sgdnet_mnewton_max_features(int n_classes);
 /*                        gather and one sweep launch per batch (what the     */
 /*                        library falls back to by itself when the GPU is     */
 /*                        shared and the launch cannot become resident)       */
+/*   "wcovariance_width"  0 (default): SGDNET_MODE_WCOVARIANCE's path kernel   */
+/*                        runs on 256 or 1024 lanes by the library's rule;    */
+/*                        256 or 1024: on that many (same bits either way;    */
+/*                        any other value makes such a fit return             */
+/*                        SGDNET_EINVAL)                                      */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

@@ -38,7 +38,7 @@ EXPORTS = [
     "sgdnet_cv_covariance_dense", "sgdnet_cv_covariance_sparse", "sgdnet_newton_max_features",
     "sgdnet_newton_probe_dense", "sgdnet_newton_probe_sparse",
     "sgdnet_cv_newton_dense", "sgdnet_cv_newton_sparse", "sgdnet_mcovariance_max_features",
-    "sgdnet_mnewton_max_features", "sgdnet_mnewton_probe",
+    "sgdnet_mnewton_max_features", "sgdnet_mnewton_probe", "sgdnet_wcovariance_max_features",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -49,6 +49,7 @@ MODES = {"exact": 0, "batched": 1, "auto": 2, "covariance": 3}
 MODE_NEWTON = 4   # SGDNET_MODE_NEWTON: reached through sgdnet_newton(), not through sgdnet(mode=...)
 MODE_MCOVARIANCE = 5   # SGDNET_MODE_MCOVARIANCE: reached through sgdnet_mcovariance(), likewise
 MODE_MNEWTON = 6   # SGDNET_MODE_MNEWTON: reached through sgdnet_mnewton(), likewise
+MODE_WCOVARIANCE = 7   # SGDNET_MODE_WCOVARIANCE: reached through sgdnet_wcovariance(), likewise
 
 UNIF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
 LOSSES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)
@@ -268,6 +269,7 @@ def load():
     L.sgdnet_cv_newton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     L.sgdnet_mcovariance_max_features.argtypes = [C.c_int]
     L.sgdnet_mnewton_max_features.argtypes = [C.c_int]
+    L.sgdnet_wcovariance_max_features.argtypes = []
     L.sgdnet_mnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(MNewtonProbe)]
     _lib = L
     return L

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODES, check, dptr
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -129,10 +129,27 @@ def sgdnet_mnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=No
                 batch=0, device=device, devices=None, min_classes=2)
 
 
+def sgdnet_wcovariance(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000,
+                       standardize=True, intercept=True, thresh=0.001, standardize_response=False, *, debug=False, device=0,
+                       devices=None):
+    """The gaussian path of sgdnet(x, y, mode="covariance") for up to wcovariance_max_features() features
+    (SGDNET_MODE_WCOVARIANCE, csrc/covariance.hip): one pass over x for the centred X'X and X'y, the scaled Gram matrix
+    kept in device memory, then cyclic coordinate descent over the coordinates that can move -- the non-zero ones and
+    those a screen with the full gradient adds -- one column of the Gram matrix read per move.  Every number of
+    features from 1 to the limit is taken; the optimum is mode="covariance"'s (not its bits).  The arguments, their
+    validation and the returned SgdnetFit are sgdnet()'s; family, debug and devices are there to be refused by name
+    (gaussian, no debug losses and one GPU only); lambda_ and nulldev are those of the other modes bit for bit.  It draws
+    no samples (draws_used = 0); maxit bounds the sweeps over the list per lambda, thresh is the largest relative
+    change a last sweep may make, npasses counts those sweeps."""
+    return _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
+                standardize_response, debug=debug, seed=0, rng=None, sample_stream=None, unif=None, mode="wcovariance",
+                modes={"wcovariance": MODE_WCOVARIANCE}, batch=0, device=device, devices=devices)
+
+
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
          standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3):
     """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton(),
-    sgdnet_mcovariance() and sgdnet_mnewton(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
+    sgdnet_mcovariance(), sgdnet_mnewton() and sgdnet_wcovariance(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
     min_classes: the fewest classes a multinomial response may have."""
     import scipy.sparse as sp
 

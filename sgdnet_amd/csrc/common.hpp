@@ -22,7 +22,7 @@ namespace sgdnet {
 void set_error(const char* fmt, ...);
 
 // Kernel A/B switches of the experiments behind DESIGN.md 5 (SGDNET_GATHER, SGDNET_LANES8, SGDNET_COMPACT,
-// SGDNET_W_LDS, SGDNET_BINNED, SGDNET_BIN_RANGES, SGDNET_LDS_GRID, SGDNET_EXACT_SMALL / _WIDE, SGDNET_REC_ALIGN; SGDNET_MCOV_WIDTH of DESIGN.md 4.5, SGDNET_MNEWTON_WIDTH of 4.6):
+// SGDNET_W_LDS, SGDNET_BINNED, SGDNET_BIN_RANGES, SGDNET_LDS_GRID, SGDNET_EXACT_SMALL / _WIDE, SGDNET_REC_ALIGN; SGDNET_MCOV_WIDTH and SGDNET_WCOV_PREFETCH of DESIGN.md 4.5, SGDNET_MNEWTON_WIDTH of 4.6):
 // environment variables in -DSGDNET_EXPERIMENTS builds, constants in the shipped library -- a user's
 // environment cannot change which kernel a fit runs.  What a user may tune is sgdnet_set_option
 // (include/sgdnet_hip.h).
@@ -39,7 +39,7 @@ inline const char* exp_env_str(const char*) { return nullptr; }
 
 // sgdnet_set_option values (solver.cpp)
 enum Option { kOptVirtualShards = 0, kOptRngGenerators, kOptWindowEigenvalue, kOptHostSetup, kOptExactEpochBlocks,
-              kOptExactRowRegisters, kOptFusedEpoch, kOptCount };
+              kOptExactRowRegisters, kOptFusedEpoch, kOptWcovarianceWidth, kOptCount };
 int option(Option o);
 
 #define SGD_HIP_TRY(expr)                                                              \

@@ -40,6 +40,11 @@
 //              bit) and cov_group_path_kernel runs cyclic BLOCK coordinate descent, a block the K coefficients of a
 //              feature: the group lasso with its l2 part, closed form per block (covariance.hpp has the LDS budget).
 //
+//   wide       wcovariance_run (SGDNET_MODE_WCOVARIANCE): beyond 198 features S does not fit one workgroup's LDS.
+//              cov_wide_scale_kernel writes it to global memory as a full symmetric matrix and cov_wide_path_kernel keeps
+//              only vectors and a list of the coordinates that can move in LDS (covariance.hpp has the budget): a
+//              moving coordinate reads its column of S, nothing else is touched.
+//
 // No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
 #include <algorithm>
@@ -506,6 +511,263 @@ __global__ __launch_bounds__(kWidth) void cov_group_path_kernel(const double* __
 constexpr int kMcovNarrow = 64, kMcovWide = 256;
 constexpr int mcov_path_width(size_t entries) { return entries <= (size_t)kMcovNarrow ? kMcovNarrow : kMcovWide; }
 
+// ---- wide covariance mode (SGDNET_MODE_WCOVARIANCE): S in global memory, only what can move is touched ----
+
+// blockIdx.x = column j of S: S[k + ld j] = M_jk / n / (sd_j sd_k), the arithmetic of cov_path_kernel's prologue, from
+// the upper triangle of the (p + 1) x (p + 1) moment matrix; rows p .. ld - 1 are the zero pad.  Also diag S and c~.
+__global__ __launch_bounds__(kBlock) void cov_wide_scale_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int ld,
+                                                                 double dn, double* __restrict__ S, double* __restrict__ Sd,
+                                                                 double* __restrict__ ct) {
+  const int j = blockIdx.x, P1 = p + 1;
+  const double sj = scale[j];
+  for (int k = threadIdx.x; k < ld; k += kBlock) {
+    double v = 0.0;
+    if (k < p) v = (k >= j ? M[(size_t)j * P1 + k] : M[(size_t)k * P1 + j]) / dn / (sj * scale[k]);
+    S[(size_t)j * ld + k] = v;
+    if (k == j) Sd[j] = v;
+  }
+  if (threadIdx.x == 0) ct[j] = M[(size_t)j * P1 + p] / dn / sj;
+}
+
+// The coordinate update of cov_wide_path_kernel, for the screen (w_j = 0) and for the sweep: from S_jj, w_j and g_j to the
+// new w_j.  Every caller passes the same words through the same operations, so every lane holds the same bits.
+__device__ __forceinline__ double cov_coord_new_w(double sjj, double wj, double gj, double al, double be, int ridge) {
+  const double z = fma(sjj, wj, -gj), denom = sjj + al;
+  double nw = z;
+  if (!ridge) nw = z > be ? z - be : (z < -be ? z + be : 0.0);
+  return denom > 0.0 ? nw / denom : 0.0;          // a constant column without an l2 term: S_jj = c~_j = 0
+}
+
+// One workgroup of kWidth lanes, the whole path, S (leading dimension ld, a multiple of 16) read from global memory.
+// LDS (covariance.hpp: wcov_state_bytes): g | c~ | w | diag S | the list | the list's bits | the compaction's counts.
+// Per lambda, warm-started:
+//   rebuild  the list becomes {j : w_j != 0}, ascending; g = sum_{j in list} S[:, j] w_j - c~ afresh (a lane owns two
+//            consecutive k, j ascends: one 16-byte load per column, four columns requested before the first is used)
+//   screen   every j outside the list: the coordinate update from w_j = 0; those that would move join.  The list is
+//            compacted again from its bits, kWidth coordinates a step: a ballot per wavefront, the wavefronts' counts
+//            through LDS -- ascending whatever kWidth is, no atomic
+//   sweep    cov_path_kernel's cyclic coordinate descent over the list: every lane computes the scalars from the same LDS
+//            words (uniform branches); a coordinate that stays costs no global read and no barrier; one that moves by d
+//            does g[k] += S[k, j] d for ALL k < p (so g stays the full gradient and the screen needs no pass over S),
+//            16 bytes a lane.  The reference's ConvergenceCheck over the list ends the sweeps; then the screen runs
+//            again, and the lambda is done when it adds nothing.
+// max_iter bounds the list sweeps of one lambda.  g[k] is updated by one lane from the same words in the same order
+// whatever kWidth is: both widths give the same bits.
+template <int kWidth, bool kPrefetch>
+__global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                                const double* __restrict__ ct, int p, int ld,
+                                                                const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                int n_lambda, int ridge, unsigned max_iter, double tol,
+                                                                double* __restrict__ W, double* __restrict__ G,
+                                                                int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kCovLdsBytes];
+  constexpr int kWaves = kWidth / 64;
+  static_assert(kWaves * 2 <= kWcovScanWords, "the compaction's counts (covariance.hpp)");
+  const int lane = threadIdx.x, wave = lane >> 6, wl = lane & 63;
+  double* g = reinterpret_cast<double*>(lds);
+  double* c = g + p;
+  double* w = c + p;
+  double* sd = w + p;
+  int32_t* list = reinterpret_cast<int32_t*>(sd + p);
+  uint32_t* bits = reinterpret_cast<uint32_t*>(list + p);
+  int32_t* counts = reinterpret_cast<int32_t*>(bits + (p + 31) / 32);
+  const int slots = (p + 1) / 2;     // a slot: k = 2 s and 2 s + 1 (p odd: the last one's second entry is S's zero pad)
+  // kPrefetch: a lane's slots of one column of S, requested while the move before it updates g (S never changes, so
+  // what is held stays valid until the sweep reaches column held_j, in this sweep or a later one)
+  constexpr int kSlots = ((kWcovMaxFeatures + 1) / 2 + kWidth - 1) / kWidth, kLookAhead = 8;
+  double2 held[kSlots];
+  int held_j = -1;
+  auto fetch = [&](int j, double2(&buf)[kSlots]) {
+    const double* col = S + (size_t)ld * j;
+#pragma unroll
+    for (int u = 0; u < kSlots; ++u) {
+      const int s = lane + u * kWidth;
+      if (s < slots) buf[u] = *reinterpret_cast<const double2*>(col + 2 * s);
+    }
+  };
+  for (int j = lane; j < p; j += kWidth) {
+    c[j] = ct[j];
+    sd[j] = Sd[j];
+    w[j] = 0.0;
+  }
+  __syncthreads();
+
+  // The list from one flag per coordinate, in ascending order; returns its length.  screen: the flag is "in the list
+  // already, or would move from 0"; else: w_j != 0.  A wavefront reads and rewrites the bits of its own 64 coordinates.
+  auto compact = [&](bool screen, double al, double be) -> int {
+    int length = 0, buf = 0;
+    for (int base = 0; base < p; base += kWidth) {
+      const int j = base + lane, first = base + wave * 64;
+      bool in = false;
+      if (j < p) {
+        if (screen) {
+          in = (bits[j >> 5] >> (j & 31)) & 1u;
+          if (!in) in = cov_coord_new_w(sd[j], 0.0, g[j], al, be, ridge) != 0.0;
+        } else {
+          in = w[j] != 0.0;
+        }
+      }
+      const unsigned long long b = __ballot(in);
+      if (wl == 0) counts[buf * kWaves + wave] = __popcll(b);
+      __syncthreads();
+      int before = 0, total = 0;
+      for (int v = 0; v < kWaves; ++v) {
+        const int n_v = counts[buf * kWaves + v];
+        before += v < wave ? n_v : 0;
+        total += n_v;
+      }
+      if (in) list[length + before + __popcll(b & ((1ull << wl) - 1ull))] = j;
+      if (wl == 0 && first < p) {
+        bits[first >> 5] = (uint32_t)b;
+        if (first + 32 < p) bits[(first >> 5) + 1] = (uint32_t)(b >> 32);
+      }
+      length += total;
+      buf ^= 1;        // (the counts of step i are read before the barrier of step i + 1 and rewritten behind it)
+    }
+    __syncthreads();
+    return length;
+  };
+
+  for (int l = 0; l < n_lambda; ++l) {
+    const double al = alpha[l], be = beta[l];
+    int n_list = compact(false, al, be);
+    // the gradient afresh at every lambda, as in cov_path_kernel
+    for (int s = lane; s < slots; s += kWidth) {
+      const int k = 2 * s;
+      const double* col = S + k;
+      double a0 = 0.0, a1 = 0.0;
+      int i = 0;
+      for (; i + 4 <= n_list; i += 4) {
+        const int j0 = list[i], j1 = list[i + 1], j2 = list[i + 2], j3 = list[i + 3];
+        const double2 v0 = *reinterpret_cast<const double2*>(col + (size_t)ld * j0);
+        const double2 v1 = *reinterpret_cast<const double2*>(col + (size_t)ld * j1);
+        const double2 v2 = *reinterpret_cast<const double2*>(col + (size_t)ld * j2);
+        const double2 v3 = *reinterpret_cast<const double2*>(col + (size_t)ld * j3);
+        const double w0 = w[j0], w1 = w[j1], w2 = w[j2], w3 = w[j3];
+        a0 = fma(v0.x, w0, a0);
+        a1 = fma(v0.y, w0, a1);
+        a0 = fma(v1.x, w1, a0);
+        a1 = fma(v1.y, w1, a1);
+        a0 = fma(v2.x, w2, a0);
+        a1 = fma(v2.y, w2, a1);
+        a0 = fma(v3.x, w3, a0);
+        a1 = fma(v3.y, w3, a1);
+      }
+      for (; i < n_list; ++i) {
+        const int j = list[i];
+        const double2 v = *reinterpret_cast<const double2*>(col + (size_t)ld * j);
+        a0 = fma(v.x, w[j], a0);
+        a1 = fma(v.y, w[j], a1);
+      }
+      g[k] = a0 - c[k];
+      if (k + 1 < p) g[k + 1] = a1 - c[k + 1];
+    }
+    __syncthreads();
+
+    unsigned sweeps = 0;
+    bool converged = false;
+    for (int screens = 0;; ++screens) {
+      const int n_new = compact(true, al, be);
+      if (screens > 0 && n_new == n_list) {      // the list had converged and nothing outside it moves
+        converged = true;
+        break;
+      }
+      n_list = n_new;
+      bool met = false;
+      while (sweeps < max_iter && !met) {
+        double max_change = 0.0, max_size = 0.0;
+        for (int i = 0; i < n_list; ++i) {
+          const int j = list[i];
+          const double wj = w[j];
+          const double nw = cov_coord_new_w(sd[j], wj, g[j], al, be, ridge);
+          const double d = nw - wj;
+          max_change = fmax(max_change, fabs(d));
+          max_size = fmax(max_size, fabs(nw));
+          if (d != 0.0 && kPrefetch) {
+            // the column of this move: the one held, or fetched now; then the request for the next entry of the list
+            // (at most kLookAhead on, wrapping to the next sweep) whose coefficient is not 0: the likeliest to move
+            double2 now[kSlots];
+            if (held_j == j) {
+#pragma unroll
+              for (int u = 0; u < kSlots; ++u) now[u] = held[u];
+            } else {
+              fetch(j, now);
+            }
+            held_j = -1;
+            for (int t = 1; t <= kLookAhead && t < n_list && held_j < 0; ++t) {
+              const int next = list[i + t < n_list ? i + t : i + t - n_list];
+              if (w[next] != 0.0) held_j = next;
+            }
+            if (held_j >= 0) fetch(held_j, held);
+            __syncthreads();                         // every lane has read w[j] and g[j]
+            if (lane == 0) w[j] = nw;
+#pragma unroll
+            for (int u = 0; u < kSlots; ++u) {
+              const int k = 2 * (lane + u * kWidth);
+              if (k + 1 < p) {
+                double2 gk = *reinterpret_cast<double2*>(g + k);
+                gk.x = fma(now[u].x, d, gk.x);
+                gk.y = fma(now[u].y, d, gk.y);
+                *reinterpret_cast<double2*>(g + k) = gk;
+              } else if (k < p) {
+                g[k] = fma(now[u].x, d, g[k]);
+              }
+            }
+            __syncthreads();
+          } else if (d != 0.0) {
+            __syncthreads();                         // every lane has read w[j] and g[j]
+            if (lane == 0) w[j] = nw;
+            const double* col = S + (size_t)ld * j;
+#pragma unroll 4
+            for (int s = lane; s < slots; s += kWidth) {
+              const int k = 2 * s;
+              const double2 v = *reinterpret_cast<const double2*>(col + k);
+              if (k + 1 < p) {
+                double2 gk = *reinterpret_cast<double2*>(g + k);
+                gk.x = fma(v.x, d, gk.x);
+                gk.y = fma(v.y, d, gk.y);
+                *reinterpret_cast<double2*>(g + k) = gk;
+              } else {
+                g[k] = fma(v.x, d, g[k]);
+              }
+            }
+            __syncthreads();
+          }
+        }
+        ++sweeps;
+        const bool all_zero = max_size == 0.0 && max_change == 0.0;
+        const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+        met = all_zero || no_change;
+      }
+      if (!met) break;                               // max_iter
+    }
+    for (int k = lane; k < p; k += kWidth) {
+      W[(size_t)l * p + k] = w[k];
+      G[(size_t)l * p + k] = g[k];
+    }
+    if (lane == 0) {
+      sweeps_out[l] = (int32_t)sweeps;
+      unconverged[l] = converged ? 0 : 1;
+    }
+  }
+}
+
+// The wide path kernel's workgroup and whether it requests the next column ahead: all four instances give the same bits;
+// profiles/wcovariance_path.txt has the path kernel's time for each at p = 198, 1000, 2000 and 4000 (100 lambdas):
+//   lanes, ahead      p = 198     1000     2000     4000
+//   256,  no           8.3 ms     85 ms   499 ms   830 ms
+//   1024, no          10.4 ms     82 ms   227 ms   340 ms
+//   256,  yes         16.1 ms    103 ms   257 ms   320 ms
+//   1024, yes         14.2 ms     83 ms   218 ms   255 ms
+// A column of 198 doubles is less than one stride of 256 lanes, and twelve more wavefronts only wait at the barriers;
+// from 1000 on the sixteen wavefronts win.  Looking ahead costs a scan of the list and a copy of the held registers per
+// move: it loses where a column comes back from L2 at once and wins (4 % at 2000, 25 % at 4000) where a move waits for
+// its column.  So: 256 lanes up to 512 features, 1024 beyond; ahead beyond 1536 (between the two measurements).
+constexpr int kWcovNarrow = 256, kWcovWide = 1024;
+constexpr int wcov_path_width(int p) { return p <= 512 ? kWcovNarrow : kWcovWide; }
+constexpr bool wcov_path_ahead(int p) { return p > 1536; }
+static_assert(kTileCols == 16 && kBlock == 256, "wcov_tile_pairs and kWcovPartialBytes (covariance.hpp) count 16-column tiles of 256 partial sums");
+
 struct Events {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;
@@ -516,14 +778,16 @@ struct Events {
   }
 };
 
-}  // namespace
-
-int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
+// covariance_run and wcovariance_run: the same uploads, moments pass and downloads around two path kernels.
+// wide: S goes to global memory (cov_wide_scale_kernel) and cov_wide_path_kernel<width> runs the path; the dense row
+// chunks follow wcov_row_chunks.  Not wide: exactly the launches covariance mode has always made.
+int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int width) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, P1 = p + 1, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
-  if (n <= 0 || p <= 0 || p > kCovMaxFeatures || L <= 0 || (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
-    set_error("covariance_run: invalid problem");
+  if (n <= 0 || p <= 0 || pb.p > (wide ? kWcovMaxFeatures : kCovMaxFeatures) || L <= 0 || (wide && width != kWcovNarrow && width != kWcovWide) ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("%s: invalid problem", wide ? "wcovariance_run" : "covariance_run");
     return SGDNET_EINVAL;
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
@@ -536,7 +800,8 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
 
   // dense x: the tile pairs and the row chunks (a function of n and p alone)
   const int T = (P1 + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+  const int64_t rows_per_chunk = wide ? ((n + wcov_row_chunks(n, p) - 1) / wcov_row_chunks(n, p) + kTileRows - 1) / kTileRows * kTileRows
+                                      : dense_rows_per_chunk(n, pairs);
   const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
 
   Arena A;
@@ -548,6 +813,9 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
   const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
   const size_t o_M = A.reserve(sizeof(double) * (size_t)P1 * (size_t)P1);
+  const int ld = (int)wcov_leading_dim(p);
+  const size_t o_S = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)p : 0);
+  const size_t o_Sd = A.reserve(wide ? sizeof(double) * (size_t)p : 0);
   const size_t o_alpha = A.reserve(sizeof(double) * (size_t)L);
   const size_t o_beta = A.reserve(sizeof(double) * (size_t)L);
   const size_t o_W = A.reserve(sizeof(double) * (size_t)L * (size_t)p);
@@ -596,9 +864,23 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  hipLaunchKernelGGL(cov_path_kernel, dim3(1), dim3(64), 0, st, d_M, A.at<double>(o_scale), p, 1, (double)n, (const double*)nullptr,
-                     A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr, pb.max_iter, pb.tol,
-                     A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  if (wide) {
+    hipLaunchKernelGGL(cov_wide_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, ld, (double)n,
+                       A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
+    SGD_HIP_TRY(hipGetLastError());
+    SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+    static const int ahead = exp_env_int("SGDNET_WCOV_PREFETCH", -1);     // (0 / 1: profiles/wcovariance_path.txt)
+    const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
+    const auto kernel = width == kWcovNarrow ? (prefetch ? cov_wide_path_kernel<kWcovNarrow, true> : cov_wide_path_kernel<kWcovNarrow, false>)
+                                             : (prefetch ? cov_wide_path_kernel<kWcovWide, true> : cov_wide_path_kernel<kWcovWide, false>);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c), p, ld,
+                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
+                       A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  } else {
+    hipLaunchKernelGGL(cov_path_kernel, dim3(1), dim3(64), 0, st, d_M, A.at<double>(o_scale), p, 1, (double)n, (const double*)nullptr,
+                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr, pb.max_iter, pb.tol,
+                       A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
 
@@ -617,8 +899,21 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) {
   SGD_HIP_TRY(hipStreamSynchronize(st));
   out->mean.resize((size_t)p);     // (entry p was the response's sum)
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
-  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  if (wide) {
+    SGD_HIP_TRY(hipEventElapsedTime(&out->scale_ms, ev.e[1], ev.e[3]));
+    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[3], ev.e[2]));
+  } else {
+    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  }
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) { return cov_run(pb, out, false, 0); }
+
+int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width) {
+  return cov_run(pb, out, true, width != 0 ? width : wcov_path_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)));
 }
 
 
@@ -897,4 +1192,5 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
 }  // namespace sgdnet
 
 extern "C" int sgdnet_covariance_max_features(void) { return sgdnet::kCovMaxFeatures; }
+extern "C" int sgdnet_wcovariance_max_features(void) { return sgdnet::kWcovMaxFeatures; }
 extern "C" int sgdnet_mcovariance_max_features(int n_responses) { return sgdnet::mcov_max_features(n_responses); }

@@ -964,8 +964,10 @@ int rescale_into(sgdnet_solver* S, const Features& X, const Response& R, const s
 // without standardize), the response of prepare_response, the penalties of regularization_path.  With an intercept the
 // optimum only sees deviations from the column means, standardised or not; without one the intercept stays at the null
 // model's value and the features are taken as the preprocessing left them: deviations from x_center.
+// SGDNET_MODE_WCOVARIANCE is the same stage around wcovariance_run (S in global memory, any p up to its own limit).
 int fit_covariance(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl,
                    sgdnet_result* out, PhaseTimer& pt) {
+  const bool wide = plan.mode == SGDNET_MODE_WCOVARIANCE;
   const int64_t n = X.n, p = X.p;
   const int L = ctl->n_lambda;
   CovarianceProblem pb;
@@ -989,9 +991,12 @@ int fit_covariance(const Features& X, const Response& R, const Path& path, const
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   CovarianceResult cr;
-  int rc = covariance_run(pb, &cr);
+  int rc = wide ? wcovariance_run(pb, &cr, option(kOptWcovarianceWidth)) : covariance_run(pb, &cr);
   if (rc) return rc;
-  if (pt.on) fprintf(stderr, "[sgdnet]   covariance: moments %.3f ms, path kernel %.3f ms\n", cr.moments_ms, cr.path_ms);
+  if (pt.on && wide)
+    fprintf(stderr, "[sgdnet]   wcovariance: moments %.3f ms, scale %.3f ms, path kernel %.3f ms\n", cr.moments_ms, cr.scale_ms, cr.path_ms);
+  else if (pt.on)
+    fprintf(stderr, "[sgdnet]   covariance: moments %.3f ms, path kernel %.3f ms\n", cr.moments_ms, cr.path_ms);
 
   // deviance from the quadratic form: |y~ - X~ w|^2 = y~'y~ - n (2 c~'w - w'S w), and w'S w = w'(g + c~) with the path
   // kernel's gradient g = S w - c~: the explained part is n sum_j w_j (c~_j - g_j), each term w_j c~_j + alpha w_j^2 +
@@ -1019,7 +1024,7 @@ int fit_covariance(const Features& X, const Response& R, const Path& path, const
   }
   out->npasses = n_sweeps;
   out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
-  pt.mark("covariance (moments + path)");
+  pt.mark(wide ? "wcovariance (moments + scale + path)" : "covariance (moments + path)");
   return SGDNET_OK;
 }
 
@@ -1241,7 +1246,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
   if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_MCOVARIANCE ||
-      ctl->mode == SGDNET_MODE_MNEWTON) {   // plan_fit says whether they may run; they need none of the SAGA setup below
+      ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WCOVARIANCE) {   // plan_fit says whether they may run; they need none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1558,7 +1563,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
   if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON && ctl->mode != SGDNET_MODE_MCOVARIANCE &&
-      ctl->mode != SGDNET_MODE_MNEWTON) {   // (those modes read x column-major, as it came)
+      ctl->mode != SGDNET_MODE_MNEWTON && ctl->mode != SGDNET_MODE_WCOVARIANCE) {   // (those modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }

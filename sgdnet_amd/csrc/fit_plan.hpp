@@ -73,7 +73,7 @@ struct FitFacts {
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
 // An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE, SGDNET_MODE_NEWTON,
-// SGDNET_MODE_MCOVARIANCE and SGDNET_MODE_MNEWTON: no other mode resolves to them.
+// SGDNET_MODE_MCOVARIANCE, SGDNET_MODE_MNEWTON and SGDNET_MODE_WCOVARIANCE: no other mode resolves to them.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -144,6 +144,27 @@ inline FitPlan plan_fit(const FitFacts& f) {
       return P;
     }
     P.mode = SGDNET_MODE_COVARIANCE;
+    P.rank_dev.assign(1, c.device);
+    P.rank_lo = {0, n};
+    return P;                          // no window, no shards, no draws
+  }
+
+  // ---- wide covariance mode: the same problem with S in global memory (covariance.hpp: kWcovMaxFeatures), every
+  // p from 1 to that limit; likewise only where it was asked for, no silent fall back ----
+  if (c.mode == SGDNET_MODE_WCOVARIANCE) {
+    const char* what = nullptr;
+    if (family != SGDNET_GAUSSIAN) what = "family = gaussian";
+    else if (K != 1) what = "one response (n_classes = 1)";
+    else if (f.p > kWcovMaxFeatures) what = "no more features than sgdnet_wcovariance_max_features()";
+    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+    if (what) {
+      P.rc = SGDNET_EUNSUPPORTED;
+      P.error = plan_text("mode = wcovariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what,
+                          family, K, (long long)f.p, kWcovMaxFeatures, c.n_gpus, c.debug);
+      return P;
+    }
+    P.mode = SGDNET_MODE_WCOVARIANCE;
     P.rank_dev.assign(1, c.device);
     P.rank_lo = {0, n};
     return P;                          // no window, no shards, no draws
