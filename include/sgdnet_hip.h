@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -136,6 +136,20 @@ extern "C" {
  * dev_ratio, intercept = 0 and standardize = 0 are SGDNET_MODE_COVARIANCE's; max_iter bounds the sweeps over the list
  * of one lambda and result.npasses counts those sweeps.  Same optimum as SGDNET_MODE_COVARIANCE, not the same bits. */
 #define SGDNET_MODE_WCOVARIANCE 7
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): SGDNET_MODE_NEWTON's
+ * problem and outer loop for up to sgdnet_wnewton_max_features() features.  Per Newton step the scaled weighted Gram
+ * matrix is written to global memory as a full symmetric matrix; one workgroup keeps the gradient, the coordinates,
+ * diag H and an ascending list of the coordinates that can move in its LDS, runs cyclic coordinate descent over that
+ * list and reads one column of H per coordinate that moves; coordinates outside the list are screened with the full
+ * gradient and join when they would move; the intercept is an unpenalised member of the list
+ * (sgdnet_amd/csrc/newton.hip: newton_wide_cd_kernel).  Takes every n_features from 1 to the limit.  Sparse x is
+ * expanded to a dense copy (at most 1 GiB) and gives the dense fit's bits.  Needs family = binomial, n_classes = 1,
+ * n_features <= sgdnet_wnewton_max_features(), n_gpus <= 1, debug = 0 and that copy within its bound; anything else
+ * returns SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition ("mode = wnewton needs ...") -- no fall back
+ * to SAGA or to SGDNET_MODE_NEWTON.  Draws, rng_state, draws_used, max_iter, tol, return_codes, npasses, lambda, nulldev,
+ * dev_ratio, intercept = 0 and standardize = 0 are SGDNET_MODE_NEWTON's.  Same optimum as SGDNET_MODE_NEWTON, not the
+ * same bits. */
+#define SGDNET_MODE_WNEWTON 8
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -232,6 +246,9 @@ int sgdnet_covariance_max_features(void);
 int sgdnet_wcovariance_max_features(void);
 /* the largest n_features SGDNET_MODE_NEWTON takes (198: the intercept is one more coordinate of the LDS-resident model) */
 int sgdnet_newton_max_features(void);
+/* the largest n_features SGDNET_MODE_WNEWTON takes (5819: with the intercept 3 P doubles, P list words and P bits in one
+ * workgroup's LDS, P = n_features + 1; at least 4096) */
+int sgdnet_wnewton_max_features(void);
 /* the largest n_features SGDNET_MODE_MCOVARIANCE takes with n_responses responses: the LDS holds p (p + 1) / 2 + 3 p K
  * doubles (195 at K = 2, 174 at K = 10, 63 at K = 96); 0 where nothing fits or n_responses < 1 */
 int sgdnet_mcovariance_max_features(int n_responses);
@@ -284,6 +301,10 @@ int sgdnet_mnewton_max_features(int n_classes);
 /*                        256 or 1024: on that many (same bits either way;    */
 /*                        any other value makes such a fit return             */
 /*                        SGDNET_EINVAL)                                      */
+/*   "wnewton_width"      0 (default): SGDNET_MODE_WNEWTON's inner solve runs  */
+/*                        on 256 or 1024 lanes by the library's rule; 256 or  */
+/*                        1024: on that many (same bits either way; any       */
+/*                        other value makes such a fit return SGDNET_EINVAL)  */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

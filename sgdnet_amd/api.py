@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODES, check, dptr
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WNEWTON, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -94,6 +94,21 @@ def sgdnet_newton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=Non
                 batch=0, device=device, devices=None)
 
 
+def sgdnet_wnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
+                   intercept=True, thresh=0.001, *, device=0):
+    """The binomial path of sgdnet_newton(x, y, ...) for up to wnewton_max_features() features (SGDNET_MODE_WNEWTON,
+    csrc/newton.hip): the same proximal Newton steps with the weighted Gram matrix kept in device memory; the inner
+    solve is cyclic coordinate descent over the coordinates that can move -- the non-zero ones, the intercept and those
+    a screen with the full gradient adds -- one column of the matrix read per move.  Every number of features from 1 to
+    the limit is taken; the optimum is sgdnet_newton()'s (not its bits).  Sparse x is expanded to a dense copy (at most
+    1 GiB) and gives the dense fit's bits.  The arguments, their validation, the response encoding and the returned
+    SgdnetFit are sgdnet()'s; lambda_ and nulldev are those of the other modes bit for bit.  It draws no samples
+    (draws_used = 0); maxit, thresh and npasses mean what they mean for sgdnet_newton()."""
+    return _fit(x, y, "binomial", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh, False,
+                debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="wnewton", modes={"wnewton": MODE_WNEWTON},
+                batch=0, device=device, devices=None)
+
+
 def sgdnet_mcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
                        intercept=True, thresh=0.001, standardize_response=False, *, device=0):
     """The multi-response path of sgdnet(x, y, family="mgaussian", ...) solved to its optimum on the device
@@ -149,7 +164,7 @@ def sgdnet_wcovariance(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
          standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3):
     """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton(),
-    sgdnet_mcovariance(), sgdnet_mnewton() and sgdnet_wcovariance(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
+    sgdnet_mcovariance(), sgdnet_mnewton(), sgdnet_wcovariance() and sgdnet_wnewton(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
     min_classes: the fewest classes a multinomial response may have."""
     import scipy.sparse as sp
 

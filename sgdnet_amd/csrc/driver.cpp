@@ -1108,8 +1108,11 @@ int fit_mcovariance(const Features& X, const Response& R, const Path& path, cons
 // The same preprocessed problem as above, for a binomial response: the features centred where fit_covariance centres
 // them, the class codes as they came, the intercept an unpenalised coordinate that starts at the null model's value
 // (and stays there without an intercept).
+// SGDNET_MODE_WNEWTON is the same stage around wnewton_run (H in global memory, any p up to its own limit; sparse x came
+// here as its dense copy: fit_sparse_impl).
 int fit_newton(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl, sgdnet_result* out,
                PhaseTimer& pt) {
+  const bool wide = plan.mode == SGDNET_MODE_WNEWTON;
   const int64_t n = X.n, p = X.p;
   const int L = ctl->n_lambda;
   NewtonProblem pb;
@@ -1135,7 +1138,7 @@ int fit_newton(const Features& X, const Response& R, const Path& path, const Fit
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   NewtonResult nr;
-  const int rc = newton_run(pb, pt.on, &nr);
+  const int rc = wide ? wnewton_run(pb, pt.on, &nr, option(kOptWnewtonWidth)) : newton_run(pb, pt.on, &nr);
   if (rc) return rc;
   double n_steps = 0.0;
   for (int li = 0; li < L; ++li) {
@@ -1151,12 +1154,15 @@ int fit_newton(const Features& X, const Response& R, const Path& path, const Fit
     const double b = ctl->intercept != 0 ? u[p] - shift : R.b0[0];
     rescale_values(X, R, ctl, li, u, &b, out);
   }
-  if (pt.on)
+  if (pt.on && wide)
+    fprintf(stderr, "[sgdnet]   wnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
+            "scale %.3f ms, inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.scale_ms, nr.cd_ms);
+  else if (pt.on)
     fprintf(stderr, "[sgdnet]   newton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
             "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);
   out->npasses = nr.passes;
   out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
-  pt.mark("newton (state + moments + cd)");
+  pt.mark(wide ? "wnewton (state + moments + scale + cd)" : "newton (state + moments + cd)");
   return SGDNET_OK;
 }
 
@@ -1246,7 +1252,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
   if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_MCOVARIANCE ||
-      ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WCOVARIANCE) {   // plan_fit says whether they may run; they need none of the SAGA setup below
+      ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WCOVARIANCE || ctl->mode == SGDNET_MODE_WNEWTON) {   // plan_fit says whether they may run; they need none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1259,7 +1265,8 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
     }
     if (ctl->mode == SGDNET_MODE_MCOVARIANCE) return fit_mcovariance(X, R, path, plan, ctl, out, pt);
     if (ctl->mode == SGDNET_MODE_MNEWTON) return fit_mnewton(X, R, path, plan, ctl, out, pt);
-    return ctl->mode == SGDNET_MODE_NEWTON ? fit_newton(X, R, path, plan, ctl, out, pt) : fit_covariance(X, R, path, plan, ctl, out, pt);
+    return ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_WNEWTON ? fit_newton(X, R, path, plan, ctl, out, pt)
+                                                                             : fit_covariance(X, R, path, plan, ctl, out, pt);
   }
   double norm_max = 0.0;
   rc = row_norm_max(X, ctl, R, Ky, trace, &norm_max);
@@ -1464,10 +1471,11 @@ int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdn
   X.raw_values = x->values;
   const int64_t n = X.n, p = X.p, nnz = x->colptr[p];
   if ((rc = validate_colptr(x)) || (rc = validate_response(ctl, y, n)) || (rc = validate_rowidx(x))) return rc;
-  if (ctl->mode == SGDNET_MODE_MNEWTON) {
-    // This mode holds at most 98 features and reads x dense.  The copy is made here, before anything is computed from x,
-    // so that the standard deviations, lambda_max and everything after them are the dense fit's of the same matrix, bit
-    // for bit.  The plan's refusals come first: one of them is the size of this copy.  Entries stored twice add up.
+  if (ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WNEWTON) {
+    // These modes read x dense (mnewton holds at most 98 features; wnewton's sparse moments would be p (p + 2) workgroups a
+    // step).  The copy is made here, before anything is computed from x, so that the standard deviations, lambda_max and
+    // everything after them are the dense fit's of the same matrix, bit for bit.  The plan's refusals come first: one of
+    // them is the size of this copy.  Entries stored twice add up.
     FitFacts facts;
     facts.ctl = ctl;
     facts.sparse = true;
@@ -1563,7 +1571,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
   if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON && ctl->mode != SGDNET_MODE_MCOVARIANCE &&
-      ctl->mode != SGDNET_MODE_MNEWTON && ctl->mode != SGDNET_MODE_WCOVARIANCE) {   // (those modes read x column-major, as it came)
+      ctl->mode != SGDNET_MODE_MNEWTON && ctl->mode != SGDNET_MODE_WCOVARIANCE && ctl->mode != SGDNET_MODE_WNEWTON) {   // (those modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }

@@ -73,7 +73,7 @@ struct FitFacts {
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
 // An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE, SGDNET_MODE_NEWTON,
-// SGDNET_MODE_MCOVARIANCE, SGDNET_MODE_MNEWTON and SGDNET_MODE_WCOVARIANCE: no other mode resolves to them.
+// SGDNET_MODE_MCOVARIANCE, SGDNET_MODE_MNEWTON, SGDNET_MODE_WCOVARIANCE and SGDNET_MODE_WNEWTON: no other mode resolves to them.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -186,6 +186,30 @@ inline FitPlan plan_fit(const FitFacts& f) {
       return P;
     }
     P.mode = SGDNET_MODE_NEWTON;
+    P.rank_dev.assign(1, c.device);
+    P.rank_lo = {0, n};
+    return P;                          // no window, no shards, no draws
+  }
+
+  // ---- wide Newton mode: the same problem with H in global memory (newton.hpp: kWnewtonMaxFeatures), every p from 1 to
+  // that limit; sparse x is expanded to a dense copy by the driver, which has its own bound; likewise only where it was
+  // asked for, no fall back to Newton mode or to SAGA ----
+  if (c.mode == SGDNET_MODE_WNEWTON) {
+    const char* what = nullptr;
+    if (family != SGDNET_BINOMIAL) what = "family = binomial";
+    else if (K != 1) what = "one response (n_classes = 1)";
+    else if (f.p > kWnewtonMaxFeatures) what = "no more features than sgdnet_wnewton_max_features()";
+    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+    else if (f.sparse && (double)n * (double)f.p * 8.0 > (double)kWnewtonDenseCopyBytes)
+      what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
+    if (what) {
+      P.rc = SGDNET_EUNSUPPORTED;
+      P.error = plan_text("mode = wnewton needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what,
+                          family, K, (long long)n, (long long)f.p, kWnewtonMaxFeatures, c.n_gpus, c.debug);
+      return P;
+    }
+    P.mode = SGDNET_MODE_WNEWTON;
     P.rank_dev.assign(1, c.device);
     P.rank_lo = {0, n};
     return P;                          // no window, no shards, no draws

@@ -34,6 +34,13 @@
 // pass.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz): the same input gives
 // the same bits.
 //
+// Wide mode (wnewton_run, SGDNET_MODE_WNEWTON): beyond 198 features H does not fit one workgroup's LDS.  The loop, the state
+// pass and the dense moments kernels are the ones above (row chunks by newton.hpp's wnewton_row_chunks); then
+// newton_wide_scale_kernel writes H = M / n / (s s') to global memory as a full symmetric matrix with diag H and q, and
+// newton_wide_cd_kernel keeps g, u, diag H and an ascending list of the coordinates that can move in LDS, sweeps that
+// list, reads one column of H per move and lets a screen with the full gradient add coordinates (newton.hpp: the budget
+// behind sgdnet_wnewton_max_features).  Dense x only: the driver expands sparse x.
+//
 // Cross-validation (newton_cv_run, include/sgdnet_hip.h: sgdnet_cv_newton_*): all fold fits of all mixes advance in
 // lock-step.  The rows are sorted by group once, so a training set is a range of rows or the complement of one; the
 // newton_cv_* kernels are the kernels above with a job dimension, each job on its own rows, centres, scales and buffers;
@@ -330,6 +337,203 @@ __global__ __launch_bounds__(64) void newton_cd_kernel(const double* __restrict_
   __shared__ double lds[newton_state_doubles(kNewtonMaxFeatures)];
   newton_cd_solve(lds, M, scale, p, dn, u_cur, al, be, ridge, fit_intercept, max_sweeps, tol, u_cand, a_cand, rec);
 }
+
+// ---- wide Newton mode (SGDNET_MODE_WNEWTON, wnewton_run): H in global memory, only what can move is touched ----
+
+// newton_blend_kernel without an array of kNewtonMaxFeatures + 1 doubles: publish_candidate reads every coordinate once,
+// by the lane that then writes it, so the blend is formed where it is read.
+struct BlendedCandidate {
+  const double* u_cur;
+  const double* u_cand;
+  double t;
+  __device__ __forceinline__ double operator[](int k) const { return t == 1.0 ? u_cand[k] : u_cur[k] + t * (u_cand[k] - u_cur[k]); }
+};
+
+__global__ __launch_bounds__(64) void newton_wide_blend_kernel(const double* u_cur, const double* __restrict__ scale, int p, double t,
+                                                                double* u_cand, double* __restrict__ a_cand, double* __restrict__ rec) {
+  publish_candidate(BlendedCandidate{u_cur, u_cand, t}, u_cur, scale, p, u_cand, a_cand, rec);
+}
+
+// blockIdx.x = column j of H over the P = p + 1 coordinates (features, then the ones): H[k + ld j] = M_jk / n / (s_j s_k),
+// the arithmetic of newton_cd_solve's prologue, from the upper triangle of the (p + 2)^2 moments; rows P .. ld - 1 are
+// the zero pad.  Also diag H and q_j = M[j, p + 1] / n / s_j.
+__global__ __launch_bounds__(kBlock) void newton_wide_scale_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p,
+                                                                    int ld, double dn, double* __restrict__ H, double* __restrict__ Hd,
+                                                                    double* __restrict__ q) {
+  const int j = blockIdx.x, P = p + 1, nc = p + 2;
+  const double sj = j < p ? scale[j] : 1.0;
+  for (int k = threadIdx.x; k < ld; k += kBlock) {
+    double v = 0.0;
+    if (k < P) {
+      const double sk = k < p ? scale[k] : 1.0;
+      v = k >= j ? M[(size_t)j * nc + k] / dn / (sj * sk) : M[(size_t)k * nc + j] / dn / (sk * sj);
+    }
+    H[(size_t)j * ld + k] = v;
+    if (k == j) Hd[j] = v;
+  }
+  if (threadIdx.x == 0) q[j] = M[(size_t)j * nc + p + 1] / dn / sj;
+}
+
+// The coordinate update of newton_cd_solve, for the screen (u_j = 0) and for the sweep: from H_jj, u_j and g_j to the new
+// u_j.  Every caller passes the same words through the same operations, so every lane holds the same bits.
+__device__ __forceinline__ double newton_coord_new_u(double hjj, double uj, double gj, double al, double be, int ridge, bool penalised) {
+  const double z = hjj * uj - gj, denom = penalised ? hjj + al : hjj;
+  double nu = z;
+  if (penalised && !ridge) nu = z > be ? z - be : (z < -be ? z + be : 0.0);
+  // a constant column without an l2 term: H_jj = q_j = 0; every weight underflowed: the intercept stays
+  return denom > 0.0 ? nu / denom : (penalised ? 0.0 : uj);
+}
+
+// One workgroup of kWidth lanes, one inner solve, H (leading dimension ld, a multiple of 16) read from global memory.
+// LDS (newton.hpp: wnewton_state_bytes): g | u | diag H | the list | the list's bits | the compaction's counts.
+//   start    u = u_cur, so g = H (u - u_cur) - q = -q exactly: no pass over H.  The list is {j < p : u_j != 0} and the
+//            intercept coordinate p when it is fitted (unpenalised, without threshold; frozen: never visited).
+//   screen   every j < p outside the list: the coordinate update from u_j = 0; those that would move join.  The list is
+//            compacted again from its bits, kWidth coordinates a step: a ballot per wavefront, the wavefronts' counts
+//            through LDS -- ascending whatever kWidth is, no atomic (cov_wide_path_kernel's)
+//   sweep    newton_cd_solve's coordinate update over the list: every lane computes the scalars from the same LDS words
+//            (uniform branches); a coordinate that stays costs no global read and no barrier; one that moves by d does
+//            g[k] += H[k, j] d for ALL k < P, 16 bytes a lane, so g stays the full gradient and the screen needs no
+//            pass over H.  The sweeps end as newton_cd_solve's do; then the screen runs again, and the solve is done when
+//            it adds nothing.
+// max_sweeps bounds the list sweeps of the solve.  g[k] is updated by one lane from the same words in the same order
+// whatever kWidth is, and the candidate is published by the first wavefront alone: both widths give the same bits.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __restrict__ H, const double* __restrict__ Hd,
+                                                                 const double* __restrict__ q, const double* __restrict__ scale, int p, int ld,
+                                                                 const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                                 int fit_intercept, unsigned max_sweeps, double tol,
+                                                                 double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                                 double* __restrict__ rec) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kWnewtonLdsBytes];
+  constexpr int kWaves = kWidth / 64;
+  static_assert(kWaves * 2 <= kWnewtonScanWords, "the compaction's counts (newton.hpp)");
+  const int lane = threadIdx.x, wave = lane >> 6, wl = lane & 63, P = p + 1;
+  double* g = reinterpret_cast<double*>(lds);
+  double* u = g + P;
+  double* hd = u + P;
+  int32_t* list = reinterpret_cast<int32_t*>(hd + P);
+  uint32_t* bits = reinterpret_cast<uint32_t*>(list + P);
+  int32_t* counts = reinterpret_cast<int32_t*>(bits + (P + 31) / 32);
+  const int slots = (P + 1) / 2;     // a slot: k = 2 s and 2 s + 1 (P odd: the last one's second entry is H's zero pad)
+  for (int k = lane; k < P; k += kWidth) {
+    g[k] = -q[k];
+    u[k] = u_cur[k];
+    hd[k] = Hd[k];
+  }
+  __syncthreads();
+
+  // The list from one flag per coordinate, in ascending order; returns its length.  screen: the flag is "in the list
+  // already, or would move from 0"; else: the start's.  A wavefront reads and rewrites the bits of its own 64 coordinates.
+  auto compact = [&](bool screen) -> int {
+    int length = 0, buf = 0;
+    for (int base = 0; base < P; base += kWidth) {
+      const int j = base + lane, first = base + wave * 64;
+      bool in = false;
+      if (j < p) {
+        if (screen) {
+          in = (bits[j >> 5] >> (j & 31)) & 1u;
+          if (!in) in = newton_coord_new_u(hd[j], 0.0, g[j], al, be, ridge, true) != 0.0;
+        } else {
+          in = u[j] != 0.0;
+        }
+      } else if (j == p) {
+        in = fit_intercept != 0;
+      }
+      const unsigned long long b = __ballot(in);
+      if (wl == 0) counts[buf * kWaves + wave] = __popcll(b);
+      __syncthreads();
+      int before = 0, total = 0;
+      for (int v = 0; v < kWaves; ++v) {
+        const int n_v = counts[buf * kWaves + v];
+        before += v < wave ? n_v : 0;
+        total += n_v;
+      }
+      if (in) list[length + before + __popcll(b & ((1ull << wl) - 1ull))] = j;
+      if (wl == 0 && first < P) {
+        bits[first >> 5] = (uint32_t)b;
+        if (first + 32 < P) bits[(first >> 5) + 1] = (uint32_t)(b >> 32);
+      }
+      length += total;
+      buf ^= 1;        // (the counts of step i are read before the barrier of step i + 1 and rewritten behind it)
+    }
+    __syncthreads();
+    return length;
+  };
+
+  int n_list = compact(false);
+  unsigned sweeps = 0;
+  bool converged = false, negligible = false;
+  for (int screens = 0;; ++screens) {
+    const int n_new = compact(true);
+    if (screens > 0 && n_new == n_list) {        // the list had converged and nothing outside it moves
+      converged = true;
+      break;
+    }
+    n_list = n_new;
+    bool met = false;
+    while (sweeps < max_sweeps && !met) {
+      double max_change = 0.0, max_size = 0.0, max_eta_sq = 0.0;
+      for (int i = 0; i < n_list; ++i) {
+        const int j = list[i];
+        const double uj = u[j], hjj = hd[j];
+        const double nu = newton_coord_new_u(hjj, uj, g[j], al, be, ridge, j < p);
+        const double d = nu - uj;
+        max_change = fmax(max_change, fabs(d));
+        max_size = fmax(max_size, fabs(nu));
+        max_eta_sq = fmax(max_eta_sq, nu * nu * hjj);
+        if (d != 0.0) {
+          __syncthreads();                         // every lane has read u[j] and g[j]
+          if (lane == 0) u[j] = nu;
+          const double* col = H + (size_t)ld * j;
+#pragma unroll 4
+          for (int s = lane; s < slots; s += kWidth) {
+            const int k = 2 * s;
+            const double2 v = *reinterpret_cast<const double2*>(col + k);
+            if (k + 1 < P) {
+              double2 gk = *reinterpret_cast<double2*>(g + k);
+              gk.x = fma(v.x, d, gk.x);
+              gk.y = fma(v.y, d, gk.y);
+              *reinterpret_cast<double2*>(g + k) = gk;
+            } else {
+              g[k] = fma(v.x, d, g[k]);
+            }
+          }
+          __syncthreads();
+        }
+      }
+      ++sweeps;
+      const bool all_zero = max_size == 0.0 && max_change == 0.0;
+      const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+      negligible = max_eta_sq <= kNewtonNegligible * kNewtonNegligible;      // zero to rounding (newton.hpp)
+      met = all_zero || no_change || negligible;
+    }
+    if (!met) break;                               // max_sweeps: the next outer step goes on from here
+  }
+  __syncthreads();
+  if (wave == 0) {
+    publish_candidate(u, u_cur, scale, p, u_cand, a_cand, rec);
+    if (lane == 0) {
+      rec[kRecSweeps] = (double)sweeps;
+      rec[kRecInnerConverged] = converged ? 1.0 : 0.0;
+      rec[kRecNegligible] = negligible ? 1.0 : 0.0;
+    }
+  }
+}
+
+// The wide inner solve's workgroup.  Both instances give the same bits; profiles/wnewton_path.txt has the inner solves'
+// time per 100-lambda path at p = 198, 1000, 2000 and 4000:
+//   lanes      p = 198     1000     2000     4000
+//   256        31.6 ms   279 ms   597 ms   970 ms
+//   1024       41.0 ms   267 ms   288 ms   426 ms
+// A column of 199 doubles is less than one stride of 256 lanes, and twelve more wavefronts only wait at the barriers; at
+// 1000 the two are within 4 %, from 2000 on sixteen wavefronts halve the solve.  So cov_wide_path_kernel's rule
+// (covariance.hip: wcov_path_width) stands here: 256 lanes up to 512 features, 1024 beyond.  That kernel's look-ahead
+// variant is not built: at p = 4000, where it gained a quarter there, the inner solve is 41 % of a fit that the moments
+// and the state pass make 3.8 times slower than auto.
+constexpr int kWnewtonNarrow = 256, kWnewtonWide = 1024;
+constexpr int wnewton_cd_width(int p) { return p <= 512 ? kWnewtonNarrow : kWnewtonWide; }
+static_assert(kTileCols == 16 && kBlock == 256, "wnewton_tile_pairs and kWnewtonPartialBytes (newton.hpp) count 16-column tiles of 256 partial sums");
 
 // ---- cross-validation (newton_cv_run): the kernels above with a job dimension ----
 // A job is one (mix, training set).  x and y hold the rows sorted by group, so the rows of a training set are one range
@@ -655,7 +859,7 @@ __global__ __launch_bounds__(64) void newton_cv_cd_kernel(const CvCmd* __restric
 
 struct Stream {
   hipStream_t st = nullptr;
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // (e[4]: the wide mode's scale kernel)
   double* rec_host = nullptr;          // pinned: the record of a state pass
   DeviceSetup S;                       // sparse x: the sample-major copy (the feature-major one lives in the arena)
   ~Stream() {
@@ -673,6 +877,11 @@ struct NewtonDevice {
   int64_t n = 0, nnz = 0;
   int p = 0, P = 0, nc = 0;
   bool sparse = false, centre = true, timed = false;
+  // the wide mode (wnewton_run; set before setup): H, diag H and q in global memory, the inner solve on `width` lanes,
+  // the row chunks of newton.hpp's wnewton_row_chunks
+  bool wide = false;
+  int width = 0, ld = 0;
+  double *d_H = nullptr, *d_Hd = nullptr, *d_q = nullptr;
   // dense x: the tile pairs and the row chunks (a function of n and p alone)
   int pairs = 0;
   int64_t rows_per_chunk = 0, chunks = 0;
@@ -703,9 +912,11 @@ struct NewtonDevice {
     nnz = sparse ? pb.colptr[p] : 0;
     const int T = (nc + kTileCols - 1) / kTileCols;
     pairs = T * (T + 1) / 2;
-    rows_per_chunk = dense_rows_per_chunk(n, pairs);
+    rows_per_chunk = wide ? ((n + wnewton_row_chunks(n, nc) - 1) / wnewton_row_chunks(n, nc) + kTileRows - 1) / kTileRows * kTileRows
+                          : dense_rows_per_chunk(n, pairs);
     chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
     state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
+    ld = (int)wnewton_leading_dim(P);
 
     const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
     const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P : 0);
@@ -724,6 +935,9 @@ struct NewtonDevice {
     const size_t o_u1 = A.reserve(sizeof(double) * (size_t)P);
     const size_t o_a = A.reserve(sizeof(double) * (size_t)P);
     const size_t o_U = A.reserve(sizeof(double) * (size_t)L * (size_t)P);
+    const size_t o_H = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)P : 0);
+    const size_t o_Hd = A.reserve(wide ? sizeof(double) * (size_t)P : 0);
+    const size_t o_q = A.reserve(wide ? sizeof(double) * (size_t)P : 0);
     SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
     SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
@@ -749,6 +963,9 @@ struct NewtonDevice {
     d_cur = A.at<double>(o_u0);
     d_cand = A.at<double>(o_u1);
     d_U = A.at<double>(o_U);
+    d_H = A.at<double>(o_H);
+    d_Hd = A.at<double>(o_Hd);
+    d_q = A.at<double>(o_q);
     if (sparse) {
       if (nnz > 0) {
         SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
@@ -790,7 +1007,8 @@ struct NewtonDevice {
 
   // publish / blend: d_cand <- d_cur + t (d_cand - d_cur), its state-pass form d_a and its record
   int publish(double t) {
-    hipLaunchKernelGGL(newton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, t, d_cand, d_a, d_rec);
+    if (wide) hipLaunchKernelGGL(newton_wide_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, t, d_cand, d_a, d_rec);
+    else hipLaunchKernelGGL(newton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, t, d_cand, d_a, d_rec);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
   }
@@ -837,6 +1055,16 @@ struct NewtonDevice {
 
   // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
   int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
+    if (wide) {                          // scale (timed: up to the event 4), then the solve on H about d_cur
+      hipLaunchKernelGGL(newton_wide_scale_kernel, dim3((unsigned)P), dim3(kBlock), 0, st, d_M, d_scale, p, ld, (double)n, d_H, d_Hd, d_q);
+      SGD_HIP_TRY(hipGetLastError());
+      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
+      const auto kernel = width == kWnewtonNarrow ? newton_wide_cd_kernel<kWnewtonNarrow> : newton_wide_cd_kernel<kWnewtonWide>;
+      hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, ld, d_cur, al, be, ridge ? 1 : 0,
+                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    }
     hipLaunchKernelGGL(newton_cd_kernel, dim3(1), dim3(64), 0, st, d_M, d_scale, p, (double)n, d_cur, al, be, ridge ? 1 : 0,
                        fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
     SGD_HIP_TRY(hipGetLastError());
@@ -846,12 +1074,18 @@ struct NewtonDevice {
 
 }  // namespace
 
-int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
+namespace {
+
+// newton_run and wnewton_run: one outer loop, one state machine.  wide: NewtonDevice scales the moments into H in global
+// memory and runs newton_wide_cd_kernel<width>; the dense row chunks follow wnewton_row_chunks; the blend has no array of
+// kNewtonMaxFeatures + 1.  Not wide: exactly the launches Newton mode has always made.
+int newton_loop(const NewtonProblem& pb, bool timed, NewtonResult* out, bool wide, int width) {
   const int p = (int)pb.p, P = p + 1, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
-  if (pb.n <= 0 || pb.p <= 0 || pb.p > kNewtonMaxFeatures || L <= 0 || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
+  if (pb.n <= 0 || pb.p <= 0 || pb.p > (wide ? kWnewtonMaxFeatures : kNewtonMaxFeatures) || L <= 0 ||
+      (wide && (sparse || (width != kWnewtonNarrow && width != kWnewtonWide))) || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
       (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
-    set_error("newton_run: invalid problem");
+    set_error("%s: invalid problem", wide ? "wnewton_run" : "newton_run");
     return SGDNET_EINVAL;
   }
   const int32_t* no_rows = nullptr;
@@ -859,12 +1093,14 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
   std::vector<double> start((size_t)P, 0.0);
   start[(size_t)p] = pb.b0;
   NewtonDevice D;
+  D.wide = wide;
+  D.width = width;
   int rc = D.setup(pb, cols, start.data(), start.data(), timed);
   if (rc) return rc;
   hipStream_t st = D.st;
 
   out->passes = out->sweeps = out->halvings = 0.0;
-  out->state_ms = out->moments_ms = out->cd_ms = 0.f;
+  out->state_ms = out->moments_ms = out->cd_ms = out->scale_ms = 0.f;
   const double* rec = D.rec;
   // the path's start: w = 0, b = b0
   rc = D.publish(1.0);
@@ -887,7 +1123,11 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
         float ms = 0.f;
         SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[0], D.sx.e[1]));
         out->moments_ms += ms;
-        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[1], D.sx.e[2]));
+        if (wide) {
+          SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[1], D.sx.e[4]));
+          out->scale_ms += ms;
+        }
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[wide ? 4 : 1], D.sx.e[2]));
         out->cd_ms += ms;
       }
       out->sweeps += rec[kRecSweeps];
@@ -925,6 +1165,14 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) {
   SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), D.d_U, sizeof(double) * (size_t)L * (size_t)P, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) { return newton_loop(pb, timed, out, false, 0); }
+
+int wnewton_run(const NewtonProblem& pb, bool timed, NewtonResult* out, int width) {
+  return newton_loop(pb, timed, out, true, width != 0 ? width : wnewton_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures)));
 }
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is
@@ -1286,3 +1534,4 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
 }  // namespace sgdnet
 
 extern "C" int sgdnet_newton_max_features(void) { return sgdnet::kNewtonMaxFeatures; }
+extern "C" int sgdnet_wnewton_max_features(void) { return sgdnet::kWnewtonMaxFeatures; }

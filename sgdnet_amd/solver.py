@@ -125,6 +125,11 @@ def newton_max_features():
     return int(_lib.load().sgdnet_newton_max_features())
 
 
+def wnewton_max_features():
+    """Largest number of features sgdnet_wnewton() takes (sgdnet_wnewton_max_features of the C ABI)."""
+    return int(_lib.load().sgdnet_wnewton_max_features())
+
+
 def wcovariance_max_features():
     """Largest number of features sgdnet_wcovariance() takes (sgdnet_wcovariance_max_features of the C ABI)."""
     return int(_lib.load().sgdnet_wcovariance_max_features())
