@@ -12,7 +12,7 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Iinclude -I
 # objects are rebuilt when the flags change (e.g. EXTRA_FLAGS=-DSGDNET_PHASE_TIMING experiments)
 if [ ! -f build/.flags ] || [ "$(cat build/.flags)" != "$FLAGS" ]; then rm -f build/*.o; echo "$FLAGS" > build/.flags; fi
 # every source of the library, compiled and linked from this one list
-SOURCES="saga_exact.hip saga_batched.hip batched_dense.hip batched_sweep.hip batched_shards.hip batched_binned.hip batched_plan.cpp r_rng_device.hip setup_device.hip score.hip gradient.hip covariance.hip newton.hip mnewton.hip solver.cpp solver_epoch.cpp solver_rng.cpp solver_shards.cpp phase_report.cpp driver.cpp r_rng.cpp mt_jump.cpp"
+SOURCES="saga_exact.hip saga_batched.hip batched_dense.hip batched_sweep.hip batched_shards.hip batched_binned.hip batched_plan.cpp r_rng_device.hip setup_device.hip score.hip gradient.hip covariance.hip newton.hip mnewton.hip solver.cpp solver_epoch.cpp solver_rng.cpp solver_shards.cpp phase_report.cpp driver.cpp driver_direct.cpp r_rng.cpp mt_jump.cpp"
 # an object is rebuilt when its source or any header ($SRC/*.hpp, include/*.h) is newer
 newest_header=include/sgdnet_hip.h
 for h in "$SRC"/*.hpp include/*.h; do [ "$h" -nt "$newest_header" ] && newest_header=$h; done

@@ -41,9 +41,10 @@
 //              feature: the group lasso with its l2 part, closed form per block (covariance.hpp has the LDS budget).
 //
 //   wide       wcovariance_run (SGDNET_MODE_WCOVARIANCE): beyond 198 features S does not fit one workgroup's LDS.
-//              cov_wide_scale_kernel writes it to global memory as a full symmetric matrix and cov_wide_path_kernel keeps
+//              wide_scale_kernel writes it to global memory as a full symmetric matrix and cov_wide_path_kernel keeps
 //              only vectors and a list of the coordinates that can move in LDS (covariance.hpp has the budget): a
-//              moving coordinate reads its column of S, nothing else is touched.
+//              moving coordinate reads its column of S, nothing else is touched.  The list compaction, the column move
+//              and the scale kernel are wide_cd_device.hpp's, shared with newton.hip; the geometry is wide_layout.hpp's.
 //
 // No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
@@ -54,6 +55,7 @@
 #include "common.hpp"
 #include "covariance.hpp"
 #include "moments_device.hpp"
+#include "wide_cd_device.hpp"
 
 namespace sgdnet {
 namespace {
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void cov_total_kernel(const double* __restr
 }
 
 // blockIdx.x = training set T: group T alone, or (rest) the total less group T.  From the (p + 2) x (p + 2) moments about the
-// common centre a to what cov_path_kernel reads for x[T], y[T] as fit_covariance / prepare_response (driver.cpp) would
+// common centre a to what cov_path_kernel reads for x[T], y[T] as fit_covariance (driver_direct.cpp) / prepare_response (driver.cpp) would
 // prepare them: the cross-products about T's own means t = a + d, the y column divided by sd_T(y), the features' sd over T,
 // n_T, and the penalties of every mix in the units of the preprocessed response.
 //   Mt     G x (p + 1) x (p + 1)      scale  G x p      mean  G x (p + 1): t (0 where the features are not centred), mean_T(y)
@@ -513,22 +515,6 @@ constexpr int mcov_path_width(size_t entries) { return entries <= (size_t)kMcovN
 
 // ---- wide covariance mode (SGDNET_MODE_WCOVARIANCE): S in global memory, only what can move is touched ----
 
-// blockIdx.x = column j of S: S[k + ld j] = M_jk / n / (sd_j sd_k), the arithmetic of cov_path_kernel's prologue, from
-// the upper triangle of the (p + 1) x (p + 1) moment matrix; rows p .. ld - 1 are the zero pad.  Also diag S and c~.
-__global__ __launch_bounds__(kBlock) void cov_wide_scale_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int ld,
-                                                                 double dn, double* __restrict__ S, double* __restrict__ Sd,
-                                                                 double* __restrict__ ct) {
-  const int j = blockIdx.x, P1 = p + 1;
-  const double sj = scale[j];
-  for (int k = threadIdx.x; k < ld; k += kBlock) {
-    double v = 0.0;
-    if (k < p) v = (k >= j ? M[(size_t)j * P1 + k] : M[(size_t)k * P1 + j]) / dn / (sj * scale[k]);
-    S[(size_t)j * ld + k] = v;
-    if (k == j) Sd[j] = v;
-  }
-  if (threadIdx.x == 0) ct[j] = M[(size_t)j * P1 + p] / dn / sj;
-}
-
 // The coordinate update of cov_wide_path_kernel, for the screen (w_j = 0) and for the sweep: from S_jj, w_j and g_j to the
 // new w_j.  Every caller passes the same words through the same operations, so every lane holds the same bits.
 __device__ __forceinline__ double cov_coord_new_w(double sjj, double wj, double gj, double al, double be, int ridge) {
@@ -544,8 +530,7 @@ __device__ __forceinline__ double cov_coord_new_w(double sjj, double wj, double 
 //   rebuild  the list becomes {j : w_j != 0}, ascending; g = sum_{j in list} S[:, j] w_j - c~ afresh (a lane owns two
 //            consecutive k, j ascends: one 16-byte load per column, four columns requested before the first is used)
 //   screen   every j outside the list: the coordinate update from w_j = 0; those that would move join.  The list is
-//            compacted again from its bits, kWidth coordinates a step: a ballot per wavefront, the wavefronts' counts
-//            through LDS -- ascending whatever kWidth is, no atomic
+//            compacted again from its bits (wide_cd_device.hpp: wide_compact)
 //   sweep    cov_path_kernel's cyclic coordinate descent over the list: every lane computes the scalars from the same LDS
 //            words (uniform branches); a coordinate that stays costs no global read and no barrier; one that moves by d
 //            does g[k] += S[k, j] d for ALL k < p (so g stays the full gradient and the screen needs no pass over S),
@@ -561,9 +546,7 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
                                                                 double* __restrict__ W, double* __restrict__ G,
                                                                 int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kCovLdsBytes];
-  constexpr int kWaves = kWidth / 64;
-  static_assert(kWaves * 2 <= kWcovScanWords, "the compaction's counts (covariance.hpp)");
-  const int lane = threadIdx.x, wave = lane >> 6, wl = lane & 63;
+  const int lane = threadIdx.x;
   double* g = reinterpret_cast<double*>(lds);
   double* c = g + p;
   double* w = c + p;
@@ -592,12 +575,11 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
   }
   __syncthreads();
 
-  // The list from one flag per coordinate, in ascending order; returns its length.  screen: the flag is "in the list
-  // already, or would move from 0"; else: w_j != 0.  A wavefront reads and rewrites the bits of its own 64 coordinates.
+  // The list from one flag per coordinate (wide_cd_device.hpp: wide_compact).  screen: the flag is "in the list already,
+  // or would move from 0"; else: w_j != 0.  (One functor with a run-time `screen` and its own j < p, not one per call site:
+  // in this shape the kernel compiles to the instructions it had with its own copy of the compaction.)
   auto compact = [&](bool screen, double al, double be) -> int {
-    int length = 0, buf = 0;
-    for (int base = 0; base < p; base += kWidth) {
-      const int j = base + lane, first = base + wave * 64;
+    return wide_compact<kWidth>(p, list, bits, counts, [&](int j) -> bool {
       bool in = false;
       if (j < p) {
         if (screen) {
@@ -607,25 +589,8 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
           in = w[j] != 0.0;
         }
       }
-      const unsigned long long b = __ballot(in);
-      if (wl == 0) counts[buf * kWaves + wave] = __popcll(b);
-      __syncthreads();
-      int before = 0, total = 0;
-      for (int v = 0; v < kWaves; ++v) {
-        const int n_v = counts[buf * kWaves + v];
-        before += v < wave ? n_v : 0;
-        total += n_v;
-      }
-      if (in) list[length + before + __popcll(b & ((1ull << wl) - 1ull))] = j;
-      if (wl == 0 && first < p) {
-        bits[first >> 5] = (uint32_t)b;
-        if (first + 32 < p) bits[(first >> 5) + 1] = (uint32_t)(b >> 32);
-      }
-      length += total;
-      buf ^= 1;        // (the counts of step i are read before the barrier of step i + 1 and rewritten behind it)
-    }
-    __syncthreads();
-    return length;
+      return in;
+    });
   };
 
   for (int l = 0; l < n_lambda; ++l) {
@@ -717,20 +682,7 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
           } else if (d != 0.0) {
             __syncthreads();                         // every lane has read w[j] and g[j]
             if (lane == 0) w[j] = nw;
-            const double* col = S + (size_t)ld * j;
-#pragma unroll 4
-            for (int s = lane; s < slots; s += kWidth) {
-              const int k = 2 * s;
-              const double2 v = *reinterpret_cast<const double2*>(col + k);
-              if (k + 1 < p) {
-                double2 gk = *reinterpret_cast<double2*>(g + k);
-                gk.x = fma(v.x, d, gk.x);
-                gk.y = fma(v.y, d, gk.y);
-                *reinterpret_cast<double2*>(g + k) = gk;
-              } else {
-                g[k] = fma(v.x, d, g[k]);
-              }
-            }
+            wide_column_move<kWidth>(g, S + (size_t)ld * j, p, d);
             __syncthreads();
           }
         }
@@ -762,11 +714,9 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
 // A column of 198 doubles is less than one stride of 256 lanes, and twelve more wavefronts only wait at the barriers;
 // from 1000 on the sixteen wavefronts win.  Looking ahead costs a scan of the list and a copy of the held registers per
 // move: it loses where a column comes back from L2 at once and wins (4 % at 2000, 25 % at 4000) where a move waits for
-// its column.  So: 256 lanes up to 512 features, 1024 beyond; ahead beyond 1536 (between the two measurements).
-constexpr int kWcovNarrow = 256, kWcovWide = 1024;
-constexpr int wcov_path_width(int p) { return p <= 512 ? kWcovNarrow : kWcovWide; }
+// its column.  So: 256 lanes up to 512 features, 1024 beyond (wide_layout.hpp: wide_cd_width); ahead beyond 1536 (between
+// the two measurements).
 constexpr bool wcov_path_ahead(int p) { return p > 1536; }
-static_assert(kTileCols == 16 && kBlock == 256, "wcov_tile_pairs and kWcovPartialBytes (covariance.hpp) count 16-column tiles of 256 partial sums");
 
 struct Events {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -779,13 +729,13 @@ struct Events {
 };
 
 // covariance_run and wcovariance_run: the same uploads, moments pass and downloads around two path kernels.
-// wide: S goes to global memory (cov_wide_scale_kernel) and cov_wide_path_kernel<width> runs the path; the dense row
-// chunks follow wcov_row_chunks.  Not wide: exactly the launches covariance mode has always made.
+// wide: S goes to global memory (wide_scale_kernel) and cov_wide_path_kernel<width> runs the path; the dense row
+// chunks follow wide_row_chunks.  Not wide: exactly the launches covariance mode has always made.
 int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int width) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, P1 = p + 1, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
-  if (n <= 0 || p <= 0 || pb.p > (wide ? kWcovMaxFeatures : kCovMaxFeatures) || L <= 0 || (wide && width != kWcovNarrow && width != kWcovWide) ||
+  if (n <= 0 || p <= 0 || pb.p > (wide ? kWcovMaxFeatures : kCovMaxFeatures) || L <= 0 || (wide && width != kWideNarrow && width != kWideFull) ||
       (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
     set_error("%s: invalid problem", wide ? "wcovariance_run" : "covariance_run");
     return SGDNET_EINVAL;
@@ -800,8 +750,7 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
 
   // dense x: the tile pairs and the row chunks (a function of n and p alone)
   const int T = (P1 + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t rows_per_chunk = wide ? ((n + wcov_row_chunks(n, p) - 1) / wcov_row_chunks(n, p) + kTileRows - 1) / kTileRows * kTileRows
-                                      : dense_rows_per_chunk(n, pairs);
+  const int64_t rows_per_chunk = wide ? wide_rows_per_chunk(n, P1, kTileRows) : dense_rows_per_chunk(n, pairs);
   const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
 
   Arena A;
@@ -813,7 +762,7 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
   const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
   const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
   const size_t o_M = A.reserve(sizeof(double) * (size_t)P1 * (size_t)P1);
-  const int ld = (int)wcov_leading_dim(p);
+  const int ld = (int)wide_leading_dim(p);
   const size_t o_S = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)p : 0);
   const size_t o_Sd = A.reserve(wide ? sizeof(double) * (size_t)p : 0);
   const size_t o_alpha = A.reserve(sizeof(double) * (size_t)L);
@@ -865,14 +814,14 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
   if (wide) {
-    hipLaunchKernelGGL(cov_wide_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, ld, (double)n,
+    hipLaunchKernelGGL(wide_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, P1, ld, (double)n,
                        A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
     SGD_HIP_TRY(hipGetLastError());
     SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
     static const int ahead = exp_env_int("SGDNET_WCOV_PREFETCH", -1);     // (0 / 1: profiles/wcovariance_path.txt)
     const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
-    const auto kernel = width == kWcovNarrow ? (prefetch ? cov_wide_path_kernel<kWcovNarrow, true> : cov_wide_path_kernel<kWcovNarrow, false>)
-                                             : (prefetch ? cov_wide_path_kernel<kWcovWide, true> : cov_wide_path_kernel<kWcovWide, false>);
+    const auto kernel = width == kWideNarrow ? (prefetch ? cov_wide_path_kernel<kWideNarrow, true> : cov_wide_path_kernel<kWideNarrow, false>)
+                                             : (prefetch ? cov_wide_path_kernel<kWideFull, true> : cov_wide_path_kernel<kWideFull, false>);
     hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c), p, ld,
                        A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
                        A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
@@ -913,7 +862,7 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
 int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) { return cov_run(pb, out, false, 0); }
 
 int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width) {
-  return cov_run(pb, out, true, width != 0 ? width : wcov_path_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)));
+  return cov_run(pb, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)));
 }
 
 

@@ -6,6 +6,9 @@
 
 #include <vector>
 
+#include "direct_problem.hpp"
+#include "wide_layout.hpp"
+
 namespace sgdnet {
 
 // The path kernel (covariance.hip: cov_path_kernel) is ONE workgroup that keeps, in f64, for the whole lambda path
@@ -25,24 +28,8 @@ constexpr int kCovMaxFeatures = cov_max_features();
 static_assert(kCovMaxFeatures == 198, "the LDS budget of the path kernel (see above)");
 static_assert(kCovMaxFeatures >= 64, "include/sgdnet_hip.h promises at least 64 features");
 
-struct CovarianceProblem {
-  int64_t n = 0, p = 0;
-  // x as the fit entry points receive it: one of the two, in host memory
-  const double* x_dense = nullptr;     // column-major n x p
-  const int32_t* colptr = nullptr;     // dgCMatrix slots; row indices ascending within a column
-  const int32_t* rowidx = nullptr;
-  const double* values = nullptr;
+struct CovarianceProblem : DirectProblem {      // max_iter: coordinate sweeps per lambda
   const double* y = nullptr;           // n: the response as the solvers see it (centred and scaled by the driver)
-  bool centre = true;                  // deviations from the column means (false: from 0 -- no intercept, no standardisation)
-  const double* scale = nullptr;       // p: the sd the driver standardises feature j with (1 where it does not)
-  int device = 0;
-  // the path, in the driver's units (regularization_path): l2 strength alpha[l], l1 strength beta[l]
-  int n_lambda = 0;
-  const double* alpha = nullptr;
-  const double* beta = nullptr;
-  bool ridge = false;                  // the ridge functor: no threshold
-  unsigned max_iter = 0;               // coordinate sweeps per lambda
-  double tol = 0.0;
 };
 
 struct CovarianceResult {
@@ -52,7 +39,7 @@ struct CovarianceResult {
   std::vector<int32_t> sweeps;         // n_lambda
   std::vector<int32_t> unconverged;    // n_lambda: all max_iter sweeps ran and tol was not met
   float moments_ms = 0.f, path_ms = 0.f;   // kernel times (SGDNET_TRACE)
-  float scale_ms = 0.f;                    // wcovariance_run only: cov_wide_scale_kernel
+  float scale_ms = 0.f;                    // wcovariance_run only: wide_scale_kernel
 };
 
 // Moments pass + path kernel (covariance.hip).  p <= kCovMaxFeatures is the caller's business (plan_fit).
@@ -61,17 +48,12 @@ int covariance_run(const CovarianceProblem& pb, CovarianceResult* out);
 // ---- wide covariance mode (SGDNET_MODE_WCOVARIANCE): the same path with S in global memory ----
 // cov_wide_path_kernel is ONE workgroup that keeps, for the whole lambda path, in its LDS
 //   the gradient g, c~, the coefficients w and diag S, in f64        4 p doubles
-//   the ascending list of the coordinates that may move, int32        p words
-//   one bit per coordinate: "is in the list" (a coordinate of the
-//   list may come to rest at 0, so w_j != 0 does not say it)          ceil(p / 32) words
-//   the wavefronts' counts of a list compaction step, twice           2 x 16 words
-// and nothing of size p^2: S = C / (n sd sd') is a full symmetric matrix in global memory whose leading dimension is p
-// rounded up to 16 doubles (every column starts on a 128-byte line; the pad is zero), written by cov_wide_scale_kernel.
+//   the list, its bits and the compaction's counts (wide_layout.hpp)  p + ceil(p / 32) + 32 words
+// and S = C / (n sd sd') in global memory, leading dimension wide_leading_dim(p), written by wide_scale_kernel.
 // In bytes: 32 p + 4 p + 4 ceil(p / 32) + 128 <= 163 840:
 //   p = 4531:  163 116 + 568 + 128 = 163 812          p = 4532:  163 152 + 568 + 128 = 163 848
-constexpr int kCovLdsBytes = 160 * 1024;
-constexpr int kWcovScanWords = 2 * 16;
-constexpr int wcov_state_bytes(int p) { return 32 * p + 4 * p + 4 * ((p + 31) / 32) + 4 * kWcovScanWords; }
+constexpr int kCovLdsBytes = kWideLdsBytes;
+constexpr int wcov_state_bytes(int p) { return 32 * p + wide_list_bytes(p); }
 constexpr int wcov_max_features() {
   int p = 1;
   while (wcov_state_bytes(p + 1) <= kCovLdsBytes) ++p;
@@ -80,25 +62,17 @@ constexpr int wcov_max_features() {
 constexpr int kWcovMaxFeatures = wcov_max_features();
 static_assert(kWcovMaxFeatures == 4531, "the LDS budget of the wide path kernel (see above)");
 static_assert(kWcovMaxFeatures >= 4096, "include/sgdnet_hip.h promises at least 4096 features");
-constexpr int64_t wcov_leading_dim(int64_t p) { return (p + 15) / 16 * 16; }
 
-// The dense moments pass of the wide mode: the partial-tile buffer holds chunks x tile pairs x 256 doubles.  Its row
-// chunks are a function of n and p alone: as many as it takes to put 1024 workgroups on the GPU (256 CUs x 4), none
-// shorter than 256 rows, and ONE once the tile pairs alone are that many -- so the buffer is 2 MiB while there are
-// chunks and pairs x 2 KiB beyond: 82.9 MB at the feature limit (284 tiles of 16 columns, 40 470 pairs).
+// The dense moments pass of the wide mode runs over ncols = p + 1 columns (wide_layout.hpp: wide_row_chunks); its
+// partial-tile buffer is 82.9 MB at the feature limit (284 tiles of 16 columns, 40 470 pairs).
 constexpr int64_t kWcovPartialBytes = (int64_t)96 << 20;
-constexpr int64_t wcov_tile_pairs(int64_t p) { return ((p + 1 + 15) / 16) * ((p + 1 + 15) / 16 + 1) / 2; }
-constexpr int64_t wcov_row_chunks(int64_t n, int64_t p) {
-  const int64_t pairs = wcov_tile_pairs(p), cap = pairs >= 1024 ? 1 : 1024 / pairs, by_rows = (n + 255) / 256;
-  return by_rows < 1 ? 1 : (by_rows < cap ? by_rows : cap);
-}
-static_assert(wcov_row_chunks(1 << 30, kWcovMaxFeatures) == 1 && wcov_tile_pairs(kWcovMaxFeatures) * 256 * 8 <= kWcovPartialBytes,
+static_assert(wide_row_chunks(1 << 30, kWcovMaxFeatures + 1) == 1 && wide_tile_pairs(kWcovMaxFeatures + 1) * 256 * 8 <= kWcovPartialBytes,
               "one chunk at the limit");
-static_assert(wcov_row_chunks(1 << 30, 1) * wcov_tile_pairs(1) * 256 * 8 <= kWcovPartialBytes, "1024 workgroups' tiles at most");
+static_assert(wide_row_chunks(1 << 30, 2) * wide_tile_pairs(2) * 256 * 8 <= kWcovPartialBytes, "1024 workgroups' tiles at most");
 
-// Moments pass + cov_wide_scale_kernel + cov_wide_path_kernel (covariance.hip).  p <= kWcovMaxFeatures is the caller's
-// business (plan_fit).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule of covariance.hip
-// (wcov_path_width); both give the same bits.
+// Moments pass + wide_scale_kernel + cov_wide_path_kernel (covariance.hip).  p <= kWcovMaxFeatures is the caller's
+// business (plan_fit).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule of wide_layout.hpp
+// (wide_cd_width); both give the same bits.
 int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width = 0);
 
 // ---- several responses (SGDNET_MODE_MCOVARIANCE): the mgaussian group-lasso path ----
@@ -121,23 +95,9 @@ static_assert(mcov_max_features(10) == 174 && mcov_max_features(16) == 159 && mc
 static_assert(mcov_max_features(64) == 86 && mcov_max_features(95) == 64 && mcov_max_features(96) == 63, "the LDS budget (see above)");
 static_assert(mcov_max_features(0) == 0 && mcov_max_features(6826) == 1 && mcov_max_features(6827) == 0, "where nothing fits");
 
-struct McovarianceProblem {
-  int64_t n = 0, p = 0;
+struct McovarianceProblem : DirectProblem {     // beta: the group threshold; max_iter: block sweeps per lambda
   int K = 0;                           // responses
-  const double* x_dense = nullptr;     // as CovarianceProblem
-  const int32_t* colptr = nullptr;
-  const int32_t* rowidx = nullptr;
-  const double* values = nullptr;
   const double* y = nullptr;           // n x K, column-major: the responses less the null model's intercepts
-  bool centre = true;
-  const double* scale = nullptr;       // p
-  int device = 0;
-  int n_lambda = 0;
-  const double* alpha = nullptr;       // l2 strength per lambda
-  const double* beta = nullptr;        // group threshold per lambda
-  bool ridge = false;
-  unsigned max_iter = 0;               // block sweeps per lambda
-  double tol = 0.0;
 };
 
 struct McovarianceResult {
@@ -197,7 +157,7 @@ struct CovarianceCvResult {
 };
 
 // Group moments + assembly + path kernel over the jobs.  p <= kCovMaxFeatures, the budget above and valid fold ids are
-// the caller's business (driver.cpp: fit_cv_covariance).
+// the caller's business (driver_direct.cpp: fit_cv_covariance).
 int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out);
 
 }  // namespace sgdnet

@@ -10,86 +10,96 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <chrono>
-#include <thread>
-#include <vector>
-
-#include "common.hpp"
-#include "covariance.hpp"
-#include "fit_plan.hpp"
-#include "mnewton.hpp"
-#include "newton.hpp"
-#include "setup_device.hpp"
+#include "driver_parts.hpp"
 
 using namespace sgdnet;
 
-namespace {
+// ---- what driver_direct.cpp uses too (driver_parts.hpp) ----
+namespace sgdnet {
 
-// SGDNET_TRACE=1: wall-clock of the driver's phases on stderr
-struct PhaseTimer {
-  bool on;
-  std::chrono::steady_clock::time_point t0;
-  PhaseTimer() : on(getenv("SGDNET_TRACE") != nullptr), t0(std::chrono::steady_clock::now()) {}
-  void mark(const char* what) {
-    if (!on) return;
-    const auto t1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[sgdnet] %-28s %8.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
-    t0 = t1;
-  }
-};
-
-struct Features {
-  bool sparse = false;
-  int64_t n = 0, p = 0;
-  // feature-major (as passed by R), preprocessed values
-  const int32_t* colptr = nullptr;
-  const int32_t* rowidx = nullptr;
-  std::vector<double> val;      // sparse values (scaled if standardize)
-  std::vector<double> xd;       // dense n x p column-major (standardised if requested)
-  // sample-major
-  std::vector<int64_t> sptr;
-  std::vector<int32_t> sidx;
-  std::vector<double> sval;
-  std::vector<double> xt;       // dense p x n
-  std::vector<double> x_center, x_scale, x_center_scaled;
-  // device-side setup (sparse): the O(nnz) passes run in setup_device.hip and the vectors
-  // above other than x_center / x_scale stay empty
-  DeviceSetup* dev = nullptr;
-  hipStream_t st = nullptr;
-  double dev_max_mean_sq = 0.0;
-  bool dense_dev = false;       // dense x prepared by dense_setup_* (large matrices)
-  // x as it came (covariance and Newton mode take their moments from it): the column-major matrix, or the dgCMatrix values
-  const double* raw_dense = nullptr;
-  const double* raw_values = nullptr;
-};
-
-// math.h:66-79 Mean / :114-130 StandardDeviation (population sd, 0 -> 1)
-// Host-side passes over dense x (R hands over a column-major matrix): per-column work is split
-// over a few threads.  Every column is still reduced by one thread in the reference's order, so
-// the results are bitwise those of the serial loops.
-template <class F>
-void parallel_for(int64_t count, double work, F f) {
-  unsigned T = std::thread::hardware_concurrency();
-  if (T > 16) T = 16;
-  if (work < 4e6 || T < 2 || count < 2) {
-    f((int64_t)0, count);
-    return;
-  }
-  if ((int64_t)T > count) T = (unsigned)count;
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < T; ++t) {
-    const int64_t lo = count * t / T, hi = count * (t + 1) / T;
-    th.emplace_back([=, &f] { f(lo, hi); });
-  }
-  for (auto& x : th) x.join();
+double binomial_link(double ybar) {     // families.h:141-150
+  const double pmin = 1e-9, pmax = 1.0 - pmin;
+  const double z = ybar > pmax ? pmax : (ybar < pmin ? pmin : ybar);
+  return log(z / (1.0 - z));
 }
 
+// class codes are used as array indices (FitNullModel, LambdaMax, the gradient kernels)
+int validate_response(const sgdnet_control* c, const double* y, int64_t n) {
+  if (c->family != SGDNET_BINOMIAL && c->family != SGDNET_MULTINOMIAL) return SGDNET_OK;
+  const double top = c->family == SGDNET_BINOMIAL ? 1.0 : (double)(c->n_classes - 1);
+  for (int64_t i = 0; i < n; ++i)
+    if (!(y[i] >= 0.0 && y[i] <= top && y[i] == floor(y[i]))) {
+      set_error("response[%lld] = %g is not a class code in 0..%d", (long long)i, y[i], (int)top);
+      return SGDNET_EINVAL;
+    }
+  return SGDNET_OK;
+}
+
+// what the device passes index with: checked before anything is uploaded
+int validate_colptr(const sgdnet_csc* x) {
+  if (x->colptr[0] != 0) {
+    set_error("colptr[0] must be 0");
+    return SGDNET_EINVAL;
+  }
+  for (int64_t j = 0; j < x->n_cols; ++j)
+    if (x->colptr[j + 1] < x->colptr[j]) {
+      set_error("colptr is not non-decreasing at column %lld", (long long)j);
+      return SGDNET_EINVAL;
+    }
+  return SGDNET_OK;
+}
+
+int validate_rowidx(const sgdnet_csc* x) {
+  const int64_t nnz = x->colptr[x->n_cols];
+  for (int64_t q = 0; q < nnz; ++q) {
+    const int32_t r = x->rowidx[q];
+    if (r < 0 || r >= x->n_rows) {
+      set_error("row index %d out of range at position %lld", r, (long long)q);
+      return SGDNET_EINVAL;
+    }
+  }
+  return SGDNET_OK;
+}
+
+int check_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error("no HIP device available: the SAGA backend has no CPU fallback");
+    return SGDNET_ENODEVICE;
+  }
+  if (device < 0 || device >= ndev) {
+    set_error("device %d out of range (%d devices)", device, ndev);
+    return SGDNET_EINVAL;
+  }
+  return SGDNET_OK;
+}
+
+void rescale_values(const Features& X, const Response& R, const sgdnet_control* ctl, int li, const double* w, const double* b,
+                    sgdnet_result* out) {
+  const int K = ctl->n_classes;
+  const int64_t p = X.p;
+  double* bo = out->beta + (size_t)li * (size_t)(K * p);
+  double* ao = out->a0 + (size_t)li * (size_t)K;
+  std::vector<double> xbb((size_t)K, 0.0);
+  for (int64_t j = 0; j < p; ++j)
+    for (int k = 0; k < K; ++k) {
+      const double v = w[(size_t)(k + j * K)] * (R.y_scale[(size_t)k] / X.x_scale[(size_t)j]);
+      bo[k + j * K] = v;
+      xbb[(size_t)k] += X.x_center[(size_t)j] * v;
+    }
+  for (int k = 0; k < K; ++k)
+    ao[k] = ctl->intercept != 0 ? b[(size_t)k] * R.y_scale[(size_t)k] + R.y_center[(size_t)k] - xbb[(size_t)k]
+                                : b[(size_t)k];
+}
+
+}  // namespace sgdnet
+
+namespace {
+
+// math.h:66-79 Mean / :114-130 StandardDeviation (population sd, 0 -> 1); the columns over a few threads (parallel_for)
 void col_mean_sd(const double* x, int64_t n, int64_t m, double* mean, double* sd) {
   parallel_for(m, (double)n * (double)m, [&](int64_t j0, int64_t j1) {
   for (int64_t j = j0; j < j1; ++j) {
@@ -158,12 +168,6 @@ double log_sum_exp_host(const double* x, int K) {
   double s = 0.0;
   for (int k = 0; k < K; ++k) s += exp(x[k] - mx);
   return log(s) + mx;
-}
-
-double binomial_link(double ybar) {     // families.h:141-150
-  const double pmin = 1e-9, pmax = 1.0 - pmin;
-  const double z = ybar > pmax ? pmax : (ybar < pmin ? pmin : ybar);
-  return log(z / (1.0 - z));
 }
 
 // Family::FitNullModel (families.h:112-117,190-201,287-298,380-385); yt is Ky x n
@@ -455,32 +459,12 @@ int validate(const sgdnet_control* c, const sgdnet_result* out, int y_cols) {
   return SGDNET_OK;
 }
 
-// class codes are used as array indices (FitNullModel, LambdaMax, the gradient kernels)
-int validate_response(const sgdnet_control* c, const double* y, int64_t n) {
-  if (c->family != SGDNET_BINOMIAL && c->family != SGDNET_MULTINOMIAL) return SGDNET_OK;
-  const double top = c->family == SGDNET_BINOMIAL ? 1.0 : (double)(c->n_classes - 1);
-  for (int64_t i = 0; i < n; ++i)
-    if (!(y[i] >= 0.0 && y[i] <= top && y[i] == floor(y[i]))) {
-      set_error("response[%lld] = %g is not a class code in 0..%d", (long long)i, y[i], (int)top);
-      return SGDNET_EINVAL;
-    }
-  return SGDNET_OK;
-}
-
 // ---- the stages of a fit (fit_common below is their list) ----
 
 using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 struct PathTimes {   // SGDNET_TRACE: where the path's time goes
   double rng = 0.0, run = 0.0, chk = 0.0, dev = 0.0;
-};
-
-struct Response {
-  std::vector<double> y;                   // n x Ky, preprocessed
-  std::vector<double> yt;                  // Ky x n, preprocessed: what the solvers read
-  std::vector<double> y_center, y_scale;
-  std::vector<double> b0;                  // the null model's intercept
-  double null_dev_scaled = 0.0;            // null deviance of the preprocessed response
 };
 
 // the response as the solvers see it; *nulldev = the null deviance of the response as it came
@@ -515,10 +499,6 @@ Response prepare_response(const double* y_in, int64_t n, int Ky, const sgdnet_co
   R.null_dev_scaled = null_deviance(family, K, R.yt.data(), Ky, n, fit_intercept);   // :211
   return R;
 }
-
-struct Path {
-  std::vector<double> lambda, alpha, beta;
-};
 
 // RegularizationPath: utils.h:142-181
 int regularization_path(const sgdnet_control* ctl, const Features& X, const Response& R, int Ky, Path& path) {
@@ -929,26 +909,6 @@ int deviance_all_ranks(Ranks& ranks, double* dev) {
   });
 }
 
-// Rescale (utils.h:352-378): the coefficients of lambda li on the scale of the data as it came
-// w (K x p) and b (K): the coefficients and intercepts of the preprocessed problem
-void rescale_values(const Features& X, const Response& R, const sgdnet_control* ctl, int li, const double* w, const double* b,
-                    sgdnet_result* out) {
-  const int K = ctl->n_classes;
-  const int64_t p = X.p;
-  double* bo = out->beta + (size_t)li * (size_t)(K * p);
-  double* ao = out->a0 + (size_t)li * (size_t)K;
-  std::vector<double> xbb((size_t)K, 0.0);
-  for (int64_t j = 0; j < p; ++j)
-    for (int k = 0; k < K; ++k) {
-      const double v = w[(size_t)(k + j * K)] * (R.y_scale[(size_t)k] / X.x_scale[(size_t)j]);
-      bo[k + j * K] = v;
-      xbb[(size_t)k] += X.x_center[(size_t)j] * v;
-    }
-  for (int k = 0; k < K; ++k)
-    ao[k] = ctl->intercept != 0 ? b[(size_t)k] * R.y_scale[(size_t)k] + R.y_center[(size_t)k] - xbb[(size_t)k]
-                                : b[(size_t)k];
-}
-
 int rescale_into(sgdnet_solver* S, const Features& X, const Response& R, const sgdnet_control* ctl, int li, std::vector<double>& w,
                  std::vector<double>& b, sgdnet_result* out) {
   int rc = sgdnet_solver_get_state(S, 0, w.data());
@@ -956,278 +916,6 @@ int rescale_into(sgdnet_solver* S, const Features& X, const Response& R, const s
   rc = sgdnet_solver_get_state(S, 1, b.data());
   if (rc) return rc;
   rescale_values(X, R, ctl, li, w.data(), b.data(), out);
-  return SGDNET_OK;
-}
-
-// ---- covariance mode (SGDNET_MODE_COVARIANCE, covariance.hip): the stage behind the plan ----
-// The preprocessed problem is the one every mode fits: features (x_j - x_center_j) / x_scale_j (x_center = 0, x_scale = 1
-// without standardize), the response of prepare_response, the penalties of regularization_path.  With an intercept the
-// optimum only sees deviations from the column means, standardised or not; without one the intercept stays at the null
-// model's value and the features are taken as the preprocessing left them: deviations from x_center.
-// SGDNET_MODE_WCOVARIANCE is the same stage around wcovariance_run (S in global memory, any p up to its own limit).
-int fit_covariance(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl,
-                   sgdnet_result* out, PhaseTimer& pt) {
-  const bool wide = plan.mode == SGDNET_MODE_WCOVARIANCE;
-  const int64_t n = X.n, p = X.p;
-  const int L = ctl->n_lambda;
-  CovarianceProblem pb;
-  pb.n = n;
-  pb.p = p;
-  if (X.sparse) {
-    pb.colptr = X.colptr;
-    pb.rowidx = X.rowidx;
-    pb.values = X.raw_values;
-  } else {
-    pb.x_dense = X.raw_dense;
-  }
-  pb.y = R.y.data();
-  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
-  pb.scale = X.x_scale.data();
-  pb.device = plan.rank_dev[0];
-  pb.n_lambda = L;
-  pb.alpha = path.alpha.data();
-  pb.beta = path.beta.data();
-  pb.ridge = plan.penalty == SGDNET_RIDGE;
-  pb.max_iter = ctl->max_iter;
-  pb.tol = ctl->tol;
-  CovarianceResult cr;
-  int rc = wide ? wcovariance_run(pb, &cr, option(kOptWcovarianceWidth)) : covariance_run(pb, &cr);
-  if (rc) return rc;
-  if (pt.on && wide)
-    fprintf(stderr, "[sgdnet]   wcovariance: moments %.3f ms, scale %.3f ms, path kernel %.3f ms\n", cr.moments_ms, cr.scale_ms, cr.path_ms);
-  else if (pt.on)
-    fprintf(stderr, "[sgdnet]   covariance: moments %.3f ms, path kernel %.3f ms\n", cr.moments_ms, cr.path_ms);
-
-  // deviance from the quadratic form: |y~ - X~ w|^2 = y~'y~ - n (2 c~'w - w'S w), and w'S w = w'(g + c~) with the path
-  // kernel's gradient g = S w - c~: the explained part is n sum_j w_j (c~_j - g_j), each term w_j c~_j + alpha w_j^2 +
-  // beta |w_j| at the optimum
-  double yy = 0.0;
-  for (int64_t i = 0; i < n; ++i) yy += R.y[(size_t)i] * R.y[(size_t)i];
-  double n_sweeps = 0.0;
-  for (int li = 0; li < L; ++li) {
-    const double* w = cr.w.data() + (size_t)li * (size_t)p;
-    const double* g = cr.g.data() + (size_t)li * (size_t)p;
-    double explained = 0.0, shift = 0.0;
-    for (int64_t j = 0; j < p; ++j) {
-      explained += w[j] * (cr.c[(size_t)j] - g[j]);
-      shift += (cr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j] * w[j];
-    }
-    const double dev = std::max(0.0, yy - (double)n * explained);
-    // (a constant response has a null deviance of 0 and nothing to explain: the ratio is 0, not 0 / 0)
-    out->dev_ratio[li] = R.null_dev_scaled > 0.0 ? 1.0 - dev / R.null_dev_scaled : 0.0;
-    out->lambda[li] = path.lambda[(size_t)li];
-    out->return_codes[li] = cr.unconverged[(size_t)li] ? 1.0 : 0.0;
-    n_sweeps += (double)cr.sweeps[(size_t)li];
-    // the intercept of the preprocessed problem: the response's mean there (R.b0) less the features' means times w
-    const double b = ctl->intercept != 0 ? R.b0[0] - shift : R.b0[0];
-    rescale_values(X, R, ctl, li, w, &b, out);
-  }
-  out->npasses = n_sweeps;
-  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
-  pt.mark(wide ? "wcovariance (moments + scale + path)" : "covariance (moments + path)");
-  return SGDNET_OK;
-}
-
-// ---- several responses (SGDNET_MODE_MCOVARIANCE, covariance.hip): the stage behind the plan ----
-// The features as fit_covariance takes them; the responses as prepare_response left them (standardised only with
-// standardize_response) less the null model's intercepts R.b0, subtracted here so that the moments pass multiplies
-// deviations.  The intercept of the preprocessed problem stays at R.b0 (less the features' mean shift times w where it
-// is fitted), as it does for one response.
-int fit_mcovariance(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl,
-                    sgdnet_result* out, PhaseTimer& pt) {
-  const int64_t n = X.n, p = X.p;
-  const int L = ctl->n_lambda, K = ctl->n_classes;
-  std::vector<double> yd((size_t)n * (size_t)K);
-  double yy = 0.0;
-  for (int r = 0; r < K; ++r)
-    for (int64_t i = 0; i < n; ++i) {
-      const double d = R.y[(size_t)(i + (int64_t)r * n)] - R.b0[(size_t)r];
-      yd[(size_t)(i + (int64_t)r * n)] = d;
-      yy += d * d;
-    }
-  McovarianceProblem pb;
-  pb.n = n;
-  pb.p = p;
-  pb.K = K;
-  if (X.sparse) {
-    pb.colptr = X.colptr;
-    pb.rowidx = X.rowidx;
-    pb.values = X.raw_values;
-  } else {
-    pb.x_dense = X.raw_dense;
-  }
-  pb.y = yd.data();
-  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
-  pb.scale = X.x_scale.data();
-  pb.device = plan.rank_dev[0];
-  pb.n_lambda = L;
-  pb.alpha = path.alpha.data();
-  pb.beta = path.beta.data();
-  pb.ridge = plan.penalty == SGDNET_RIDGE;
-  pb.max_iter = ctl->max_iter;
-  pb.tol = ctl->tol;
-  static const int width = exp_env_int("SGDNET_MCOV_WIDTH", 0);     // (64 or 256 lanes: profiles/mcovariance_path.txt)
-  McovarianceResult cr;
-  const int rc = mcovariance_run(pb, &cr, width);
-  if (rc) return rc;
-
-  // deviance from the quadratic form, as in fit_covariance: sum_r |y~_r - X~ w_r|^2 = sum_r y~_r'y~_r - n sum_jr w_jr (c~_jr - g_jr)
-  const size_t pK = (size_t)p * (size_t)K;
-  double n_sweeps = 0.0;
-  std::vector<double> b((size_t)K);
-  for (int li = 0; li < L; ++li) {
-    const double* w = cr.w.data() + (size_t)li * pK;
-    const double* g = cr.g.data() + (size_t)li * pK;
-    double explained = 0.0;
-    std::fill(b.begin(), b.end(), 0.0);
-    for (int64_t j = 0; j < p; ++j) {
-      const double shift = (cr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j];
-      for (int r = 0; r < K; ++r) {
-        const size_t e = (size_t)j * (size_t)K + (size_t)r;
-        explained += w[e] * (cr.c[e] - g[e]);
-        b[(size_t)r] += shift * w[e];
-      }
-    }
-    const double dev = std::max(0.0, yy - (double)n * explained);
-    out->dev_ratio[li] = R.null_dev_scaled > 0.0 ? 1.0 - dev / R.null_dev_scaled : 0.0;
-    out->lambda[li] = path.lambda[(size_t)li];
-    out->return_codes[li] = cr.unconverged[(size_t)li] ? 1.0 : 0.0;
-    n_sweeps += (double)cr.sweeps[(size_t)li];
-    for (int r = 0; r < K; ++r) b[(size_t)r] = ctl->intercept != 0 ? R.b0[(size_t)r] - b[(size_t)r] : R.b0[(size_t)r];
-    rescale_values(X, R, ctl, li, w, b.data(), out);
-  }
-  if (pt.on)
-    fprintf(stderr, "[sgdnet]   mcovariance: moments %.3f ms, path kernel %.3f ms, %.0f sweeps\n", cr.moments_ms, cr.path_ms, n_sweeps);
-  out->npasses = n_sweeps;
-  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
-  pt.mark("mcovariance (moments + path)");
-  return SGDNET_OK;
-}
-
-// ---- Newton mode (SGDNET_MODE_NEWTON, newton.hip): the stage behind the plan ----
-// The same preprocessed problem as above, for a binomial response: the features centred where fit_covariance centres
-// them, the class codes as they came, the intercept an unpenalised coordinate that starts at the null model's value
-// (and stays there without an intercept).
-// SGDNET_MODE_WNEWTON is the same stage around wnewton_run (H in global memory, any p up to its own limit; sparse x came
-// here as its dense copy: fit_sparse_impl).
-int fit_newton(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl, sgdnet_result* out,
-               PhaseTimer& pt) {
-  const bool wide = plan.mode == SGDNET_MODE_WNEWTON;
-  const int64_t n = X.n, p = X.p;
-  const int L = ctl->n_lambda;
-  NewtonProblem pb;
-  pb.n = n;
-  pb.p = p;
-  if (X.sparse) {
-    pb.colptr = X.colptr;
-    pb.rowidx = X.rowidx;
-    pb.values = X.raw_values;
-  } else {
-    pb.x_dense = X.raw_dense;
-  }
-  pb.y = R.y.data();
-  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
-  pb.scale = X.x_scale.data();
-  pb.fit_intercept = ctl->intercept != 0;
-  pb.b0 = R.b0[0];
-  pb.device = plan.rank_dev[0];
-  pb.n_lambda = L;
-  pb.alpha = path.alpha.data();
-  pb.beta = path.beta.data();
-  pb.ridge = plan.penalty == SGDNET_RIDGE;
-  pb.max_iter = ctl->max_iter;
-  pb.tol = ctl->tol;
-  NewtonResult nr;
-  const int rc = wide ? wnewton_run(pb, pt.on, &nr, option(kOptWnewtonWidth)) : newton_run(pb, pt.on, &nr);
-  if (rc) return rc;
-  double n_steps = 0.0;
-  for (int li = 0; li < L; ++li) {
-    const double* u = nr.u.data() + (size_t)li * (size_t)(p + 1);
-    double shift = 0.0;
-    for (int64_t j = 0; j < p; ++j) shift += (nr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j] * u[j];
-    // Family::Loss summed over the samples, doubled (families.h; saga_loss_kernel): the state pass left its mean
-    out->dev_ratio[li] = 1.0 - 2.0 * (double)n * nr.loss[(size_t)li] / R.null_dev_scaled;
-    out->lambda[li] = path.lambda[(size_t)li];
-    out->return_codes[li] = nr.unconverged[(size_t)li] ? 1.0 : 0.0;
-    n_steps += (double)nr.steps[(size_t)li];
-    // the intercept of the preprocessed problem: the one at the centres less the centres' distance from x_center times w
-    const double b = ctl->intercept != 0 ? u[p] - shift : R.b0[0];
-    rescale_values(X, R, ctl, li, u, &b, out);
-  }
-  if (pt.on && wide)
-    fprintf(stderr, "[sgdnet]   wnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
-            "scale %.3f ms, inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.scale_ms, nr.cd_ms);
-  else if (pt.on)
-    fprintf(stderr, "[sgdnet]   newton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
-            "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);
-  out->npasses = nr.passes;
-  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
-  pt.mark(wide ? "wnewton (state + moments + scale + cd)" : "newton (state + moments + cd)");
-  return SGDNET_OK;
-}
-
-// ---- multinomial Newton mode (SGDNET_MODE_MNEWTON, mnewton.hip): the stage behind the plan ----
-// The preprocessed problem of fit_newton with K classes: the class codes as they came, per class an unpenalised intercept
-// that starts at the null model's value (and stays there without an intercept).  The loss does not see a shift common
-// to all intercepts: they are returned with their class mean removed (kkt.py removes the class mean of G0 likewise).
-int fit_mnewton(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl, sgdnet_result* out,
-                PhaseTimer& pt) {
-  const int64_t n = X.n, p = X.p;
-  const int L = ctl->n_lambda, K = ctl->n_classes;
-  MNewtonProblem pb;
-  pb.n = n;
-  pb.p = p;
-  pb.K = K;
-  pb.x_dense = X.raw_dense;            // (sparse x came here as its dense copy: fit_sparse_impl)
-  pb.y = R.y.data();
-  pb.centre = ctl->intercept != 0 || ctl->standardize != 0;
-  pb.scale = X.x_scale.data();
-  pb.fit_intercept = ctl->intercept != 0;
-  pb.b0 = R.b0.data();
-  pb.device = plan.rank_dev[0];
-  pb.n_lambda = L;
-  pb.alpha = path.alpha.data();
-  pb.beta = path.beta.data();
-  pb.ridge = plan.penalty == SGDNET_RIDGE;
-  pb.max_iter = ctl->max_iter;
-  pb.tol = ctl->tol;
-  static const int width = exp_env_int("SGDNET_MNEWTON_WIDTH", 0);  // (64 or 256 lanes: profiles/mnewton_path.txt)
-  MNewtonResult nr;
-  const int rc = mnewton_run(pb, pt.on, &nr, width);
-  if (rc) return rc;
-  const int64_t P = p + 1;
-  double n_steps = 0.0;
-  std::vector<double> w((size_t)K * (size_t)p), b((size_t)K);
-  for (int li = 0; li < L; ++li) {
-    const double* u = nr.u.data() + (size_t)li * (size_t)(K * P);
-    double b_mean = 0.0;
-    for (int k = 0; k < K; ++k) {
-      const double* uk = u + (size_t)k * (size_t)P;
-      double shift = 0.0;
-      for (int64_t j = 0; j < p; ++j) {
-        w[(size_t)(k + j * K)] = uk[j];
-        shift += (nr.mean[(size_t)j] - X.x_center[(size_t)j]) / X.x_scale[(size_t)j] * uk[j];
-      }
-      // the intercept of the preprocessed problem: the one at the centres less the centres' distance from x_center times w
-      b[(size_t)k] = ctl->intercept != 0 ? uk[p] - shift : R.b0[(size_t)k];
-      b_mean += b[(size_t)k];
-    }
-    b_mean /= (double)K;
-    if (ctl->intercept != 0)
-      for (int k = 0; k < K; ++k) b[(size_t)k] -= b_mean;
-    // Family::Loss summed over the samples, doubled (families.h; saga_loss_kernel): the state pass left its mean
-    out->dev_ratio[li] = 1.0 - 2.0 * (double)n * nr.loss[(size_t)li] / R.null_dev_scaled;
-    out->lambda[li] = path.lambda[(size_t)li];
-    out->return_codes[li] = nr.unconverged[(size_t)li] ? 1.0 : 0.0;
-    n_steps += (double)nr.steps[(size_t)li];
-    rescale_values(X, R, ctl, li, w.data(), b.data(), out);
-  }
-  if (pt.on)
-    fprintf(stderr, "[sgdnet]   mnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
-            "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);
-  out->npasses = nr.passes;
-  out->draws_used = 0;                 // no sample is drawn: control.rng_state stays as it came
-  pt.mark("mnewton (state + moments + cd)");
   return SGDNET_OK;
 }
 
@@ -1251,8 +939,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   Path path;
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
-  if (ctl->mode == SGDNET_MODE_COVARIANCE || ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_MCOVARIANCE ||
-      ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WCOVARIANCE || ctl->mode == SGDNET_MODE_WNEWTON) {   // plan_fit says whether they may run; they need none of the SAGA setup below
+  if (is_direct_mode(ctl->mode)) {     // plan_fit says whether it may run; it needs none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1263,10 +950,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
       set_error("%s", plan.error.c_str());
       return plan.rc;
     }
-    if (ctl->mode == SGDNET_MODE_MCOVARIANCE) return fit_mcovariance(X, R, path, plan, ctl, out, pt);
-    if (ctl->mode == SGDNET_MODE_MNEWTON) return fit_mnewton(X, R, path, plan, ctl, out, pt);
-    return ctl->mode == SGDNET_MODE_NEWTON || ctl->mode == SGDNET_MODE_WNEWTON ? fit_newton(X, R, path, plan, ctl, out, pt)
-                                                                             : fit_covariance(X, R, path, plan, ctl, out, pt);
+    return fit_direct(X, R, path, plan, ctl, out, pt);       // driver_direct.cpp
   }
   double norm_max = 0.0;
   rc = row_norm_max(X, ctl, R, Ky, trace, &norm_max);
@@ -1404,15 +1088,8 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
 // Runs body(X) with x's device setup and its stream in place: X.dev and X.st are set for the call and gone after it
 template <class F>
 int with_device_setup(const sgdnet_control* ctl, Features& X, F body) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: the SAGA backend has no CPU fallback");
-    return SGDNET_ENODEVICE;
-  }
-  if (ctl->device < 0 || ctl->device >= ndev) {
-    set_error("device %d out of range (%d devices)", ctl->device, ndev);
-    return SGDNET_EINVAL;
-  }
+  const int rc_dev = check_device(ctl->device);
+  if (rc_dev) return rc_dev;
   SGD_HIP_TRY(hipSetDevice(ctl->device));
   DeviceSetup dev;
   hipStream_t st = nullptr;
@@ -1423,32 +1100,6 @@ int with_device_setup(const sgdnet_control* ctl, Features& X, F body) {
   dev.release();
   (void)hipStreamDestroy(st);
   return rc;
-}
-
-// what the device passes index with: checked before anything is uploaded
-int validate_colptr(const sgdnet_csc* x) {
-  if (x->colptr[0] != 0) {
-    set_error("colptr[0] must be 0");
-    return SGDNET_EINVAL;
-  }
-  for (int64_t j = 0; j < x->n_cols; ++j)
-    if (x->colptr[j + 1] < x->colptr[j]) {
-      set_error("colptr is not non-decreasing at column %lld", (long long)j);
-      return SGDNET_EINVAL;
-    }
-  return SGDNET_OK;
-}
-
-int validate_rowidx(const sgdnet_csc* x) {
-  const int64_t nnz = x->colptr[x->n_cols];
-  for (int64_t q = 0; q < nnz; ++q) {
-    const int32_t r = x->rowidx[q];
-    if (r < 0 || r >= x->n_rows) {
-      set_error("row index %d out of range at position %lld", r, (long long)q);
-      return SGDNET_EINVAL;
-    }
-  }
-  return SGDNET_OK;
 }
 
 int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y_cols, const sgdnet_control* ctl, sgdnet_result* out,
@@ -1570,8 +1221,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     col_mean_sd(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
-  if (ctl->mode != SGDNET_MODE_COVARIANCE && ctl->mode != SGDNET_MODE_NEWTON && ctl->mode != SGDNET_MODE_MCOVARIANCE &&
-      ctl->mode != SGDNET_MODE_MNEWTON && ctl->mode != SGDNET_MODE_WCOVARIANCE && ctl->mode != SGDNET_MODE_WNEWTON) {   // (those modes read x column-major, as it came)
+  if (!is_direct_mode(ctl->mode)) {    // (the direct modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }
@@ -1595,498 +1245,9 @@ int with_exact_fallback(const sgdnet_control* ctl, F fit) {
 }
 
 
-// ---- cross-validation in covariance mode (covariance.hip: covariance_cv_run): the stage behind sgdnet_cv_covariance_* ----
-// Every job (mix, training set T) is fit_covariance on x[T], y[T] by definition: the response centred and scaled by its
-// moments over T (prepare_response), the features centred (and scaled) by theirs, the penalties of regularization_path
-// in the units of that response.  The device assembles all of it from the group moments; what is left for the host is
-// the way back to the scale of the data (rescale_values) and the deviance from the quadratic form, per job.
-int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                      int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_cov_result* out) {
-  const int64_t n = pb.n, p = pb.p;
-  if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !pb.y ||
-      !fold || !alphas || !lambdas) {
-    set_error("sgdnet_cv_covariance: null pointer");
-    return SGDNET_EINVAL;
-  }
-  if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
-      (train_on_rest && n_groups < 2)) {
-    set_error("sgdnet_cv_covariance: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
-    return SGDNET_EINVAL;
-  }
-  const int L = ctl->n_lambda;
-  const char* what = nullptr;
-  if (ctl->family != SGDNET_GAUSSIAN) what = "family = gaussian";
-  else if (p > kCovMaxFeatures) what = "no more features than sgdnet_covariance_max_features()";
-  else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-  else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
-  if (what) {
-    set_error("mode = covariance needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)p,
-              kCovMaxFeatures, ctl->n_gpus, ctl->debug);
-    return SGDNET_EUNSUPPORTED;
-  }
-  const size_t moment_bytes = (size_t)n_groups * (size_t)(p + 2) * (size_t)(p + 2) * sizeof(double);
-  if (moment_bytes > kCovGroupMomentBytes) {
-    set_error("mode = covariance needs the group moments within %zu bytes: %d groups x (%lld + 2)^2 doubles are %zu bytes",
-              kCovGroupMomentBytes, n_groups, (long long)p, moment_bytes);
-    return SGDNET_EUNSUPPORTED;
-  }
-  std::vector<int64_t> count((size_t)n_groups, 0);
-  for (int64_t i = 0; i < n; ++i) {
-    if (fold[i] < 0 || fold[i] >= n_groups) {
-      set_error("fold[%lld] = %d is not a group id in 0..%d", (long long)i, fold[i], n_groups - 1);
-      return SGDNET_EINVAL;
-    }
-    ++count[(size_t)fold[i]];
-  }
-  for (int g = 0; g < n_groups; ++g)
-    if (count[(size_t)g] == 0) {
-      set_error("group %d of %d is empty", g, n_groups);
-      return SGDNET_EINVAL;
-    }
-  for (int a = 0; a < n_alpha; ++a) {
-    if (!(alphas[a] >= 0.0 && alphas[a] <= 1.0)) {
-      set_error("alphas[%d] = %g is not an elastic-net mix in [0, 1]", a, alphas[a]);
-      return SGDNET_EINVAL;
-    }
-    for (int l = 0; l < L; ++l)
-      if (!(lambdas[(size_t)a * L + l] >= 0.0)) {
-        set_error("lambdas[%d][%d] = %g is negative", a, l, lambdas[(size_t)a * L + l]);
-        return SGDNET_EINVAL;
-      }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: the SAGA backend has no CPU fallback");
-    return SGDNET_ENODEVICE;
-  }
-  if (ctl->device < 0 || ctl->device >= ndev) {
-    set_error("device %d out of range (%d devices)", ctl->device, ndev);
-    return SGDNET_EINVAL;
-  }
-  PhaseTimer pt;
-  const bool intercept = ctl->intercept != 0;
-  pb.fold = fold;
-  pb.n_groups = n_groups;
-  pb.train_on_rest = train_on_rest != 0;
-  pb.centre = intercept || ctl->standardize != 0;
-  pb.standardize = ctl->standardize != 0;
-  pb.device = ctl->device;
-  pb.n_mix = n_alpha;
-  pb.n_lambda = L;
-  pb.mix = alphas;
-  pb.lambda = lambdas;
-  pb.max_iter = ctl->max_iter;
-  pb.tol = ctl->tol;
-  CovarianceCvResult cr;
-  const int rc = covariance_cv_run(pb, &cr);
-  if (rc) return rc;
-  if (pt.on)
-    fprintf(stderr, "[sgdnet]   cv covariance: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", cr.moments_ms,
-            cr.assemble_ms, n_alpha * n_groups, cr.path_ms);
-
-  const size_t P = (size_t)p, P1 = P + 1;
-  for (int a = 0; a < n_alpha; ++a)
-    for (int t = 0; t < n_groups; ++t) {
-      const size_t job = (size_t)a * (size_t)n_groups + (size_t)t;
-      const double nT = cr.n_train[(size_t)t], ys = cr.y_scale[(size_t)t], yy = cr.yy[(size_t)t];
-      const double* mean = cr.mean.data() + (size_t)t * P1;
-      const double* scale = cr.scale.data() + (size_t)t * P;
-      const double* c = cr.c.data() + job * P;
-      double n_sweeps = 0.0;
-      for (int li = 0; li < L; ++li) {
-        const size_t at = job * (size_t)L + (size_t)li;
-        const double* w = cr.w.data() + at * P;
-        const double* g = cr.g.data() + at * P;
-        double* bo = out->beta + at * P;
-        // fit_covariance: the explained part of the deviance is n sum_j w_j (c~_j - g_j); the intercept is the response's
-        // mean over T less the features' means times the coefficients, on the scale of the data
-        double explained = 0.0, xbb = 0.0;
-        for (size_t j = 0; j < P; ++j) {
-          explained += w[j] * (c[j] - g[j]);
-          bo[j] = w[j] * (ys / scale[j]);
-          xbb += mean[j] * bo[j];
-        }
-        const double dev = std::max(0.0, yy - nT * explained);
-        out->dev_ratio[at] = yy > 0.0 ? 1.0 - dev / yy : 0.0;
-        out->a0[at] = intercept ? mean[P] - xbb : 0.0;
-        out->return_codes[at] = cr.unconverged[at] ? 1.0 : 0.0;
-        n_sweeps += (double)cr.sweeps[at];
-      }
-      out->nulldev[job] = yy * ys * ys;
-      out->npasses[job] = n_sweeps;
-    }
-  pt.mark("cv covariance (all folds)");
-  return SGDNET_OK;
-}
-
-// ---- cross-validation in Newton mode (newton.hip: newton_cv_run): the stage behind sgdnet_cv_newton_* ----
-// Every job (mix, training set T) is fit_newton on x[T], y[T] by definition.  The rows are stably sorted by group here,
-// once, so that T is a range of rows or the complement of one; what fit_newton takes from the preprocessing of x[T],
-// y[T] -- x_center and x_scale over T, the null model's intercept, the null deviance, regularization_path's penalties
-// for the user's lambdas -- is formed here per training set, the features' moments pooled from per-group sums of
-// deviations about the whole-data column means (formed before anything is squared: DESIGN.md 4.6).
-struct CvNewtonMatrix {
-  int64_t n = 0, p = 0;
-  const double* dense = nullptr;
-  const int32_t* colptr = nullptr;
-  const int32_t* rowidx = nullptr;
-  const double* values = nullptr;
-};
-
-int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                  int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_newton_result* out) {
-  const int64_t n = X.n, p = X.p;
-  if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !out->steps ||
-      !out->halvings || !y || !fold || !alphas || !lambdas) {
-    set_error("sgdnet_cv_newton: null pointer");
-    return SGDNET_EINVAL;
-  }
-  if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
-      (train_on_rest && n_groups < 2)) {
-    set_error("sgdnet_cv_newton: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
-    return SGDNET_EINVAL;
-  }
-  const int L = ctl->n_lambda, G = n_groups;
-  const bool sparse = X.dense == nullptr, rest = train_on_rest != 0;
-  const char* what = nullptr;
-  if (ctl->family != SGDNET_BINOMIAL) what = "family = binomial";
-  else if (p > kNewtonMaxFeatures) what = "no more features than sgdnet_newton_max_features()";
-  else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-  else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
-  if (what) {
-    set_error("mode = newton needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)p,
-              kNewtonMaxFeatures, ctl->n_gpus, ctl->debug);
-    return SGDNET_EUNSUPPORTED;
-  }
-  int rc = validate_response(ctl, y, n);
-  if (rc) return rc;
-  std::vector<int64_t> start((size_t)G + 1, 0);
-  for (int64_t i = 0; i < n; ++i) {
-    if (fold[i] < 0 || fold[i] >= G) {
-      set_error("fold[%lld] = %d is not a group id in 0..%d", (long long)i, fold[i], G - 1);
-      return SGDNET_EINVAL;
-    }
-    ++start[(size_t)fold[i] + 1];
-  }
-  for (int g = 0; g < G; ++g) {
-    if (start[(size_t)g + 1] == 0) {
-      set_error("group %d of %d is empty", g, G);
-      return SGDNET_EINVAL;
-    }
-    start[(size_t)g + 1] += start[(size_t)g];
-  }
-  for (int a = 0; a < n_alpha; ++a) {
-    if (!(alphas[a] >= 0.0 && alphas[a] <= 1.0)) {
-      set_error("alphas[%d] = %g is not an elastic-net mix in [0, 1]", a, alphas[a]);
-      return SGDNET_EINVAL;
-    }
-    for (int l = 0; l < L; ++l)
-      if (!(lambdas[(size_t)a * L + l] >= 0.0)) {
-        set_error("lambdas[%d][%d] = %g is negative", a, l, lambdas[(size_t)a * L + l]);
-        return SGDNET_EINVAL;
-      }
-  }
-  // the rows stably sorted by group: row i goes to position to[i]
-  std::vector<int64_t> to((size_t)n);
-  {
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) to[(size_t)i] = fill[(size_t)fold[i]]++;
-  }
-  std::vector<double> ys((size_t)n);
-  for (int64_t i = 0; i < n; ++i) ys[(size_t)to[(size_t)i]] = y[i];
-  // the response of every training set: both classes, the null model and its deviance (fit_null_model, null_deviance)
-  const bool intercept = ctl->intercept != 0;
-  std::vector<int64_t> n_t((size_t)G);
-  std::vector<double> b0((size_t)G), nulldev((size_t)G);
-  {
-    double ones_all = 0.0;
-    std::vector<double> ones((size_t)G, 0.0);
-    for (int g = 0; g < G; ++g) {
-      for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) ones[(size_t)g] += ys[(size_t)i];
-      ones_all += ones[(size_t)g];
-    }
-    for (int g = 0; g < G; ++g) {
-      const int64_t own = start[(size_t)g + 1] - start[(size_t)g];
-      n_t[(size_t)g] = rest ? n - own : own;
-      const double k = rest ? ones_all - ones[(size_t)g] : ones[(size_t)g];
-      if (k <= 0.0 || k >= (double)n_t[(size_t)g]) {
-        set_error("the training set of group %d of %d holds one class only (%lld rows, %lld of class 1)", g, G, (long long)n_t[(size_t)g],
-                  (long long)k);
-        return SGDNET_EINVAL;
-      }
-      b0[(size_t)g] = intercept ? binomial_link(k / (double)n_t[(size_t)g]) : 0.0;
-      // sum over T of log(1 + e^b0) - y b0, its equal terms counted instead of added one by one
-      const double lp = b0[(size_t)g];
-      nulldev[(size_t)g] = 2.0 * ((double)n_t[(size_t)g] * log(1.0 + exp(lp)) - k * lp);
-    }
-  }
-  if ((int64_t)n_alpha * G > kNewtonCvMaxJobs) {
-    set_error("mode = newton needs no more than %lld jobs in one cross-validation call: %d mixes x %d groups", (long long)kNewtonCvMaxJobs,
-              n_alpha, G);
-    return SGDNET_EUNSUPPORTED;
-  }
-  const size_t workspace = newton_cv_workspace_bytes(n, p, sparse, n_t.data(), G, n_alpha);
-  if (workspace > kNewtonCvWorkspaceBytes) {
-    set_error("mode = newton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of (2 x %lld rows + (%lld + 2)^2 moments%s) "
-              "doubles are %zu bytes", kNewtonCvWorkspaceBytes, n_alpha, G, (long long)n, (long long)p, sparse ? "" : " + row-chunk partials",
-              workspace);
-    return SGDNET_EUNSUPPORTED;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: the SAGA backend has no CPU fallback");
-    return SGDNET_ENODEVICE;
-  }
-  if (ctl->device < 0 || ctl->device >= ndev) {
-    set_error("device %d out of range (%d devices)", ctl->device, ndev);
-    return SGDNET_EINVAL;
-  }
-  PhaseTimer pt;
-
-  // x with its rows sorted, and per group and column the sums of d = x - a and of d^2 about the whole-data mean a
-  const size_t P = (size_t)p;
-  std::vector<double> xs, abar(P, 0.0), s1((size_t)G * P, 0.0), s2((size_t)G * P, 0.0);
-  std::vector<int32_t> rows, cut;
-  if (sparse) {
-    const int64_t nnz = X.colptr[p];
-    xs.resize((size_t)nnz);
-    rows.resize((size_t)nnz);
-    cut.resize(P * ((size_t)G + 1));
-    std::vector<int64_t> at((size_t)G + 1);
-    for (int64_t j = 0; j < p; ++j) {
-      const int64_t q0 = X.colptr[j], q1 = X.colptr[j + 1];
-      double sum = 0.0;
-      for (int64_t q = q0; q < q1; ++q) sum += X.values[q];
-      const double a = abar[(size_t)j] = sum / (double)n;
-      // a counting pass: the entries of a group keep their order, so the sorted rows ascend within the column
-      std::fill(at.begin(), at.end(), 0);
-      for (int64_t q = q0; q < q1; ++q) ++at[(size_t)fold[X.rowidx[q]] + 1];
-      at[0] = q0;
-      for (int g = 0; g < G; ++g) at[(size_t)g + 1] += at[(size_t)g];
-      int32_t* c = cut.data() + (size_t)j * ((size_t)G + 1);
-      for (int g = 0; g <= G; ++g) c[g] = (int32_t)at[(size_t)g];
-      for (int g = 0; g < G; ++g) {     // the rows of the group that store nothing: d = -a
-        const double zeros = (double)((start[(size_t)g + 1] - start[(size_t)g]) - (at[(size_t)g + 1] - at[(size_t)g]));
-        s1[(size_t)g * P + (size_t)j] = zeros * -a;
-        s2[(size_t)g * P + (size_t)j] = zeros * (a * a);
-      }
-      for (int64_t q = q0; q < q1; ++q) {
-        const int32_t r = X.rowidx[q];
-        const int g = fold[r];
-        const int64_t dst = at[(size_t)g]++;
-        rows[(size_t)dst] = (int32_t)to[(size_t)r];
-        xs[(size_t)dst] = X.values[q];
-        const double d = X.values[q] - a;
-        s1[(size_t)g * P + (size_t)j] += d;
-        s2[(size_t)g * P + (size_t)j] += d * d;
-      }
-      // (the pair kernel looks rows up by binary search: a column that came with its rows out of order is put in order)
-      bool ascending = true;
-      for (int64_t q = q0 + 1; q < q1 && ascending; ++q) ascending = rows[(size_t)q] > rows[(size_t)q - 1];
-      if (!ascending) {
-        std::vector<std::pair<int32_t, double>> e((size_t)(q1 - q0));
-        for (int64_t q = q0; q < q1; ++q) e[(size_t)(q - q0)] = {rows[(size_t)q], xs[(size_t)q]};
-        std::stable_sort(e.begin(), e.end(), [](const std::pair<int32_t, double>& l, const std::pair<int32_t, double>& r) { return l.first < r.first; });
-        for (int64_t q = q0; q < q1; ++q) {
-          rows[(size_t)q] = e[(size_t)(q - q0)].first;
-          xs[(size_t)q] = e[(size_t)(q - q0)].second;
-        }
-      }
-    }
-  } else {
-    xs.resize((size_t)n * P);
-    parallel_for(p, (double)n * (double)p, [&](int64_t j0, int64_t j1) {
-      for (int64_t j = j0; j < j1; ++j) {
-        const double* col = X.dense + j * n;
-        double* dst = xs.data() + j * n;
-        double sum = 0.0;
-        for (int64_t i = 0; i < n; ++i) {
-          dst[to[(size_t)i]] = col[i];
-          sum += col[i];
-        }
-        const double a = abar[(size_t)j] = sum / (double)n;
-        for (int g = 0; g < G; ++g) {
-          double t1 = 0.0, t2 = 0.0;
-          for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) {
-            const double d = dst[i] - a;
-            t1 += d;
-            t2 += d * d;
-          }
-          s1[(size_t)g * P + (size_t)j] = t1;
-          s2[(size_t)g * P + (size_t)j] = t2;
-        }
-      }
-    });
-  }
-  // pooled per training set (the group's own sums, or the total -- added in group order -- less them) and moved to the
-  // set's own mean: mean_T = a + S1 / n_T, var_T = S2 / n_T - (S1 / n_T)^2
-  const bool centre = intercept || ctl->standardize != 0;
-  std::vector<double> mean((size_t)G * P, 0.0), scale((size_t)G * P, 1.0);
-  for (size_t j = 0; j < P; ++j) {
-    const double a = abar[j];
-    double t1 = 0.0, t2 = 0.0;
-    for (int g = 0; g < G; ++g) {
-      t1 += s1[(size_t)g * P + j];
-      t2 += s2[(size_t)g * P + j];
-    }
-    for (int g = 0; g < G; ++g) {
-      const double nT = (double)n_t[(size_t)g];
-      const double d = (rest ? t1 - s1[(size_t)g * P + j] : s1[(size_t)g * P + j]) / nT;
-      const double var = (rest ? t2 - s2[(size_t)g * P + j] : s2[(size_t)g * P + j]) / nT - d * d;
-      if (centre) mean[(size_t)g * P + j] = a + d;
-      if (ctl->standardize) scale[(size_t)g * P + j] = var > 0.0 ? sqrt(var) : 1.0;
-    }
-  }
-  pt.mark("cv newton: rows sorted, moments");
-
-  // regularization_path for user lambdas and a binomial response (its y_scale is 1)
-  std::vector<double> l2((size_t)n_alpha * (size_t)L), l1(l2.size());
-  std::vector<uint8_t> ridge((size_t)n_alpha);
-  for (int a = 0; a < n_alpha; ++a) {
-    ridge[(size_t)a] = alphas[a] == 0.0;
-    for (int l = 0; l < L; ++l) {
-      l2[(size_t)a * L + l] = (1.0 - alphas[a]) * lambdas[(size_t)a * L + l] / 1.0;
-      l1[(size_t)a * L + l] = alphas[a] * lambdas[(size_t)a * L + l] / 1.0;
-    }
-  }
-  NewtonCvProblem pb;
-  pb.n = n;
-  pb.p = p;
-  if (sparse) {
-    pb.colptr = X.colptr;
-    pb.rowidx = rows.data();
-    pb.values = xs.data();
-    pb.cut = cut.data();
-  } else {
-    pb.x_dense = xs.data();
-  }
-  pb.y = ys.data();
-  pb.n_sets = G;
-  pb.start = start.data();
-  pb.train_on_rest = rest;
-  pb.centre = centre;
-  pb.fit_intercept = intercept;
-  pb.mean = mean.data();
-  pb.scale = scale.data();
-  pb.b0 = b0.data();
-  pb.device = ctl->device;
-  pb.n_mix = n_alpha;
-  pb.n_lambda = L;
-  pb.l2 = l2.data();
-  pb.l1 = l1.data();
-  pb.ridge = ridge.data();
-  pb.max_iter = ctl->max_iter;
-  pb.tol = ctl->tol;
-  NewtonCvResult nr;
-  rc = newton_cv_run(pb, pt.on, &nr);
-  if (rc) return rc;
-
-  const size_t P1 = P + 1;
-  double most_steps = 0.0, most_halvings = 0.0;
-  for (int a = 0; a < n_alpha; ++a)
-    for (int t = 0; t < G; ++t) {
-      const size_t job = (size_t)a * (size_t)G + (size_t)t;
-      const double* m = mean.data() + (size_t)t * P;
-      const double* s = scale.data() + (size_t)t * P;
-      for (int li = 0; li < L; ++li) {
-        const size_t at = job * (size_t)L + (size_t)li;
-        const double* u = nr.u.data() + at * P1;
-        double* bo = out->beta + at * P;
-        // fit_newton and rescale_values: the intercept at the centres less the centres times the coefficients
-        double xbb = 0.0;
-        for (size_t j = 0; j < P; ++j) {
-          bo[j] = u[j] / s[j];
-          xbb += m[j] * bo[j];
-        }
-        out->a0[at] = intercept ? u[P] - xbb : b0[(size_t)t];
-        out->dev_ratio[at] = 1.0 - 2.0 * (double)n_t[(size_t)t] * nr.loss[at] / nulldev[(size_t)t];
-        out->return_codes[at] = nr.unconverged[at] ? 1.0 : 0.0;
-      }
-      out->nulldev[job] = nulldev[(size_t)t];
-      out->npasses[job] = nr.passes[job];
-      out->steps[job] = nr.steps[job];
-      out->halvings[job] = nr.halvings[job];
-      most_steps = std::max(most_steps, nr.steps[job] + nr.halvings[job]);
-      most_halvings = std::max(most_halvings, nr.halvings[job]);
-    }
-  if (pt.on)
-    fprintf(stderr, "[sgdnet]   cv newton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
-            "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
-            nr.moments_ms, nr.cd_ms, nr.state_ms);
-  pt.mark("cv newton (all folds)");
-  return SGDNET_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int sgdnet_cv_covariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
-                               int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
-                               sgdnet_cv_cov_result* out) {
-  if (!x) {
-    set_error("sgdnet_cv_covariance_dense: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  CovarianceCvProblem pb;
-  pb.n = n;
-  pb.p = p;
-  pb.x_dense = x;
-  pb.y = y;
-  return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
-}
-
-int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
-                                const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
-                                sgdnet_cv_cov_result* out) {
-  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
-    set_error("sgdnet_cv_covariance_sparse: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  int rc;
-  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
-  CovarianceCvProblem pb;
-  pb.n = x->n_rows;
-  pb.p = x->n_cols;
-  pb.colptr = x->colptr;
-  pb.rowidx = x->rowidx;
-  pb.values = x->values;
-  pb.y = y;
-  return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
-}
-
-int sgdnet_cv_newton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
-                           const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
-                           sgdnet_cv_newton_result* out) {
-  if (!x) {
-    set_error("sgdnet_cv_newton_dense: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  CvNewtonMatrix X;
-  X.n = n;
-  X.p = p;
-  X.dense = x;
-  return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
-}
-
-int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
-                            const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
-                            sgdnet_cv_newton_result* out) {
-  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
-    set_error("sgdnet_cv_newton_sparse: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  int rc;
-  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
-  CvNewtonMatrix X;
-  X.n = x->n_rows;
-  X.p = x->n_cols;
-  X.colptr = x->colptr;
-  X.rowidx = x->rowidx;
-  X.values = x->values;
-  return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
-}
-
 int sgdnet_fit_sparse(const sgdnet_csc* x, const double* y, int y_cols, const sgdnet_control* ctl,
                       sgdnet_result* out) {
   return with_exact_fallback(ctl, [&](const sgdnet_control* c, bool* gave_up) { return fit_sparse_impl(x, y, y_cols, c, out, gave_up); });
@@ -2166,114 +1327,6 @@ int sgdnet_setup_probe_dense(const double* x, int64_t n, int64_t p, int standard
     SGD_HIP_TRY(hipMemcpy(out->xt, dev.xd_t, sizeof(double) * (size_t)n * (size_t)p, hipMemcpyDeviceToHost));
     return (int)SGDNET_OK;
   });
-}
-
-// ---- diagnostics: one outer step of Newton mode (newton.hip: newton_probe) ----
-
-namespace {
-// what both probes check after their matrix; the refusals of the plan (fit_plan.hpp) by the same name
-int newton_probe_checked(NewtonProblem& pb, int device, sgdnet_newton_probe* io, const char* who) {
-  if (!io || !io->y || !io->scale || !io->u_cur || !io->u || io->max_sweeps == 0) {
-    set_error("%s: invalid argument", who);
-    return SGDNET_EINVAL;
-  }
-  if (pb.p > kNewtonMaxFeatures) {
-    set_error("mode = newton needs no more features than sgdnet_newton_max_features(): %lld features (limit %d)", (long long)pb.p,
-              kNewtonMaxFeatures);
-    return SGDNET_EUNSUPPORTED;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: the SAGA backend has no CPU fallback");
-    return SGDNET_ENODEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    set_error("device %d out of range (%d devices)", device, ndev);
-    return SGDNET_EINVAL;
-  }
-  pb.y = io->y;
-  pb.centre = io->centre != 0;
-  pb.scale = io->scale;
-  pb.device = device;
-  pb.n_lambda = 1;
-  return newton_probe(pb, io);
-}
-}  // namespace
-
-int sgdnet_newton_probe_dense(const double* x, int64_t n, int64_t p, int device, sgdnet_newton_probe* io) {
-  if (!x || n <= 0 || p <= 0) {
-    set_error("sgdnet_newton_probe_dense: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  NewtonProblem pb;
-  pb.n = n;
-  pb.p = p;
-  pb.x_dense = x;
-  return newton_probe_checked(pb, device, io, "sgdnet_newton_probe_dense");
-}
-
-int sgdnet_newton_probe_sparse(const sgdnet_csc* x, int device, sgdnet_newton_probe* io) {
-  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
-    set_error("sgdnet_newton_probe_sparse: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  int rc;
-  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
-  NewtonProblem pb;
-  pb.n = x->n_rows;
-  pb.p = x->n_cols;
-  pb.colptr = x->colptr;
-  pb.rowidx = x->rowidx;
-  pb.values = x->values;
-  return newton_probe_checked(pb, device, io, "sgdnet_newton_probe_sparse");
-}
-
-// ---- diagnostics: one outer step of multinomial Newton mode (mnewton.hip: mnewton_probe) ----
-
-namespace {
-// the refusals of the plan (fit_plan.hpp) by the same name
-int mnewton_probe_checked(MNewtonProblem& pb, int device, sgdnet_mnewton_probe_io* io, const char* who) {
-  if (!io || !io->y || !io->scale || !io->u_cur || !io->u || io->K < 2 || io->max_sweeps == 0 ||
-      (io->width != 0 && io->width != 64 && io->width != 256)) {
-    set_error("%s: invalid argument", who);
-    return SGDNET_EINVAL;
-  }
-  const int limit = mnewton_max_features(io->K);
-  if (pb.p > limit) {
-    set_error("mode = mnewton needs no more features than sgdnet_mnewton_max_features(n_classes): n_classes %d, %lld features (limit %d)",
-              io->K, (long long)pb.p, limit);
-    return SGDNET_EUNSUPPORTED;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: the SAGA backend has no CPU fallback");
-    return SGDNET_ENODEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    set_error("device %d out of range (%d devices)", device, ndev);
-    return SGDNET_EINVAL;
-  }
-  pb.K = io->K;
-  pb.y = io->y;
-  pb.centre = io->centre != 0;
-  pb.scale = io->scale;
-  pb.fit_intercept = io->fit_intercept != 0;
-  pb.device = device;
-  pb.n_lambda = 1;
-  return mnewton_probe(pb, io);
-}
-}  // namespace
-
-int sgdnet_mnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_mnewton_probe_io* io) {
-  if (!x || n <= 0 || p <= 0) {
-    set_error("sgdnet_mnewton_probe: invalid matrix");
-    return SGDNET_EINVAL;
-  }
-  MNewtonProblem pb;
-  pb.n = n;
-  pb.p = p;
-  pb.x_dense = x;
-  return mnewton_probe_checked(pb, device, io, "sgdnet_mnewton_probe");
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The fit driver's own rules (driver.cpp obeys them): which mode a fit runs in, its first window, how the job is
+// The fit driver's own rules (driver.cpp and driver_direct.cpp obey them): which mode a fit runs in, its first window, how the job is
 // cut over the GPUs, shards and generators, and the stability ladder of the automatic window.
 //
 // Pure functions of shapes, options and a handful of observed numbers: no HIP call, no environment variable, no
@@ -117,6 +117,49 @@ inline DrawKind draw_kind(const FitFacts& f, int mode) {
   return (mode == SGDNET_MODE_EXACT && !c.debug && f.opt.exact_epoch_blocks) ? DrawKind::kEpochBlocks : DrawKind::kPipeline;
 }
 
+// A direct mode solves the path from a Gram or Hessian matrix on the device: no window, no shards, no draws.
+inline bool is_direct_mode(int mode) {
+  return mode == SGDNET_MODE_COVARIANCE || mode == SGDNET_MODE_NEWTON || mode == SGDNET_MODE_MCOVARIANCE ||
+         mode == SGDNET_MODE_MNEWTON || mode == SGDNET_MODE_WCOVARIANCE || mode == SGDNET_MODE_WNEWTON;
+}
+
+// What differs between the direct modes' refusals; plan_direct asks in this order
+struct DirectRule {
+  const char* name;            // as "mode = %s" spells it
+  int family;
+  const char* family_text;
+  const char* responses;       // what the number of responses / classes breaks, or nullptr
+  int limit;                   // features
+  const char* limit_text;
+  size_t dense_copy_bytes;     // the driver expands sparse x to a dense copy that stays within this; 0: sparse x is read as it is
+  enum { kFeaturesOnly, kClasses, kSamples } prints;   // what the message reports before the features
+};
+
+// (P comes with its penalty set; no symbol of the library: driver.cpp and driver_direct.cpp each inline it)
+static inline void plan_direct(FitPlan& P, const FitFacts& f, const DirectRule& r) {
+  const sgdnet_control& c = *f.ctl;
+  const char* what = nullptr;
+  if (c.family != r.family) what = r.family_text;
+  else if (r.responses) what = r.responses;
+  else if (f.p > r.limit) what = r.limit_text;
+  else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+  else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
+  else if (r.dense_copy_bytes && f.sparse && (double)f.n * (double)f.p * 8.0 > (double)r.dense_copy_bytes)
+    what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
+  if (what) {
+    std::string shape = plan_text("family %d", c.family);
+    if (r.prints != DirectRule::kFeaturesOnly) shape += plan_text(", n_classes %d", c.n_classes);
+    if (r.prints == DirectRule::kSamples) shape += plan_text(", %lld samples", (long long)f.n);
+    P.rc = SGDNET_EUNSUPPORTED;
+    P.error = plan_text("mode = %s needs %s: %s, %lld features (limit %d), n_gpus %d, debug %d", r.name, what, shape.c_str(),
+                        (long long)f.p, r.limit, c.n_gpus, c.debug);
+    return;
+  }
+  P.mode = c.mode;
+  P.rank_dev.assign(1, c.device);
+  P.rank_lo = {0, f.n};                // no window, no shards, no draws
+}
+
 inline FitPlan plan_fit(const FitFacts& f) {
   const sgdnet_control& c = *f.ctl;
   const int family = c.family, K = c.n_classes;
@@ -128,138 +171,40 @@ inline FitPlan plan_fit(const FitFacts& f) {
   else if (family == SGDNET_MGAUSSIAN || (family == SGDNET_MULTINOMIAL && c.type_multinomial == 1))
     P.penalty = SGDNET_GROUPLASSO;
 
-  // ---- covariance mode: only where it was asked for (mode = auto must not move existing results), and only for
-  // the problem its path kernel holds in one workgroup's LDS (covariance.hpp); no silent fall back ----
-  if (c.mode == SGDNET_MODE_COVARIANCE) {
-    const char* what = nullptr;
-    if (family != SGDNET_GAUSSIAN) what = "family = gaussian";
-    else if (K != 1) what = "one response (n_classes = 1)";
-    else if (f.p > kCovMaxFeatures) what = "no more features than sgdnet_covariance_max_features()";
-    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
-    if (what) {
-      P.rc = SGDNET_EUNSUPPORTED;
-      P.error = plan_text("mode = covariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what,
-                          family, K, (long long)f.p, kCovMaxFeatures, c.n_gpus, c.debug);
-      return P;
+  // ---- the direct modes: only where they were asked for (mode = auto must not move existing results; they draw nothing
+  // and stop elsewhere than SAGA does), and only for the problem their kernels hold (covariance.hpp, newton.hpp,
+  // mnewton.hpp); no silent fall back, neither to SAGA nor from a wide mode to its narrow one ----
+  if (is_direct_mode(c.mode)) {
+    const char* one = K != 1 ? "one response (n_classes = 1)" : nullptr;
+    switch (c.mode) {
+      case SGDNET_MODE_COVARIANCE:      // S in one workgroup's LDS
+        plan_direct(P, f, {"covariance", SGDNET_GAUSSIAN, "family = gaussian", one, kCovMaxFeatures,
+                           "no more features than sgdnet_covariance_max_features()", 0, DirectRule::kClasses});
+        break;
+      case SGDNET_MODE_WCOVARIANCE:     // S in global memory: every p from 1 to its own limit
+        plan_direct(P, f, {"wcovariance", SGDNET_GAUSSIAN, "family = gaussian", one, kWcovMaxFeatures,
+                           "no more features than sgdnet_wcovariance_max_features()", 0, DirectRule::kClasses});
+        break;
+      case SGDNET_MODE_NEWTON:          // H in one wavefront's LDS
+        plan_direct(P, f, {"newton", SGDNET_BINOMIAL, "family = binomial", one, kNewtonMaxFeatures,
+                           "no more features than sgdnet_newton_max_features()", 0, DirectRule::kFeaturesOnly});
+        break;
+      case SGDNET_MODE_WNEWTON:         // H in global memory; sparse x is expanded to a dense copy by the driver
+        plan_direct(P, f, {"wnewton", SGDNET_BINOMIAL, "family = binomial", one, kWnewtonMaxFeatures,
+                           "no more features than sgdnet_wnewton_max_features()", kWnewtonDenseCopyBytes, DirectRule::kSamples});
+        break;
+      case SGDNET_MODE_MCOVARIANCE:     // several responses from one Gram matrix
+        plan_direct(P, f, {"mcovariance", SGDNET_MGAUSSIAN, "family = mgaussian", nullptr, mcov_max_features(K),
+                           "no more features than sgdnet_mcovariance_max_features(n_classes)", 0, DirectRule::kClasses});
+        break;
+      default: {                        // SGDNET_MODE_MNEWTON: the joint Hessian in LDS; sparse x as for wnewton
+        const char* classes = (K < 2 || K >= 100) ? "2 to 99 classes"
+                              : c.type_multinomial != 0 ? "the ungrouped penalty (type_multinomial = 0)" : nullptr;
+        plan_direct(P, f, {"mnewton", SGDNET_MULTINOMIAL, "family = multinomial", classes, mnewton_max_features(K),
+                           "no more features than sgdnet_mnewton_max_features(n_classes)", kMNewtonDenseCopyBytes, DirectRule::kSamples});
+      }
     }
-    P.mode = SGDNET_MODE_COVARIANCE;
-    P.rank_dev.assign(1, c.device);
-    P.rank_lo = {0, n};
-    return P;                          // no window, no shards, no draws
-  }
-
-  // ---- wide covariance mode: the same problem with S in global memory (covariance.hpp: kWcovMaxFeatures), every
-  // p from 1 to that limit; likewise only where it was asked for, no silent fall back ----
-  if (c.mode == SGDNET_MODE_WCOVARIANCE) {
-    const char* what = nullptr;
-    if (family != SGDNET_GAUSSIAN) what = "family = gaussian";
-    else if (K != 1) what = "one response (n_classes = 1)";
-    else if (f.p > kWcovMaxFeatures) what = "no more features than sgdnet_wcovariance_max_features()";
-    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
-    if (what) {
-      P.rc = SGDNET_EUNSUPPORTED;
-      P.error = plan_text("mode = wcovariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what,
-                          family, K, (long long)f.p, kWcovMaxFeatures, c.n_gpus, c.debug);
-      return P;
-    }
-    P.mode = SGDNET_MODE_WCOVARIANCE;
-    P.rank_dev.assign(1, c.device);
-    P.rank_lo = {0, n};
-    return P;                          // no window, no shards, no draws
-  }
-
-  // ---- Newton mode: likewise only where it was asked for (it draws nothing and stops elsewhere than SAGA does), and
-  // only for the problem its inner solve holds in one workgroup's LDS (newton.hpp); no silent fall back ----
-  if (c.mode == SGDNET_MODE_NEWTON) {
-    const char* what = nullptr;
-    if (family != SGDNET_BINOMIAL) what = "family = binomial";
-    else if (K != 1) what = "one response (n_classes = 1)";
-    else if (f.p > kNewtonMaxFeatures) what = "no more features than sgdnet_newton_max_features()";
-    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
-    if (what) {
-      P.rc = SGDNET_EUNSUPPORTED;
-      P.error = plan_text("mode = newton needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, family,
-                          (long long)f.p, kNewtonMaxFeatures, c.n_gpus, c.debug);
-      return P;
-    }
-    P.mode = SGDNET_MODE_NEWTON;
-    P.rank_dev.assign(1, c.device);
-    P.rank_lo = {0, n};
-    return P;                          // no window, no shards, no draws
-  }
-
-  // ---- wide Newton mode: the same problem with H in global memory (newton.hpp: kWnewtonMaxFeatures), every p from 1 to
-  // that limit; sparse x is expanded to a dense copy by the driver, which has its own bound; likewise only where it was
-  // asked for, no fall back to Newton mode or to SAGA ----
-  if (c.mode == SGDNET_MODE_WNEWTON) {
-    const char* what = nullptr;
-    if (family != SGDNET_BINOMIAL) what = "family = binomial";
-    else if (K != 1) what = "one response (n_classes = 1)";
-    else if (f.p > kWnewtonMaxFeatures) what = "no more features than sgdnet_wnewton_max_features()";
-    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
-    else if (f.sparse && (double)n * (double)f.p * 8.0 > (double)kWnewtonDenseCopyBytes)
-      what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
-    if (what) {
-      P.rc = SGDNET_EUNSUPPORTED;
-      P.error = plan_text("mode = wnewton needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what,
-                          family, K, (long long)n, (long long)f.p, kWnewtonMaxFeatures, c.n_gpus, c.debug);
-      return P;
-    }
-    P.mode = SGDNET_MODE_WNEWTON;
-    P.rank_dev.assign(1, c.device);
-    P.rank_lo = {0, n};
-    return P;                          // no window, no shards, no draws
-  }
-
-  // ---- several responses from one Gram matrix: likewise only where it was asked for, and only for the problem its path
-  // kernel holds in one workgroup's LDS (covariance.hpp: mcov_max_features); no silent fall back ----
-  if (c.mode == SGDNET_MODE_MCOVARIANCE) {
-    const int limit = mcov_max_features(K);
-    const char* what = nullptr;
-    if (family != SGDNET_MGAUSSIAN) what = "family = mgaussian";
-    else if (f.p > limit) what = "no more features than sgdnet_mcovariance_max_features(n_classes)";
-    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
-    if (what) {
-      P.rc = SGDNET_EUNSUPPORTED;
-      P.error = plan_text("mode = mcovariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what,
-                          family, K, (long long)f.p, limit, c.n_gpus, c.debug);
-      return P;
-    }
-    P.mode = SGDNET_MODE_MCOVARIANCE;
-    P.rank_dev.assign(1, c.device);
-    P.rank_lo = {0, n};
-    return P;                          // no window, no shards, no draws
-  }
-
-  // ---- multinomial Newton mode: likewise only where it was asked for, and only for the problem whose joint Hessian its
-  // inner solve holds in one workgroup's LDS (mnewton.hpp: mnewton_max_features); sparse x is expanded to a dense copy
-  // by the driver, which has its own bound; no silent fall back ----
-  if (c.mode == SGDNET_MODE_MNEWTON) {
-    const int limit = mnewton_max_features(K);
-    const char* what = nullptr;
-    if (family != SGDNET_MULTINOMIAL) what = "family = multinomial";
-    else if (K < 2 || K >= 100) what = "2 to 99 classes";
-    else if (c.type_multinomial != 0) what = "the ungrouped penalty (type_multinomial = 0)";
-    else if (f.p > limit) what = "no more features than sgdnet_mnewton_max_features(n_classes)";
-    else if (c.n_gpus > 1) what = "one GPU (n_gpus <= 1)";
-    else if (c.debug) what = "debug = 0 (there are no epochs to report losses of)";
-    else if (f.sparse && (double)n * (double)f.p * 8.0 > (double)kMNewtonDenseCopyBytes)
-      what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
-    if (what) {
-      P.rc = SGDNET_EUNSUPPORTED;
-      P.error = plan_text("mode = mnewton needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what,
-                          family, K, (long long)n, (long long)f.p, limit, c.n_gpus, c.debug);
-      return P;
-    }
-    P.mode = SGDNET_MODE_MNEWTON;
-    P.rank_dev.assign(1, c.device);
-    P.rank_lo = {0, n};
-    return P;                          // no window, no shards, no draws
+    return P;
   }
 
   P.mode = resolved_mode(c.mode, K);

@@ -40,23 +40,11 @@ static_assert(mnewton_max_features(100) == 0 && mnewton_max_features(1) == 0 && 
 // within the workspace bound of the Newton cross-validation (newton.hpp: 1 GiB).
 constexpr size_t kMNewtonDenseCopyBytes = kNewtonCvWorkspaceBytes;
 
-struct MNewtonProblem {
-  int64_t n = 0, p = 0;
+struct MNewtonProblem : DirectProblem {         // x_dense only (sparse x: the driver's dense copy); max_iter: outer steps per lambda
   int K = 0;                           // classes
-  const double* x_dense = nullptr;     // column-major n x p, in host memory (sparse x: the driver's dense copy)
   const double* y = nullptr;           // n: class codes 0 .. K - 1
-  bool centre = true;                  // deviations from the column means (false: from 0 -- no intercept, no standardisation)
-  const double* scale = nullptr;       // p: the sd the driver standardises feature j with (1 where it does not)
   bool fit_intercept = true;           // false: the intercepts stay at b0
   const double* b0 = nullptr;          // K: the null model's intercepts: where the path starts
-  int device = 0;
-  // the path, in the driver's units (regularization_path): l2 strength alpha[l], l1 strength beta[l]
-  int n_lambda = 0;
-  const double* alpha = nullptr;
-  const double* beta = nullptr;
-  bool ridge = false;                  // the ridge functor: no threshold
-  unsigned max_iter = 0;               // outer steps per lambda
-  double tol = 0.0;
 };
 
 struct MNewtonResult {

@@ -35,11 +35,12 @@
 // the same bits.
 //
 // Wide mode (wnewton_run, SGDNET_MODE_WNEWTON): beyond 198 features H does not fit one workgroup's LDS.  The loop, the state
-// pass and the dense moments kernels are the ones above (row chunks by newton.hpp's wnewton_row_chunks); then
-// newton_wide_scale_kernel writes H = M / n / (s s') to global memory as a full symmetric matrix with diag H and q, and
+// pass and the dense moments kernels are the ones above (row chunks by wide_layout.hpp's wide_row_chunks); then
+// wide_scale_kernel writes H = M / n / (s s') to global memory as a full symmetric matrix with diag H and q, and
 // newton_wide_cd_kernel keeps g, u, diag H and an ascending list of the coordinates that can move in LDS, sweeps that
 // list, reads one column of H per move and lets a screen with the full gradient add coordinates (newton.hpp: the budget
-// behind sgdnet_wnewton_max_features).  Dense x only: the driver expands sparse x.
+// behind sgdnet_wnewton_max_features).  The scale kernel, the list compaction and the column move are wide_cd_device.hpp's,
+// shared with covariance.hip.  Dense x only: the driver expands sparse x.
 //
 // Cross-validation (newton_cv_run, include/sgdnet_hip.h: sgdnet_cv_newton_*): all fold fits of all mixes advance in
 // lock-step.  The rows are sorted by group once, so a training set is a range of rows or the complement of one; the
@@ -56,6 +57,7 @@
 #include "moments_device.hpp"
 #include "newton.hpp"
 #include "setup_device.hpp"
+#include "wide_cd_device.hpp"
 
 namespace sgdnet {
 namespace {
@@ -354,26 +356,6 @@ __global__ __launch_bounds__(64) void newton_wide_blend_kernel(const double* u_c
   publish_candidate(BlendedCandidate{u_cur, u_cand, t}, u_cur, scale, p, u_cand, a_cand, rec);
 }
 
-// blockIdx.x = column j of H over the P = p + 1 coordinates (features, then the ones): H[k + ld j] = M_jk / n / (s_j s_k),
-// the arithmetic of newton_cd_solve's prologue, from the upper triangle of the (p + 2)^2 moments; rows P .. ld - 1 are
-// the zero pad.  Also diag H and q_j = M[j, p + 1] / n / s_j.
-__global__ __launch_bounds__(kBlock) void newton_wide_scale_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p,
-                                                                    int ld, double dn, double* __restrict__ H, double* __restrict__ Hd,
-                                                                    double* __restrict__ q) {
-  const int j = blockIdx.x, P = p + 1, nc = p + 2;
-  const double sj = j < p ? scale[j] : 1.0;
-  for (int k = threadIdx.x; k < ld; k += kBlock) {
-    double v = 0.0;
-    if (k < P) {
-      const double sk = k < p ? scale[k] : 1.0;
-      v = k >= j ? M[(size_t)j * nc + k] / dn / (sj * sk) : M[(size_t)k * nc + j] / dn / (sk * sj);
-    }
-    H[(size_t)j * ld + k] = v;
-    if (k == j) Hd[j] = v;
-  }
-  if (threadIdx.x == 0) q[j] = M[(size_t)j * nc + p + 1] / dn / sj;
-}
-
 // The coordinate update of newton_cd_solve, for the screen (u_j = 0) and for the sweep: from H_jj, u_j and g_j to the new
 // u_j.  Every caller passes the same words through the same operations, so every lane holds the same bits.
 __device__ __forceinline__ double newton_coord_new_u(double hjj, double uj, double gj, double al, double be, int ridge, bool penalised) {
@@ -389,8 +371,7 @@ __device__ __forceinline__ double newton_coord_new_u(double hjj, double uj, doub
 //   start    u = u_cur, so g = H (u - u_cur) - q = -q exactly: no pass over H.  The list is {j < p : u_j != 0} and the
 //            intercept coordinate p when it is fitted (unpenalised, without threshold; frozen: never visited).
 //   screen   every j < p outside the list: the coordinate update from u_j = 0; those that would move join.  The list is
-//            compacted again from its bits, kWidth coordinates a step: a ballot per wavefront, the wavefronts' counts
-//            through LDS -- ascending whatever kWidth is, no atomic (cov_wide_path_kernel's)
+//            compacted again from its bits (wide_cd_device.hpp: wide_compact, cov_wide_path_kernel's too)
 //   sweep    newton_cd_solve's coordinate update over the list: every lane computes the scalars from the same LDS words
 //            (uniform branches); a coordinate that stays costs no global read and no barrier; one that moves by d does
 //            g[k] += H[k, j] d for ALL k < P, 16 bytes a lane, so g stays the full gradient and the screen needs no
@@ -406,16 +387,13 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
                                                                  double* __restrict__ u_cand, double* __restrict__ a_cand,
                                                                  double* __restrict__ rec) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kWnewtonLdsBytes];
-  constexpr int kWaves = kWidth / 64;
-  static_assert(kWaves * 2 <= kWnewtonScanWords, "the compaction's counts (newton.hpp)");
-  const int lane = threadIdx.x, wave = lane >> 6, wl = lane & 63, P = p + 1;
+  const int lane = threadIdx.x, wave = lane >> 6, P = p + 1;
   double* g = reinterpret_cast<double*>(lds);
   double* u = g + P;
   double* hd = u + P;
   int32_t* list = reinterpret_cast<int32_t*>(hd + P);
   uint32_t* bits = reinterpret_cast<uint32_t*>(list + P);
   int32_t* counts = reinterpret_cast<int32_t*>(bits + (P + 31) / 32);
-  const int slots = (P + 1) / 2;     // a slot: k = 2 s and 2 s + 1 (P odd: the last one's second entry is H's zero pad)
   for (int k = lane; k < P; k += kWidth) {
     g[k] = -q[k];
     u[k] = u_cur[k];
@@ -423,12 +401,12 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
   }
   __syncthreads();
 
-  // The list from one flag per coordinate, in ascending order; returns its length.  screen: the flag is "in the list
-  // already, or would move from 0"; else: the start's.  A wavefront reads and rewrites the bits of its own 64 coordinates.
+  // The list from one flag per coordinate (wide_cd_device.hpp: wide_compact).  screen: the flag is "in the list already,
+  // or would move from 0"; else: the start's.  Coordinate p is in iff the intercept is fitted.  (One functor with a
+  // run-time `screen` and its own bounds, not one per call site: in this shape the kernel compiles to the instructions
+  // it had with its own copy of the compaction.)
   auto compact = [&](bool screen) -> int {
-    int length = 0, buf = 0;
-    for (int base = 0; base < P; base += kWidth) {
-      const int j = base + lane, first = base + wave * 64;
+    return wide_compact<kWidth>(P, list, bits, counts, [&](int j) -> bool {
       bool in = false;
       if (j < p) {
         if (screen) {
@@ -440,25 +418,8 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
       } else if (j == p) {
         in = fit_intercept != 0;
       }
-      const unsigned long long b = __ballot(in);
-      if (wl == 0) counts[buf * kWaves + wave] = __popcll(b);
-      __syncthreads();
-      int before = 0, total = 0;
-      for (int v = 0; v < kWaves; ++v) {
-        const int n_v = counts[buf * kWaves + v];
-        before += v < wave ? n_v : 0;
-        total += n_v;
-      }
-      if (in) list[length + before + __popcll(b & ((1ull << wl) - 1ull))] = j;
-      if (wl == 0 && first < P) {
-        bits[first >> 5] = (uint32_t)b;
-        if (first + 32 < P) bits[(first >> 5) + 1] = (uint32_t)(b >> 32);
-      }
-      length += total;
-      buf ^= 1;        // (the counts of step i are read before the barrier of step i + 1 and rewritten behind it)
-    }
-    __syncthreads();
-    return length;
+      return in;
+    });
   };
 
   int n_list = compact(false);
@@ -485,20 +446,7 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
         if (d != 0.0) {
           __syncthreads();                         // every lane has read u[j] and g[j]
           if (lane == 0) u[j] = nu;
-          const double* col = H + (size_t)ld * j;
-#pragma unroll 4
-          for (int s = lane; s < slots; s += kWidth) {
-            const int k = 2 * s;
-            const double2 v = *reinterpret_cast<const double2*>(col + k);
-            if (k + 1 < P) {
-              double2 gk = *reinterpret_cast<double2*>(g + k);
-              gk.x = fma(v.x, d, gk.x);
-              gk.y = fma(v.y, d, gk.y);
-              *reinterpret_cast<double2*>(g + k) = gk;
-            } else {
-              g[k] = fma(v.x, d, g[k]);
-            }
-          }
+          wide_column_move<kWidth>(g, H + (size_t)ld * j, P, d);
           __syncthreads();
         }
       }
@@ -528,12 +476,9 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
 //   1024       41.0 ms   267 ms   288 ms   426 ms
 // A column of 199 doubles is less than one stride of 256 lanes, and twelve more wavefronts only wait at the barriers; at
 // 1000 the two are within 4 %, from 2000 on sixteen wavefronts halve the solve.  So cov_wide_path_kernel's rule
-// (covariance.hip: wcov_path_width) stands here: 256 lanes up to 512 features, 1024 beyond.  That kernel's look-ahead
+// (wide_layout.hpp: wide_cd_width) stands here: 256 lanes up to 512 features, 1024 beyond.  That kernel's look-ahead
 // variant is not built: at p = 4000, where it gained a quarter there, the inner solve is 41 % of a fit that the moments
 // and the state pass make 3.8 times slower than auto.
-constexpr int kWnewtonNarrow = 256, kWnewtonWide = 1024;
-constexpr int wnewton_cd_width(int p) { return p <= 512 ? kWnewtonNarrow : kWnewtonWide; }
-static_assert(kTileCols == 16 && kBlock == 256, "wnewton_tile_pairs and kWnewtonPartialBytes (newton.hpp) count 16-column tiles of 256 partial sums");
 
 // ---- cross-validation (newton_cv_run): the kernels above with a job dimension ----
 // A job is one (mix, training set).  x and y hold the rows sorted by group, so the rows of a training set are one range
@@ -878,7 +823,7 @@ struct NewtonDevice {
   int p = 0, P = 0, nc = 0;
   bool sparse = false, centre = true, timed = false;
   // the wide mode (wnewton_run; set before setup): H, diag H and q in global memory, the inner solve on `width` lanes,
-  // the row chunks of newton.hpp's wnewton_row_chunks
+  // the row chunks of wide_layout.hpp's wide_row_chunks
   bool wide = false;
   int width = 0, ld = 0;
   double *d_H = nullptr, *d_Hd = nullptr, *d_q = nullptr;
@@ -912,11 +857,11 @@ struct NewtonDevice {
     nnz = sparse ? pb.colptr[p] : 0;
     const int T = (nc + kTileCols - 1) / kTileCols;
     pairs = T * (T + 1) / 2;
-    rows_per_chunk = wide ? ((n + wnewton_row_chunks(n, nc) - 1) / wnewton_row_chunks(n, nc) + kTileRows - 1) / kTileRows * kTileRows
+    rows_per_chunk = wide ? wide_rows_per_chunk(n, nc, kTileRows)
                           : dense_rows_per_chunk(n, pairs);
     chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
     state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
-    ld = (int)wnewton_leading_dim(P);
+    ld = (int)wide_leading_dim(P);
 
     const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
     const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P : 0);
@@ -1056,10 +1001,10 @@ struct NewtonDevice {
   // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
   int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
     if (wide) {                          // scale (timed: up to the event 4), then the solve on H about d_cur
-      hipLaunchKernelGGL(newton_wide_scale_kernel, dim3((unsigned)P), dim3(kBlock), 0, st, d_M, d_scale, p, ld, (double)n, d_H, d_Hd, d_q);
+      hipLaunchKernelGGL(wide_scale_kernel, dim3((unsigned)P), dim3(kBlock), 0, st, d_M, d_scale, p, p + 2, ld, (double)n, d_H, d_Hd, d_q);
       SGD_HIP_TRY(hipGetLastError());
       if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
-      const auto kernel = width == kWnewtonNarrow ? newton_wide_cd_kernel<kWnewtonNarrow> : newton_wide_cd_kernel<kWnewtonWide>;
+      const auto kernel = width == kWideNarrow ? newton_wide_cd_kernel<kWideNarrow> : newton_wide_cd_kernel<kWideFull>;
       hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, ld, d_cur, al, be, ridge ? 1 : 0,
                          fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
       SGD_HIP_TRY(hipGetLastError());
@@ -1077,13 +1022,13 @@ struct NewtonDevice {
 namespace {
 
 // newton_run and wnewton_run: one outer loop, one state machine.  wide: NewtonDevice scales the moments into H in global
-// memory and runs newton_wide_cd_kernel<width>; the dense row chunks follow wnewton_row_chunks; the blend has no array of
+// memory and runs newton_wide_cd_kernel<width>; the dense row chunks follow wide_row_chunks; the blend has no array of
 // kNewtonMaxFeatures + 1.  Not wide: exactly the launches Newton mode has always made.
 int newton_loop(const NewtonProblem& pb, bool timed, NewtonResult* out, bool wide, int width) {
   const int p = (int)pb.p, P = p + 1, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
   if (pb.n <= 0 || pb.p <= 0 || pb.p > (wide ? kWnewtonMaxFeatures : kNewtonMaxFeatures) || L <= 0 ||
-      (wide && (sparse || (width != kWnewtonNarrow && width != kWnewtonWide))) || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
+      (wide && (sparse || (width != kWideNarrow && width != kWideFull))) || !pb.y || !pb.scale || !pb.alpha || !pb.beta || pb.max_iter == 0 ||
       (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
     set_error("%s: invalid problem", wide ? "wnewton_run" : "newton_run");
     return SGDNET_EINVAL;
@@ -1172,7 +1117,7 @@ int newton_loop(const NewtonProblem& pb, bool timed, NewtonResult* out, bool wid
 int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out) { return newton_loop(pb, timed, out, false, 0); }
 
 int wnewton_run(const NewtonProblem& pb, bool timed, NewtonResult* out, int width) {
-  return newton_loop(pb, timed, out, true, width != 0 ? width : wnewton_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures)));
+  return newton_loop(pb, timed, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures)));
 }
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is

@@ -6,7 +6,9 @@
 
 #include <vector>
 
+#include "direct_problem.hpp"
 #include "sgdnet_hip.h"
+#include "wide_layout.hpp"
 
 namespace sgdnet {
 
@@ -46,16 +48,12 @@ constexpr unsigned kNewtonMaxSweeps = 1000;
 // ---- wide Newton mode (SGDNET_MODE_WNEWTON): the same outer loop with H in global memory ----
 // newton_wide_cd_kernel is ONE workgroup that keeps, for one inner solve over the P = p + 1 coordinates, in its LDS
 //   the gradient g, u and diag H, in f64                               3 P doubles
-//   the ascending list of the coordinates that may move, int32          P words
-//   one bit per coordinate: "is in the list"                            ceil(P / 32) words
-//   the wavefronts' counts of a list compaction step, twice             2 x 16 words
-// and nothing of size P^2: H = M / n / (s s') is a full symmetric matrix in global memory whose leading dimension is P
-// rounded up to 16 doubles (every column starts on a 128-byte line; the pad is zero), written by newton_wide_scale_kernel
-// with diag H and q.  In bytes: 24 P + 4 P + 4 ceil(P / 32) + 128 <= 163 840:
+//   the list, its bits and the compaction's counts (wide_layout.hpp)    P + ceil(P / 32) + 32 words
+// and H = M / n / (s s') in global memory, leading dimension wide_leading_dim(P), written by wide_scale_kernel with
+// diag H and q.  In bytes: 24 P + 4 P + 4 ceil(P / 32) + 128 <= 163 840:
 //   P = 5820:  162 960 + 728 + 128 = 163 816          P = 5821:  162 988 + 728 + 128 = 163 844
-constexpr int kWnewtonLdsBytes = 160 * 1024;
-constexpr int kWnewtonScanWords = 2 * 16;
-constexpr int wnewton_state_bytes(int P) { return 24 * P + 4 * P + 4 * ((P + 31) / 32) + 4 * kWnewtonScanWords; }
+constexpr int kWnewtonLdsBytes = kWideLdsBytes;
+constexpr int wnewton_state_bytes(int P) { return 24 * P + wide_list_bytes(P); }
 constexpr int wnewton_max_features() {
   int p = 1;
   while (wnewton_state_bytes(p + 2) <= kWnewtonLdsBytes) ++p;
@@ -64,46 +62,22 @@ constexpr int wnewton_max_features() {
 constexpr int kWnewtonMaxFeatures = wnewton_max_features();
 static_assert(kWnewtonMaxFeatures == 5819, "the LDS budget of the wide inner solve (see above)");
 static_assert(kWnewtonMaxFeatures >= 4096, "include/sgdnet_hip.h promises at least 4096 features");
-constexpr int64_t wnewton_leading_dim(int64_t P) { return (P + 15) / 16 * 16; }
 
-// The dense moments pass of the wide mode runs once per outer step over ncols = p + 2 columns; its partial-tile buffer holds
-// chunks x tile pairs x 256 doubles.  The row chunks are a function of n and ncols alone: as many as it takes to put 1024
-// workgroups on the GPU, none shorter than 256 rows, and ONE once the tile pairs alone are that many -- so the buffer is
-// 2 MiB while there are chunks and pairs x 2 KiB beyond: 136 MB at the feature limit (364 tiles of 16 columns, 66 430
-// pairs).  (newton mode's dense_rows_per_chunk never takes fewer than 16 chunks: 2.2 GB there.)
+// The dense moments pass of the wide mode runs once per outer step over ncols = p + 2 columns (wide_layout.hpp:
+// wide_row_chunks); its partial-tile buffer is 136 MB at the feature limit (364 tiles of 16 columns, 66 430 pairs).
+// (newton mode's dense_rows_per_chunk never takes fewer than 16 chunks: 2.2 GB there.)
 constexpr int64_t kWnewtonPartialBytes = (int64_t)160 << 20;
-constexpr int64_t wnewton_tile_pairs(int64_t ncols) { return ((ncols + 15) / 16) * ((ncols + 15) / 16 + 1) / 2; }
-constexpr int64_t wnewton_row_chunks(int64_t n, int64_t ncols) {
-  const int64_t pairs = wnewton_tile_pairs(ncols), cap = pairs >= 1024 ? 1 : 1024 / pairs, by_rows = (n + 255) / 256;
-  return by_rows < 1 ? 1 : (by_rows < cap ? by_rows : cap);
-}
-static_assert(wnewton_row_chunks(1 << 30, kWnewtonMaxFeatures + 2) == 1 &&
-              wnewton_tile_pairs(kWnewtonMaxFeatures + 2) * 256 * 8 <= kWnewtonPartialBytes, "one chunk at the limit");
-static_assert(wnewton_row_chunks(1 << 30, 3) * wnewton_tile_pairs(3) * 256 * 8 <= kWnewtonPartialBytes, "1024 workgroups' tiles at most");
+static_assert(wide_row_chunks(1 << 30, kWnewtonMaxFeatures + 2) == 1 &&
+              wide_tile_pairs(kWnewtonMaxFeatures + 2) * 256 * 8 <= kWnewtonPartialBytes, "one chunk at the limit");
+static_assert(wide_row_chunks(1 << 30, 3) * wide_tile_pairs(3) * 256 * 8 <= kWnewtonPartialBytes, "1024 workgroups' tiles at most");
 // Sparse x is expanded to a column-major dense copy by the driver (the sparse pair kernel launches p (p + 2) workgroups per
 // outer step); the copy stays within this many bytes.
 constexpr size_t kWnewtonDenseCopyBytes = (size_t)1 << 30;
 
-struct NewtonProblem {
-  int64_t n = 0, p = 0;
-  // x as the fit entry points receive it: one of the two, in host memory
-  const double* x_dense = nullptr;     // column-major n x p
-  const int32_t* colptr = nullptr;     // dgCMatrix slots
-  const int32_t* rowidx = nullptr;
-  const double* values = nullptr;
+struct NewtonProblem : DirectProblem {          // max_iter: outer steps per lambda
   const double* y = nullptr;           // n: class codes 0 / 1
-  bool centre = true;                  // deviations from the column means (false: from 0 -- no intercept, no standardisation)
-  const double* scale = nullptr;       // p: the sd the driver standardises feature j with (1 where it does not)
   bool fit_intercept = true;           // false: the last coordinate stays at b0
   double b0 = 0.0;                     // the null model's intercept: where the path starts
-  int device = 0;
-  // the path, in the driver's units (regularization_path): l2 strength alpha[l], l1 strength beta[l]
-  int n_lambda = 0;
-  const double* alpha = nullptr;
-  const double* beta = nullptr;
-  bool ridge = false;                  // the ridge functor: no threshold
-  unsigned max_iter = 0;               // outer steps per lambda
-  double tol = 0.0;
 };
 
 struct NewtonResult {
@@ -115,14 +89,14 @@ struct NewtonResult {
   double passes = 0.0;                 // state passes over the whole path
   double sweeps = 0.0, halvings = 0.0; // (SGDNET_TRACE)
   float state_ms = 0.f, moments_ms = 0.f, cd_ms = 0.f;   // kernel times summed over the path (SGDNET_TRACE only: they cost a sync per step)
-  float scale_ms = 0.f;                                  // wnewton_run only: newton_wide_scale_kernel
+  float scale_ms = 0.f;                                  // wnewton_run only: wide_scale_kernel
 };
 
 // The Newton loop (newton.hip).  p <= kNewtonMaxFeatures is the caller's business (plan_fit).  timed: fill the *_ms fields.
 int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out);
 
 // The same loop around the wide inner solve (newton.hip): dense x only, p <= kWnewtonMaxFeatures is the caller's business
-// (plan_fit).  width: lanes of the inner solve's workgroup (256 or 1024), 0 = the rule of newton.hip (wnewton_cd_width);
+// (plan_fit).  width: lanes of the inner solve's workgroup (256 or 1024), 0 = the rule of wide_layout.hpp (wide_cd_width);
 // both give the same bits.
 int wnewton_run(const NewtonProblem& pb, bool timed, NewtonResult* out, int width = 0);
 

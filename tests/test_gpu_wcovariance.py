@@ -1,4 +1,4 @@
-"""sa.sgdnet_wcovariance (SGDNET_MODE_WCOVARIANCE, sgdnet_amd/csrc/covariance.hip: cov_wide_scale_kernel and
+"""sa.sgdnet_wcovariance (SGDNET_MODE_WCOVARIANCE, sgdnet_amd/csrc/covariance.hip: wide_scale_kernel and
 cov_wide_path_kernel): the gaussian path of one response solved to its optimum with the scaled Gram matrix in global
 memory, for up to wcovariance_max_features() features.  Checked against the optimality conditions of the problem the
 driver solves (sa.kkt), as tests/test_gpu_covariance.py checks mode = "covariance", and against that mode where both run.
@@ -81,10 +81,11 @@ def test_same_optimum_as_covariance_mode(sa, shape, sparse, mix):
 # ---- (iii) determinism: the workgroup's width, and a second call ----
 
 # (40, limit): the instance that requests the next column while a move updates the gradient (beyond 1536 features)
-@pytest.mark.parametrize("shape, sparse", [((65, 1025), False), ((65, 1025), True), ((63, 15), False), ((63, 15), True), ((40, None), False)])
+@pytest.mark.parametrize("shape, sparse", [((65, 1025), False), ((65, 1025), True), ((63, 15), False), ((63, 15), True), ((40, None), False)]
+                         + [(shape, False) for shape in wr.WIDTH_SHAPES])
 def test_both_widths_and_a_second_call_give_the_same_bits(sa, shape, sparse):
     x, y = tc.problem(shape[0], shape[1] or sa.wcovariance_max_features(), sparse)
-    kw = dict(alpha=0.5, nlambda=4 if shape[1] is None else 5, lambda_min_ratio=0.1 if shape[1] is None else 5e-2, **KW)
+    kw = dict(alpha=0.5, **(dict(nlambda=4, lambda_min_ratio=0.1) if shape[1] is None else wr.WIDTH_PATH), **KW)
     with sa.option("wcovariance_width", 256):
         narrow = sa.sgdnet_wcovariance(x, y, **kw)
     with sa.option("wcovariance_width", 1024):

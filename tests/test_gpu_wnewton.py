@@ -1,4 +1,4 @@
-"""sa.sgdnet_wnewton (SGDNET_MODE_WNEWTON, sgdnet_amd/csrc/newton.hip: newton_wide_scale_kernel and newton_wide_cd_kernel):
+"""sa.sgdnet_wnewton (SGDNET_MODE_WNEWTON, sgdnet_amd/csrc/newton.hip: wide_scale_kernel and newton_wide_cd_kernel):
 the binomial path of one response solved to its optimum by proximal Newton steps with the weighted Gram matrix in global
 memory, for up to wnewton_max_features() features.  Checked against the optimality conditions of the problem the driver
 solves (sa.kkt), as tests/test_gpu_newton.py checks sa.sgdnet_newton, and against that mode where both run.  The shapes
@@ -106,7 +106,8 @@ def test_same_optimum_as_newton_mode_in_as_many_passes(sa, shape, sparse, mix):
 
 # ---- (iii) determinism: the workgroup's width, a second call, and sparse x ----
 
-@pytest.mark.parametrize("shape, sparse", [((65, 1024), False), ((65, 1024), True), ((63, 14), False), ((63, 14), True), ((40, None), False)])
+@pytest.mark.parametrize("shape, sparse", [((65, 1024), False), ((65, 1024), True), ((63, 14), False), ((63, 14), True), ((40, None), False)]
+                         + [(shape, False) for shape in wr.WIDTH_SHAPES])
 def test_both_widths_and_a_second_call_give_the_same_bits(sa, shape, sparse):
     x, y = tn.problem(shape[0], shape[1] or sa.wnewton_max_features(), sparse)
     nlambda, ratio = wr.path_of(shape[0], shape[1], 0.5)

@@ -22,7 +22,7 @@ def state_bytes(p):
 
 
 def max_features():
-    """sgdnet_wcovariance_max_features: through the library where it loads, else restated from covariance.hpp's text."""
+    """sgdnet_wcovariance_max_features: through the library where it loads, else restated from covariance.hpp's budget."""
     try:
         import sgdnet_amd as sa
         return sa.wcovariance_max_features()
@@ -45,19 +45,11 @@ def test_header_binding_package_and_shim_agree():
     assert _lib.MODES == {"exact": 0, "batched": 1, "auto": 2, "covariance": 3}      # sgdnet(mode=...) does not reach mode 7
     shim = open(os.path.join(ROOT, "shim", "sgdnet_shim.c")).read()
     assert '"wcovariance") == 0) c->mode = SGDNET_MODE_WCOVARIANCE' in shim
-    plan = open(os.path.join(ROOT, "sgdnet_amd", "csrc", "fit_plan.hpp")).read()
-    assert '"mode = wcovariance needs %s' in plan
-    block = plan[plan.index("c.mode == SGDNET_MODE_WCOVARIANCE"):]
-    block = block[:block.index("return P;                          // no window")]
-    for what in ("family = gaussian", "one response (n_classes = 1)", "sgdnet_wcovariance_max_features()", "one GPU (n_gpus <= 1)",
-                 "debug = 0"):
-        assert what in block
+    # (what the plan refuses of this mode, rung by rung and byte for byte: test_direct_plan_host.py)
 
 
 def test_feature_limit_is_the_lds_budget():
-    src = open(os.path.join(ROOT, "sgdnet_amd", "csrc", "covariance.hpp")).read()
-    assert "return 32 * p + 4 * p + 4 * ((p + 31) / 32) + 4 * kWcovScanWords;" in src
-    assert "kCovLdsBytes = 160 * 1024;" in src and "kWcovScanWords = 2 * 16;" in src
+    # (covariance.hpp's wcov_state_bytes is state_bytes above, value by value: test_direct_plan_host.py)
     p = max_features()
     assert p == wr.LIMIT and p >= 4096
     assert state_bytes(p) <= LDS_BYTES < state_bytes(p + 1)
@@ -105,6 +97,14 @@ def test_restatement_is_optimal_on_the_gpu_inputs(shape, sparse, mix):
     for intercept, standardize in wr.settings_of(shape[1]):
         lam = wr.automatic_lambdas(x, y, mix, standardize, nlambda, ratio)
         check_restatement(x, y, lam, mix, standardize, intercept, (n, p, sparse, mix, intercept, standardize))
+
+
+@pytest.mark.parametrize("shape", wr.WIDTH_SHAPES)
+def test_restatement_is_optimal_on_the_width_inputs(shape):
+    """test_gpu_wcovariance.py::test_both_widths_and_a_second_call_give_the_same_bits: its further dense inputs, on its path"""
+    x, y = tc.problem(shape[0], shape[1], False)
+    lam = wr.automatic_lambdas(x, y, 0.5, True, wr.WIDTH_PATH["nlambda"], wr.WIDTH_PATH["lambda_min_ratio"])
+    check_restatement(x, y, lam, 0.5, True, True, ("width", shape))
 
 
 @pytest.mark.parametrize("sparse", [False, True])

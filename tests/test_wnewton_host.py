@@ -30,19 +30,11 @@ def test_header_binding_package_and_shim_agree():
     assert _lib.MODES == {"exact": 0, "batched": 1, "auto": 2, "covariance": 3}      # sgdnet(mode=...) does not reach mode 8
     shim = open(os.path.join(ROOT, "shim", "sgdnet_shim.c")).read()
     assert '"wnewton") == 0) c->mode = SGDNET_MODE_WNEWTON' in shim
-    plan = open(os.path.join(ROOT, "sgdnet_amd", "csrc", "fit_plan.hpp")).read()
-    assert '"mode = wnewton needs %s' in plan
-    block = plan[plan.index("c.mode == SGDNET_MODE_WNEWTON"):]
-    block = block[:block.index("return P;                          // no window")]
-    for what in ("family = binomial", "one response (n_classes = 1)", "sgdnet_wnewton_max_features()", "one GPU (n_gpus <= 1)",
-                 "debug = 0", "the dense copy of a sparse x"):
-        assert what in block
+    # (what the plan refuses of this mode, rung by rung and byte for byte: test_direct_plan_host.py)
 
 
 def test_feature_limit_is_the_lds_budget():
-    src = open(os.path.join(ROOT, "sgdnet_amd", "csrc", "newton.hpp")).read()
-    assert "return 24 * P + 4 * P + 4 * ((P + 31) / 32) + 4 * kWnewtonScanWords;" in src
-    assert "kWnewtonLdsBytes = 160 * 1024;" in src and "kWnewtonScanWords = 2 * 16;" in src
+    # (newton.hpp's wnewton_state_bytes is wr.state_bytes, value by value: test_direct_plan_host.py)
     p = wr.LIMIT
     assert p == 5819 and p >= 4096
     assert wr.state_bytes(p + 1) <= wr.LDS_BYTES < wr.state_bytes(p + 2)
@@ -50,7 +42,7 @@ def test_feature_limit_is_the_lds_budget():
         import sgdnet_amd as sa
         assert sa.wnewton_max_features() == p
     except OSError:
-        pass                                                    # (the library does not load here: the text above is the check)
+        pass                                                    # (the library does not load here: the compiled header is the check)
 
 
 def test_mode_string_is_not_one_of_sgdnet():
@@ -103,6 +95,15 @@ def test_restatement_is_optimal_on_the_gpu_inputs(shape, sparse, mix):
     for intercept, standardize in wr.settings_of(shape[1]):
         lam = wr.automatic_lambdas(x, y, mix, standardize, nlambda, ratio)
         check_restatement(x, y, lam, mix, standardize, intercept, (n, p, sparse, mix, intercept, standardize), newton_too=p <= 198)
+
+
+@pytest.mark.parametrize("shape", wr.WIDTH_SHAPES)
+def test_restatement_is_optimal_on_the_width_inputs(shape):
+    """test_gpu_wnewton.py::test_both_widths_and_a_second_call_give_the_same_bits: its further dense inputs, on its path"""
+    x, y = tn.problem(shape[0], shape[1], False)
+    nlambda, ratio = wr.path_of(shape[0], shape[1], 0.5)
+    lam = wr.automatic_lambdas(x, y, 0.5, True, nlambda, ratio)
+    check_restatement(x, y, lam, 0.5, True, True, ("width", shape), newton_too=shape[1] <= 198)
 
 
 @pytest.mark.parametrize("sparse", [False, True])

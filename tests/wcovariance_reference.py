@@ -99,6 +99,11 @@ def automatic_lambdas(x, y, mix, standardize, nlambda, ratio):
 # workgroup; (65, 1025): one past a stride of the 1024-lane one; (40, limit): the whole LDS budget.
 SHAPES = [(2, 1), (63, 15), (300, 199), (65, 257), (65, 1025), (40, None)]
 MIXES = [0.0, 0.5, 1.0]
+# Further dense inputs of the width test, where the list compaction (csrc/wide_cd_device.hpp) can go wrong: a single
+# coordinate; a bit word without and with its upper half (31, 33); a wavefront boundary (64, 65); one stride of the
+# 256-lane workgroup from both sides (255, 256, 257); odd and even slot tails; the first p of the look-ahead instance (1537)
+WIDTH_SHAPES = [(65, p) for p in (1, 31, 33, 64, 65, 255, 256, 257, 1537)]
+WIDTH_PATH = dict(nlambda=5, lambda_min_ratio=5e-2)       # (the feature limit has its own in the test)
 
 
 def path_of(n, p, mix):

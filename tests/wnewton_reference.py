@@ -1,4 +1,4 @@
-"""sa.sgdnet_wnewton (SGDNET_MODE_WNEWTON, sgdnet_amd/csrc/newton.hip: newton_wide_scale_kernel and newton_wide_cd_kernel)
+"""sa.sgdnet_wnewton (SGDNET_MODE_WNEWTON, sgdnet_amd/csrc/newton.hip: wide_scale_kernel and newton_wide_cd_kernel)
 restated in numpy, and the inputs its tests share: tests/test_gpu_wnewton.py runs them on the device,
 tests/test_wnewton_host.py runs the restatement on the same inputs on the CPU.
 
@@ -150,6 +150,10 @@ automatic_lambdas = tn.automatic_lambdas
 SHAPES = [(40, 1), (63, 14), (65, 15), (300, 199), (65, 255), (65, 256), (65, 1024), (40, None)]
 MIXES = [0.0, 0.5, 1.0]
 BOTH_MODES = [(600, 198), (200, 33)]      # where mode = newton runs too
+# Further dense inputs of the width test, where the list compaction (csrc/wide_cd_device.hpp) can go wrong over the
+# P = p + 1 coordinates: a single feature; a bit word without and with its upper half (P = 31, 33); a wavefront boundary
+# (P = 64, 65); one stride of the 256-lane workgroup from both sides (P = 255, 256, 257); odd and even slot tails
+WIDTH_SHAPES = [(65, p) for p in (1, 30, 32, 63, 64, 254, 255, 256)]
 BOTH_MODES_PATH = dict(nlambda=6, lambda_min_ratio=1e-2)
 
 
