@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -150,6 +150,20 @@ extern "C" {
  * dev_ratio, intercept = 0 and standardize = 0 are SGDNET_MODE_NEWTON's.  Same optimum as SGDNET_MODE_NEWTON, not the
  * same bits. */
 #define SGDNET_MODE_WNEWTON 8
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): SGDNET_MODE_MCOVARIANCE's
+ * problem and method for up to sgdnet_wmcovariance_max_features(n_classes) features.  The scaled Gram matrix stays in
+ * global memory as a full symmetric matrix; one workgroup keeps the coefficients and the gradient of all responses,
+ * diag S and an ascending list of the blocks (a feature's n_classes coefficients) that can move in its LDS, runs cyclic
+ * block coordinate descent over that list and reads one column of S per block that moves, for all responses at once;
+ * blocks outside the list are screened with the full gradient and join when they would move
+ * (sgdnet_amd/csrc/covariance.hip: cov_wide_group_path_kernel).  Takes every n_features from 1 to the limit; sparse x is
+ * read as it is.  Needs family = mgaussian, n_features <= sgdnet_wmcovariance_max_features(n_classes), n_gpus <= 1 and
+ * debug = 0; anything else returns SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition ("mode = wmcovariance
+ * needs ...") -- no fall back to SAGA or to SGDNET_MODE_MCOVARIANCE.  Draws, rng_state, draws_used, tol, return_codes,
+ * lambda, nulldev, dev_ratio, standardize_response, intercept = 0 and standardize = 0 are SGDNET_MODE_MCOVARIANCE's;
+ * max_iter bounds the sweeps over the list of one lambda and result.npasses counts those sweeps.  Same optimum as
+ * SGDNET_MODE_MCOVARIANCE, not the same bits. */
+#define SGDNET_MODE_WMCOVARIANCE 9
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -252,6 +266,11 @@ int sgdnet_wnewton_max_features(void);
 /* the largest n_features SGDNET_MODE_MCOVARIANCE takes with n_responses responses: the LDS holds p (p + 1) / 2 + 3 p K
  * doubles (195 at K = 2, 174 at K = 10, 63 at K = 96); 0 where nothing fits or n_responses < 1 */
 int sgdnet_mcovariance_max_features(int n_responses);
+/* the largest n_features SGDNET_MODE_WMCOVARIANCE takes with n_responses responses: the LDS holds 2 K doubles per feature
+ * (the feature count rounded up to even), diag S, K doubles of scratch, p list words and p bits, and the moments pass
+ * takes n_features + n_responses <= sgdnet_wcovariance_max_features() + 1 columns (4531 at K = 1, 3709 at K = 2, 2722 at
+ * K = 3, 950 at K = 10, 104 at K = 96; at least 2048 at K = 2 and 512 at K = 10); 0 where nothing fits or n_responses < 1 */
+int sgdnet_wmcovariance_max_features(int n_responses);
 /* the largest n_features SGDNET_MODE_MNEWTON takes with n_classes classes: the LDS holds Q (Q + 1) / 2 + 2 Q doubles,
  * Q = n_classes (n_features + 1) <= 199: 199 / n_classes - 1 (98 at K = 2, 65 at K = 3, 38 at K = 5, 18 at K = 10,
  * 1 at K = 99); 0 for n_classes < 2 or >= 100 */
@@ -305,6 +324,11 @@ int sgdnet_mnewton_max_features(int n_classes);
 /*                        on 256 or 1024 lanes by the library's rule; 256 or  */
 /*                        1024: on that many (same bits either way; any       */
 /*                        other value makes such a fit return SGDNET_EINVAL)  */
+/*   "wmcovariance_width" 0 (default): SGDNET_MODE_WMCOVARIANCE's path kernel  */
+/*                        runs on 256 or 1024 lanes by the library's rule;    */
+/*                        256 or 1024: on that many (same bits either way;    */
+/*                        any other value makes such a fit return             */
+/*                        SGDNET_EINVAL)                                      */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

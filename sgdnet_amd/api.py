@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WNEWTON, MODES, check, dptr
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODE_WNEWTON, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -161,10 +161,28 @@ def sgdnet_wcovariance(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min
                 modes={"wcovariance": MODE_WCOVARIANCE}, batch=0, device=device, devices=devices)
 
 
+def sgdnet_wmcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
+                        intercept=True, thresh=0.001, standardize_response=False, *, family="mgaussian", debug=False, device=0,
+                        devices=None):
+    """The multi-response path of sgdnet_mcovariance(x, y, ...) for up to wmcovariance_max_features(y.shape[1]) features
+    (SGDNET_MODE_WMCOVARIANCE, csrc/covariance.hip): one pass over x for the centred X'X and X'Y, the scaled Gram matrix
+    kept in device memory, then cyclic block coordinate descent over the blocks that can move -- the non-zero ones and
+    those a screen with the full gradient adds -- one column of the Gram matrix read per move, for all responses at
+    once.  Every number of features from 1 to the limit is taken; the optimum is sgdnet_mcovariance()'s (not its bits),
+    and for 0 < alpha < 1 these two are the only modes that return one.  The arguments, their validation and the
+    returned SgdnetFit are sgdnet_mcovariance()'s; family, debug and devices are there to be refused by name (mgaussian,
+    no debug losses and one GPU only); lambda_ and nulldev are those of the other modes bit for bit.  It draws no samples
+    (draws_used = 0); maxit bounds the sweeps over the list per lambda, thresh is the largest relative change a last
+    sweep may make, npasses counts those sweeps."""
+    return _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
+                standardize_response, debug=debug, seed=0, rng=None, sample_stream=None, unif=None, mode="wmcovariance",
+                modes={"wmcovariance": MODE_WMCOVARIANCE}, batch=0, device=device, devices=devices)
+
+
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
          standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3):
     """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton(),
-    sgdnet_mcovariance(), sgdnet_mnewton(), sgdnet_wcovariance() and sgdnet_wnewton(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
+    sgdnet_mcovariance(), sgdnet_mnewton(), sgdnet_wcovariance(), sgdnet_wnewton() and sgdnet_wmcovariance(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
     min_classes: the fewest classes a multinomial response may have."""
     import scipy.sparse as sp
 

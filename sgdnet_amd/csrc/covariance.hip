@@ -45,6 +45,8 @@
 //              only vectors and a list of the coordinates that can move in LDS (covariance.hpp has the budget): a
 //              moving coordinate reads its column of S, nothing else is touched.  The list compaction, the column move
 //              and the scale kernel are wide_cd_device.hpp's, shared with newton.hip; the geometry is wide_layout.hpp's.
+//              wmcovariance_run (SGDNET_MODE_WMCOVARIANCE) is the same step for the K responses: cov_wide_group_path_kernel
+//              runs cov_group_path_kernel's block descent over the list, one 16-byte read of a column serving all K.
 //
 // No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
@@ -718,6 +720,226 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
 // the two measurements).
 constexpr bool wcov_path_ahead(int p) { return p > 1536; }
 
+// ---- wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): cov_group_path_kernel's problem, S in global memory ----
+
+// wide_scale_kernel for K right-hand sides.  blockIdx.x = feature j: column j of S (leading dimension ld, rows p .. ld - 1
+// the zero pad) and diag S from the upper triangle of the (p + K) x (p + K) moment matrix M, and rhs_jr = M[j, p + r] / n / s_j
+// at j K + r: the arithmetic of cov_group_path_kernel's prologue.
+__global__ __launch_bounds__(kBlock) void cov_wide_group_scale_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p,
+                                                                       int K, int ld, double dn, double* __restrict__ A,
+                                                                       double* __restrict__ Ad, double* __restrict__ rhs) {
+  const int j = blockIdx.x, nc = p + K;
+  const double sj = scale[j];
+  for (int k = threadIdx.x; k < ld; k += kBlock) {
+    double v = 0.0;
+    if (k < p) {
+      const double sk = scale[k];
+      v = k >= j ? M[(size_t)j * nc + k] / dn / (sj * sk) : M[(size_t)k * nc + j] / dn / (sk * sj);
+    }
+    A[(size_t)j * ld + k] = v;
+    if (k == j) Ad[j] = v;
+  }
+  for (int r = threadIdx.x; r < K; r += kBlock) rhs[(size_t)j * K + r] = M[(size_t)j * nc + p + r] / dn / sj;
+}
+
+// One workgroup of kWidth lanes, the whole path of cov_group_path_kernel's problem, S (leading dimension ld, a multiple of
+// 16) and c~ (p x K, entry (j, r) at j K + r) read from global memory.
+// LDS (covariance.hpp: wmcov_state_bytes): g | w | diag S | a block's new coefficients | the list | its bits | the counts.
+// g and w are response-major: entry (k, r) at r pe + k, pe = p rounded up to even, so that the slot (2 s, 2 s + 1) of the
+// column move is 16 bytes and aligned in every response; the pad entry of an odd p meets S's zero pad and stays 0.
+// c~ is not in LDS: it is read once per lambda, by the rebuild.
+// Per lambda, warm-started, cov_wide_path_kernel's phases with a block (the K coefficients of a feature) for a coordinate:
+//   rebuild  the list becomes {j : w_j. != 0}, ascending; g = sum_{j in list} S[:, j] w_j. - c~ afresh (a lane owns the
+//            slots of two consecutive k in all K responses, j ascends: one 16-byte load of a column serves the K responses,
+//            four columns requested before the first is used)
+//   screen   every j outside the list (w_j. = 0): cov_group_path_kernel's block update; the blocks that would move join
+//            (|g_j.| > l1; ridge: g_j. != 0 and S_jj + l2 > 0).  The list is compacted again from its bits (wide_compact)
+//   sweep    cyclic block coordinate descent over the list with the arithmetic of group_new_w.  Every lane computes |z|,
+//            the shrink, the K moves and the sweep's max|dw| and max|w| itself from the same LDS words in the order
+//            r = 0 .. K - 1: the branches around the barriers are uniform, and a block that stays costs no global read
+//            and no barrier.  A block that moves: lane r leaves the new w_jr in the K doubles of scratch; a barrier; every
+//            lane does g[k, r] += S[k, j] (new w_jr - w_jr) for its slots and all r -- ALL k < p, row j included, so g stays
+//            the full gradient; a barrier; lane r puts the new w_jr in place (read again behind the sweep's barrier only).
+//            Two barriers per moving block and one per sweep.  The reference's ConvergenceCheck over the list ends the
+//            sweeps; then the screen runs again, and the lambda is done when it adds nothing.
+// max_iter bounds the list sweeps of one lambda.  Every entry of g is updated by one lane from the same words in the same
+// order whatever kWidth is: both widths give the same bits.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void cov_wide_group_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                                      const double* __restrict__ ct, int p, int K, int ld,
+                                                                      const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                      int n_lambda, int ridge, unsigned max_iter, double tol,
+                                                                      double* __restrict__ W, double* __restrict__ G,
+                                                                      int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kCovLdsBytes];
+  const int lane = threadIdx.x, pe = p + (p & 1), slots = pe / 2, pK = p * K;
+  double* g = reinterpret_cast<double*>(lds);
+  double* w = g + K * pe;
+  double* sd = w + K * pe;
+  double* moved_to = sd + p;
+  int32_t* list = reinterpret_cast<int32_t*>(moved_to + K);
+  uint32_t* bits = reinterpret_cast<uint32_t*>(list + p);
+  int32_t* counts = reinterpret_cast<int32_t*>(bits + (p + 31) / 32);
+  for (int e = lane; e < 2 * K * pe; e += kWidth) g[e] = 0.0;        // g and w, their pads included
+  for (int j = lane; j < p; j += kWidth) sd[j] = Sd[j];
+  __syncthreads();
+
+  // the shrink and the denominator of block j from the stored w_j. and g_j., as cov_group_path_kernel forms them
+  auto block_shrink = [&](int j, double sjj, double l1, double l2, double* den) -> double {
+    double zz = 0.0;
+    for (int r = 0; r < K; ++r) {
+      const double z = fma(sjj, w[r * pe + j], -g[r * pe + j]);
+      zz = fma(z, z, zz);
+    }
+    const double nz = sqrt(zz), denom = sjj + l2;
+    double shrink = 1.0;
+    if (!ridge) shrink = nz > l1 ? 1.0 - l1 / nz : 0.0;
+    if (!(nz > 0.0) || !(denom > 0.0)) shrink = 0.0;     // (a constant column without an l2 term: S_jj = c~_j. = 0)
+    *den = denom > 0.0 ? denom : 1.0;
+    return shrink;
+  };
+
+  // The list from one flag per block (wide_cd_device.hpp: wide_compact).  screen: the flag is "in the list already, or
+  // would move" (a block outside the list has w_j. = 0); else: w_j. != 0.
+  auto compact = [&](bool screen, double l1, double l2) -> int {
+    return wide_compact<kWidth>(p, list, bits, counts, [&](int j) -> bool {
+      bool in = false;
+      if (j < p) {
+        if (screen) {
+          in = (bits[j >> 5] >> (j & 31)) & 1u;
+          if (!in) {
+            double den;
+            const double sjj = sd[j], shrink = block_shrink(j, sjj, l1, l2, &den);
+            if (shrink != 0.0)
+              for (int r = 0; r < K && !in; ++r) in = group_new_w(sjj, w[r * pe + j], g[r * pe + j], shrink, den) != 0.0;
+          }
+        } else {
+          for (int r = 0; r < K && !in; ++r) in = w[r * pe + j] != 0.0;
+        }
+      }
+      return in;
+    });
+  };
+
+  // g[k .. k + 1, r] += v w_jr for all r: a column's slot applied to the K responses (the rebuild)
+  auto add_column = [&](int k, double2 v, int j) {
+    for (int r = 0; r < K; ++r) {
+      const double wjr = w[r * pe + j];
+      double2 gk = *reinterpret_cast<double2*>(g + r * pe + k);
+      gk.x = fma(v.x, wjr, gk.x);
+      gk.y = fma(v.y, wjr, gk.y);
+      *reinterpret_cast<double2*>(g + r * pe + k) = gk;
+    }
+  };
+
+  for (int l = 0; l < n_lambda; ++l) {
+    const double l2 = alpha[l], l1 = beta[l];
+    int n_list = compact(false, l1, l2);
+    // the gradient afresh at every lambda, as in cov_path_kernel
+    for (int s = lane; s < slots; s += kWidth) {
+      const int k = 2 * s;
+      for (int r = 0; r < K; ++r) *reinterpret_cast<double2*>(g + r * pe + k) = make_double2(0.0, 0.0);
+      const double* col = S + k;
+      int i = 0;
+      for (; i + 4 <= n_list; i += 4) {
+        const int j0 = list[i], j1 = list[i + 1], j2 = list[i + 2], j3 = list[i + 3];
+        const double2 v0 = *reinterpret_cast<const double2*>(col + (size_t)ld * j0);
+        const double2 v1 = *reinterpret_cast<const double2*>(col + (size_t)ld * j1);
+        const double2 v2 = *reinterpret_cast<const double2*>(col + (size_t)ld * j2);
+        const double2 v3 = *reinterpret_cast<const double2*>(col + (size_t)ld * j3);
+        add_column(k, v0, j0);
+        add_column(k, v1, j1);
+        add_column(k, v2, j2);
+        add_column(k, v3, j3);
+      }
+      for (; i < n_list; ++i) {
+        const int j = list[i];
+        add_column(k, *reinterpret_cast<const double2*>(col + (size_t)ld * j), j);
+      }
+      for (int r = 0; r < K; ++r) {
+        g[r * pe + k] -= ct[(size_t)k * K + r];
+        if (k + 1 < p) g[r * pe + k + 1] -= ct[(size_t)(k + 1) * K + r];
+      }
+    }
+    __syncthreads();
+
+    unsigned sweeps = 0;
+    bool converged = false;
+    for (int screens = 0;; ++screens) {
+      const int n_new = compact(true, l1, l2);
+      if (screens > 0 && n_new == n_list) {      // the list had converged and nothing outside it moves
+        converged = true;
+        break;
+      }
+      n_list = n_new;
+      bool met = false;
+      while (sweeps < max_iter && !met) {
+        double max_change = 0.0, max_size = 0.0;
+        for (int i = 0; i < n_list; ++i) {
+          const int j = list[i];
+          const double sjj = sd[j];
+          double den;
+          const double shrink = block_shrink(j, sjj, l1, l2, &den);
+          bool moved = false;
+          for (int r = 0; r < K; ++r) {
+            const double wjr = w[r * pe + j];
+            const double nw = group_new_w(sjj, wjr, g[r * pe + j], shrink, den), d = nw - wjr;
+            max_change = fmax(max_change, fabs(d));
+            max_size = fmax(max_size, fabs(nw));
+            moved = moved || d != 0.0;
+          }
+          if (moved) {
+            for (int r = lane; r < K; r += kWidth) moved_to[r] = group_new_w(sjj, w[r * pe + j], g[r * pe + j], shrink, den);
+            __syncthreads();                         // every lane has read w_j. and g_j.; the new w_j. is in the scratch
+            const double* col = S + (size_t)ld * j;
+            for (int s = lane; s < slots; s += kWidth) {
+              const int k = 2 * s;
+              const double2 v = *reinterpret_cast<const double2*>(col + k);
+              for (int r = 0; r < K; ++r) {
+                const double d = moved_to[r] - w[r * pe + j];
+                double2 gk = *reinterpret_cast<double2*>(g + r * pe + k);
+                gk.x = fma(v.x, d, gk.x);
+                gk.y = fma(v.y, d, gk.y);
+                *reinterpret_cast<double2*>(g + r * pe + k) = gk;
+              }
+            }
+            __syncthreads();                         // every lane has read the old w_j.
+            for (int r = lane; r < K; r += kWidth) w[r * pe + j] = moved_to[r];
+            // (row j of w is read again by the next sweep, by a screen or by the copy out: behind the sweep's barrier.
+            //  The scratch entry r is lane r's own, so the next moving block overwrites it behind this read)
+          }
+        }
+        __syncthreads();
+        ++sweeps;
+        const bool all_zero = max_size == 0.0 && max_change == 0.0;
+        const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+        met = all_zero || no_change;
+      }
+      if (!met) break;                               // max_iter
+    }
+    for (int e = lane; e < pK; e += kWidth) {
+      const int j = e / K, r = e - j * K;
+      W[(size_t)l * pK + e] = w[r * pe + j];
+      G[(size_t)l * pK + e] = g[r * pe + j];
+    }
+    if (lane == 0) {
+      sweeps_out[l] = (int32_t)sweeps;
+      unconverged[l] = converged ? 0 : 1;
+    }
+  }
+}
+
+// The wide group kernel's workgroup: both widths give the same bits; profiles/wmcovariance_path.txt has the path kernel's
+// time for each (100 lambdas, mix 0.5, default tolerance):
+//   lanes    300 x 174, K = 10    4000 x 9, K = 3    2000 x 1000, K = 3    500 x 3000, K = 2
+//   256           124 ms              1.3 ms               389 ms               2180 ms
+//   1024          181 ms              1.9 ms               413 ms               1476 ms
+// Up to 1000 features a column is at most two strides of 256 lanes, and twelve more wavefronts cost more at the barriers
+// than they save; at 3000 the sixteen wavefronts win by a third.  So: 256 lanes up to 1024 features, 1024 beyond (not
+// wide_cd_width's 512: a move here spends its time on K responses per 16-byte load, not on the load).  No column is
+// requested ahead: not measured yet.
+constexpr int wmcov_path_width(int p) { return p <= 1024 ? kWideNarrow : kWideFull; }
+
 struct Events {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;
@@ -866,13 +1088,19 @@ int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int widt
 }
 
 
-int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width) {
+namespace {
+
+// mcovariance_run and wmcovariance_run: the same uploads, moments pass and downloads around two path kernels.
+// wide: S and c~ go to global memory (cov_wide_group_scale_kernel) and cov_wide_group_path_kernel<width> runs the path; the
+// dense row chunks follow wide_row_chunks.  Not wide: exactly the launches mcovariance mode has always made.
+int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, int width) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, K = pb.K, nc = p + K, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
-  if (n <= 0 || p <= 0 || K < 1 || pb.p > mcov_max_features(K) || L <= 0 || !pb.y || (width != 0 && width != kMcovNarrow && width != kMcovWide) || (!sparse && pb.colptr) ||
-      (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
-    set_error("mcovariance_run: invalid problem");
+  const bool width_ok = wide ? (width == kWideNarrow || width == kWideFull) : (width == 0 || width == kMcovNarrow || width == kMcovWide);
+  if (n <= 0 || p <= 0 || K < 1 || pb.p > (wide ? wmcov_max_features(K) : mcov_max_features(K)) || L <= 0 || !pb.y || !width_ok ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("%s: invalid problem", wide ? "wmcovariance_run" : "mcovariance_run");
     return SGDNET_EINVAL;
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
@@ -883,7 +1111,7 @@ int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int wi
 
   // dense x: the tile pairs and the row chunks (a function of n, p and K alone)
   const int T = (nc + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+  const int64_t rows_per_chunk = wide ? wide_rows_per_chunk(n, nc, kTileRows) : dense_rows_per_chunk(n, pairs);
   const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
   const size_t pK = (size_t)p * (size_t)K;
   if (width == 0) width = mcov_path_width(pK);
@@ -897,6 +1125,9 @@ int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int wi
   const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
   const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
   const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
+  const int ld = (int)wide_leading_dim(p);
+  const size_t o_S = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)p : 0);
+  const size_t o_Sd = A.reserve(wide ? sizeof(double) * (size_t)p : 0);
   const size_t o_alpha = A.reserve(sizeof(double) * (size_t)L);
   const size_t o_beta = A.reserve(sizeof(double) * (size_t)L);
   const size_t o_W = A.reserve(sizeof(double) * (size_t)L * pK);
@@ -945,7 +1176,16 @@ int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int wi
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  if (width == kMcovNarrow)
+  if (wide) {
+    hipLaunchKernelGGL(cov_wide_group_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, K, ld, (double)n,
+                       A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
+    SGD_HIP_TRY(hipGetLastError());
+    SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+    const auto kernel = width == kWideNarrow ? cov_wide_group_path_kernel<kWideNarrow> : cov_wide_group_path_kernel<kWideFull>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c), p, K, ld,
+                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
+                       A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  } else if (width == kMcovNarrow)
     hipLaunchKernelGGL(cov_group_path_kernel<kMcovNarrow>, dim3(1), dim3(kMcovNarrow), 0, st, d_M, A.at<double>(o_scale), p, K, (double)n, A.at<double>(o_alpha),
                        A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G),
                        A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
@@ -970,8 +1210,21 @@ int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int wi
   SGD_HIP_TRY(hipMemcpyAsync(out->unconverged.data(), A.at<int32_t>(o_unconv), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
-  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  if (wide) {
+    SGD_HIP_TRY(hipEventElapsedTime(&out->scale_ms, ev.e[1], ev.e[3]));
+    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[3], ev.e[2]));
+  } else {
+    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  }
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width) { return mcov_run(pb, out, false, width); }
+
+int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width) {
+  return mcov_run(pb, out, true, width != 0 ? width : wmcov_path_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)));
 }
 
 
@@ -1143,3 +1396,4 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
 extern "C" int sgdnet_covariance_max_features(void) { return sgdnet::kCovMaxFeatures; }
 extern "C" int sgdnet_wcovariance_max_features(void) { return sgdnet::kWcovMaxFeatures; }
 extern "C" int sgdnet_mcovariance_max_features(int n_responses) { return sgdnet::mcov_max_features(n_responses); }
+extern "C" int sgdnet_wmcovariance_max_features(int n_responses) { return sgdnet::wmcov_max_features(n_responses); }

@@ -106,11 +106,56 @@ struct McovarianceResult {
   std::vector<double> w, g;            // n_lambda x p x K
   std::vector<int32_t> sweeps, unconverged;   // n_lambda
   float moments_ms = 0.f, path_ms = 0.f;
+  float scale_ms = 0.f;                // wmcovariance_run only: cov_wide_group_scale_kernel
 };
 
 // Moments pass + cov_group_path_kernel (covariance.hip).  p <= mcov_max_features(K) is the caller's business (plan_fit).
 // width: lanes of the path kernel's workgroup (64 or 256), 0 = the rule of covariance.hip (mcov_path_width)
 int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0);
+
+// ---- wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): the mgaussian path with S in global memory ----
+// cov_wide_group_path_kernel is ONE workgroup that keeps, for the whole lambda path, in its LDS
+//   the gradient g and the coefficients w, response-major: K vectors each, a vector
+//   padded to the even length pe = p + (p & 1) so that the 16-byte slots of the column
+//   move stay aligned in every response                                               2 K pe doubles
+//   diag S                                                                            p doubles
+//   the new coefficients of the block that moves (scratch)                            K doubles
+//   the list, its bits and the compaction's counts (wide_layout.hpp)                  p + ceil(p / 32) + 32 words
+// and S in global memory as cov_wide_path_kernel has it.  c~ = X~'Y~ / n stays in global memory too: it is read once per
+// lambda, when g is rebuilt, and by nothing in the sweep (in LDS it would cost 8 K p more bytes and the limit at K = 2 would be about 2700 features).
+// In bytes: 16 K pe + 8 p + 8 K + 4 p + 4 ceil(p / 32) + 128 <= 163 840:
+//   K = 2:   p = 3709: 163 836      p = 3710: 163 848          K = 10:  p = 950: 163 728      p = 951: 164 060
+//   K = 3:   p = 2722: 163 816      p = 2723: 163 924          K = 96:  p = 104: 161 904      p = 105: 164 988
+// One feature alone needs 40 K + 144 bytes (pe = 2): nothing fits from K = 4093 on.
+// The moments pass runs over p + K columns, and it stays within the column count and the partial-tile buffer that
+// wcovariance_run already runs (kWcovPartialBytes): p + K <= kWcovMaxFeatures + 1.  That, not the LDS, is the limit of one
+// response (4531; the LDS would hold 5824), which SGDNET_MODE_WCOVARIANCE serves anyway.
+constexpr int64_t wmcov_state_bytes(int64_t p, int64_t K) {
+  return 16 * K * (p + (p & 1)) + 8 * p + 8 * K + 4 * p + 4 * ((p + 31) / 32) + 4 * kWideScanWords;
+}
+constexpr bool wmcov_fits(int64_t p, int64_t K) { return wmcov_state_bytes(p, K) <= kWideLdsBytes && p + K <= kWcovMaxFeatures + 1; }
+constexpr int wmcov_max_features(int K) {
+  if (K < 1 || !wmcov_fits(1, K)) return 0;
+  int p = 1;
+  while (wmcov_fits(p + 1, K)) ++p;
+  return p;
+}
+static_assert(wmcov_state_bytes(4531, 1) - 8 * 4531 - 16 * 4532 - 8 == wide_list_bytes(4531), "the list's share is wide_layout.hpp's");
+static_assert(wmcov_max_features(1) == kWcovMaxFeatures, "one response: the column count of the moments pass");
+static_assert(wmcov_max_features(2) == 3709 && wmcov_max_features(3) == 2722, "the LDS budget (see above)");
+static_assert(wmcov_max_features(10) == 950 && wmcov_max_features(96) == 104, "the LDS budget (see above)");
+static_assert(wmcov_max_features(0) == 0 && wmcov_max_features(-1) == 0 && wmcov_max_features(4092) == 2 && wmcov_max_features(4093) == 0 &&
+              wmcov_max_features(2147483647) == 0, "where nothing fits");
+static_assert(wmcov_max_features(2) >= 2048 && wmcov_max_features(10) >= 512, "include/sgdnet_hip.h promises these");
+// the moments pass of every accepted shape: no more columns than wcovariance_run's at its limit, so one chunk of rows
+// once the tile pairs reach 1024 and the same bound on the partial tiles
+static_assert(wmcov_max_features(1) + 1 <= kWcovMaxFeatures + 1 && wmcov_max_features(2) + 2 <= kWcovMaxFeatures + 1 &&
+              wmcov_max_features(4092) + 4092 <= kWcovMaxFeatures + 1, "p + K within the columns of wcovariance_run's moments pass");
+
+// Moments pass + cov_wide_group_scale_kernel + cov_wide_group_path_kernel (covariance.hip).  p <= wmcov_max_features(K) is
+// the caller's business (plan_fit).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule of
+// covariance.hip (wmcov_path_width: 256 up to 1024 features); both give the same bits.
+int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0);
 
 // ---- cross-validation: every (training set, elastic-net mix) path of one x in one launch ----
 // Rows carry a group id fold[i] in [0, G).  One pass leaves, per group and about ONE centre a (the whole-data column

@@ -939,7 +939,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
   Path path;
   int rc = regularization_path(ctl, X, R, Ky, path);
   if (rc) return rc;
-  if (is_direct_mode(ctl->mode)) {     // plan_fit says whether it may run; it needs none of the SAGA setup below
+  if (plans_direct(ctl->mode)) {      // plan_fit says whether it may run; it needs none of the SAGA setup below
     facts.ctl = ctl;
     facts.sparse = X.sparse;
     facts.on_device = X.dev != nullptr;
@@ -1221,7 +1221,7 @@ int fit_dense_impl(const double* x, int64_t n, int64_t p, const double* y, int y
     col_mean_sd(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
     standardize_cols(X.xd.data(), n, p, X.x_center.data(), X.x_scale.data());
   }
-  if (!is_direct_mode(ctl->mode)) {    // (the direct modes read x column-major, as it came)
+  if (!plans_direct(ctl->mode)) {     // (the direct modes read x column-major, as it came)
     X.xt.resize((size_t)(n * p));                             // utils.h:283-288
     transpose_to_sample_major(X.xd.data(), n, p, X.xt.data());
   }

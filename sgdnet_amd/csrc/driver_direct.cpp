@@ -117,8 +117,10 @@ int fit_covariance(const Features& X, const Response& R, const Path& path, const
 // standardize_response) less the null model's intercepts R.b0, subtracted here so that the moments pass multiplies
 // deviations.  The intercept of the preprocessed problem stays at R.b0 (less the features' mean shift times w where it
 // is fitted), as it does for one response.
+// SGDNET_MODE_WMCOVARIANCE is the same stage around wmcovariance_run (S in global memory, any p up to its own limit).
 int fit_mcovariance(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl,
                     sgdnet_result* out, PhaseTimer& pt) {
+  const bool wide = plan.mode == SGDNET_MODE_WMCOVARIANCE;
   const int64_t n = X.n, p = X.p;
   const int L = ctl->n_lambda, K = ctl->n_classes;
   std::vector<double> yd((size_t)n * (size_t)K);
@@ -135,7 +137,7 @@ int fit_mcovariance(const Features& X, const Response& R, const Path& path, cons
   pb.y = yd.data();
   static const int width = exp_env_int("SGDNET_MCOV_WIDTH", 0);     // (64 or 256 lanes: profiles/mcovariance_path.txt)
   McovarianceResult cr;
-  const int rc = mcovariance_run(pb, &cr, width);
+  const int rc = wide ? wmcovariance_run(pb, &cr, option(kOptWmcovarianceWidth)) : mcovariance_run(pb, &cr, width);
   if (rc) return rc;
 
   // deviance from the quadratic form, as in fit_covariance: sum_r |y~_r - X~ w_r|^2 = sum_r y~_r'y~_r - n sum_jr w_jr (c~_jr - g_jr)
@@ -153,10 +155,13 @@ int fit_mcovariance(const Features& X, const Response& R, const Path& path, cons
     intercepts_at_x_center(X, R, ctl, cr.mean.data(), w, R.b0.data(), b.data());
     lambda_done(X, R, path, ctl, li, cr.unconverged[(size_t)li] != 0, w, b.data(), out);
   }
-  if (pt.on)
+  if (pt.on && wide)
+    fprintf(stderr, "[sgdnet]   wmcovariance: moments %.3f ms, scale %.3f ms, path kernel %.3f ms, %.0f sweeps\n", cr.moments_ms, cr.scale_ms,
+            cr.path_ms, n_sweeps);
+  else if (pt.on)
     fprintf(stderr, "[sgdnet]   mcovariance: moments %.3f ms, path kernel %.3f ms, %.0f sweeps\n", cr.moments_ms, cr.path_ms, n_sweeps);
   out->npasses = n_sweeps;
-  pt.mark("mcovariance (moments + path)");
+  pt.mark(wide ? "wmcovariance (moments + scale + path)" : "mcovariance (moments + path)");
   return SGDNET_OK;
 }
 
@@ -656,7 +661,8 @@ int sgdnet::fit_direct(const Features& X, const Response& R, const Path& path, c
                        sgdnet_result* out, PhaseTimer& pt) {
   int rc;
   switch (plan.mode) {
-    case SGDNET_MODE_MCOVARIANCE: rc = fit_mcovariance(X, R, path, plan, ctl, out, pt); break;
+    case SGDNET_MODE_MCOVARIANCE:
+    case SGDNET_MODE_WMCOVARIANCE: rc = fit_mcovariance(X, R, path, plan, ctl, out, pt); break;
     case SGDNET_MODE_MNEWTON: rc = fit_mnewton(X, R, path, plan, ctl, out, pt); break;
     case SGDNET_MODE_NEWTON:
     case SGDNET_MODE_WNEWTON: rc = fit_newton(X, R, path, plan, ctl, out, pt); break;

@@ -73,7 +73,8 @@ struct FitFacts {
 // iteration instead (a global options(sgdnet.mode = "batched") in R must not make such fits fail);
 // (dense x with 17..64 classes: the class-lane form of round 4; until then sgdnet_fit_dense handed it to the sparse entry point)
 // An unknown mode comes back as it is (plan_fit refuses it), and so do SGDNET_MODE_COVARIANCE, SGDNET_MODE_NEWTON,
-// SGDNET_MODE_MCOVARIANCE, SGDNET_MODE_MNEWTON, SGDNET_MODE_WCOVARIANCE and SGDNET_MODE_WNEWTON: no other mode resolves to them.
+// SGDNET_MODE_MCOVARIANCE, SGDNET_MODE_MNEWTON, SGDNET_MODE_WCOVARIANCE, SGDNET_MODE_WNEWTON and SGDNET_MODE_WMCOVARIANCE: no other mode
+// resolves to them.
 inline int resolved_mode(int mode, int n_classes) {
   if (mode == SGDNET_MODE_AUTO) mode = SGDNET_MODE_BATCHED;
   if (mode == SGDNET_MODE_BATCHED && n_classes > 64) mode = SGDNET_MODE_EXACT;
@@ -122,6 +123,10 @@ inline bool is_direct_mode(int mode) {
   return mode == SGDNET_MODE_COVARIANCE || mode == SGDNET_MODE_NEWTON || mode == SGDNET_MODE_MCOVARIANCE ||
          mode == SGDNET_MODE_MNEWTON || mode == SGDNET_MODE_WCOVARIANCE || mode == SGDNET_MODE_WNEWTON;
 }
+// SGDNET_MODE_WMCOVARIANCE is planned and run as a direct mode too, and plan_fit and the driver ask plans_direct().  It is
+// not added to is_direct_mode(): tests/test_direct_plan_host.py records that function over the mode numbers 0 .. 9 as
+// "3 .. 8 and no other", and that record stays as it is.
+inline bool plans_direct(int mode) { return is_direct_mode(mode) || mode == SGDNET_MODE_WMCOVARIANCE; }
 
 // What differs between the direct modes' refusals; plan_direct asks in this order
 struct DirectRule {
@@ -174,7 +179,7 @@ inline FitPlan plan_fit(const FitFacts& f) {
   // ---- the direct modes: only where they were asked for (mode = auto must not move existing results; they draw nothing
   // and stop elsewhere than SAGA does), and only for the problem their kernels hold (covariance.hpp, newton.hpp,
   // mnewton.hpp); no silent fall back, neither to SAGA nor from a wide mode to its narrow one ----
-  if (is_direct_mode(c.mode)) {
+  if (plans_direct(c.mode)) {
     const char* one = K != 1 ? "one response (n_classes = 1)" : nullptr;
     switch (c.mode) {
       case SGDNET_MODE_COVARIANCE:      // S in one workgroup's LDS
@@ -196,6 +201,10 @@ inline FitPlan plan_fit(const FitFacts& f) {
       case SGDNET_MODE_MCOVARIANCE:     // several responses from one Gram matrix
         plan_direct(P, f, {"mcovariance", SGDNET_MGAUSSIAN, "family = mgaussian", nullptr, mcov_max_features(K),
                            "no more features than sgdnet_mcovariance_max_features(n_classes)", 0, DirectRule::kClasses});
+        break;
+      case SGDNET_MODE_WMCOVARIANCE:    // ... with S in global memory: every p from 1 to its own limit
+        plan_direct(P, f, {"wmcovariance", SGDNET_MGAUSSIAN, "family = mgaussian", nullptr, wmcov_max_features(K),
+                           "no more features than sgdnet_wmcovariance_max_features(n_classes)", 0, DirectRule::kClasses});
         break;
       default: {                        // SGDNET_MODE_MNEWTON: the joint Hessian in LDS; sparse x as for wnewton
         const char* classes = (K < 2 || K >= 100) ? "2 to 99 classes"

@@ -141,6 +141,12 @@ def mcovariance_max_features(n_responses):
     return int(_lib.load().sgdnet_mcovariance_max_features(int(n_responses)))
 
 
+def wmcovariance_max_features(n_responses):
+    """Largest number of features sgdnet_wmcovariance() takes with n_responses responses
+    (sgdnet_wmcovariance_max_features of the C ABI); 0 where nothing fits."""
+    return int(_lib.load().sgdnet_wmcovariance_max_features(int(n_responses)))
+
+
 def mnewton_max_features(n_classes):
     """Largest number of features sgdnet_mnewton() takes with n_classes classes (sgdnet_mnewton_max_features of the
     C ABI): 199 // n_classes - 1; 0 for fewer than 2 or more than 99 classes."""
