@@ -164,6 +164,21 @@ extern "C" {
  * max_iter bounds the sweeps over the list of one lambda and result.npasses counts those sweeps.  Same optimum as
  * SGDNET_MODE_MCOVARIANCE, not the same bits. */
 #define SGDNET_MODE_WMCOVARIANCE 9
+/* sgdnet_fit_* only, and only when asked for (no other mode resolves to it; an addition of ABI 6): SGDNET_MODE_MNEWTON's
+ * problem and outer loop for up to sgdnet_wmnewton_max_features(n_classes) features.  Per Newton step the scaled joint
+ * Hessian of all Q = n_classes x (n_features + 1) coordinates is written to global memory as a full symmetric matrix;
+ * one workgroup keeps the gradient, the coordinates, diag H and an ascending list of the coordinates that can move in
+ * its LDS, runs cyclic coordinate descent over that list and reads one column of H per coordinate that moves;
+ * coordinates outside the list are screened with the full gradient and join when they would move; the n_classes
+ * intercepts are unpenalised members of the list (sgdnet_amd/csrc/mnewton.hip: mnewton_wide_cd_kernel).  Takes every
+ * n_features from 1 to the limit.  Sparse x is expanded to a dense copy (at most 1 GiB) and gives the dense fit's bits.
+ * Needs family = multinomial with the ungrouped penalty, 2 <= n_classes <= 99, n_features <=
+ * sgdnet_wmnewton_max_features(n_classes), n_gpus <= 1, debug = 0 and that copy within its bound; anything else returns
+ * SGDNET_EUNSUPPORTED and sgdnet_last_error() names the condition ("mode = wmnewton needs ...") -- no fall back to SAGA
+ * or to SGDNET_MODE_MNEWTON.  Draws, rng_state, draws_used, max_iter, tol, return_codes, npasses, the class-centred a0,
+ * lambda, nulldev, dev_ratio, intercept = 0 and standardize = 0 are SGDNET_MODE_MNEWTON's.  Same optimum as
+ * SGDNET_MODE_MNEWTON, not the same bits. */
+#define SGDNET_MODE_WMNEWTON 10
 
 /* x as R passes it to SgdnetSparse: the slots of a dgCMatrix (R/sgdnet.R:226). */
 typedef struct sgdnet_csc {
@@ -275,6 +290,10 @@ int sgdnet_wmcovariance_max_features(int n_responses);
  * Q = n_classes (n_features + 1) <= 199: 199 / n_classes - 1 (98 at K = 2, 65 at K = 3, 38 at K = 5, 18 at K = 10,
  * 1 at K = 99); 0 for n_classes < 2 or >= 100 */
 int sgdnet_mnewton_max_features(int n_classes);
+/* the largest n_features SGDNET_MODE_WMNEWTON takes with n_classes classes: the LDS holds 3 Q doubles, Q list words and
+ * Q bits, Q = n_classes (n_features + 1) <= 5820: 5820 / n_classes - 1 (2909 at K = 2, 1939 at K = 3, 1163 at K = 5,
+ * 581 at K = 10, 57 at K = 99); 0 for n_classes < 2 or >= 100 */
+int sgdnet_wmnewton_max_features(int n_classes);
 
 /* ------------------------------------------------------------------------ */
 /* Process-wide backend options.  These are the ONLY switches that change    */
@@ -329,6 +348,10 @@ int sgdnet_mnewton_max_features(int n_classes);
 /*                        256 or 1024: on that many (same bits either way;    */
 /*                        any other value makes such a fit return             */
 /*                        SGDNET_EINVAL)                                      */
+/*   "wmnewton_width"     0 (default): SGDNET_MODE_WMNEWTON's inner solve runs */
+/*                        on 256 or 1024 lanes by the library's rule; 256 or  */
+/*                        1024: on that many (same bits either way; any       */
+/*                        other value makes such a fit return SGDNET_EINVAL)  */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

@@ -5,13 +5,13 @@ include/sgdnet_hip.h).  This package is the host-side mirror of the reference's
 R front-end for the fit path plus benchmark/multi-GPU plumbing.
 """
 from ._lib import LIB_PATH, SgdnetError, load  # noqa: F401
-from .api import SgdnetFit, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance, sgdnet_wnewton  # noqa: F401
+from .api import SgdnetFit, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance, sgdnet_wmnewton, sgdnet_wnewton  # noqa: F401
 from .cv import CvSgdnet, cv_covariance_fits, cv_newton_fits, cv_sgdnet, cv_sgdnet_newton  # noqa: F401
 from .kkt import (evaluation_intercepts, feature_moments, kkt, kkt_from_gradient, path_gradient,  # noqa: F401
                   response_moments)
 from .predict import coef, predict  # noqa: F401
 from .score import score  # noqa: F401
-from .solver import (RRng, SagaSolver, auto_batch, covariance_max_features, get_option, link_peers, mcovariance_max_features, mnewton_max_features, newton_max_features, option, set_option, wcovariance_max_features, wmcovariance_max_features, wnewton_max_features,  # noqa: F401
+from .solver import (RRng, SagaSolver, auto_batch, covariance_max_features, get_option, link_peers, mcovariance_max_features, mnewton_max_features, newton_max_features, option, set_option, wcovariance_max_features, wmcovariance_max_features, wmnewton_max_features, wnewton_max_features,  # noqa: F401
                      shard_window)
 
 __all__ = ["sgdnet", "SgdnetFit", "SagaSolver", "RRng", "auto_batch", "SgdnetError", "load", "LIB_PATH",
@@ -20,4 +20,5 @@ __all__ = ["sgdnet", "SgdnetFit", "SagaSolver", "RRng", "auto_batch", "SgdnetErr
            "covariance_max_features", "cv_covariance_fits", "sgdnet_newton", "newton_max_features",
            "cv_newton_fits", "cv_sgdnet_newton", "sgdnet_mcovariance", "mcovariance_max_features",
            "sgdnet_mnewton", "mnewton_max_features", "sgdnet_wcovariance", "wcovariance_max_features",
-           "sgdnet_wnewton", "wnewton_max_features", "sgdnet_wmcovariance", "wmcovariance_max_features"]
+           "sgdnet_wnewton", "wnewton_max_features", "sgdnet_wmcovariance", "wmcovariance_max_features",
+           "sgdnet_wmnewton", "wmnewton_max_features"]

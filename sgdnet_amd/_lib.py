@@ -39,7 +39,7 @@ EXPORTS = [
     "sgdnet_newton_probe_dense", "sgdnet_newton_probe_sparse",
     "sgdnet_cv_newton_dense", "sgdnet_cv_newton_sparse", "sgdnet_mcovariance_max_features",
     "sgdnet_mnewton_max_features", "sgdnet_mnewton_probe", "sgdnet_wcovariance_max_features",
-    "sgdnet_wnewton_max_features", "sgdnet_wmcovariance_max_features",
+    "sgdnet_wnewton_max_features", "sgdnet_wmcovariance_max_features", "sgdnet_wmnewton_max_features",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -53,6 +53,7 @@ MODE_MNEWTON = 6   # SGDNET_MODE_MNEWTON: reached through sgdnet_mnewton(), like
 MODE_WCOVARIANCE = 7   # SGDNET_MODE_WCOVARIANCE: reached through sgdnet_wcovariance(), likewise
 MODE_WNEWTON = 8   # SGDNET_MODE_WNEWTON: reached through sgdnet_wnewton(), likewise
 MODE_WMCOVARIANCE = 9   # SGDNET_MODE_WMCOVARIANCE: reached through sgdnet_wmcovariance(), likewise
+MODE_WMNEWTON = 10   # SGDNET_MODE_WMNEWTON: reached through sgdnet_wmnewton(), likewise
 
 UNIF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
 LOSSES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)
@@ -273,6 +274,7 @@ def load():
     L.sgdnet_mcovariance_max_features.argtypes = [C.c_int]
     L.sgdnet_mnewton_max_features.argtypes = [C.c_int]
     L.sgdnet_wmcovariance_max_features.argtypes = [C.c_int]
+    L.sgdnet_wmnewton_max_features.argtypes = [C.c_int]
     L.sgdnet_wcovariance_max_features.argtypes = []
     L.sgdnet_wnewton_max_features.argtypes = []
     L.sgdnet_mnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(MNewtonProbe)]

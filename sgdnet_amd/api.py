@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODE_WNEWTON, MODES, check, dptr
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODE_WMNEWTON, MODE_WNEWTON, MODES, check, dptr
 
 _FAMILY_CHOICES = ("gaussian", "binomial", "multinomial", "mgaussian")
 
@@ -179,10 +179,26 @@ def sgdnet_wmcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambd
                 modes={"wmcovariance": MODE_WMCOVARIANCE}, batch=0, device=device, devices=devices)
 
 
+def sgdnet_wmnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
+                    intercept=True, thresh=0.001, *, device=0):
+    """The multinomial path of sgdnet_mnewton(x, y, ...) for up to wmnewton_max_features(K) = 5820 // K - 1 features
+    (2909 at K = 2, 1939 at K = 3, 581 at K = 10), K <= 99 (SGDNET_MODE_WMNEWTON, csrc/mnewton.hip): sgdnet_mnewton()'s
+    outer loop with the joint Hessian of all K (p + 1) coordinates kept in device memory and cyclic coordinate descent
+    over the coordinates that can move -- the non-zero ones, the intercepts and those a screen with the full gradient
+    adds -- one column of the Hessian read per move.  Every number of features from 1 to the limit is taken; the optimum
+    is sgdnet_mnewton()'s (not its bits); neither falls back to the other.  Sparse x is expanded to a dense copy first
+    (at most 1 GiB) and gives the dense fit's bits.  The arguments, their validation, the response encoding, the
+    returned SgdnetFit, the class-centred a0, what maxit, thresh and npasses mean and the remark on alpha = 1 with an
+    even number of classes are sgdnet_mnewton()'s."""
+    return _fit(x, y, "multinomial", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh, False,
+                debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="wmnewton", modes={"wmnewton": MODE_WMNEWTON},
+                batch=0, device=device, devices=None, min_classes=2)
+
+
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
          standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3):
     """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton(),
-    sgdnet_mcovariance(), sgdnet_mnewton(), sgdnet_wcovariance(), sgdnet_wnewton() and sgdnet_wmcovariance(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
+    sgdnet_mcovariance(), sgdnet_mnewton(), sgdnet_wcovariance(), sgdnet_wnewton(), sgdnet_wmcovariance() and sgdnet_wmnewton(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
     min_classes: the fewest classes a multinomial response may have."""
     import scipy.sparse as sp
 

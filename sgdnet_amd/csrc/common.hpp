@@ -40,7 +40,7 @@ inline const char* exp_env_str(const char*) { return nullptr; }
 // sgdnet_set_option values (solver.cpp)
 enum Option { kOptVirtualShards = 0, kOptRngGenerators, kOptWindowEigenvalue, kOptHostSetup, kOptExactEpochBlocks,
               kOptExactRowRegisters, kOptFusedEpoch, kOptWcovarianceWidth, kOptWnewtonWidth, kOptWmcovarianceWidth,
-              kOptCount };
+              kOptWmnewtonWidth, kOptCount };
 int option(Option o);
 
 #define SGD_HIP_TRY(expr)                                                              \

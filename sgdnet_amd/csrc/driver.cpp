@@ -1122,9 +1122,9 @@ int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdn
   X.raw_values = x->values;
   const int64_t n = X.n, p = X.p, nnz = x->colptr[p];
   if ((rc = validate_colptr(x)) || (rc = validate_response(ctl, y, n)) || (rc = validate_rowidx(x))) return rc;
-  if (ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WNEWTON) {
+  if (ctl->mode == SGDNET_MODE_MNEWTON || ctl->mode == SGDNET_MODE_WNEWTON || ctl->mode == SGDNET_MODE_WMNEWTON) {
     // These modes read x dense (mnewton holds at most 98 features; wnewton's sparse moments would be p (p + 2) workgroups a
-    // step).  The copy is made here, before anything is computed from x, so that the standard deviations, lambda_max and
+    // step; wmnewton's class-pair moments have no sparse form).  The copy is made here, before anything is computed from x, so that the standard deviations, lambda_max and
     // everything after them are the dense fit's of the same matrix, bit for bit.  The plan's refusals come first: one of
     // them is the size of this copy.  Entries stored twice add up.
     FitFacts facts;

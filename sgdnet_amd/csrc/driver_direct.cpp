@@ -210,8 +210,10 @@ int fit_newton(const Features& X, const Response& R, const Path& path, const Fit
 // that starts at the null model's value (and stays there without an intercept).  The loss does not see a shift common
 // to all intercepts: they are returned with their class mean removed (kkt.py removes the class mean of G0 likewise).
 // (sparse x came here as its dense copy: fit_sparse_impl)
+// SGDNET_MODE_WMNEWTON is the same stage around wmnewton_run (the joint Hessian in global memory, any p up to its own limit).
 int fit_mnewton(const Features& X, const Response& R, const Path& path, const FitPlan& plan, const sgdnet_control* ctl, sgdnet_result* out,
                 PhaseTimer& pt) {
+  const bool wide = plan.mode == SGDNET_MODE_WMNEWTON;
   const int64_t n = X.n, p = X.p;
   const int L = ctl->n_lambda, K = ctl->n_classes;
   MNewtonProblem pb;
@@ -222,7 +224,7 @@ int fit_mnewton(const Features& X, const Response& R, const Path& path, const Fi
   pb.b0 = R.b0.data();
   static const int width = exp_env_int("SGDNET_MNEWTON_WIDTH", 0);  // (64 or 256 lanes: profiles/mnewton_path.txt)
   MNewtonResult nr;
-  const int rc = mnewton_run(pb, pt.on, &nr, width);
+  const int rc = wide ? wmnewton_run(pb, pt.on, &nr, option(kOptWmnewtonWidth)) : mnewton_run(pb, pt.on, &nr, width);
   if (rc) return rc;
   const int64_t P = p + 1;
   double n_steps = 0.0;
@@ -245,11 +247,14 @@ int fit_mnewton(const Features& X, const Response& R, const Path& path, const Fi
     n_steps += (double)nr.steps[(size_t)li];
     lambda_done(X, R, path, ctl, li, nr.unconverged[(size_t)li] != 0, w.data(), b.data(), out);
   }
-  if (pt.on)
+  if (pt.on && wide)
+    fprintf(stderr, "[sgdnet]   wmnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
+            "scale %.3f ms, inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.scale_ms, nr.cd_ms);
+  else if (pt.on)
     fprintf(stderr, "[sgdnet]   mnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
             "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);
   out->npasses = nr.passes;
-  pt.mark("mnewton (state + moments + cd)");
+  pt.mark(wide ? "wmnewton (state + moments + scale + cd)" : "mnewton (state + moments + cd)");
   return SGDNET_OK;
 }
 
@@ -663,7 +668,8 @@ int sgdnet::fit_direct(const Features& X, const Response& R, const Path& path, c
   switch (plan.mode) {
     case SGDNET_MODE_MCOVARIANCE:
     case SGDNET_MODE_WMCOVARIANCE: rc = fit_mcovariance(X, R, path, plan, ctl, out, pt); break;
-    case SGDNET_MODE_MNEWTON: rc = fit_mnewton(X, R, path, plan, ctl, out, pt); break;
+    case SGDNET_MODE_MNEWTON:
+    case SGDNET_MODE_WMNEWTON: rc = fit_mnewton(X, R, path, plan, ctl, out, pt); break;
     case SGDNET_MODE_NEWTON:
     case SGDNET_MODE_WNEWTON: rc = fit_newton(X, R, path, plan, ctl, out, pt); break;
     default: rc = fit_covariance(X, R, path, plan, ctl, out, pt); break;

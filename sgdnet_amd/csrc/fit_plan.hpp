@@ -123,10 +123,10 @@ inline bool is_direct_mode(int mode) {
   return mode == SGDNET_MODE_COVARIANCE || mode == SGDNET_MODE_NEWTON || mode == SGDNET_MODE_MCOVARIANCE ||
          mode == SGDNET_MODE_MNEWTON || mode == SGDNET_MODE_WCOVARIANCE || mode == SGDNET_MODE_WNEWTON;
 }
-// SGDNET_MODE_WMCOVARIANCE is planned and run as a direct mode too, and plan_fit and the driver ask plans_direct().  It is
-// not added to is_direct_mode(): tests/test_direct_plan_host.py records that function over the mode numbers 0 .. 9 as
-// "3 .. 8 and no other", and that record stays as it is.
-inline bool plans_direct(int mode) { return is_direct_mode(mode) || mode == SGDNET_MODE_WMCOVARIANCE; }
+// SGDNET_MODE_WMCOVARIANCE and SGDNET_MODE_WMNEWTON are planned and run as direct modes too, and plan_fit and the driver ask
+// plans_direct().  They are not added to is_direct_mode(): tests/test_direct_plan_host.py records that function over the mode
+// numbers 0 .. 9 as "3 .. 8 and no other", and that record stays as it is.
+inline bool plans_direct(int mode) { return is_direct_mode(mode) || mode == SGDNET_MODE_WMCOVARIANCE || mode == SGDNET_MODE_WMNEWTON; }
 
 // What differs between the direct modes' refusals; plan_direct asks in this order
 struct DirectRule {
@@ -209,8 +209,12 @@ inline FitPlan plan_fit(const FitFacts& f) {
       default: {                        // SGDNET_MODE_MNEWTON: the joint Hessian in LDS; sparse x as for wnewton
         const char* classes = (K < 2 || K >= 100) ? "2 to 99 classes"
                               : c.type_multinomial != 0 ? "the ungrouped penalty (type_multinomial = 0)" : nullptr;
-        plan_direct(P, f, {"mnewton", SGDNET_MULTINOMIAL, "family = multinomial", classes, mnewton_max_features(K),
-                           "no more features than sgdnet_mnewton_max_features(n_classes)", kMNewtonDenseCopyBytes, DirectRule::kSamples});
+        if (c.mode == SGDNET_MODE_WMNEWTON)     // ... with the joint Hessian in global memory: every p from 1 to its own limit
+          plan_direct(P, f, {"wmnewton", SGDNET_MULTINOMIAL, "family = multinomial", classes, wmnewton_max_features(K),
+                             "no more features than sgdnet_wmnewton_max_features(n_classes)", kWmnewtonDenseCopyBytes, DirectRule::kSamples});
+        else
+          plan_direct(P, f, {"mnewton", SGDNET_MULTINOMIAL, "family = multinomial", classes, mnewton_max_features(K),
+                             "no more features than sgdnet_mnewton_max_features(n_classes)", kMNewtonDenseCopyBytes, DirectRule::kSamples});
       }
     }
     return P;

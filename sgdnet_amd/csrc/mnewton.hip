@@ -28,6 +28,12 @@
 //   accept     the state pass at the candidate gives its objective; the host halves a step after which it rose
 //              (mnewton_blend_kernel), at most kNewtonMaxHalvings times.  The accepted candidate's pass is the next step's.
 //
+// Wide multinomial Newton mode (SGDNET_MODE_WMNEWTON, wmnewton_run) is the same outer loop for Q up to 5820 (mnewton.hpp):
+// the state and moments passes as they are (the row chunks by wmnewton_row_chunks), then mnewton_wide_scale_kernel writes
+// the full symmetric H, diag H and q to global memory and mnewton_wide_cd_kernel runs the shared wide descent core
+// (wide_cd_device.hpp) over the Q coordinates; the blend forms its value where it is read (mnewton_wide_blend_kernel).
+// Same optimum as the narrow mode, not the same bits; neither falls back to the other.
+//
 // x is dense, column-major: this mode's p is at most 98, and the driver expands sparse x before anything is computed from
 // it (driver.cpp: fit_sparse_impl), so that a sparse fit is the dense fit of the same matrix from the standard deviations
 // and lambda_max on, bit for bit.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K):
@@ -44,6 +50,7 @@
 #include "device_math.hpp"
 #include "mnewton.hpp"
 #include "moments_device.hpp"
+#include "wide_cd_device.hpp"
 
 namespace sgdnet {
 namespace {
@@ -299,9 +306,182 @@ __global__ __launch_bounds__(kWidth) void mnewton_cd_kernel(const double* __rest
 // One wavefront while one stride of it covers the coordinates; 256 lanes beyond (profiles/mnewton_path.txt).
 int mnewton_cd_width(int Q) { return Q <= 64 ? 64 : 256; }
 
+// ---- wide multinomial Newton mode (SGDNET_MODE_WMNEWTON, wmnewton_run): H in global memory, only what can move is touched ----
+
+// mnewton_blend_kernel without an array of kMNewtonMaxCoordinates doubles: mnewton_publish reads every coordinate once, by
+// the lane that then writes it, so the blend is formed where it is read (newton.hip: BlendedCandidate).
+struct BlendedCandidate {
+  const double* u_cur;
+  const double* u_cand;
+  double t;
+  __device__ __forceinline__ double operator[](int c) const { return t == 1.0 ? u_cand[c] : u_cur[c] + t * (u_cand[c] - u_cur[c]); }
+};
+
+__global__ __launch_bounds__(64) void mnewton_wide_blend_kernel(const double* u_cur, const double* __restrict__ scale, int p, int Q, double t,
+                                                                 double* u_cand, double* __restrict__ a_cand, double* __restrict__ rec) {
+  mnewton_publish(BlendedCandidate{u_cur, u_cand, t}, u_cur, scale, p, Q, u_cand, a_cand, rec);
+}
+
+// blockIdx.x = column c2 of the joint Hessian over the Q = K P coordinates: H[c1 + ld c2] for all c1 < Q from the
+// K (K + 1) / 2 pair moments with the arithmetic of mnewton_cd_kernel's prologue -- M[pair(k, l)][lo nc + hi] / dn / (s_a s_b),
+// the class pair in ascending order on either side of the diagonal, s = scale for the p features and 1 for the intercepts --
+// so an entry has the bits the narrow kernel would hold; rows Q .. ld - 1 are the zero pad.  Also diag H, and
+// q[c2] = M[pair(l, l)][b nc + p + 1] / dn / s_b.
+__global__ __launch_bounds__(kBlock) void mnewton_wide_scale_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
+                                                                     int ld, double dn, double* __restrict__ H, double* __restrict__ Hd,
+                                                                     double* __restrict__ q) {
+  const int P = p + 1, nc = p + 2, Q = K * P;
+  const size_t block = (size_t)nc * (size_t)nc;
+  const int c2 = blockIdx.x, l = c2 / P, b = c2 - l * P;
+  const double sb = b < p ? scale[b] : 1.0;
+  for (int c1 = threadIdx.x; c1 < ld; c1 += kBlock) {
+    double v = 0.0;
+    if (c1 < Q) {
+      const int k = c1 / P, a = c1 - k * P;
+      const int lo = a < b ? a : b, hi = a < b ? b : a;
+      const double sa = a < p ? scale[a] : 1.0;
+      const int pair = k <= l ? class_pair_index(k, l, K) : class_pair_index(l, k, K);
+      // (the narrow kernel multiplies the scale of the smaller coordinate by that of the larger; the product commutes)
+      v = M[(size_t)pair * block + (size_t)lo * nc + hi] / dn / (sa * sb);
+    }
+    H[(size_t)c2 * ld + c1] = v;
+    if (c1 == c2) Hd[c2] = v;
+  }
+  if (threadIdx.x == 0) q[c2] = M[(size_t)class_pair_index(l, l, K) * block + (size_t)b * nc + p + 1] / dn / sb;
+}
+
+// The coordinate update of mnewton_cd_kernel, for the screen (u_j = 0) and for the sweep: from H_jj, u_j and g_j to the new
+// u_j.  Its two rules that newton_coord_new_u has not: a coordinate whose denominator is not positive stays where it is, and
+// what the threshold leaves of a penalised coordinate when |z| equals it but for rounding is an exact zero (where the
+// denominator is positive, and not under ridge).  Every caller passes the same words through the same operations, so every
+// lane holds the same bits.
+__device__ __forceinline__ double mnewton_coord_new_u(double hjj, double uj, double gj, double al, double be, int ridge, bool penalised) {
+  const double z = hjj * uj - gj, denom = penalised ? hjj + al : hjj;
+  double nu = z;
+  if (penalised && !ridge) nu = z > be ? z - be : (z < -be ? z + be : 0.0);
+  nu = denom > 0.0 ? nu / denom : uj;
+  if (penalised && !ridge && denom > 0.0 && nu * nu * hjj <= kNewtonNegligible * kNewtonNegligible) nu = 0.0;
+  return nu;
+}
+
+// One workgroup of kWidth lanes, one inner solve, H (leading dimension ld, a multiple of 16) read from global memory:
+// newton_wide_cd_kernel over the Q joint coordinates.
+// LDS (mnewton.hpp: wmnewton_state_bytes): g | U | diag H | the list | the list's bits | the compaction's counts.
+//   start    U = U_cur, so g = H (U - U_cur) - q = -q exactly: no pass over H.  The list is {c : c mod P < p, U_c != 0} and
+//            the K intercept coordinates c mod P == p when they are fitted (unpenalised, without threshold; frozen: never
+//            visited).
+//   screen   every penalised c outside the list: the coordinate update from U_c = 0; those that would move join.  The list
+//            is compacted again in ascending order (wide_cd_device.hpp: wide_compact).
+//   sweep    mnewton_cd_kernel's coordinate update over the list: every lane computes the scalars from the same LDS words
+//            (uniform branches); a coordinate that stays costs no global read and no barrier; one that moves by d does
+//            g[c'] += H[c', c] d for ALL c' < Q, 16 bytes a lane, so g stays the full gradient and the screen needs no pass
+//            over H.  The sweeps end as mnewton_cd_kernel's do; then the screen runs again, and the solve is done when it
+//            adds nothing.
+// max_sweeps bounds the list sweeps of the solve.  g[c] is updated by one lane from the same words in the same order
+// whatever kWidth is, and the candidate is published by the first wavefront alone: both widths give the same bits.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void mnewton_wide_cd_kernel(const double* __restrict__ H, const double* __restrict__ Hd,
+                                                                  const double* __restrict__ q, const double* __restrict__ scale, int p, int K,
+                                                                  int ld, const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                                  int fit_intercept, unsigned max_sweeps, double tol,
+                                                                  double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                                  double* __restrict__ rec) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kWmnewtonLdsBytes];
+  const int lane = threadIdx.x, wave = lane >> 6, P = p + 1, Q = K * P;
+  double* g = reinterpret_cast<double*>(lds);
+  double* u = g + Q;
+  double* hd = u + Q;
+  int32_t* list = reinterpret_cast<int32_t*>(hd + Q);
+  uint32_t* bits = reinterpret_cast<uint32_t*>(list + Q);
+  int32_t* counts = reinterpret_cast<int32_t*>(bits + (Q + 31) / 32);
+  for (int c = lane; c < Q; c += kWidth) {
+    g[c] = -q[c];
+    u[c] = u_cur[c];
+    hd[c] = Hd[c];
+  }
+  __syncthreads();
+
+  // The list from one flag per coordinate (wide_compact).  screen: the flag is "in the list already, or would move from 0";
+  // else: the start's.  An intercept coordinate is in iff the intercepts are fitted.
+  auto compact = [&](bool screen) -> int {
+    return wide_compact<kWidth>(Q, list, bits, counts, [&](int c) -> bool {
+      bool in = false;
+      if (c < Q) {
+        if (c % P < p) {
+          if (screen) {
+            in = (bits[c >> 5] >> (c & 31)) & 1u;
+            if (!in) in = mnewton_coord_new_u(hd[c], 0.0, g[c], al, be, ridge, true) != 0.0;
+          } else {
+            in = u[c] != 0.0;
+          }
+        } else {
+          in = fit_intercept != 0;
+        }
+      }
+      return in;
+    });
+  };
+
+  int n_list = compact(false);
+  unsigned sweeps = 0;
+  bool converged = false, negligible = false;
+  for (int screens = 0;; ++screens) {
+    const int n_new = compact(true);
+    if (screens > 0 && n_new == n_list) {        // the list had converged and nothing outside it moves
+      converged = true;
+      break;
+    }
+    n_list = n_new;
+    bool met = false;
+    while (sweeps < max_sweeps && !met) {
+      double max_change = 0.0, max_size = 0.0, max_eta_sq = 0.0;
+      for (int i = 0; i < n_list; ++i) {
+        const int c = list[i];
+        const double uj = u[c], hjj = hd[c];
+        const double nu = mnewton_coord_new_u(hjj, uj, g[c], al, be, ridge, c % P < p);
+        const double d = nu - uj;
+        max_change = fmax(max_change, fabs(d));
+        max_size = fmax(max_size, fabs(nu));
+        max_eta_sq = fmax(max_eta_sq, nu * nu * hjj);
+        if (d != 0.0) {
+          __syncthreads();                         // every lane has read u[c] and g[c]
+          if (lane == 0) u[c] = nu;
+          wide_column_move<kWidth>(g, H + (size_t)ld * c, Q, d);
+          __syncthreads();
+        }
+      }
+      ++sweeps;
+      const bool all_zero = max_size == 0.0 && max_change == 0.0;
+      const bool no_change = max_size != 0.0 && max_change / max_size <= tol;
+      negligible = max_eta_sq <= kNewtonNegligible * kNewtonNegligible;      // zero to rounding (newton.hpp)
+      met = all_zero || no_change || negligible;
+    }
+    if (!met) break;                               // max_sweeps: the next outer step goes on from here
+  }
+  __syncthreads();
+  if (wave == 0) {
+    mnewton_publish(u, u_cur, scale, p, Q, u_cand, a_cand, rec);
+    if (lane == 0) {
+      rec[kRecSweeps] = (double)sweeps;
+      rec[kRecInnerConverged] = converged ? 1.0 : 0.0;
+      rec[kRecNegligible] = negligible ? 1.0 : 0.0;
+    }
+  }
+}
+
+// The wide inner solve's workgroup.  Both instances give the same bits; profiles/wmnewton_path.txt has the inner solves'
+// time per 100-lambda path (mix 0.5) at Q = K (p + 1) = 15, 198, 2010, 3003 and 5002:
+//   lanes      Q = 15     198      2010     3003     5002
+//   256        11.3 ms   89.4 ms   1442 ms  2931 ms  2353 ms
+//   1024       14.7 ms   118 ms     679 ms  1851 ms  1240 ms
+// Up to one stride of 256 lanes twelve more wavefronts only wait at the barriers; from 2000 coordinates on sixteen
+// wavefronts take 0.47 to 0.63 of the time.  Nothing was measured between 198 and 2010, so wide_layout.hpp's rule over
+// the Q coordinates (256 lanes up to 512, 1024 beyond), which both ends agree with, stands here too.
+int wmnewton_cd_width(int Q) { return wide_cd_width(Q); }
+
 struct Stream {
   hipStream_t st = nullptr;
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // (4: wide only, behind the scale kernel)
   double* rec_host = nullptr;          // pinned: the record of a state pass
   ~Stream() {
     for (hipEvent_t v : e)
@@ -316,6 +496,11 @@ struct MNewtonDevice {
   int64_t n = 0;
   int p = 0, P = 0, nc = 0, K = 0, Q = 0, class_pairs = 0, width = 64;
   bool timed = false;
+  // the wide mode (wmnewton_run; set before setup): H, diag H and q in global memory, the inner solve on `width` lanes
+  // (256 or 1024), the row chunks of mnewton.hpp's wmnewton_row_chunks
+  bool wide = false;
+  int ld = 0;
+  double *d_H = nullptr, *d_Hd = nullptr, *d_q = nullptr;
   int pairs = 0;                       // the tile pairs and the row chunks (a function of n, p and K alone)
   int64_t rows_per_chunk = 0, chunks = 0;
   int state_blocks = 0;
@@ -338,14 +523,16 @@ struct MNewtonDevice {
     Q = K * P;
     class_pairs = K * (K + 1) / 2;
     timed = timed_;
-    width = width_ == 64 || width_ == 256 ? width_ : mnewton_cd_width(Q);
+    if (wide) width = width_;            // (wmnewton_loop's caller has resolved and checked it)
+    else width = width_ == 64 || width_ == 256 ? width_ : mnewton_cd_width(Q);
     const int L = pb.n_lambda;
     SGD_HIP_TRY(hipSetDevice(pb.device));
     const int T = (nc + kTileCols - 1) / kTileCols;
     pairs = T * (T + 1) / 2;
     // (the chunk count shrinks with all the workgroups of a chunk: tile pairs x class pairs)
-    rows_per_chunk = dense_rows_per_chunk(n, pairs * class_pairs);
+    rows_per_chunk = wide ? wmnewton_rows_per_chunk(n, nc, K, kTileRows) : dense_rows_per_chunk(n, pairs * class_pairs);
     chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    ld = (int)wide_leading_dim(Q);
     state_blocks = (int)std::min<int64_t>(kStateMaxBlocks, (n + kBlock - 1) / kBlock);
 
     const size_t o_x = A.reserve(sizeof(double) * (size_t)(n * (int64_t)p));
@@ -361,6 +548,9 @@ struct MNewtonDevice {
     const size_t o_u1 = A.reserve(sizeof(double) * (size_t)Q);
     const size_t o_a = A.reserve(sizeof(double) * (size_t)Q);
     const size_t o_U = A.reserve(sizeof(double) * (size_t)L * (size_t)Q);
+    const size_t o_H = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)Q : 0);
+    const size_t o_Hd = A.reserve(wide ? sizeof(double) * (size_t)Q : 0);
+    const size_t o_q = A.reserve(wide ? sizeof(double) * (size_t)Q : 0);
     SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
     SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
@@ -382,6 +572,9 @@ struct MNewtonDevice {
     d_cur = A.at<double>(o_u0);
     d_cand = A.at<double>(o_u1);
     d_U = A.at<double>(o_U);
+    d_H = A.at<double>(o_H);
+    d_Hd = A.at<double>(o_Hd);
+    d_q = A.at<double>(o_q);
     SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
     SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
     SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
@@ -396,7 +589,8 @@ struct MNewtonDevice {
 
   // publish / blend: d_cand <- d_cur + t (d_cand - d_cur), its state-pass form d_a and its record
   int publish(double t) {
-    hipLaunchKernelGGL(mnewton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
+    if (wide) hipLaunchKernelGGL(mnewton_wide_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
+    else hipLaunchKernelGGL(mnewton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
   }
@@ -433,6 +627,16 @@ struct MNewtonDevice {
 
   // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
   int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
+    if (wide) {                          // scale (timed: up to the event 4), then the solve on H about d_cur
+      hipLaunchKernelGGL(mnewton_wide_scale_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, d_M, d_scale, p, K, ld, (double)n, d_H, d_Hd, d_q);
+      SGD_HIP_TRY(hipGetLastError());
+      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
+      const auto kernel = width == kWideNarrow ? mnewton_wide_cd_kernel<kWideNarrow> : mnewton_wide_cd_kernel<kWideFull>;
+      hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, K, ld, d_cur, al, be, ridge ? 1 : 0,
+                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+      SGD_HIP_TRY(hipGetLastError());
+      return SGDNET_OK;
+    }
     if (width == 256)
       hipLaunchKernelGGL(mnewton_cd_kernel<256>, dim3(1), dim3(256), 0, st, d_M, d_scale, p, K, (double)n, d_cur, al, be, ridge ? 1 : 0,
                          fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
@@ -446,23 +650,30 @@ struct MNewtonDevice {
 
 }  // namespace
 
-int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width) {
+namespace {
+
+// mnewton_run and wmnewton_run: one outer loop, one state machine (newton.hip: newton_loop).  wide: MNewtonDevice scales the
+// pair moments into H in global memory and runs mnewton_wide_cd_kernel<width>; the row chunks follow wmnewton_row_chunks;
+// the blend has no array of kMNewtonMaxCoordinates.  Not wide: exactly the launches multinomial Newton mode has always made.
+int mnewton_loop(const MNewtonProblem& pb, bool timed, MNewtonResult* out, bool wide, int width) {
   const int p = (int)pb.p, P = p + 1, K = pb.K, L = pb.n_lambda;
-  if (pb.n <= 0 || pb.p <= 0 || K < 2 || pb.p > mnewton_max_features(K) || L <= 0 || !pb.x_dense || !pb.y || !pb.scale || !pb.b0 || !pb.alpha ||
-      !pb.beta || pb.max_iter == 0) {
-    set_error("mnewton_run: invalid problem");
+  if (pb.n <= 0 || pb.p <= 0 || K < 2 || pb.p > (wide ? wmnewton_max_features(K) : mnewton_max_features(K)) || L <= 0 ||
+      (wide && width != kWideNarrow && width != kWideFull) || !pb.x_dense || !pb.y || !pb.scale || !pb.b0 || !pb.alpha || !pb.beta ||
+      pb.max_iter == 0) {
+    set_error("%s: invalid problem", wide ? "wmnewton_run" : "mnewton_run");
     return SGDNET_EINVAL;
   }
   const int Q = K * P;
   std::vector<double> start((size_t)Q, 0.0);
   for (int k = 0; k < K; ++k) start[(size_t)k * (size_t)P + (size_t)p] = pb.b0[k];
   MNewtonDevice D;
+  D.wide = wide;
   int rc = D.setup(pb, start.data(), start.data(), timed, width);
   if (rc) return rc;
   hipStream_t st = D.st;
 
   out->passes = out->sweeps = out->halvings = 0.0;
-  out->state_ms = out->moments_ms = out->cd_ms = 0.f;
+  out->state_ms = out->moments_ms = out->cd_ms = out->scale_ms = 0.f;
   const double* rec = D.rec;
   // the path's start: w = 0, b = b0
   rc = D.publish(1.0);
@@ -485,7 +696,11 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
         float ms = 0.f;
         SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[0], D.sx.e[1]));
         out->moments_ms += ms;
-        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[1], D.sx.e[2]));
+        if (wide) {
+          SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[1], D.sx.e[4]));
+          out->scale_ms += ms;
+        }
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, D.sx.e[wide ? 4 : 1], D.sx.e[2]));
         out->cd_ms += ms;
       }
       out->sweeps += rec[kRecSweeps];
@@ -523,6 +738,15 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
   SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), D.d_U, sizeof(double) * (size_t)L * (size_t)Q, hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width) { return mnewton_loop(pb, timed, out, false, width); }
+
+int wmnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width) {
+  const int64_t Q = (int64_t)pb.K * (pb.p + 1);
+  return mnewton_loop(pb, timed, out, true, width != 0 ? width : wmnewton_cd_width((int)std::min<int64_t>(Q, kWmnewtonMaxCoordinates)));
 }
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is
@@ -563,3 +787,4 @@ int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io) {
 }  // namespace sgdnet
 
 extern "C" int sgdnet_mnewton_max_features(int n_classes) { return sgdnet::mnewton_max_features(n_classes); }
+extern "C" int sgdnet_wmnewton_max_features(int n_classes) { return sgdnet::wmnewton_max_features(n_classes); }

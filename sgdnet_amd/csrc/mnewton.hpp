@@ -40,6 +40,72 @@ static_assert(mnewton_max_features(100) == 0 && mnewton_max_features(1) == 0 && 
 // within the workspace bound of the Newton cross-validation (newton.hpp: 1 GiB).
 constexpr size_t kMNewtonDenseCopyBytes = kNewtonCvWorkspaceBytes;
 
+// ---- wide multinomial Newton mode (SGDNET_MODE_WMNEWTON): the same outer loop with the joint Hessian in global memory ----
+// mnewton_wide_cd_kernel is ONE workgroup with newton_wide_cd_kernel's LDS layout over the Q = K (p + 1) coordinates:
+//   the gradient g, U and diag H, in f64                               3 Q doubles
+//   the list, its bits and the compaction's counts (wide_layout.hpp)    Q + ceil(Q / 32) + 32 words
+// and H in global memory, leading dimension wide_leading_dim(Q), written by mnewton_wide_scale_kernel with diag H and q.
+// In bytes: 24 Q + 4 Q + 4 ceil(Q / 32) + 128 <= 163 840:
+//   Q = 5820:  162 960 + 728 + 128 = 163 816          Q = 5821:  162 988 + 728 + 128 = 163 844
+// so K classes leave room for 5820 / K - 1 features: 2909 at K = 2, 1939 at K = 3, 581 at K = 10, 57 at K = 99.  K stays
+// within 2 .. 99 as for mnewton: the class pair rides in blockIdx.z, and K (K + 1) / 2 = 4950 moment matrices is the most
+// memory this mode should take.
+constexpr int kWmnewtonLdsBytes = kWideLdsBytes;
+constexpr int wmnewton_state_bytes(int Q) { return 24 * Q + wide_list_bytes(Q); }
+constexpr int wmnewton_max_coordinates() {
+  int Q = 1;
+  while (wmnewton_state_bytes(Q + 1) <= kWmnewtonLdsBytes) ++Q;
+  return Q;
+}
+constexpr int kWmnewtonMaxCoordinates = wmnewton_max_coordinates();
+static_assert(kWmnewtonMaxCoordinates == 5820, "the LDS budget of the wide inner solve (see above)");
+constexpr int kWmnewtonMaxClasses = 99;
+constexpr int wmnewton_max_features(int K) {
+  if (K < 2 || K > kWmnewtonMaxClasses) return 0;
+  return kWmnewtonMaxCoordinates / K - 1;
+}
+static_assert(wmnewton_max_features(2) == 2909 && wmnewton_max_features(3) == 1939 && wmnewton_max_features(4) == 1454, "the LDS budget (see above)");
+static_assert(wmnewton_max_features(5) == 1163 && wmnewton_max_features(10) == 581 && wmnewton_max_features(20) == 290, "the LDS budget (see above)");
+static_assert(wmnewton_max_features(50) == 115 && wmnewton_max_features(99) == 57, "the LDS budget (see above)");
+static_assert(wmnewton_max_features(100) == 0 && wmnewton_max_features(1) == 0 && wmnewton_max_features(0) == 0 && wmnewton_max_features(-3) == 0,
+              "where nothing fits");
+
+// The class-pair moments pass of the wide mode (mnewton_pair_tile_kernel, unchanged) launches tile pairs x class pairs
+// workgroups per row chunk.  Its chunks follow wide_layout.hpp's wide_row_chunks with THAT product where the rule has
+// the tile pairs: as many chunks as put about 1024 workgroups on the GPU, none shorter than 256 rows, ONE once a chunk
+// alone has 1024 workgroups; the rows of a chunk rounded up to whole steps of tile_rows staged rows.
+// (mnewton's dense_rows_per_chunk never takes fewer than 16 chunks: over 1 GB of partial tiles at ~50 000 workgroups.)
+constexpr int64_t wmnewton_chunk_workgroups(int64_t ncols, int64_t K) { return wide_tile_pairs(ncols) * (K * (K + 1) / 2); }
+constexpr int64_t wmnewton_row_chunks(int64_t n, int64_t ncols, int64_t K) {
+  const int64_t wg = wmnewton_chunk_workgroups(ncols, K), cap = wg >= 1024 ? 1 : 1024 / wg, by_rows = (n + 255) / 256;
+  return by_rows < 1 ? 1 : (by_rows < cap ? by_rows : cap);
+}
+constexpr int64_t wmnewton_rows_per_chunk(int64_t n, int64_t ncols, int64_t K, int64_t tile_rows) {
+  return ((n + wmnewton_row_chunks(n, ncols, K) - 1) / wmnewton_row_chunks(n, ncols, K) + tile_rows - 1) / tile_rows * tile_rows;
+}
+
+// What the mode keeps in device memory beyond x and mu, at each K's feature limit (the largest p is the largest of each):
+//   the joint matrix      wide_leading_dim(Q) Q doubles                     271.2 MB at K = 2 (Q = 5820)
+//   the pair moments      K (K + 1) / 2 (p + 2)^2 doubles                   203.4 MB at K = 2 (3 x 2911^2)
+//   the partial tiles     chunks x workgroups of a chunk x 256 doubles       125.8 MB at K = 90 (61 425 workgroups, one chunk);
+//                         with several chunks there are at most 1024 workgroups in all: 2 MiB
+constexpr int64_t kWmnewtonMatrixBytes = (int64_t)260 << 20, kWmnewtonMomentsBytes = (int64_t)194 << 20, kWmnewtonPartialBytes = (int64_t)120 << 20;
+constexpr bool wmnewton_memory_fits() {
+  for (int K = 2; K <= kWmnewtonMaxClasses; ++K) {
+    const int64_t p = wmnewton_max_features(K), Q = K * (p + 1), nc = p + 2;
+    if (Q > kWmnewtonMaxCoordinates || wide_leading_dim(Q) * Q * 8 > kWmnewtonMatrixBytes) return false;
+    if ((int64_t)K * (K + 1) / 2 * nc * nc * 8 > kWmnewtonMomentsBytes) return false;
+    // any n: the chunks are the cap's at most; fewer features only have fewer workgroups per chunk
+    if (wmnewton_row_chunks((int64_t)1 << 40, nc, K) * wmnewton_chunk_workgroups(nc, K) * 256 * 8 > kWmnewtonPartialBytes) return false;
+  }
+  return true;
+}
+static_assert(wmnewton_memory_fits(), "the device memory of the wide mode at every K's limit (see above)");
+static_assert(wmnewton_row_chunks((int64_t)1 << 40, 3, 2) * wmnewton_chunk_workgroups(3, 2) * 256 * 8 <= (int64_t)2 << 20 &&
+              wmnewton_row_chunks((int64_t)1 << 40, 2911, 2) == 1, "1024 workgroups' tiles while there are chunks, one chunk at the limit");
+// Sparse x is expanded to a column-major dense copy by the driver, as for mnewton; the copy stays within this many bytes.
+constexpr size_t kWmnewtonDenseCopyBytes = (size_t)1 << 30;
+
 struct MNewtonProblem : DirectProblem {         // x_dense only (sparse x: the driver's dense copy); max_iter: outer steps per lambda
   int K = 0;                           // classes
   const double* y = nullptr;           // n: class codes 0 .. K - 1
@@ -56,11 +122,17 @@ struct MNewtonResult {
   double passes = 0.0;                 // state passes over the whole path
   double sweeps = 0.0, halvings = 0.0; // (SGDNET_TRACE)
   float state_ms = 0.f, moments_ms = 0.f, cd_ms = 0.f;   // kernel times summed over the path (SGDNET_TRACE only: they cost a sync per step)
+  float scale_ms = 0.f;                                  // wmnewton_run only: mnewton_wide_scale_kernel
 };
 
 // The Newton loop (mnewton.hip).  2 <= K and p <= mnewton_max_features(K) are the caller's business (plan_fit).
 // timed: fill the *_ms fields.  width: lanes of the inner solve's workgroup (64 or 256), 0 = the rule of mnewton.hip
 int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width = 0);
+
+// The same loop around the wide inner solve (mnewton.hip): 2 <= K <= 99 and p <= wmnewton_max_features(K) are the caller's
+// business (plan_fit).  width: lanes of the inner solve's workgroup (256 or 1024), 0 = the rule of mnewton.hip
+// (wmnewton_cd_width); both give the same bits.
+int wmnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width = 0);
 
 // Diagnostics (include/sgdnet_hip.h: sgdnet_mnewton_probe): one outer step through the host steps mnewton_run takes, every
 // output copied back.  pb: n, p, K, x_dense, y, centre, scale, device and n_lambda = 1; the rest is read from io.

@@ -347,9 +347,9 @@ const OptionDef kOptionDefs[sgdnet::kOptCount] = {
     {"virtual_shards", -1, -1, 8}, {"rng_generators", 0, 0, 64},     {"window_eigenvalue", 1, 0, 1},
     {"host_setup", 0, 0, 1},       {"exact_epoch_blocks", 1, 0, 1}, {"exact_row_registers", 1, 0, 4},
     {"fused_epoch", 1, 0, 2},      {"wcovariance_width", 0, 0, 1024}, {"wnewton_width", 0, 0, 1024},
-    {"wmcovariance_width", 0, 0, 1024},
+    {"wmcovariance_width", 0, 0, 1024}, {"wmnewton_width", 0, 0, 1024},
 };
-std::atomic<int> g_options[sgdnet::kOptCount] = {{-1}, {0}, {1}, {0}, {1}, {1}, {1}, {0}, {0}, {0}};
+std::atomic<int> g_options[sgdnet::kOptCount] = {{-1}, {0}, {1}, {0}, {1}, {1}, {1}, {0}, {0}, {0}, {0}};
 int find_option(const char* name) {
   if (name)
     for (int i = 0; i < sgdnet::kOptCount; ++i)

@@ -1,7 +1,8 @@
-// The descent core the wide kernels share (covariance.hip: cov_wide_path_kernel, newton.hip: newton_wide_cd_kernel): the
-// scale kernel that writes their matrix to global memory, the ascending list compaction and the column move.  The geometry
-// is wide_layout.hpp's.  Included by those two units only, after moments_device.hpp; everything has internal linkage (each
-// unit gets its own copy, as if it were written in it).
+// The descent core the wide kernels share (covariance.hip: cov_wide_path_kernel, newton.hip: newton_wide_cd_kernel,
+// mnewton.hip: mnewton_wide_cd_kernel): the scale kernel that writes their matrix to global memory (mnewton.hip has its
+// own, over the class pairs), the ascending list compaction and the column move.  The geometry is wide_layout.hpp's.
+// Included by those three units only, after moments_device.hpp; everything has internal linkage (each unit gets its own
+// copy, as if it were written in it).
 #pragma once
 
 #include "moments_device.hpp"

@@ -147,6 +147,12 @@ def wmcovariance_max_features(n_responses):
     return int(_lib.load().sgdnet_wmcovariance_max_features(int(n_responses)))
 
 
+def wmnewton_max_features(n_classes):
+    """Largest number of features sgdnet_wmnewton() takes with n_classes classes (sgdnet_wmnewton_max_features of the
+    C ABI): 5820 // n_classes - 1; 0 for fewer than 2 or more than 99 classes."""
+    return int(_lib.load().sgdnet_wmnewton_max_features(int(n_classes)))
+
+
 def mnewton_max_features(n_classes):
     """Largest number of features sgdnet_mnewton() takes with n_classes classes (sgdnet_mnewton_max_features of the
     C ABI): 199 // n_classes - 1; 0 for fewer than 2 or more than 99 classes."""

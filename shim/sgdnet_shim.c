@@ -29,7 +29,7 @@
  *     (src/sgdnet.cpp:275-284);
  *   - inputs are borrowed read-only; failures become R errors after cleanup.
  * Backend extensions are read from R options so that the R code needs no change:
- *   options(sgdnet.mode = "exact" | "batched" | "auto" | "covariance" | "newton" | "mcovariance" | "mnewton" | "wcovariance" | "wnewton" | "wmcovariance", sgdnet.batch = <int>, sgdnet.device = <int>,
+ *   options(sgdnet.mode = "exact" | "batched" | "auto" | "covariance" | "newton" | "mcovariance" | "mnewton" | "wcovariance" | "wnewton" | "wmcovariance" | "wmnewton", sgdnet.batch = <int>, sgdnet.device = <int>,
  *           sgdnet.gpus = <int>)
  */
 #include <R.h>
@@ -121,6 +121,7 @@ static void fill_control(SEXP control, sgdnet_control* c) {
   if (opt != R_NilValue && strcmp(CHAR(Rf_asChar(opt)), "wcovariance") == 0) c->mode = SGDNET_MODE_WCOVARIANCE;
   if (opt != R_NilValue && strcmp(CHAR(Rf_asChar(opt)), "wnewton") == 0) c->mode = SGDNET_MODE_WNEWTON;
   if (opt != R_NilValue && strcmp(CHAR(Rf_asChar(opt)), "wmcovariance") == 0) c->mode = SGDNET_MODE_WMCOVARIANCE;
+  if (opt != R_NilValue && strcmp(CHAR(Rf_asChar(opt)), "wmnewton") == 0) c->mode = SGDNET_MODE_WMNEWTON;
   opt = Rf_GetOption1(Rf_install("sgdnet.batch"));
   if (opt != R_NilValue) c->batch = (int64_t)Rf_asReal(opt);
   opt = Rf_GetOption1(Rf_install("sgdnet.device"));
