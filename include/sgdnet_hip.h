@@ -859,6 +859,53 @@ int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t*
                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
                             sgdnet_cv_newton_result* out);
 
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in multi-response covariance mode (additions only; the    */
+/* ABI version stays): every fold fit of every elastic-net mix of an          */
+/* mgaussian cross-validation in ONE call.  The arguments are those of        */
+/* sgdnet_cv_covariance_*, with y n x K column-major and                      */
+/* control.n_classes = K.  Job (alpha a, group g) is by definition            */
+/* sgdnet_fit_*(x[T], y[T]) in SGDNET_MODE_MCOVARIANCE with                   */
+/* elasticnet_mix = alphas[a] and the user lambdas lambdas[a][.], T as above: */
+/* the features centred (and scaled) by their moments over T, the responses   */
+/* standardised by theirs only with standardize_response (the fit then stays  */
+/* on that scale), the null model's intercepts subtracted, the penalties      */
+/* (1 - mix) lambda and mix lambda.  One pass over x leaves the               */
+/* (n_features + K + 1)^2 moments of every group on the device; the moments   */
+/* of a training set are pooled from them and all n_alpha * n_groups block    */
+/* coordinate descents run side by side, one workgroup and one compute        */
+/* unit's LDS each (sgdnet_amd/csrc/covariance.hip: mcovariance_cv_run).      */
+/* control supplies intercept, standardize, standardize_response, max_iter    */
+/* (block sweeps per lambda), tol, n_lambda, n_classes and device; family     */
+/* must be mgaussian; elasticnet_mix and lambda are ignored in favour of the  */
+/* arrays.  No sample is drawn.  The same input gives the same bits, and a    */
+/* job's bits do not depend on which other jobs share the call.               */
+/* SGDNET_EUNSUPPORTED ("mode = mcovariance needs ..."): a family other than  */
+/* mgaussian, n_classes < 2, more than                                        */
+/* sgdnet_mcovariance_max_features(n_classes) features, n_gpus > 1, debug,    */
+/* more than 65 535 groups (dense x: row chunks), or group moments --         */
+/* n_groups x (n_features + n_classes + 1)^2 doubles -- above 64 MiB (which   */
+/* still holds a leave-one-out CV of 213 rows at 195 features and 2           */
+/* responses, of 327 rows at 63 features and 96 responses).                   */
+/* SGDNET_EINVAL: the cases of sgdnet_cv_covariance_*.                        */
+/* ------------------------------------------------------------------------ */
+typedef struct sgdnet_cv_mcov_result {   /* caller-allocated; job = alpha_index * n_groups + group, L = control.n_lambda, K = control.n_classes */
+  double* a0;            /* jobs x L x K                                                     */
+  double* beta;          /* jobs x L x K x n_features: per job and lambda the layout of sgdnet_result.beta, entry (k, j) at k + j K */
+  double* dev_ratio;     /* jobs x L                                                         */
+  double* return_codes;  /* jobs x L, 0 converged / 1 max_iter sweeps without meeting tol    */
+  double* nulldev;       /* jobs: the null deviance of y[T]                                  */
+  double* npasses;       /* jobs: block sweeps summed over the path                          */
+} sgdnet_cv_mcov_result;
+
+/* x n x p column-major, y n x K column-major, fold n; lambdas n_alpha x control.n_lambda, a row per alpha */
+int sgdnet_cv_mcovariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                                int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                                const double* lambdas, sgdnet_cv_mcov_result* out);
+int sgdnet_cv_mcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                 const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                 sgdnet_cv_mcov_result* out);
+
 #ifdef __cplusplus
 }
 #endif

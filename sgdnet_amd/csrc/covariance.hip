@@ -39,6 +39,11 @@
 //              response count (columns p .. p + K - 1 of the augmented matrix; one response is the case above, bit for
 //              bit) and cov_group_path_kernel runs cyclic BLOCK coordinate descent, a block the K coefficients of a
 //              feature: the group lasso with its l2 part, closed form per block (covariance.hpp has the LDS budget).
+//              mcovariance_cv_run: the folds of an mgaussian cross-validation the same way.  The augmented rows are
+//              [x - a | y_1 - a_y1 .. y_K - a_yK | 1], a group's matrix is (p + K + 1)^2 (sparse x: its K x K response block, the K
+//              sums and n_g from cov_group_responses_kernel), mcov_assemble_kernel re-centres all p + K columns to T's own
+//              means -- the responses always: the null model's intercepts -- and scales a response only with
+//              standardize_response, and cov_group_path_kernel takes its job (mix, T) from blockIdx.x.
 //
 //   wide       wcovariance_run (SGDNET_MODE_WCOVARIANCE): beyond 198 features S does not fit one workgroup's LDS.
 //              wide_scale_kernel writes it to global memory as a full symmetric matrix and cov_wide_path_kernel keeps
@@ -48,7 +53,7 @@
 //              wmcovariance_run (SGDNET_MODE_WMCOVARIANCE) is the same step for the K responses: cov_wide_group_path_kernel
 //              runs cov_group_path_kernel's block descent over the list, one 16-byte read of a column serving all K.
 //
-// No floating-point atomic anywhere and every reduction in an order fixed by (n, p, nnz, fold): the same input gives the
+// No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
 #include <algorithm>
 #include <numeric>
@@ -65,7 +70,8 @@ namespace {
 // blockIdx.x: the pair (tj <= tk) of column tiles of the augmented matrix, blockIdx.y: the chunk of rows.
 // One fit: ncols = p + nresp, the matrix is [x - mu | y_1 .. y_nresp] (y as the driver preprocessed it, n x nresp column-major),
 // chunk c is rows [c rows_per_chunk, ...).
-// Group moments: nresp = 1, ncols = p + 2, [x - mu | y - mean(y) | 1], chunk c is the sorted rows perm[chunk_begin[c] .. chunk_begin[c + 1]).
+// Group moments: ncols = p + nresp + 1, [x - mu | y_r - mean(y_r) | 1] (the mean of response r at mu[p + nresp + r]), chunk c is the
+// sorted rows perm[chunk_begin[c] .. chunk_begin[c + 1]).
 __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __restrict__ x, const double* __restrict__ y,
                                                                  const double* __restrict__ mu, int64_t n, int p, int nresp,
                                                                  int ncols, int64_t rows_per_chunk, const int64_t* __restrict__ perm,
@@ -89,13 +95,13 @@ __global__ __launch_bounds__(kBlock) void cov_dense_tile_kernel(const double* __
     r1 = r0 + rows_per_chunk < n ? r0 + rows_per_chunk : n;
   }
   const bool grouped = perm != nullptr;
-  const double y_centre = grouped ? mu[p + 1] : 0.0;
   auto dev = [&](int a, int64_t i) -> double {
     if (i >= r1 || a >= ncols) return 0.0;
     if (a >= p + nresp) return 1.0;
     const int64_t r = grouped ? perm[i] : i;
     if (a < p) return x[r + (int64_t)a * n] - mu[a];
-    return grouped ? y[r] - y_centre : y[r + (int64_t)(a - p) * n];
+    const double yr = y[r + (int64_t)(a - p) * n];
+    return grouped ? yr - mu[a + nresp] : yr;
   };
   double acc = 0.0;
   for (int64_t base = r0; base < r1; base += kTileRows) {
@@ -139,26 +145,69 @@ __global__ __launch_bounds__(kBlock) void cov_group_response_kernel(const double
   }
 }
 
+// mu[p + K + r] = the mean of response r from its sum mu[p + r] (cov_sum_kernel leaves it itself for one response)
+__global__ void cov_response_centre_kernel(double* __restrict__ mu, int64_t n, int p, int K) {
+  for (int r = threadIdx.x; r < K; r += blockDim.x) mu[p + K + r] = mu[p + r] / (double)n;
+}
+
+// cov_group_response_kernel for K responses (y is n x K, column-major; a_r = mu[p + K + r]): blockIdx.x = response r,
+// blockIdx.y = response s >= r, blockIdx.z = group g.  M[g] is (p + K + 1) x (p + K + 1) and gets sum (y_r - a_r)(y_s - a_s) at
+// (p + r, p + s) and (p + s, p + r); the block r = s also leaves sum (y_r - a_r) at (p + r, p + K) and (p + K, p + r), and the
+// block r = s = 0 n_g in the corner: each over the rows of g in row order
+__global__ __launch_bounds__(kBlock) void cov_group_responses_kernel(const double* __restrict__ y, const int32_t* __restrict__ fold,
+                                                                      const double* __restrict__ mu, int64_t n, int p, int K,
+                                                                      double* __restrict__ M) {
+  __shared__ double sh[kBlock];
+  const int r = blockIdx.x, t = blockIdx.y, g = blockIdx.z, Pa = p + K + 1, one = p + K;
+  if (t < r) return;
+  const double ar = mu[p + K + r], at = mu[p + K + t];
+  const double* yr = y + (int64_t)r * n;
+  const double* yt = y + (int64_t)t * n;
+  double s = 0.0, q = 0.0, c = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += kBlock)
+    if (fold[i] == g) {
+      const double d = yr[i] - ar;
+      s += d;
+      q += d * (yt[i] - at);
+      c += 1.0;
+    }
+  s = block_sum(s, sh);
+  q = block_sum(q, sh);
+  c = block_sum(c, sh);
+  if (threadIdx.x == 0) {
+    double* Mg = M + (size_t)g * Pa * Pa;
+    Mg[(size_t)(p + r) * Pa + p + t] = q;
+    Mg[(size_t)(p + t) * Pa + p + r] = q;
+    if (r == t) {
+      Mg[(size_t)(p + r) * Pa + one] = s;
+      Mg[(size_t)one * Pa + p + r] = s;
+      if (r == 0) Mg[(size_t)one * Pa + one] = c;
+    }
+  }
+}
+
 // blockIdx.x = column j < p, blockIdx.y = column k in [j, p + nresp); k = p + r is response r (y is n x nresp, column-major;
 // mu[p + r] its sum) and M is (p + nresp) x (p + nresp), its response-by-response block left alone.
-// kGrouped: nresp = 1, blockIdx.z = group g, only the stored entries whose row is in g count, n becomes n_g, the response is
-// y - a_y, k runs to p + 1 (the column of ones: the group's sum of deviations) and M[g] is (p + 2) x (p + 2) with the
-// response's own entries already in place (cov_group_response_kernel).
+// kGrouped: blockIdx.z = group g, only the stored entries whose row is in g count, n becomes n_g, response r is
+// y_r - a_r (a_r = mu[p + nresp + r]), k runs to p + nresp (the column of ones: the group's sum of deviations) and M[g] is
+// (p + nresp + 1) x (p + nresp + 1) with the responses' own entries already in place (cov_group_response_kernel; several
+// responses: cov_group_responses_kernel).
 template <bool kGrouped>
 __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* __restrict__ colptr, const int32_t* __restrict__ rowidx,
                                                                   const double* __restrict__ val, const double* __restrict__ y,
                                                                   const double* __restrict__ mu, int64_t n, int p, int nresp,
                                                                   const int32_t* __restrict__ fold, double* __restrict__ M) {
   __shared__ double sh[kBlock];
-  const int j = blockIdx.x, k = blockIdx.y, nc = kGrouped ? p + 2 : p + nresp, tid = threadIdx.x;
+  const int one = p + nresp;            // kGrouped: the column of ones
+  const int j = blockIdx.x, k = blockIdx.y, nc = kGrouped ? one + 1 : p + nresp, tid = threadIdx.x;
   const int g = kGrouped ? (int)blockIdx.z : 0;
   if (k < j) return;
   if (kGrouped) M += (size_t)g * nc * nc;
   auto mine = [&](int32_t r) -> bool { return !kGrouped || fold[r] == g; };
   const int q0 = colptr[j], q1 = colptr[j + 1];
   const double mj = mu[j];
-  if (kGrouped ? k == p : k >= p) {
-    const double ay = kGrouped ? mu[p + 1] : 0.0;
+  if (kGrouped ? (k >= p && k < one) : k >= p) {
+    const double ay = kGrouped ? mu[k + nresp] : 0.0;
     const double* yk = y + (int64_t)(k - p) * n;
     double a = 0.0, ys = 0.0;
     for (int q = q0 + tid; q < q1; q += kBlock) {
@@ -171,14 +220,14 @@ __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* 
     ys = block_sum(ys, sh);
     if (tid == 0) {
       // the response over the samples NOT stored: none, or all - stored
-      const double rest = kGrouped ? M[(size_t)p * nc + p + 1] - ys : ((int64_t)(q1 - q0) == n ? 0.0 : mu[k] - ys);
+      const double rest = kGrouped ? M[(size_t)k * nc + one] - ys : ((int64_t)(q1 - q0) == n ? 0.0 : mu[k] - ys);
       const double c = a - mj * rest;
       M[(size_t)j * nc + k] = c;
       M[(size_t)k * nc + j] = c;
     }
     return;
   }
-  if (kGrouped && k == p + 1) {          // the sum of the group's deviations: stored entries, then the implicit -mj
+  if (kGrouped && k == one) {            // the sum of the group's deviations: stored entries, then the implicit -mj
     double a = 0.0, cnt = 0.0;
     for (int q = q0 + tid; q < q1; q += kBlock)
       if (mine(rowidx[q])) {
@@ -188,9 +237,9 @@ __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* 
     a = block_sum(a, sh);
     cnt = block_sum(cnt, sh);
     if (tid == 0) {
-      const double c = a - (M[(size_t)(p + 1) * nc + p + 1] - cnt) * mj;
-      M[(size_t)j * nc + p + 1] = c;
-      M[(size_t)(p + 1) * nc + j] = c;
+      const double c = a - (M[(size_t)one * nc + one] - cnt) * mj;
+      M[(size_t)j * nc + one] = c;
+      M[(size_t)one * nc + j] = c;
     }
     return;
   }
@@ -227,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void cov_sparse_pair_kernel(const int32_t* 
     cnt_k = j == k ? cnt_j : block_sum(cnt_k, sh);
   }
   if (tid == 0) {
-    const double in_neither = kGrouped ? M[(size_t)(p + 1) * nc + p + 1] - (cnt_j + cnt_k - cnt)
+    const double in_neither = kGrouped ? M[(size_t)one * nc + one] - (cnt_j + cnt_k - cnt)
                                        : (double)n - ((double)(q1 - q0) + (double)(s1 - s0) - cnt);
     const double c = both - mk * only_j - mj * only_k + in_neither * mj * mk;
     M[(size_t)j * nc + k] = c;
@@ -296,6 +345,78 @@ __global__ __launch_bounds__(kBlock) void cov_assemble_kernel(const double* __re
     const size_t at = ((size_t)a * n_groups + t) * n_lambda + l;
     alpha[at] = (1.0 - mix[a]) * lambda[e] / sd_y;
     beta[at] = mix[a] * lambda[e] / sd_y;
+    if (l == 0) ridge[(size_t)a * n_groups + t] = mix[a] == 0.0 ? 1 : 0;
+  }
+}
+
+// cov_assemble_kernel for K responses: blockIdx.x = training set T, from the (p + K + 1) x (p + K + 1) group moments about the
+// common centre to what cov_group_path_kernel reads for x[T], y[T] as fit_mcovariance (driver_direct.cpp) would prepare
+// them: every response less its own mean over T (the null model's intercept), divided by its sd over T only with
+// standardize_response; the fit stays on that scale, so the penalties are those of the mix and the lambda alone.
+//   Mt     G x p x (p + K): rows j < p of the (p + K) x (p + K) matrix (all the path kernel reads)      scale  G x p
+//   mean   G x (p + K): the means of x over T (0 where the features are not centred), then those of the responses AS THE FIT
+//          SEES THEM (the null model's intercepts: mean_T(y_r), or 0 on the standardised scale)
+//   tstat  3 x G: n_T | y~'y~ = sum_r y~_r'y~_r | the null deviance of y[T] as it came = sum_r |y_r - mean_T(y_r)|^2, both in
+//          the order r = 0 .. K - 1           l2, l1  jobs x n_lambda, job = mix * G + T      ridge  jobs
+// The staging arrays (the sums s and the shifts d of the p + K columns) are 2 (p + K) doubles of dynamic LDS.
+__global__ __launch_bounds__(kBlock) void mcov_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
+                                                                const double* __restrict__ mu, int n_groups, int p, int K, int rest,
+                                                                int centre, int standardize, int standardize_response,
+                                                                const double* __restrict__ mix, const double* __restrict__ lambda,
+                                                                int n_mix, int n_lambda, double* __restrict__ Mt,
+                                                                double* __restrict__ scale, double* __restrict__ mean,
+                                                                double* __restrict__ tstat, double* __restrict__ l2,
+                                                                double* __restrict__ l1, int32_t* __restrict__ ridge) {
+  extern __shared__ double staged[];
+  const int t = blockIdx.x, tid = threadIdx.x, nc = p + K, Pa = nc + 1;
+  double* s = staged;
+  double* d = staged + nc;
+  const double* Ct = Mg + (size_t)t * Pa * Pa;
+  auto C = [&](int j, int k) -> double {
+    const double v = Ct[(size_t)j * Pa + k];
+    return rest ? total[(size_t)j * Pa + k] - v : v;
+  };
+  const double nT = C(nc, nc);
+  for (int j = tid; j < nc; j += kBlock) {
+    s[j] = C(j, nc);
+    d[j] = (j >= p || centre) ? s[j] / nT : 0.0;
+  }
+  __syncthreads();
+  auto recentred = [&](int j, int k) -> double { return C(j, k) - d[j] * s[k] - d[k] * s[j] + nT * d[j] * d[k]; };
+  // the sd response r is divided by (1 without standardize_response; a constant response: 0 -> 1)
+  auto sd_y = [&](int r) -> double {
+    if (!standardize_response) return 1.0;
+    const double v = recentred(p + r, p + r) / nT;
+    return v > 0.0 ? sqrt(v) : 1.0;
+  };
+  for (int e = tid; e < p * nc; e += kBlock) {
+    const int j = e / nc, k = e - j * nc;
+    double m = recentred(j, k);
+    if (k >= p) m /= sd_y(k - p);
+    Mt[(size_t)t * p * nc + e] = m;
+  }
+  for (int j = tid; j < p; j += kBlock) {
+    const double v = recentred(j, j) / nT;
+    scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+    mean[(size_t)t * nc + j] = centre ? mu[j] + d[j] : 0.0;
+  }
+  for (int r = tid; r < K; r += kBlock) mean[(size_t)t * nc + p + r] = standardize_response ? 0.0 : mu[nc + r] + d[p + r];
+  if (tid == 0) {
+    double yy = 0.0, nulldev = 0.0;
+    for (int r = 0; r < K; ++r) {
+      const double q = recentred(p + r, p + r), sd = sd_y(r);
+      nulldev += q;
+      yy += q / sd / sd;
+    }
+    tstat[t] = nT;
+    tstat[n_groups + t] = yy;
+    tstat[2 * n_groups + t] = nulldev;
+  }
+  for (int e = tid; e < n_mix * n_lambda; e += kBlock) {
+    const int a = e / n_lambda, l = e - a * n_lambda;
+    const size_t at = ((size_t)a * n_groups + t) * n_lambda + l;
+    l2[at] = (1.0 - mix[a]) * lambda[e];
+    l1[at] = mix[a] * lambda[e];
     if (l == 0) ridge[(size_t)a * n_groups + t] = mix[a] == 0.0 ? 1 : 0;
   }
 }
@@ -401,15 +522,31 @@ __device__ __forceinline__ double group_new_w(double sjj, double wjr, double gjr
 // (k, r), k != j, of g and recompute the move d_r of their response from w_j. and g_j. (still the old ones: there is no
 // room in the budget for K more doubles), then -- a barrier later -- row j of w and g is replaced: two barriers per
 // moving block and one per sweep.
+// blockIdx.x = job, as in cov_path_kernel: its training set is job % n_sets (rows j < p of M, scale and n per set), its
+// penalties and outputs are the job's own.  One fit is a grid of 1 with n_sets = 1: n and the functor come as scalars
+// (dn_sets = ridge_jobs = null).  The kernel declares the CU's whole LDS: one job runs per CU, the others queue.
 template <int kWidth>
 __global__ __launch_bounds__(kWidth) void cov_group_path_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
-                                                                 double dn, const double* __restrict__ alpha,
-                                                                 const double* __restrict__ beta, int n_lambda, int ridge,
+                                                                 int n_sets, double dn_one, const double* __restrict__ dn_sets,
+                                                                 const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                 int n_lambda, int ridge_one, const int32_t* __restrict__ ridge_jobs,
                                                                  unsigned max_iter, double tol, double* __restrict__ W,
                                                                  double* __restrict__ G, double* __restrict__ c_out,
                                                                  int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
   __shared__ double lds[kCovLdsDoubles];
   const int lane = threadIdx.x, nc = p + K, pK = p * K;
+  const size_t job = blockIdx.x, set = job % (size_t)n_sets;
+  M += set * (size_t)p * (size_t)nc;
+  scale += set * (size_t)p;
+  const double dn = dn_sets ? dn_sets[set] : dn_one;
+  const int ridge = ridge_jobs ? ridge_jobs[job] : ridge_one;
+  alpha += job * (size_t)n_lambda;
+  beta += job * (size_t)n_lambda;
+  W += job * (size_t)n_lambda * (size_t)pK;
+  G += job * (size_t)n_lambda * (size_t)pK;
+  c_out += job * (size_t)pK;
+  sweeps_out += job * (size_t)n_lambda;
+  unconverged += job * (size_t)n_lambda;
   double* S = lds;
   double* c = S + p * (p + 1) / 2;
   double* w = c + pK;
@@ -1186,13 +1323,15 @@ int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, in
                        A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
                        A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
   } else if (width == kMcovNarrow)
-    hipLaunchKernelGGL(cov_group_path_kernel<kMcovNarrow>, dim3(1), dim3(kMcovNarrow), 0, st, d_M, A.at<double>(o_scale), p, K, (double)n, A.at<double>(o_alpha),
-                       A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G),
-                       A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+    hipLaunchKernelGGL(cov_group_path_kernel<kMcovNarrow>, dim3(1), dim3(kMcovNarrow), 0, st, d_M, A.at<double>(o_scale), p, K, 1, (double)n,
+                       (const double*)nullptr, A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr,
+                       pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps),
+                       A.at<int32_t>(o_unconv));
   else
-    hipLaunchKernelGGL(cov_group_path_kernel<kMcovWide>, dim3(1), dim3(kMcovWide), 0, st, d_M, A.at<double>(o_scale), p, K, (double)n, A.at<double>(o_alpha),
-                       A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G),
-                       A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+    hipLaunchKernelGGL(cov_group_path_kernel<kMcovWide>, dim3(1), dim3(kMcovWide), 0, st, d_M, A.at<double>(o_scale), p, K, 1, (double)n,
+                       (const double*)nullptr, A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr,
+                       pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps),
+                       A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
 
@@ -1385,6 +1524,180 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
   out->n_train.assign(tstat.begin(), tstat.begin() + G);
   out->y_scale.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
   out->yy.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
+  return SGDNET_OK;
+}
+
+int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups) {
+  const int64_t T = (p + K + 1 + kTileCols - 1) / kTileCols;
+  const int64_t rows_per_chunk = dense_rows_per_chunk(n, (int)(T * (T + 1) / 2));
+  int64_t chunks = 0;
+  for (int g = 0; g < n_groups; ++g) chunks += (count[g] + rows_per_chunk - 1) / rows_per_chunk;
+  return chunks;
+}
+
+// covariance_cv_run for K responses: the same group moments with the columns p .. p + K - 1 the responses and column p + K the
+// ones, mcov_assemble_kernel, and cov_group_path_kernel over the jobs.
+int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out) {
+  const int64_t n = pb.n;
+  const int p = (int)pb.p, K = pb.K, nc = p + K, Pa = nc + 1, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
+  const bool sparse = pb.x_dense == nullptr;
+  const bool width_ok = pb.width == 0 || pb.width == kMcovNarrow || pb.width == kMcovWide;
+  if (n <= 0 || p <= 0 || K < 1 || pb.p > mcov_max_features(K) || L <= 0 || G <= 0 || A_mix <= 0 || !pb.fold || !pb.y || !pb.mix ||
+      !pb.lambda || !width_ok || (pb.train_on_rest && G < 2) || mcov_group_moment_bytes(G, p, K) > kCovGroupMomentBytes ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("mcovariance_cv_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  const size_t jobs = (size_t)A_mix * (size_t)G, pK = (size_t)p * (size_t)K;
+  const int width = pb.width != 0 ? pb.width : mcov_path_width(pK);
+
+  // dense x: the rows sorted by group and cut into chunks, none across a group's end, as covariance_cv_run cuts them
+  const int T = (Pa + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
+  std::vector<int64_t> perm, chunk_begin;
+  std::vector<int32_t> group_chunk;
+  if (!sparse) {
+    std::vector<int64_t> start((size_t)G + 1, 0);
+    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
+    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
+    perm.resize((size_t)n);
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
+    const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
+    group_chunk.assign((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
+      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
+    }
+    chunk_begin.push_back(n);
+  }
+  if ((sparse ? (size_t)G : chunk_begin.size() - 1) > (size_t)kCovMaxRowChunks) {     // (gridDim.y of the tile kernel, .z of the pair kernel)
+    set_error("mcovariance_cv_run: more than %d row chunks or groups", kCovMaxRowChunks);
+    return SGDNET_EINVAL;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
+  const size_t Melems = (size_t)Pa * (size_t)Pa;
+
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
+  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
+  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
+  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(nc + K));      // the features' centres | the responses' sums | their means
+  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
+  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
+  const size_t o_total = A.reserve(sizeof(double) * Melems);
+  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
+  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  const size_t o_Mt = A.reserve(sizeof(double) * (size_t)G * (size_t)p * (size_t)nc);
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
+  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
+  const size_t o_l2 = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_l1 = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
+  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
+  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
+  const size_t o_c = A.reserve(sizeof(double) * jobs * pK);
+  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Events ev;
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
+  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  hipStream_t st = ev.st;
+  double* d_x = A.at<double>(o_x);
+  double* d_y = A.at<double>(o_y);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_Mg = A.at<double>(o_Mg);
+  double* d_tstat = A.at<double>(o_tstat);
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)(p + 1), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n * (size_t)K, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
+
+  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
+  if (sparse) {
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, K,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
+    hipLaunchKernelGGL(cov_group_responses_kernel, dim3((unsigned)K, (unsigned)K, (unsigned)G), dim3(kBlock), 0, st, d_y,
+                       A.at<int32_t>(o_fold), d_mu, n, p, K, d_Mg);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
+                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, K, A.at<int32_t>(o_fold), d_Mg);
+  } else {
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, K,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, Pa,
+                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
+  }
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  if (pb.train_on_rest)
+    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
+                       A.at<double>(o_total));
+  // (2 (p + K) doubles of LDS: the moment budget keeps p + K + 1 below 2897, so below 64 KiB)
+  hipLaunchKernelGGL(mcov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), sizeof(double) * 2 * (size_t)nc, st, d_Mg, A.at<double>(o_total),
+                     d_mu, G, p, K, pb.train_on_rest ? 1 : 0, pb.centre ? 1 : 0, pb.standardize ? 1 : 0, pb.standardize_response ? 1 : 0,
+                     A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_Mt), A.at<double>(o_scale),
+                     A.at<double>(o_mean), d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  const auto kernel = width == kMcovNarrow ? cov_group_path_kernel<kMcovNarrow> : cov_group_path_kernel<kMcovWide>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_Mt), A.at<double>(o_scale), p, K, G, 0.0,
+                     d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), L, 0, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol,
+                     A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+
+  std::vector<double> tstat(3 * (size_t)G);
+  out->mean.resize((size_t)G * (size_t)nc);
+  out->scale.resize((size_t)G * (size_t)p);
+  out->c.resize(jobs * pK);
+  out->w.resize(jobs * (size_t)L * pK);
+  out->g.resize(jobs * (size_t)L * pK);
+  out->sweeps.resize(jobs * (size_t)L);
+  out->unconverged.resize(jobs * (size_t)L);
+  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
+  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
+  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
+  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
+  SGD_HIP_TRY(fetch(out->c.data(), o_c, sizeof(double) * out->c.size()));
+  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
+  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
+  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
+  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  out->n_train.assign(tstat.begin(), tstat.begin() + G);
+  out->yy.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
+  out->nulldev.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));

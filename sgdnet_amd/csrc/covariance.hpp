@@ -205,4 +205,61 @@ struct CovarianceCvResult {
 // the caller's business (driver_direct.cpp: fit_cv_covariance).
 int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out);
 
+// ---- the same for K responses (SGDNET_MODE_MCOVARIANCE) ----
+// The augmented rows are [x - a | y_1 - a_y1 .. y_K - a_yK | 1]: per group a (p + K + 1) x (p + K + 1) moment matrix, the
+// response-by-response block included (a training set's y~'y~ and null deviance come from its diagonal).
+// mcov_assemble_kernel re-centres every response to its own mean over T -- the null model's intercept, subtracted before
+// anything is multiplied because the moments are of deviations about a centre of the order of that mean -- and divides it
+// by its sd over T only with standardize_response; the penalties are (1 - mix) lambda and mix lambda (mgaussian: y_scale
+// = 1).  A job is (mix, T) as above and runs cov_group_path_kernel, one workgroup and one CU's LDS each.
+//
+// The budget: G (p + K + 1)^2 doubles within kCovGroupMomentBytes, so p + K + 1 <= 2896 whatever G is and the assembly's
+// staging (2 (p + K) doubles of LDS) stays below 64 KiB.  At K = 96, p = 63 a 10-fold CV takes 2.0 MB of it.
+constexpr size_t mcov_group_moment_bytes(int64_t G, int64_t p, int64_t K) {
+  return (size_t)G * (size_t)(p + K + 1) * (size_t)(p + K + 1) * sizeof(double);
+}
+
+struct McovarianceCvProblem {
+  int64_t n = 0, p = 0;
+  int K = 0;                           // responses
+  const double* x_dense = nullptr;     // as CovarianceCvProblem
+  const int32_t* colptr = nullptr;
+  const int32_t* rowidx = nullptr;
+  const double* values = nullptr;
+  const double* y = nullptr;           // n x K, column-major: the responses as they came
+  const int32_t* fold = nullptr;       // n: group ids in [0, n_groups), no group empty (the caller's business)
+  int n_groups = 0;
+  bool train_on_rest = false;
+  bool centre = true, standardize = true, standardize_response = false;
+  int device = 0;
+  int n_mix = 0, n_lambda = 0;
+  const double* mix = nullptr;         // n_mix
+  const double* lambda = nullptr;      // n_mix x n_lambda, a row per mix
+  unsigned max_iter = 0;
+  double tol = 0.0;
+  int width = 0;                       // lanes of the path kernel's workgroup (64 or 256), 0 = mcov_path_width; the same bits
+};
+
+struct McovarianceCvResult {
+  // per training set T (n_groups of them)
+  std::vector<double> n_train;         // G
+  std::vector<double> mean;            // G x (p + K): the means of x over T (0 where centre is false), then the null model's
+                                       // intercepts of the responses as the fit sees them (mean_T(y_r); 0 once standardised)
+  std::vector<double> scale;           // G x p
+  std::vector<double> yy, nulldev;     // G: sum_r y~_r'y~_r of the preprocessed responses; the null deviance of y[T] as it came
+  // per job
+  std::vector<double> c;               // jobs x p x K, entry (j, r) at j K + r
+  std::vector<double> w, g;            // jobs x n_lambda x p x K
+  std::vector<int32_t> sweeps, unconverged;   // jobs x n_lambda
+  float moments_ms = 0.f, assemble_ms = 0.f, path_ms = 0.f;
+};
+
+// The row chunks of the dense group moments pass (gridDim.y): count[g] rows in group g, none across a group's end.
+int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups);
+
+// Group moments + assembly + path kernel over the jobs.  p <= mcov_max_features(K), the budget above, at most
+// kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business
+// (driver_direct.cpp: fit_cv_mcovariance).
+int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out);
+
 }  // namespace sgdnet

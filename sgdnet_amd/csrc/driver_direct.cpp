@@ -5,6 +5,7 @@
 //                       problem every mode fills the same way, the kernels' run, and per lambda the deviance and the way
 //                       back to the scale of the data
 //   fit_cv_covariance   every fold fit of a cross-validation in one launch       (sgdnet_cv_covariance_*)
+//   fit_cv_mcovariance  the same for the K responses of an mgaussian fit         (sgdnet_cv_mcovariance_*)
 //   fit_cv_newton       every fold fit through the Newton loop in lock-step      (sgdnet_cv_newton_*)
 //   the probes          one outer step of the Newton modes, everything copied back (sgdnet_newton_probe_*, sgdnet_mnewton_probe)
 #include <math.h>
@@ -390,6 +391,120 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
   return SGDNET_OK;
 }
 
+// ---- cross-validation in multi-response covariance mode (covariance.hip: mcovariance_cv_run): the stage behind sgdnet_cv_mcovariance_* ----
+// Every job (mix, training set T) is fit_mcovariance on x[T], y[T] by definition: the features centred (and scaled) by their
+// moments over T, the responses standardised by theirs only with standardize_response (the fit then stays on that scale:
+// mgaussian has y_scale = 1), the null model's intercepts b0_r = mean_T(y~_r) subtracted, the penalties (1 - mix) lambda and
+// mix lambda.  The device assembles all of it from the group moments; the host is left with the way back to the scale of
+// the features (rescale_values) and the deviance from the quadratic form, per job.
+int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
+                       int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mcov_result* out) {
+  const int64_t n = pb.n, p = pb.p;
+  if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !pb.y ||
+      !fold || !alphas || !lambdas) {
+    set_error("sgdnet_cv_mcovariance: null pointer");
+    return SGDNET_EINVAL;
+  }
+  if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
+      (train_on_rest && n_groups < 2)) {
+    set_error("sgdnet_cv_mcovariance: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    return SGDNET_EINVAL;
+  }
+  const int L = ctl->n_lambda, K = ctl->n_classes;
+  const int limit = mcov_max_features(K);
+  const char* what = nullptr;
+  if (ctl->family != SGDNET_MGAUSSIAN) what = "family = mgaussian";
+  else if (K < 2) what = "at least two responses (n_classes >= 2)";
+  else if (p > limit) what = "no more features than sgdnet_mcovariance_max_features(n_classes)";
+  else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+  else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
+  if (what) {
+    set_error("mode = mcovariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, K,
+              (long long)p, limit, ctl->n_gpus, ctl->debug);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const size_t moment_bytes = mcov_group_moment_bytes(n_groups, p, K);
+  if (moment_bytes > kCovGroupMomentBytes) {
+    set_error("mode = mcovariance needs the group moments within %zu bytes: %d groups x (%lld + %d + 1)^2 doubles are %zu bytes",
+              kCovGroupMomentBytes, n_groups, (long long)p, K, moment_bytes);
+    return SGDNET_EUNSUPPORTED;
+  }
+  std::vector<int64_t> count;
+  int rc = count_groups(fold, n, n_groups, count);
+  if (!rc) rc = validate_mixes(n_alpha, alphas, L, lambdas);
+  if (rc) return rc;
+  const bool sparse = pb.x_dense == nullptr;
+  const int64_t chunks = sparse ? n_groups : mcov_cv_row_chunks(n, p, K, count.data(), n_groups);
+  if (chunks > kCovMaxRowChunks) {
+    set_error("mode = mcovariance needs at most %d %s: %d groups of %lld rows are %lld", kCovMaxRowChunks,
+              sparse ? "groups of sparse rows" : "row chunks of the groups", n_groups, (long long)n, (long long)chunks);
+    return SGDNET_EUNSUPPORTED;
+  }
+  rc = check_device(ctl->device);
+  if (rc) return rc;
+  PhaseTimer pt;
+  const bool intercept = ctl->intercept != 0;
+  pb.K = K;
+  pb.fold = fold;
+  pb.n_groups = n_groups;
+  pb.train_on_rest = train_on_rest != 0;
+  pb.centre = intercept || ctl->standardize != 0;
+  pb.standardize = ctl->standardize != 0;
+  pb.standardize_response = ctl->standardize_response != 0;
+  pb.device = ctl->device;
+  pb.n_mix = n_alpha;
+  pb.n_lambda = L;
+  pb.mix = alphas;
+  pb.lambda = lambdas;
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  static const int width = exp_env_int("SGDNET_MCOV_WIDTH", 0);     // (64 or 256 lanes, as fit_mcovariance takes it)
+  pb.width = width;
+  McovarianceCvResult cr;
+  rc = mcovariance_cv_run(pb, &cr);
+  if (rc) return rc;
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   cv mcovariance: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", cr.moments_ms,
+            cr.assemble_ms, n_alpha * n_groups, cr.path_ms);
+
+  const size_t P = (size_t)p, Ks = (size_t)K, pK = P * Ks;
+  std::vector<double> xbb(Ks);
+  for (int a = 0; a < n_alpha; ++a)
+    for (int t = 0; t < n_groups; ++t) {
+      const size_t job = (size_t)a * (size_t)n_groups + (size_t)t;
+      const double nT = cr.n_train[(size_t)t], yy = cr.yy[(size_t)t];
+      const double* mean = cr.mean.data() + (size_t)t * (P + Ks);
+      const double* scale = cr.scale.data() + (size_t)t * P;
+      const double* c = cr.c.data() + job * pK;
+      double n_sweeps = 0.0;
+      for (int li = 0; li < L; ++li) {
+        const size_t at = job * (size_t)L + (size_t)li;
+        const double* w = cr.w.data() + at * pK;
+        const double* g = cr.g.data() + at * pK;
+        double* bo = out->beta + at * pK;
+        // fit_mcovariance: the explained part of the deviance is n sum_jr w_jr (c~_jr - g_jr); rescale_values with y_scale = 1
+        double explained = 0.0;
+        std::fill(xbb.begin(), xbb.end(), 0.0);
+        for (size_t j = 0; j < P; ++j)
+          for (size_t r = 0; r < Ks; ++r) {
+            const size_t e = j * Ks + r;
+            explained += w[e] * (c[e] - g[e]);
+            bo[e] = w[e] * (1.0 / scale[j]);
+            xbb[r] += mean[j] * bo[e];
+          }
+        const double dev = std::max(0.0, yy - nT * explained);
+        out->dev_ratio[at] = yy > 0.0 ? 1.0 - dev / yy : 0.0;
+        for (size_t r = 0; r < Ks; ++r) out->a0[at * Ks + r] = intercept ? mean[P + r] - xbb[r] : mean[P + r];
+        out->return_codes[at] = cr.unconverged[at] ? 1.0 : 0.0;
+        n_sweeps += (double)cr.sweeps[at];
+      }
+      out->nulldev[job] = cr.nulldev[(size_t)t];
+      out->npasses[job] = n_sweeps;
+    }
+  pt.mark("cv mcovariance (all folds)");
+  return SGDNET_OK;
+}
+
 // ---- cross-validation in Newton mode (newton.hip: newton_cv_run): the stage behind sgdnet_cv_newton_* ----
 // Every job (mix, training set T) is fit_newton on x[T], y[T] by definition.  The rows are stably sorted by group here,
 // once, so that T is a range of rows or the complement of one; what fit_newton takes from the preprocessing of x[T],
@@ -712,6 +827,40 @@ int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int3
   pb.values = x->values;
   pb.y = y;
   return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_mcovariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                                int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                sgdnet_cv_mcov_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_mcovariance_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  McovarianceCvProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  pb.y = y;
+  return fit_cv_mcovariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_mcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                 const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                 sgdnet_cv_mcov_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_mcovariance_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  McovarianceCvProblem pb;
+  pb.n = x->n_rows;
+  pb.p = x->n_cols;
+  pb.colptr = x->colptr;
+  pb.rowidx = x->rowidx;
+  pb.values = x->values;
+  pb.y = y;
+  return fit_cv_mcovariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
 }
 
 int sgdnet_cv_newton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,

@@ -21,7 +21,12 @@ The full fits, the fold ids, the scoring and the result are those of the default
 
 cv_sgdnet_newton() is the binomial CV whose fits are sgdnet_newton(); its fold_fits="batched" runs all fold fits through
 cv_newton_fits -> sgdnet_cv_newton_*: the Newton loops of all jobs advance in lock-step, every kernel launched once per
-round over all of them (csrc/newton.hip: newton_cv_run).  _cv() is the body both CVs share; they differ in the fit they inject.
+round over all of them (csrc/newton.hip: newton_cv_run).
+
+cv_sgdnet_mcovariance() is the mgaussian CV whose fits are sgdnet_mcovariance(); its fold_fits="batched" runs all fold fits
+through cv_mcovariance_fits -> sgdnet_cv_mcovariance_*: the group moments of the K responses from one pass, every training
+set pooled from them, one workgroup per path (csrc/covariance.hip: mcovariance_cv_run).
+_cv() is the body the three CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -30,8 +35,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_NEWTON, MODES, check, dptr
-from .api import SgdnetFit, _levels, sgdnet, sgdnet_newton
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_NEWTON, MODES, check, dptr
+from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_newton
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -121,13 +126,32 @@ def cv_newton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000,
                              thresh=thresh, device=device)
 
 
+def cv_mcovariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                        thresh=0.001, standardize_response=False, device=0):
+    """Every fold fit of an mgaussian cross-validation in multi-response covariance mode from one native call.
+
+    The arguments are cv_covariance_fits's; y is n x K with K >= 2 responses.  Returns a list of SgdnetFit, alpha-major:
+    entry a * nfolds + j is sgdnet_mcovariance(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a],
+    standardize_response=standardize_response) for the training set T of fold j."""
+    y_arr = np.asarray(y)
+    if y_arr.ndim != 2 or y_arr.shape[1] < 2:
+        raise ValueError("response for multivariate Gaussian regression must not be one-dimensional; try family = 'gaussian'.")
+    if y_arr.dtype.kind not in "fiub":
+        raise ValueError("non-numeric response.")
+    return _native_fold_fits(x, np.asfortranarray(y_arr, dtype=np.float64), foldid, alpha, lambda_, train_on, family="mgaussian",
+                             classnames=None, maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh,
+                             standardize_response=standardize_response, device=device)
+
+
 def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, classnames, maxit, standardize, intercept, thresh,
-                      device):
-    """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*)
-    and cv_newton_fits (binomial: sgdnet_cv_newton_*); y_enc: the response as the backend takes it."""
+                      device, standardize_response=False):
+    """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*),
+    cv_newton_fits (binomial: sgdnet_cv_newton_*) and cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*); y_enc: the
+    response as the backend takes it (mgaussian: n x K, column-major)."""
     import scipy.sparse as sp
 
-    newton = family == "binomial"
+    newton, multi = family == "binomial", family == "mgaussian"
+    K = y_enc.shape[1] if multi else 1
     if train_on not in ("fold", "rest"):
         raise ValueError("train_on must be 'fold' or 'rest'")
     if not all(isinstance(v, (bool, np.bool_)) for v in (intercept, standardize)):
@@ -149,7 +173,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
         raise ValueError("maximum number of iterations cannot be negative or zero.")
     n, p = x.shape
     foldid = np.asarray(foldid).reshape(-1)
-    if y_enc.size != n or foldid.size != n:
+    if y_enc.shape[0] != n or foldid.size != n:
         raise ValueError("the number of samples in 'x', 'y' and 'foldid' must match")
     values, fold = np.unique(foldid, return_inverse=True)
     fold = np.ascontiguousarray(fold, dtype=np.int32)
@@ -158,11 +182,12 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     ctl = _lib.Control()
     ctl.family = FAMILIES[family]
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
-    ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, 1
-    ctl.mode, ctl.device = (MODE_NEWTON if newton else MODES["covariance"]), int(device)
+    ctl.standardize_response = int(bool(standardize_response))
+    ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, K
+    ctl.mode, ctl.device = (MODE_NEWTON if newton else MODE_MCOVARIANCE if multi else MODES["covariance"]), int(device)
     jobs = A * G
-    a0 = np.zeros((jobs, nl))
-    beta = np.zeros((jobs, nl, p))
+    a0 = np.zeros((jobs, nl, K) if multi else (jobs, nl))
+    beta = np.zeros((jobs, nl, p, K) if multi else (jobs, nl, p))      # (mgaussian: entry (k, j) at k + j K)
     dev_ratio = np.zeros((jobs, nl))
     rcodes = np.zeros((jobs, nl))
     nulldev = np.zeros(jobs)
@@ -172,10 +197,12 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
         res = _lib.CvNewtonResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses), dptr(steps),
                                   dptr(halvings))
     else:
-        res = _lib.CvCovResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses))
+        res = (_lib.CvMcovResult if multi else _lib.CvCovResult)(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev),
+                                                                 dptr(npasses))
     tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
             dptr(lam), C.byref(res))
     L = _lib.load()
+    stem = "sgdnet_cv_newton" if newton else "sgdnet_cv_mcovariance" if multi else "sgdnet_cv_covariance"
     if sp.issparse(x):
         xs = sp.csc_matrix(x, dtype=np.float64)
         xs.sort_indices()
@@ -187,22 +214,31 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
         csc.colptr = colptr.ctypes.data_as(C.POINTER(C.c_int32))
         csc.rowidx = rowidx.ctypes.data_as(C.POINTER(C.c_int32))
         csc.values = dptr(vals)
-        check((L.sgdnet_cv_newton_sparse if newton else L.sgdnet_cv_covariance_sparse)(C.byref(csc), *tail))
+        check(getattr(L, stem + "_sparse")(C.byref(csc), *tail))
     else:
         xd = np.asfortranarray(np.asarray(x, dtype=np.float64).reshape(n, p))
-        check((L.sgdnet_cv_newton_dense if newton else L.sgdnet_cv_covariance_dense)(dptr(xd), n, p, *tail))
+        check(getattr(L, stem + "_dense")(dptr(xd), n, p, *tail))
 
     counts = np.bincount(fold, minlength=G)
     fits = []
     for a in range(A):
         for j in range(G):
             job = a * G + j
-            b = beta[job].T.copy()                                # (p, n_lambda)
-            fits.append(SgdnetFit(a0=a0[job].copy(), beta=b, lambda_=lam[a].copy(), dev_ratio=dev_ratio[job].copy(),
-                                  df=(b != 0).sum(axis=0), nulldev=float(nulldev[job]), npasses=float(npasses[job]),
-                                  alpha=float(alphas[a]), offset=False, classnames=classnames, grouped=False,
+            dfmat = None
+            if multi:                                             # the shapes _fit() returns for mgaussian
+                a0_job = a0[job].T.copy()                         # (K, n_lambda)
+                b = [beta[job, :, :, k].T.copy() for k in range(K)]
+                df = (sum(b) != 0).sum(axis=0)
+                dfmat = np.vstack([(np.abs(bk) > 0).sum(axis=0) for bk in b])
+            else:
+                a0_job = a0[job].copy()
+                b = beta[job].T.copy()                            # (p, n_lambda)
+                df = (b != 0).sum(axis=0)
+            fits.append(SgdnetFit(a0=a0_job, beta=b, lambda_=lam[a].copy(), dev_ratio=dev_ratio[job].copy(),
+                                  df=df, nulldev=float(nulldev[job]), npasses=float(npasses[job]),
+                                  alpha=float(alphas[a]), offset=False, classnames=classnames, grouped=multi,
                                   nobs=int(n - counts[j] if train_on == "rest" else counts[j]), family=family,
-                                  return_codes=rcodes[job].copy(), draws_used=0,
+                                  dfmat=dfmat, return_codes=rcodes[job].copy(), draws_used=0,
                                   diagnostics=dict(steps=float(steps[job]), halvings=float(halvings[job])) if newton else {}))
     return fits
 
@@ -267,8 +303,32 @@ def cv_sgdnet_newton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_m
                train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
 
 
+def cv_sgdnet_mcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                          train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                          standardize=True, intercept=True, thresh=0.001, standardize_response=False):
+    """cv_sgdnet(family="mgaussian") with every fit a sgdnet_mcovariance(): the fold ids, the scoring, the generator and the
+    returned CvSgdnet are cv_sgdnet's.  For 0 < alpha < 1 this is the cross-validation over an alpha grid that has optima
+    to compare (sgdnet_mcovariance()).  fold_fits="separate" (the default) runs one sgdnet_mcovariance per fold; "batched"
+    runs all fold fits of all alphas through ONE native call (cv_mcovariance_fits) with the full fits' lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh, standardize_response=standardize_response)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_mcovariance(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio,
+                                  device=dev, **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_mcovariance_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="mgaussian", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
 def _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, *, family, devices, rng, seed, train_on, densify, fit_one, batched_fits):
-    """The cross-validation behind cv_sgdnet() and cv_sgdnet_newton(): the full fits, the fold ids, the fold fits, the scores
+    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton() and cv_sgdnet_mcovariance(): the full fits, the fold ids, the fold fits, the scores
     and the summary.  fit_one(x, y, lambda, alpha, device, seed, rng, sequential) is a fit; batched_fits(x, y, foldid, alpha,
     lambdas, device), where given, returns every fold fit from one call (alpha-major), else the folds are fitted one by one."""
     import scipy.sparse as sp
