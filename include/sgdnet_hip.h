@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width, sgdnet_cv_mnewton_* (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -905,6 +905,64 @@ int sgdnet_cv_mcovariance_dense(const double* x, int64_t n, int64_t p, const dou
 int sgdnet_cv_mcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
                                  const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
                                  sgdnet_cv_mcov_result* out);
+
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in multinomial Newton mode (additions only; the ABI       */
+/* version stays): every fold fit of every elastic-net mix in ONE call, all   */
+/* of them advancing in lock-step.  The arguments are those of                */
+/* sgdnet_cv_newton_*, with control.n_classes = K.  Job (alpha a, group g) is */
+/* by definition sgdnet_fit_*(x[T], y[T]) in SGDNET_MODE_MNEWTON with         */
+/* n_classes = K, elasticnet_mix = alphas[a] and the user lambdas             */
+/* lambdas[a][.], T as above: the same preprocessed problem (x_center and     */
+/* x_scale over T; the null model of y[T]: the class-centred logs of T's      */
+/* class proportions, or of 1 / K each without an intercept; its null         */
+/* deviance), the same stopping rule, constants and accept / halve rule,      */
+/* return_codes, npasses (state passes of that job) and the class-centred     */
+/* intercepts meaning what they mean there.  y holds the class codes          */
+/* 0 .. K - 1 of the WHOLE response.  Sparse x is expanded to the dense copy  */
+/* a single fit in this mode makes: a sparse call gives the dense call's      */
+/* bits.  The rows are sorted by group on the host and uploaded once; every   */
+/* kernel of the loop runs over all jobs at once, each job on the rows of its */
+/* own training set with the grids a single fit of that many rows would       */
+/* choose, and per round the host sends one command per job (step / halve /   */
+/* idle, the penalties, which iterate is current, where to store an accepted  */
+/* one) and reads all records back in one copy                                */
+/* (sgdnet_amd/csrc/mnewton.hip: mnewton_cv_run).  It is the optimum of the   */
+/* separate fit, not its bits: the centres of a training set are formed on    */
+/* the host here.  control supplies intercept, standardize, max_iter (Newton  */
+/* steps per lambda), tol, n_lambda, n_classes and device; family must be     */
+/* multinomial.  No sample is drawn.  The same input gives the same bits, and */
+/* a job's bits do not depend on which other jobs share the call.             */
+/* SGDNET_EUNSUPPORTED ("mode = mnewton needs ..."): a family other than      */
+/* multinomial, n_classes outside 2 .. 99, the grouped penalty, more than     */
+/* sgdnet_mnewton_max_features(n_classes) features, n_gpus > 1, debug, a      */
+/* dense copy of a sparse x above 1 GiB, more than 65 535 jobs or jobs x      */
+/* K (K + 1) / 2 class pairs, or a workspace -- per job rows x K +            */
+/* K (K + 1) / 2 x ((n_features + 2)^2 + row chunks x tile pairs x 256) +     */
+/* 1024 + (n_lambda + 3) x K (n_features + 1) + 8 doubles, and x and y once   */
+/* -- above 1 GiB (which still holds 5 mixes x 10 folds of 30 000 rows each   */
+/* at 10 classes and 18 features).                                            */
+/* SGDNET_EINVAL: the cases of sgdnet_cv_covariance_*, a response that is not */
+/* a class code in 0 .. K - 1, and a training set that holds no row of some   */
+/* class (the message names the group and the class).                         */
+/* ------------------------------------------------------------------------ */
+typedef struct sgdnet_cv_mnewton_result {  /* caller-allocated; job = alpha_index * n_groups + group, L = control.n_lambda, K = control.n_classes */
+  double* a0;            /* jobs x L x K: per job the layout of sgdnet_result.a0, the class mean removed */
+  double* beta;          /* jobs x L x n_features x K: per job the layout of sgdnet_result.beta, entry (k, j) at k + j K */
+  double* dev_ratio;     /* jobs x L                                                         */
+  double* return_codes;  /* jobs x L, 0 converged / 1 max_iter steps without meeting tol     */
+  double* nulldev;       /* jobs: the null deviance of y[T]                                  */
+  double* npasses;       /* jobs: state passes over the path                                 */
+  double* steps;         /* jobs: Newton steps over the path                                 */
+  double* halvings;      /* jobs: steps halved (each costs one more state pass)              */
+} sgdnet_cv_mnewton_result;
+
+int sgdnet_cv_mnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                            int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                            const double* lambdas, sgdnet_cv_mnewton_result* out);
+int sgdnet_cv_mnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                             sgdnet_cv_mnewton_result* out);
 
 #ifdef __cplusplus
 }

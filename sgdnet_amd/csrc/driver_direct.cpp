@@ -7,6 +7,7 @@
 //   fit_cv_covariance   every fold fit of a cross-validation in one launch       (sgdnet_cv_covariance_*)
 //   fit_cv_mcovariance  the same for the K responses of an mgaussian fit         (sgdnet_cv_mcovariance_*)
 //   fit_cv_newton       every fold fit through the Newton loop in lock-step      (sgdnet_cv_newton_*)
+//   fit_cv_mnewton      the same through the multinomial Newton loop             (sgdnet_cv_mnewton_*)
 //   the probes          one outer step of the Newton modes, everything copied back (sgdnet_newton_probe_*, sgdnet_mnewton_probe)
 #include <math.h>
 
@@ -505,6 +506,74 @@ int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, cons
   return SGDNET_OK;
 }
 
+// ---- what the two Newton cross-validations (fit_cv_newton, fit_cv_mnewton) form alike from a dense x ----
+
+// The rows stably sorted by group: row i goes to position to[i]; start[g] is the first position of group g (G + 1 entries).
+void sort_by_group(const int32_t* fold, int64_t n, const std::vector<int64_t>& count, std::vector<int64_t>& start, std::vector<int64_t>& to) {
+  const size_t G = count.size();
+  start.assign(G + 1, 0);
+  for (size_t g = 0; g < G; ++g) start[g + 1] = start[g] + count[g];
+  to.resize((size_t)n);
+  std::vector<int64_t> fill(start.begin(), start.end() - 1);
+  for (int64_t i = 0; i < n; ++i) to[(size_t)i] = fill[(size_t)fold[i]]++;
+}
+
+// xs: x (column-major n x p) with its rows sorted; abar: the whole-data column means; s1, s2 (G x p): per group and column
+// the sums of d = x - abar and of d^2 (the deviations formed before anything is squared: DESIGN.md 4.6)
+void sorted_dense_moments(const double* dense, int64_t n, int64_t p, int G, const std::vector<int64_t>& to, const std::vector<int64_t>& start,
+                          std::vector<double>& xs, std::vector<double>& abar, std::vector<double>& s1, std::vector<double>& s2) {
+  const size_t P = (size_t)p;
+  xs.resize((size_t)n * P);
+  parallel_for(p, (double)n * (double)p, [&](int64_t j0, int64_t j1) {
+    for (int64_t j = j0; j < j1; ++j) {
+      const double* col = dense + j * n;
+      double* dst = xs.data() + j * n;
+      double sum = 0.0;
+      for (int64_t i = 0; i < n; ++i) {
+        dst[to[(size_t)i]] = col[i];
+        sum += col[i];
+      }
+      const double a = abar[(size_t)j] = sum / (double)n;
+      for (int g = 0; g < G; ++g) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) {
+          const double d = dst[i] - a;
+          t1 += d;
+          t2 += d * d;
+        }
+        s1[(size_t)g * P + (size_t)j] = t1;
+        s2[(size_t)g * P + (size_t)j] = t2;
+      }
+    }
+  });
+}
+
+// mean, scale (G x p): pooled per training set (the group's own sums, or the total -- added in group order -- less them)
+// and moved to the set's own mean: mean_T = a + S1 / n_T, var_T = S2 / n_T - (S1 / n_T)^2
+void pooled_centres_and_scales(const std::vector<double>& abar, const std::vector<double>& s1, const std::vector<double>& s2,
+                               const std::vector<int64_t>& n_t, bool rest, bool centre, bool standardize, std::vector<double>& mean,
+                               std::vector<double>& scale) {
+  const size_t P = abar.size();
+  const int G = (int)n_t.size();
+  mean.assign((size_t)G * P, 0.0);
+  scale.assign((size_t)G * P, 1.0);
+  for (size_t j = 0; j < P; ++j) {
+    const double a = abar[j];
+    double t1 = 0.0, t2 = 0.0;
+    for (int g = 0; g < G; ++g) {
+      t1 += s1[(size_t)g * P + j];
+      t2 += s2[(size_t)g * P + j];
+    }
+    for (int g = 0; g < G; ++g) {
+      const double nT = (double)n_t[(size_t)g];
+      const double d = (rest ? t1 - s1[(size_t)g * P + j] : s1[(size_t)g * P + j]) / nT;
+      const double var = (rest ? t2 - s2[(size_t)g * P + j] : s2[(size_t)g * P + j]) / nT - d * d;
+      if (centre) mean[(size_t)g * P + j] = a + d;
+      if (standardize) scale[(size_t)g * P + j] = var > 0.0 ? sqrt(var) : 1.0;
+    }
+  }
+}
+
 // ---- cross-validation in Newton mode (newton.hip: newton_cv_run): the stage behind sgdnet_cv_newton_* ----
 // Every job (mix, training set T) is fit_newton on x[T], y[T] by definition.  The rows are stably sorted by group here,
 // once, so that T is a range of rows or the complement of one; what fit_newton takes from the preprocessing of x[T],
@@ -546,17 +615,11 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
   }
   int rc = validate_response(ctl, y, n);
   if (rc) return rc;
-  std::vector<int64_t> count, start((size_t)G + 1, 0);
+  std::vector<int64_t> count, start, to;
   rc = count_groups(fold, n, G, count);
   if (!rc) rc = validate_mixes(n_alpha, alphas, L, lambdas);
   if (rc) return rc;
-  for (int g = 0; g < G; ++g) start[(size_t)g + 1] = start[(size_t)g] + count[(size_t)g];
-  // the rows stably sorted by group: row i goes to position to[i]
-  std::vector<int64_t> to((size_t)n);
-  {
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) to[(size_t)i] = fill[(size_t)fold[i]]++;
-  }
+  sort_by_group(fold, n, count, start, to);
   std::vector<double> ys((size_t)n);
   for (int64_t i = 0; i < n; ++i) ys[(size_t)to[(size_t)i]] = y[i];
   // the response of every training set: both classes, the null model and its deviance (fit_null_model, null_deviance)
@@ -652,49 +715,11 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
       }
     }
   } else {
-    xs.resize((size_t)n * P);
-    parallel_for(p, (double)n * (double)p, [&](int64_t j0, int64_t j1) {
-      for (int64_t j = j0; j < j1; ++j) {
-        const double* col = X.dense + j * n;
-        double* dst = xs.data() + j * n;
-        double sum = 0.0;
-        for (int64_t i = 0; i < n; ++i) {
-          dst[to[(size_t)i]] = col[i];
-          sum += col[i];
-        }
-        const double a = abar[(size_t)j] = sum / (double)n;
-        for (int g = 0; g < G; ++g) {
-          double t1 = 0.0, t2 = 0.0;
-          for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) {
-            const double d = dst[i] - a;
-            t1 += d;
-            t2 += d * d;
-          }
-          s1[(size_t)g * P + (size_t)j] = t1;
-          s2[(size_t)g * P + (size_t)j] = t2;
-        }
-      }
-    });
+    sorted_dense_moments(X.dense, n, p, G, to, start, xs, abar, s1, s2);
   }
-  // pooled per training set (the group's own sums, or the total -- added in group order -- less them) and moved to the
-  // set's own mean: mean_T = a + S1 / n_T, var_T = S2 / n_T - (S1 / n_T)^2
   const bool centre = intercept || ctl->standardize != 0;
-  std::vector<double> mean((size_t)G * P, 0.0), scale((size_t)G * P, 1.0);
-  for (size_t j = 0; j < P; ++j) {
-    const double a = abar[j];
-    double t1 = 0.0, t2 = 0.0;
-    for (int g = 0; g < G; ++g) {
-      t1 += s1[(size_t)g * P + j];
-      t2 += s2[(size_t)g * P + j];
-    }
-    for (int g = 0; g < G; ++g) {
-      const double nT = (double)n_t[(size_t)g];
-      const double d = (rest ? t1 - s1[(size_t)g * P + j] : s1[(size_t)g * P + j]) / nT;
-      const double var = (rest ? t2 - s2[(size_t)g * P + j] : s2[(size_t)g * P + j]) / nT - d * d;
-      if (centre) mean[(size_t)g * P + j] = a + d;
-      if (ctl->standardize) scale[(size_t)g * P + j] = var > 0.0 ? sqrt(var) : 1.0;
-    }
-  }
+  std::vector<double> mean, scale;
+  pooled_centres_and_scales(abar, s1, s2, n_t, rest, centre, ctl->standardize != 0, mean, scale);
   pt.mark("cv newton: rows sorted, moments");
 
   // regularization_path for user lambdas and a binomial response (its y_scale is 1)
@@ -772,6 +797,209 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
             "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
             nr.moments_ms, nr.cd_ms, nr.state_ms);
   pt.mark("cv newton (all folds)");
+  return SGDNET_OK;
+}
+
+// ---- cross-validation in multinomial Newton mode (mnewton.hip: mnewton_cv_run): the stage behind sgdnet_cv_mnewton_* ----
+// Every job (mix, training set T) is fit_mnewton on x[T], y[T] by definition.  Sparse x is expanded to the dense copy a
+// single fit makes (driver.cpp: fit_sparse_impl; entries stored twice add up), before anything is computed from it, so a
+// sparse call gives the dense call's bits.  Then fit_cv_newton's steps with K classes: the rows sorted, per training set
+// x_center and x_scale, the null model's intercepts (the class-centred logs of T's class proportions, or of 1 / K each
+// without an intercept) and its deviance, and regularization_path's penalties for the user's lambdas.  A training set
+// without a row of some class is refused: its separate fit would silently be a model of fewer classes.
+// Every refusal is decided before the first HIP call.
+int fit_cv_mnewton(const CvNewtonMatrix& X, const double* y, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
+                   int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mnewton_result* out) {
+  const int64_t n = X.n, p = X.p;
+  if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !out->steps ||
+      !out->halvings || !y || !fold || !alphas || !lambdas) {
+    set_error("sgdnet_cv_mnewton: null pointer");
+    return SGDNET_EINVAL;
+  }
+  if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
+      (train_on_rest && n_groups < 2)) {
+    set_error("sgdnet_cv_mnewton: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    return SGDNET_EINVAL;
+  }
+  const int L = ctl->n_lambda, G = n_groups, K = ctl->n_classes;
+  const bool sparse = X.dense == nullptr, rest = train_on_rest != 0;
+  const int limit = mnewton_max_features(K);
+  const char* what = nullptr;
+  if (ctl->family != SGDNET_MULTINOMIAL) what = "family = multinomial";
+  else if (K < 2 || K >= 100) what = "2 to 99 classes";
+  else if (ctl->type_multinomial != 0) what = "the ungrouped penalty (type_multinomial = 0)";
+  else if (p > limit) what = "no more features than sgdnet_mnewton_max_features(n_classes)";
+  else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
+  else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
+  else if (sparse && (double)n * (double)p * 8.0 > (double)kMNewtonDenseCopyBytes)
+    what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
+  if (what) {
+    set_error("mode = mnewton needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family,
+              K, (long long)n, (long long)p, limit, ctl->n_gpus, ctl->debug);
+    return SGDNET_EUNSUPPORTED;
+  }
+  int rc = validate_response(ctl, y, n);
+  if (rc) return rc;
+  std::vector<int64_t> count, start, to;
+  rc = count_groups(fold, n, G, count);
+  if (!rc) rc = validate_mixes(n_alpha, alphas, L, lambdas);
+  if (rc) return rc;
+  sort_by_group(fold, n, count, start, to);
+  std::vector<double> ys((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ys[(size_t)to[(size_t)i]] = y[i];
+  // the response of every training set: every class, the null model and its deviance (fit_null_model, null_deviance), the
+  // equal terms counted instead of added one by one
+  const bool intercept = ctl->intercept != 0;
+  std::vector<int64_t> n_t((size_t)G);
+  std::vector<double> b0((size_t)G * (size_t)K), nulldev((size_t)G);
+  {
+    std::vector<int64_t> in_group((size_t)G * (size_t)K, 0), in_all((size_t)K, 0);
+    for (int g = 0; g < G; ++g)
+      for (int64_t i = start[(size_t)g]; i < start[(size_t)g + 1]; ++i) {
+        const size_t k = (size_t)(ys[(size_t)i] + 0.5);
+        ++in_group[(size_t)g * (size_t)K + k];
+        ++in_all[k];
+      }
+    for (int g = 0; g < G; ++g) {
+      const int64_t own = start[(size_t)g + 1] - start[(size_t)g];
+      const double nT = (double)(n_t[(size_t)g] = rest ? n - own : own);
+      double* b = b0.data() + (size_t)g * (size_t)K;
+      double log_sum = 0.0;
+      for (int k = 0; k < K; ++k) {
+        const int64_t c = rest ? in_all[(size_t)k] - in_group[(size_t)g * (size_t)K + (size_t)k] : in_group[(size_t)g * (size_t)K + (size_t)k];
+        if (c <= 0) {
+          set_error("the training set of group %d of %d holds no row of class %d (%lld rows)", g, G, k, (long long)n_t[(size_t)g]);
+          return SGDNET_EINVAL;
+        }
+        b[k] = log(intercept ? (double)c / nT : 1.0 / (double)K);
+        log_sum += b[k];
+      }
+      double mx = b[0] - log_sum / (double)K, sum = 0.0, picked = 0.0;
+      for (int k = 0; k < K; ++k) {
+        b[k] -= log_sum / (double)K;
+        mx = std::max(mx, b[k]);
+      }
+      for (int k = 0; k < K; ++k) {
+        const int64_t c = rest ? in_all[(size_t)k] - in_group[(size_t)g * (size_t)K + (size_t)k] : in_group[(size_t)g * (size_t)K + (size_t)k];
+        sum += exp(b[k] - mx);
+        picked += (double)c * b[k];
+      }
+      // sum over T of log sum_k e^b_k - b_{y_i}
+      nulldev[(size_t)g] = 2.0 * (nT * (log(sum) + mx) - picked);
+    }
+  }
+  const int64_t class_pairs = (int64_t)K * (K + 1) / 2;
+  if ((int64_t)n_alpha * G > kNewtonCvMaxJobs || (int64_t)n_alpha * G * class_pairs > kMNewtonCvMaxGridZ) {
+    set_error("mode = mnewton needs no more than %lld jobs and %lld jobs x class pairs in one cross-validation call: %d mixes x %d groups "
+              "x %lld class pairs", (long long)kNewtonCvMaxJobs, (long long)kMNewtonCvMaxGridZ, n_alpha, G, (long long)class_pairs);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const double workspace = mnewton_cv_workspace_bytes(n, p, K, n_t.data(), G, n_alpha, L);
+  if (workspace > (double)kNewtonCvWorkspaceBytes) {
+    set_error("mode = mnewton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of (rows x %d classes + %lld class pairs x "
+              "((%lld + 2)^2 moments + row-chunk partials) + %d lambdas x %lld coordinates) doubles are %.0f bytes", kNewtonCvWorkspaceBytes,
+              n_alpha, G, K, (long long)class_pairs, (long long)p, L, (long long)(K * (p + 1)), workspace);
+    return SGDNET_EUNSUPPORTED;
+  }
+  rc = check_device(ctl->device);
+  if (rc) return rc;
+  PhaseTimer pt;
+
+  std::vector<double> expanded;
+  const double* dense = X.dense;
+  if (sparse) {
+    expanded.assign((size_t)(n * p), 0.0);
+    for (int64_t j = 0; j < p; ++j)
+      for (int64_t q = X.colptr[j]; q < X.colptr[j + 1]; ++q) expanded[(size_t)(X.rowidx[q] + j * n)] += X.values[q];
+    dense = expanded.data();
+  }
+  const size_t P = (size_t)p;
+  std::vector<double> xs, abar(P, 0.0), s1((size_t)G * P, 0.0), s2((size_t)G * P, 0.0), mean, scale;
+  sorted_dense_moments(dense, n, p, G, to, start, xs, abar, s1, s2);
+  std::vector<double>().swap(expanded);
+  const bool centre = intercept || ctl->standardize != 0;
+  pooled_centres_and_scales(abar, s1, s2, n_t, rest, centre, ctl->standardize != 0, mean, scale);
+  pt.mark("cv mnewton: rows sorted, moments");
+
+  // regularization_path for user lambdas and a multinomial response (its y_scale is 1)
+  std::vector<double> l2((size_t)n_alpha * (size_t)L), l1(l2.size());
+  std::vector<uint8_t> ridge((size_t)n_alpha);
+  for (int a = 0; a < n_alpha; ++a) {
+    ridge[(size_t)a] = alphas[a] == 0.0;
+    for (int l = 0; l < L; ++l) {
+      l2[(size_t)a * L + l] = (1.0 - alphas[a]) * lambdas[(size_t)a * L + l] / 1.0;
+      l1[(size_t)a * L + l] = alphas[a] * lambdas[(size_t)a * L + l] / 1.0;
+    }
+  }
+  MNewtonCvProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.K = K;
+  pb.x_dense = xs.data();
+  pb.y = ys.data();
+  pb.n_sets = G;
+  pb.start = start.data();
+  pb.train_on_rest = rest;
+  pb.fit_intercept = intercept;
+  pb.mean = mean.data();
+  pb.scale = scale.data();
+  pb.b0 = b0.data();
+  pb.device = ctl->device;
+  pb.n_mix = n_alpha;
+  pb.n_lambda = L;
+  pb.l2 = l2.data();
+  pb.l1 = l1.data();
+  pb.ridge = ridge.data();
+  pb.max_iter = ctl->max_iter;
+  pb.tol = ctl->tol;
+  MNewtonCvResult nr;
+  rc = mnewton_cv_run(pb, pt.on, &nr);
+  if (rc) return rc;
+
+  const size_t P1 = P + 1, Q = (size_t)K * P1;
+  double most_steps = 0.0, most_halvings = 0.0;
+  std::vector<double> b((size_t)K);
+  for (int a = 0; a < n_alpha; ++a)
+    for (int t = 0; t < G; ++t) {
+      const size_t job = (size_t)a * (size_t)G + (size_t)t;
+      const double* m = mean.data() + (size_t)t * P;
+      const double* s = scale.data() + (size_t)t * P;
+      for (int li = 0; li < L; ++li) {
+        const size_t at = job * (size_t)L + (size_t)li;
+        const double* u = nr.u.data() + at * Q;
+        double* bo = out->beta + at * P * (size_t)K;     // entry (k, j) at k + j K
+        double* ao = out->a0 + at * (size_t)K;
+        // fit_mnewton and rescale_values: per class the intercept at the centres less the centres times the coefficients,
+        // then the class mean of the intercepts removed
+        double b_mean = 0.0;
+        for (int k = 0; k < K; ++k) {
+          const double* uk = u + (size_t)k * P1;
+          double xbb = 0.0;
+          for (size_t j = 0; j < P; ++j) {
+            const double v = uk[j] / s[j];
+            bo[(size_t)k + j * (size_t)K] = v;
+            xbb += m[j] * v;
+          }
+          b[(size_t)k] = intercept ? uk[P] - xbb : b0[(size_t)t * (size_t)K + (size_t)k];
+          b_mean += b[(size_t)k];
+        }
+        b_mean /= (double)K;
+        for (int k = 0; k < K; ++k) ao[k] = intercept ? b[(size_t)k] - b_mean : b[(size_t)k];
+        out->dev_ratio[at] = 1.0 - 2.0 * (double)n_t[(size_t)t] * nr.loss[at] / nulldev[(size_t)t];
+        out->return_codes[at] = nr.unconverged[at] ? 1.0 : 0.0;
+      }
+      out->nulldev[job] = nulldev[(size_t)t];
+      out->npasses[job] = nr.passes[job];
+      out->steps[job] = nr.steps[job];
+      out->halvings[job] = nr.halvings[job];
+      most_steps = std::max(most_steps, nr.steps[job] + nr.halvings[job]);
+      most_halvings = std::max(most_halvings, nr.halvings[job]);
+    }
+  if (pt.on)
+    fprintf(stderr, "[sgdnet]   cv mnewton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
+            "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
+            nr.moments_ms, nr.cd_ms, nr.state_ms);
+  pt.mark("cv mnewton (all folds)");
   return SGDNET_OK;
 }
 
@@ -893,6 +1121,38 @@ int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t*
   X.rowidx = x->rowidx;
   X.values = x->values;
   return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_mnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                            const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                            sgdnet_cv_mnewton_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_mnewton_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  CvNewtonMatrix X;
+  X.n = n;
+  X.p = p;
+  X.dense = x;
+  return fit_cv_mnewton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_mnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                             sgdnet_cv_mnewton_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_mnewton_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  CvNewtonMatrix X;
+  X.n = x->n_rows;
+  X.p = x->n_cols;
+  X.colptr = x->colptr;
+  X.rowidx = x->rowidx;
+  X.values = x->values;
+  return fit_cv_mnewton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
 }
 
 // ---- diagnostics: one outer step of Newton mode (newton.hip: newton_probe) ----

@@ -34,6 +34,13 @@
 // (wide_cd_device.hpp) over the Q coordinates; the blend forms its value where it is read (mnewton_wide_blend_kernel).
 // Same optimum as the narrow mode, not the same bits; neither falls back to the other.
 //
+// Cross-validation (mnewton_cv_run, include/sgdnet_hip.h: sgdnet_cv_mnewton_*): all fold fits of all mixes advance in
+// lock-step, as newton.hip's newton_cv_run runs the binomial ones.  The rows are sorted by group once, so a training set is
+// a range of rows or the complement of one; the mnewton_cv_* kernels are the narrow mode's kernels with a job dimension,
+// each job on its own rows, centres, scales and buffers (mu by the job's local row; (job, class pair) in one grid
+// dimension of the moments pass); the command, the job and the host's state machine per job are newton_cv_device.hpp's,
+// shared with newton.hip.
+//
 // x is dense, column-major: this mode's p is at most 98, and the driver expands sparse x before anything is computed from
 // it (driver.cpp: fit_sparse_impl), so that a sparse fit is the dense fit of the same matrix from the standard deviations
 // and lambda_max on, bit for bit.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K):
@@ -50,6 +57,7 @@
 #include "device_math.hpp"
 #include "mnewton.hpp"
 #include "moments_device.hpp"
+#include "newton_cv_device.hpp"
 #include "wide_cd_device.hpp"
 
 namespace sgdnet {
@@ -57,8 +65,7 @@ namespace {
 
 constexpr int kStateMaxBlocks = 1024;   // workgroups of the state pass: each leaves one sum
 
-// the record of a candidate, in device memory; the host reads it after every state pass (newton.hip)
-enum Rec { kRecLoss = 0, kRecHalfSq, kRecAbs, kRecChange, kRecSize, kRecSweeps, kRecInnerConverged, kRecNegligible, kRecLen };
+// (the record of a candidate, in device memory, read by the host after every state pass: newton_cv_device.hpp)
 
 // a[k P + j] = w_kj / s_j (j < p), a[k P + p] = b_k: the candidate as the state pass multiplies it.  mu[i + k n] holds
 // eta_ik, then e^(eta_ik - max), then mu_ik.  Workgroup b leaves its sum of the loss in partial[b].
@@ -232,12 +239,12 @@ __global__ __launch_bounds__(64) void mnewton_blend_kernel(const double* __restr
 // (newton_cd_kernel); the width only spreads the update of g, an entry per lane, so both widths give the same bits.
 // M: the K (K + 1) / 2 pair moments, (p + 2)^2 each (upper triangle), dn = n; the quadratic model about u_cur is
 //   (U - U0)'H (U - U0) / 2 - q'(U - U0) + sum_k (al/2 |w_k|^2 + be |w_k|_1),     its smooth gradient g = H (U - U0) - q.
+// (the body of mnewton_cd_kernel and of mnewton_cv_cd_kernel, which runs it once per job; lds: the workgroup's whole LDS)
 template <int kWidth>
-__global__ __launch_bounds__(kWidth) void mnewton_cd_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
-                                                             double dn, const double* __restrict__ u_cur, double al, double be, int ridge,
-                                                             int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
-                                                             double* __restrict__ a_cand, double* __restrict__ rec) {
-  __shared__ double lds[mnewton_state_doubles(kMNewtonMaxCoordinates)];
+__device__ __forceinline__ void mnewton_cd_solve(double* lds, const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
+                                                 double dn, const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                 int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                 double* __restrict__ a_cand, double* __restrict__ rec) {
   const int lane = threadIdx.x, P = p + 1, nc = p + 2, Q = K * P;
   const size_t block = (size_t)nc * (size_t)nc;
   double* H = lds;
@@ -303,8 +310,201 @@ __global__ __launch_bounds__(kWidth) void mnewton_cd_kernel(const double* __rest
   }
 }
 
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void mnewton_cd_kernel(const double* __restrict__ M, const double* __restrict__ scale, int p, int K,
+                                                             double dn, const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                             int fit_intercept, unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                             double* __restrict__ a_cand, double* __restrict__ rec) {
+  __shared__ double lds[mnewton_state_doubles(kMNewtonMaxCoordinates)];
+  mnewton_cd_solve<kWidth>(lds, M, scale, p, K, dn, u_cur, al, be, ridge, fit_intercept, max_sweeps, tol, u_cand, a_cand, rec);
+}
+
 // One wavefront while one stride of it covers the coordinates; 256 lanes beyond (profiles/mnewton_path.txt).
 int mnewton_cd_width(int Q) { return Q <= 64 ? 64 : 256; }
+
+// ---- cross-validation (mnewton_cv_run): the kernels above with a job dimension ----
+// A job is one (mix, training set), its command, its rows (cv_row) and its record as newton_cv_device.hpp has them: shared
+// with newton.hip's cross-validation.  Every job has its own a, mu, sums, pair moments, record, two iterates and slice of
+// U; its centres and scales are its training set's; its grids (state workgroups, row chunks, the inner solve's width) are
+// those mnewton_run would choose for n_t rows, so its arithmetic is the same whichever other jobs share the launch.
+// mu of a job is indexed by the job's LOCAL row li = 0 .. n_t - 1, a column per class, from mu_at[job] on.
+
+// mnewton_state_kernel for the job blockIdx.y over the job's rows; workgroup b of the job leaves its sum in partial[job][b]
+__global__ __launch_bounds__(kBlock) void mnewton_cv_state_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                   const int64_t* __restrict__ mu_at, const double* __restrict__ x,
+                                                                   const double* __restrict__ y, const double* __restrict__ m_all,
+                                                                   const double* __restrict__ a_all, int64_t n, int p, int K,
+                                                                   double* __restrict__ mu_all, double* __restrict__ partial_all) {
+  __shared__ double sh[kBlock];
+  const int job = blockIdx.y;
+  if (cmd[job].action == kCvIdle) return;
+  const CvJob J = jobs[job];
+  if ((int)blockIdx.x >= J.state_blocks) return;
+  const int P = p + 1;
+  const int64_t nt = J.n_t;
+  const double* __restrict__ m = m_all + (size_t)J.set * (size_t)p;
+  const double* __restrict__ a = a_all + (size_t)job * (size_t)K * (size_t)P;
+  double* __restrict__ mu = mu_all + mu_at[job];
+  double loss = 0.0;
+  for (int64_t li = (int64_t)blockIdx.x * kBlock + threadIdx.x; li < nt; li += (int64_t)J.state_blocks * kBlock) {
+    const int64_t i = cv_row(J, li);
+    const int yi = (int)(y[i] + 0.5);
+    double mx = 0.0, eta_y = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double* __restrict__ ak = a + (size_t)k * (size_t)P;
+      double eta = 0.0;
+      for (int j = 0; j < p; ++j) eta += (x[i + (int64_t)j * n] - m[j]) * ak[j];
+      eta += ak[p];
+      mu[li + (int64_t)k * nt] = eta;
+      mx = k == 0 ? eta : fmax(mx, eta);
+      if (k == yi) eta_y = eta;
+    }
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double e = SGD_EXP(mu[li + (int64_t)k * nt] - mx);
+      mu[li + (int64_t)k * nt] = e;
+      s += e;
+    }
+    for (int k = 0; k < K; ++k) mu[li + (int64_t)k * nt] /= s;
+    loss += (SGD_LOG(s) + mx) - eta_y;
+  }
+  loss = block_sum(loss, sh);
+  if (threadIdx.x == 0) partial_all[(size_t)job * kStateMaxBlocks + blockIdx.x] = loss;
+}
+
+// mnewton_finish_kernel for the job blockIdx.x: the mean is over the job's n_t rows
+__global__ __launch_bounds__(kBlock) void mnewton_cv_finish_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                    const double* __restrict__ partial_all, double* __restrict__ rec_all) {
+  __shared__ double sh[kBlock];
+  const int job = blockIdx.x;
+  if (cmd[job].action == kCvIdle) return;
+  const double* __restrict__ partial = partial_all + (size_t)job * kStateMaxBlocks;
+  const int blocks = jobs[job].state_blocks;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < blocks; b += kBlock) s += partial[b];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) rec_all[(size_t)job * kRecLen + kRecLoss] = s / (double)jobs[job].n_t;
+}
+
+// mnewton_pair_tile_kernel with (job, class pair) = blockIdx.z / class pairs, blockIdx.z % class pairs: blockIdx.y is a chunk
+// of the JOB's rows.  part[job][pair][chunk <= max_chunks][tile pair][tid].
+__global__ __launch_bounds__(kBlock) void mnewton_cv_pair_tile_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                       const int64_t* __restrict__ mu_at, const double* __restrict__ x,
+                                                                       const double* __restrict__ y, const double* __restrict__ mu_all,
+                                                                       const double* __restrict__ m_all, int64_t n, int p, int K,
+                                                                       int max_chunks, double* __restrict__ part) {
+  __shared__ double A[kTileCols][kTileRows + 1], B[kTileCols][kTileRows + 1];
+  const int class_pairs = K * (K + 1) / 2;
+  const int job = (int)blockIdx.z / class_pairs, cp = (int)blockIdx.z - job * class_pairs;
+  if (cmd[job].action != kCvStep) return;
+  const CvJob J = jobs[job];
+  if ((int)blockIdx.y >= J.chunks) return;
+  const double* __restrict__ m = m_all + (size_t)J.set * (size_t)p;
+  const int tid = threadIdx.x, ncols = p + 2;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  int ck, cl;
+  class_pair(cp, K, &ck, &cl);
+  const double* __restrict__ mu_k = mu_all + mu_at[job] + (int64_t)ck * J.n_t;
+  const double* __restrict__ mu_l = mu_all + mu_at[job] + (int64_t)cl * J.n_t;
+  const int ta = tid & (kTileCols - 1), tb = tid / kTileCols;
+  const int64_t r0 = (int64_t)blockIdx.y * J.rows_per_chunk;
+  const int64_t r1 = r0 + J.rows_per_chunk < J.n_t ? r0 + J.rows_per_chunk : J.n_t;
+  double acc = 0.0;
+  for (int64_t base = r0; base < r1; base += kTileRows) {
+    for (int e = tid; e < kTileCols * kTileRows; e += kBlock) {
+      const int row = e & (kTileRows - 1), col = e / kTileRows;
+      const int64_t li = base + row;
+      const int ca = tj * kTileCols + col, cb = tk * kTileCols + col;
+      double da = 0.0, db = 0.0;
+      if (li < r1) {
+        const int64_t i = cv_row(J, li);
+        if (ca <= p) da = ca < p ? x[i + (int64_t)ca * n] - m[ca] : 1.0;
+        if (cb == p + 1) {
+          if (ck == cl) db = ((int)(y[i] + 0.5) == ck ? 1.0 : 0.0) - mu_k[li];
+        } else if (cb <= p) {
+          const double v = ck == cl ? mu_k[li] * (1.0 - mu_k[li]) : -(mu_k[li] * mu_l[li]);
+          db = v * (cb < p ? x[i + (int64_t)cb * n] - m[cb] : 1.0);
+        }
+      }
+      A[col][row] = da;
+      B[col][row] = db;
+    }
+    __syncthreads();
+    for (int i = 0; i < kTileRows; ++i) acc += A[ta][i] * B[tb][i];
+    __syncthreads();
+  }
+  part[(((size_t)blockIdx.z * (size_t)max_chunks + blockIdx.y) * gridDim.x + blockIdx.x) * kBlock + tid] = acc;
+}
+
+// mnewton_pair_reduce_kernel for (job, class pair) = blockIdx.y: the job's chunks added in chunk order into M[job][pair]
+__global__ __launch_bounds__(kBlock) void mnewton_cv_pair_reduce_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                         const double* __restrict__ part, int class_pairs, int max_chunks,
+                                                                         int ncols, double* __restrict__ M_all) {
+  const int job = (int)blockIdx.y / class_pairs;
+  if (cmd[job].action != kCvStep) return;
+  const int tid = threadIdx.x;
+  const int T = (ncols + kTileCols - 1) / kTileCols;
+  int pair = blockIdx.x, tj = 0;
+  while (pair >= T - tj) {
+    pair -= T - tj;
+    ++tj;
+  }
+  const int tk = tj + pair;
+  const int a = tj * kTileCols + (tid & (kTileCols - 1)), b = tk * kTileCols + tid / kTileCols;
+  if (a >= ncols || b >= ncols) return;
+  const int chunks = jobs[job].chunks;
+  double* __restrict__ M = M_all + (size_t)blockIdx.y * (size_t)ncols * (size_t)ncols;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += part[(((size_t)blockIdx.y * (size_t)max_chunks + c) * gridDim.x + blockIdx.x) * kBlock + tid];
+  M[(size_t)a * ncols + b] = s;
+  if (tj != tk) M[(size_t)b * ncols + a] = s;
+}
+
+// mnewton_blend_kernel for the job blockIdx.x: a halving (t = 1/2), or the path's start published as it is (t = 1)
+__global__ __launch_bounds__(64) void mnewton_cv_blend_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                               const double* __restrict__ scale_all, int p, int Q, double* __restrict__ u_all,
+                                                               double* __restrict__ a_all, double* __restrict__ rec_all) {
+  __shared__ double un[kMNewtonMaxCoordinates];
+  const int job = blockIdx.x;
+  const CvCmd c = cmd[job];
+  if (c.action != kCvHalve && c.action != kCvStart) return;
+  const double* __restrict__ u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)Q;
+  double* __restrict__ u_cand = u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)Q;
+  const double t = c.action == kCvStart ? 1.0 : 0.5;
+  for (int k = threadIdx.x; k < Q; k += 64) un[k] = t == 1.0 ? u_cand[k] : u_cur[k] + t * (u_cand[k] - u_cur[k]);
+  __syncthreads();
+  mnewton_publish(un, u_cur, scale_all + (size_t)jobs[job].set * (size_t)p, p, Q, u_cand, a_all + (size_t)job * (size_t)Q,
+                  rec_all + (size_t)job * kRecLen);
+}
+
+// mnewton_cd_kernel for the job blockIdx.x: one workgroup per job, each declaring the whole LDS, so the jobs spread one
+// per CU.  Before anything else it stores the current iterate into U[slot] where the host says it answers a lambda.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void mnewton_cv_cd_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                const double* __restrict__ M_all, const double* __restrict__ scale_all, int p,
+                                                                int K, int n_lambda, int fit_intercept, unsigned max_sweeps, double tol,
+                                                                double* __restrict__ u_all, double* __restrict__ a_all,
+                                                                double* __restrict__ rec_all, double* __restrict__ U_all) {
+  __shared__ double lds[mnewton_state_doubles(kMNewtonMaxCoordinates)];
+  const int job = blockIdx.x, nc = p + 2, Q = K * (p + 1), class_pairs = K * (K + 1) / 2;
+  const CvCmd c = cmd[job];
+  const double* __restrict__ u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)Q;
+  if (c.slot >= 0) {
+    double* __restrict__ U = U_all + ((size_t)job * (size_t)n_lambda + (size_t)c.slot) * (size_t)Q;
+    for (int k = threadIdx.x; k < Q; k += kWidth) U[k] = u_cur[k];
+  }
+  if (c.action != kCvStep) return;
+  mnewton_cd_solve<kWidth>(lds, M_all + (size_t)job * (size_t)class_pairs * (size_t)nc * (size_t)nc,
+                           scale_all + (size_t)jobs[job].set * (size_t)p, p, K, (double)jobs[job].n_t, u_cur, c.l2, c.l1, c.ridge,
+                           fit_intercept, max_sweeps, tol, u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)Q,
+                           a_all + (size_t)job * (size_t)Q, rec_all + (size_t)job * kRecLen);
+}
 
 // ---- wide multinomial Newton mode (SGDNET_MODE_WMNEWTON, wmnewton_run): H in global memory, only what can move is touched ----
 
@@ -747,6 +947,203 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
 int wmnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width) {
   const int64_t Q = (int64_t)pb.K * (pb.p + 1);
   return mnewton_loop(pb, timed, out, true, width != 0 ? width : wmnewton_cd_width((int)std::min<int64_t>(Q, kWmnewtonMaxCoordinates)));
+}
+
+namespace {
+
+// the geometry of a call's jobs: a function of (p, K, the groups, the number of mixes) alone
+struct MCvGeometry {
+  int pairs = 0, class_pairs = 0, max_chunks = 0, max_state_blocks = 0;
+  std::vector<CvJob> jobs;
+  std::vector<int64_t> mu_at;          // jobs + 1: where a job's mu starts, in doubles
+  MCvGeometry(int64_t p, int K, const int64_t* n_t, int n_sets, int n_mix) {
+    const int nc = (int)p + 2, T = (nc + kTileCols - 1) / kTileCols;
+    pairs = T * (T + 1) / 2;
+    class_pairs = K * (K + 1) / 2;
+    jobs.resize((size_t)n_sets * (size_t)n_mix);
+    mu_at.assign(jobs.size() + 1, 0);
+    for (int a = 0; a < n_mix; ++a)
+      for (int t = 0; t < n_sets; ++t) {
+        const size_t job = (size_t)a * (size_t)n_sets + (size_t)t;
+        CvJob& J = jobs[job];
+        J = CvJob{};
+        J.n_t = n_t[t];
+        J.set = t;
+        J.rows_per_chunk = dense_rows_per_chunk(J.n_t, pairs * class_pairs);
+        J.chunks = (int32_t)((J.n_t + J.rows_per_chunk - 1) / J.rows_per_chunk);
+        J.state_blocks = (int32_t)std::min<int64_t>(kStateMaxBlocks, (J.n_t + kBlock - 1) / kBlock);
+        max_chunks = std::max(max_chunks, (int)J.chunks);
+        max_state_blocks = std::max(max_state_blocks, (int)J.state_blocks);
+        mu_at[job + 1] = mu_at[job] + J.n_t * K;
+      }
+  }
+};
+
+static_assert(kStateMaxBlocks == kMNewtonCvStateMaxBlocks && kRecLen == kMNewtonCvRecordDoubles && kTileRows == 64 && kBlock == 256,
+              "mnewton.hpp: mnewton_cv_workspace_bytes counts these");
+
+}  // namespace
+
+// The lock-step loop: newton_cv_run's (newton.hip) around the kernels of the multinomial step.  A round: the commands go up
+// in one copy, every kernel is launched once over all jobs (a job whose command does not need a kernel leaves it at once),
+// the records come back in one copy, and every job's state machine moves as mnewton_run moves its one
+// (newton_cv_device.hpp: cv_job_advance).  The loop ends when every job has finished its last lambda; one last launch
+// stores the iterates still owed.
+int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out) {
+  const int p = (int)pb.p, P = p + 1, nc = p + 2, K = pb.K, L = pb.n_lambda, G = pb.n_sets;
+  const int64_t n = pb.n;
+  if (n <= 0 || pb.p <= 0 || K < 2 || pb.p > mnewton_max_features(K) || L <= 0 || G <= 0 || pb.n_mix <= 0 || !pb.x_dense || !pb.y || !pb.start ||
+      !pb.mean || !pb.scale || !pb.b0 || !pb.l2 || !pb.l1 || !pb.ridge || pb.max_iter == 0 || (int64_t)G * pb.n_mix > kNewtonCvMaxJobs ||
+      (int64_t)G * pb.n_mix * (K * (K + 1) / 2) > kMNewtonCvMaxGridZ) {
+    set_error("mnewton_cv_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  const int Q = K * P;
+  std::vector<int64_t> n_t((size_t)G);
+  for (int t = 0; t < G; ++t) {
+    const int64_t own = pb.start[t + 1] - pb.start[t];
+    n_t[(size_t)t] = pb.train_on_rest ? n - own : own;
+    if (own <= 0 || n_t[(size_t)t] <= 0) {
+      set_error("mnewton_cv_run: empty training set %d", t);
+      return SGDNET_EINVAL;
+    }
+  }
+  MCvGeometry geo(p, K, n_t.data(), G, pb.n_mix);
+  const int jobs = (int)geo.jobs.size(), class_pairs = geo.class_pairs;
+  for (CvJob& J : geo.jobs) {
+    cv_job_rows(J, pb.start, n, pb.train_on_rest);
+    if (J.chunks != mnewton_cv_chunks(J.n_t, (int64_t)geo.pairs * class_pairs)) {    // (what the caller sized the workspace with)
+      set_error("mnewton_cv_run: the row chunks of %lld rows differ from mnewton_cv_chunks", (long long)J.n_t);
+      return SGDNET_EINVAL;
+    }
+  }
+  const int width = mnewton_cd_width(Q);
+
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(n * (int64_t)p));
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_m = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_jobs = A.reserve(sizeof(CvJob) * (size_t)jobs);
+  const size_t o_cmd = A.reserve(sizeof(CvCmd) * (size_t)jobs);
+  const size_t o_mu_at = A.reserve(sizeof(int64_t) * (size_t)jobs);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)geo.mu_at[(size_t)jobs]);
+  const size_t o_part = A.reserve(sizeof(double) * (size_t)jobs * (size_t)class_pairs * (size_t)geo.max_chunks * (size_t)geo.pairs * kBlock);
+  const size_t o_M = A.reserve(sizeof(double) * (size_t)jobs * (size_t)class_pairs * (size_t)nc * (size_t)nc);
+  const size_t o_partial = A.reserve(sizeof(double) * (size_t)jobs * kStateMaxBlocks);
+  const size_t o_rec = A.reserve(sizeof(double) * kRecLen * (size_t)jobs);
+  const size_t o_u = A.reserve(sizeof(double) * 2 * (size_t)Q * (size_t)jobs);
+  const size_t o_a = A.reserve(sizeof(double) * (size_t)Q * (size_t)jobs);
+  const size_t o_U = A.reserve(sizeof(double) * (size_t)jobs * (size_t)L * (size_t)Q);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+  double *d_x = A.at<double>(o_x), *d_y = A.at<double>(o_y), *d_m = A.at<double>(o_m), *d_scale = A.at<double>(o_scale),
+         *d_mu = A.at<double>(o_mu), *d_part = A.at<double>(o_part), *d_M = A.at<double>(o_M), *d_partial = A.at<double>(o_partial),
+         *d_rec = A.at<double>(o_rec), *d_u = A.at<double>(o_u), *d_a = A.at<double>(o_a), *d_U = A.at<double>(o_U);
+  CvJob* d_jobs = A.at<CvJob>(o_jobs);
+  CvCmd* d_cmd = A.at<CvCmd>(o_cmd);
+  int64_t* d_mu_at = A.at<int64_t>(o_mu_at);
+
+  Stream sx;                           // (its rec_host is not used here: the records of all jobs come back into `pinned`)
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&sx.st, hipStreamNonBlocking));
+  hipStream_t st = sx.st;
+  if (timed)
+    for (hipEvent_t& e : sx.e) SGD_HIP_TRY(hipEventCreate(&e));
+  CvPinned pinned;                     // the commands of a round, then the records of its state passes
+  SGD_HIP_TRY(hipHostMalloc(&pinned.p, sizeof(CvCmd) * (size_t)jobs + sizeof(double) * kRecLen * (size_t)jobs, hipHostMallocDefault));
+  CvCmd* cmd = static_cast<CvCmd*>(pinned.p);
+  const double* rec_all = reinterpret_cast<const double*>(cmd + jobs);
+
+  // upload: x, y, the training sets' centres and scales, the jobs; both iterates of every job start at (0, b0)
+  std::vector<double> start((size_t)jobs * 2 * (size_t)Q, 0.0);
+  for (int job = 0; job < jobs; ++job)
+    for (int b = 0; b < 2; ++b)
+      for (int k = 0; k < K; ++k)
+        start[((size_t)job * 2 + (size_t)b) * (size_t)Q + (size_t)k * (size_t)P + (size_t)p] = pb.b0[(size_t)geo.jobs[(size_t)job].set * (size_t)K + (size_t)k];
+  SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_m, pb.mean, sizeof(double) * (size_t)G * (size_t)p, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_scale, pb.scale, sizeof(double) * (size_t)G * (size_t)p, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_jobs, geo.jobs.data(), sizeof(CvJob) * (size_t)jobs, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_mu_at, geo.mu_at.data(), sizeof(int64_t) * (size_t)jobs, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(d_u, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(double) * kRecLen * (size_t)jobs, st));
+
+  out->loss.assign((size_t)jobs * (size_t)L, 0.0);
+  out->unconverged.assign((size_t)jobs * (size_t)L, 0);
+  out->passes.assign((size_t)jobs, 0.0);
+  out->steps.assign((size_t)jobs, 0.0);
+  out->halvings.assign((size_t)jobs, 0.0);
+  out->sweeps = 0.0;
+  out->rounds = 0;
+  out->moments_ms = out->cd_ms = out->state_ms = 0.f;
+
+  std::vector<CvJobState> state((size_t)jobs);
+  const int fit_intercept = pb.fit_intercept ? 1 : 0;
+  auto penalties = [&](int job, int l, double* al, double* be) {
+    const size_t at = (size_t)(job / G) * (size_t)L + (size_t)l;
+    *al = pb.l2[at];
+    *be = pb.ridge[job / G] ? 0.0 : pb.l1[at];
+  };
+  int live = jobs;
+  for (;;) {
+    bool any_step = false, any_blend = false;
+    for (int job = 0; job < jobs; ++job) {
+      const CvJobState& s = state[(size_t)job];
+      cv_command(cmd[job], s, pb.ridge[job / G] != 0, [&](int l, double* al, double* be) { penalties(job, l, al, be); });
+      any_step |= s.action == kCvStep;
+      any_blend |= s.action == kCvHalve || s.action == kCvStart;
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(d_cmd, cmd, sizeof(CvCmd) * (size_t)jobs, hipMemcpyHostToDevice, st));
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
+    if (any_step) {
+      hipLaunchKernelGGL(mnewton_cv_pair_tile_kernel, dim3((unsigned)geo.pairs, (unsigned)geo.max_chunks, (unsigned)(jobs * class_pairs)),
+                         dim3(kBlock), 0, st, d_cmd, d_jobs, d_mu_at, d_x, d_y, d_mu, d_m, n, p, K, geo.max_chunks, d_part);
+      hipLaunchKernelGGL(mnewton_cv_pair_reduce_kernel, dim3((unsigned)geo.pairs, (unsigned)(jobs * class_pairs)), dim3(kBlock), 0, st, d_cmd,
+                         d_jobs, d_part, class_pairs, geo.max_chunks, nc, d_M);
+    }
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
+    // (the inner solve's kernel also stores the iterates owed to U: it runs in every round)
+    if (width == 256)
+      hipLaunchKernelGGL(mnewton_cv_cd_kernel<256>, dim3((unsigned)jobs), dim3(256), 0, st, d_cmd, d_jobs, d_M, d_scale, p, K, L, fit_intercept,
+                         kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
+    else
+      hipLaunchKernelGGL(mnewton_cv_cd_kernel<64>, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_M, d_scale, p, K, L, fit_intercept,
+                         kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
+    if (any_blend)
+      hipLaunchKernelGGL(mnewton_cv_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, Q, d_u, d_a, d_rec);
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
+    if (live > 0) {
+      hipLaunchKernelGGL(mnewton_cv_state_kernel, dim3((unsigned)geo.max_state_blocks, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs,
+                         d_mu_at, d_x, d_y, d_m, d_a, n, p, K, d_mu, d_partial);
+      hipLaunchKernelGGL(mnewton_cv_finish_kernel, dim3((unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs, d_partial, d_rec);
+    }
+    SGD_HIP_TRY(hipGetLastError());
+    if (live == 0) break;              // (that was the launch that stores the last iterates)
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[3], st));
+    SGD_HIP_TRY(hipMemcpyAsync(const_cast<double*>(rec_all), d_rec, sizeof(double) * kRecLen * (size_t)jobs, hipMemcpyDeviceToHost, st));
+    SGD_HIP_TRY(hipStreamSynchronize(st));
+    ++out->rounds;
+    if (timed) {
+      float ms = 0.f;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[0], sx.e[1]));
+      out->moments_ms += ms;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[2]));
+      out->cd_ms += ms;
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
+      out->state_ms += ms;
+    }
+    for (int job = 0; job < jobs; ++job)
+      if (cv_job_advance(state[(size_t)job], rec_all + (size_t)job * kRecLen, L, pb.max_iter, pb.tol,
+                         [&](int l, double* al, double* be) { penalties(job, l, al, be); }, out->loss.data() + (size_t)job * (size_t)L,
+                         out->unconverged.data() + (size_t)job * (size_t)L, &out->passes[(size_t)job], &out->steps[(size_t)job],
+                         &out->halvings[(size_t)job], &out->sweeps))
+        --live;
+  }
+  out->u.resize((size_t)jobs * (size_t)L * (size_t)Q);
+  SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), d_U, sizeof(double) * out->u.size(), hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  return SGDNET_OK;
 }
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is

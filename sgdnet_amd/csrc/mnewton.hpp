@@ -134,6 +134,84 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
 // (wmnewton_cd_width); both give the same bits.
 int wmnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width = 0);
 
+// ---- cross-validation: every fold fit of every mix through the loop above in lock-step (mnewton.hip: mnewton_cv_run) ----
+// Job (mix a, training set t) = a * n_sets + t is mnewton_run on the rows of its training set, as newton.hpp's
+// newton_cv_run is newton_run: x and y come with the rows stably sorted by group, and with everything mnewton_run takes per
+// problem per training set.  x is dense (sparse x: the driver's dense copy, as for a single fit).
+//
+// What a call keeps on the device, in doubles.  Per job: mu by LOCAL row (n_t K, a column per class: by global row the K
+// columns of a job that trains on its fold would leave (G - 1) / G of them unused), the pair moments (K (K + 1) / 2 matrices
+// of (p + 2)^2), the row chunks' partial tiles (chunks x tile pairs x K (K + 1) / 2 x 256, the chunks of the job with the
+// most), the state pass's sums (1024), two iterates and the state-pass form of the candidate (3 Q), the record and the
+// path (n_lambda Q).  Once: x and y (n (p + 1)).  Calls that need more than newton.hpp's kNewtonCvWorkspaceBytes are refused;
+// so are those whose jobs (kNewtonCvMaxJobs) or jobs x class pairs do not fit a grid dimension.
+constexpr int64_t kMNewtonCvMaxGridZ = 65535;
+constexpr int kMNewtonCvStateMaxBlocks = 1024, kMNewtonCvRecordDoubles = 8;
+// moments_device.hpp's dense_rows_per_chunk in plain constexpr (mnewton.hip checks the two against each other): at most
+// max(16, min(256, 1024 / workgroups)) chunks, none shorter than 256 rows, whole steps of 64 staged rows
+constexpr int64_t mnewton_cv_rows_per_chunk(int64_t n_t, int64_t workgroups) {
+  const int64_t by_grid = 1024 / workgroups < 256 ? 1024 / workgroups : 256, cap = by_grid > 16 ? by_grid : 16;
+  const int64_t by_rows = (n_t + 255) / 256, chunks = by_rows < cap ? by_rows : cap;
+  return ((n_t + chunks - 1) / chunks + 63) / 64 * 64;
+}
+constexpr int64_t mnewton_cv_chunks(int64_t n_t, int64_t workgroups) {
+  return (n_t + mnewton_cv_rows_per_chunk(n_t, workgroups) - 1) / mnewton_cv_rows_per_chunk(n_t, workgroups);
+}
+// n_t: the rows of each training set.  (In double: a call far beyond the bound must not wrap.)
+constexpr double mnewton_cv_workspace_bytes(int64_t n, int64_t p, int K, const int64_t* n_t, int n_sets, int n_mix, int n_lambda) {
+  const int64_t class_pairs = (int64_t)K * (K + 1) / 2, tile_pairs = wide_tile_pairs(p + 2), Q = (int64_t)K * (p + 1);
+  int64_t max_chunks = 0;
+  double rows = 0.0;
+  for (int t = 0; t < n_sets; ++t) {
+    const int64_t c = mnewton_cv_chunks(n_t[t], tile_pairs * class_pairs);
+    max_chunks = c > max_chunks ? c : max_chunks;
+    rows += (double)n_t[t];
+  }
+  const double per_job = (double)class_pairs * (double)((p + 2) * (p + 2)) + (double)max_chunks * (double)tile_pairs * (double)class_pairs * 256.0 +
+                         (double)kMNewtonCvStateMaxBlocks + 3.0 * (double)Q + (double)kMNewtonCvRecordDoubles + (double)n_lambda * (double)Q;
+  return 8.0 * ((double)n_mix * (rows * (double)K + (double)n_sets * per_job) + (double)n * (double)(p + 1));
+}
+constexpr int64_t kMNewtonCvFoldRows[10] = {30000, 30000, 30000, 30000, 30000, 30000, 30000, 30000, 30000, 30000};
+// 50 jobs (5 mixes x 10 folds) of 30 000 rows each at K = 10 and its 18 features, 100 lambdas: about 455 MB
+static_assert(mnewton_cv_workspace_bytes(300000, 18, 10, kMNewtonCvFoldRows, 10, 5, 100) <= (double)kNewtonCvWorkspaceBytes, "the workspace bound (see above)");
+static_assert(mnewton_cv_chunks(1, 1) == 1 && mnewton_cv_chunks(335, 3) == 2 && mnewton_cv_chunks(903, 10) == 4 && mnewton_cv_chunks(100, 10) == 1 &&
+              mnewton_cv_chunks((int64_t)1 << 30, 55 * 3) == 16 && mnewton_cv_chunks((int64_t)1 << 30, 1) == 256, "the row chunks (see above)");
+static_assert(kNewtonCvMaxJobs <= kMNewtonCvMaxGridZ, "a job per workgroup of the inner solve's grid");
+
+struct MNewtonCvProblem {
+  int64_t n = 0, p = 0;
+  int K = 0;                           // classes
+  const double* x_dense = nullptr;     // column-major n x p, the rows sorted by group, in host memory
+  const double* y = nullptr;           // n: class codes 0 .. K - 1, rows sorted as x's
+  int n_sets = 0;                      // the groups; training set t is group t or everything else
+  const int64_t* start = nullptr;      // n_sets + 1: the first row of each group
+  bool train_on_rest = false;
+  bool fit_intercept = true;
+  const double* mean = nullptr;        // n_sets x p: the centres of training set t (its own column means; 0 where nothing is centred)
+  const double* scale = nullptr;       // n_sets x p: the sd the driver standardises with over the training set (1 where it does not)
+  const double* b0 = nullptr;          // n_sets x K: the null model's intercepts
+  int device = 0;
+  int n_mix = 0, n_lambda = 0;
+  const double* l2 = nullptr;          // n_mix x n_lambda: regularization_path's alpha[l]
+  const double* l1 = nullptr;          // n_mix x n_lambda: regularization_path's beta[l]
+  const uint8_t* ridge = nullptr;      // n_mix: the ridge functor (no threshold)
+  unsigned max_iter = 0;
+  double tol = 0.0;
+};
+
+struct MNewtonCvResult {               // job-major
+  std::vector<double> u;               // jobs x n_lambda x K (p + 1): as MNewtonResult::u, at the centres of the job's training set
+  std::vector<double> loss;            // jobs x n_lambda
+  std::vector<int32_t> unconverged;    // jobs x n_lambda
+  std::vector<double> passes, steps, halvings;   // jobs: state passes, outer steps and halvings over the path
+  double sweeps = 0.0;
+  int rounds = 0;                      // rounds of the lock-step loop: launches shared by all jobs
+  float moments_ms = 0.f, cd_ms = 0.f, state_ms = 0.f;   // (timed only)
+};
+
+// The lock-step loop.  The caller has checked the sizes, the feature limit, the job counts and the workspace.
+int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out);
+
 // Diagnostics (include/sgdnet_hip.h: sgdnet_mnewton_probe): one outer step through the host steps mnewton_run takes, every
 // output copied back.  pb: n, p, K, x_dense, y, centre, scale, device and n_lambda = 1; the rest is read from io.
 int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io);

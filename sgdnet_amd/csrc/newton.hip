@@ -56,6 +56,7 @@
 #include "device_math.hpp"
 #include "moments_device.hpp"
 #include "newton.hpp"
+#include "newton_cv_device.hpp"
 #include "setup_device.hpp"
 #include "wide_cd_device.hpp"
 
@@ -63,9 +64,6 @@ namespace sgdnet {
 namespace {
 
 constexpr int kStateMaxBlocks = 1024;   // workgroups of the state pass: each leaves three sums
-
-// the record of a candidate, in device memory; the host reads it after every state pass
-enum Rec { kRecLoss = 0, kRecHalfSq, kRecAbs, kRecChange, kRecSize, kRecSweeps, kRecInnerConverged, kRecNegligible, kRecLen };
 
 // a[j] = w_j / s_j (j < p), a[p] = b: the candidate as the state pass multiplies it.  Workgroup b leaves its sums of
 // the loss, v and r in partial[3 b ..].
@@ -481,34 +479,10 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
 // and the state pass make 3.8 times slower than auto.
 
 // ---- cross-validation (newton_cv_run): the kernels above with a job dimension ----
-// A job is one (mix, training set).  x and y hold the rows sorted by group, so the rows of a training set are one range
-// of rows or two: [a0, a1) and [b0, b1) (the second empty when the job trains on its own group).  Row li of the job's
-// problem, li = 0 .. n_t - 1, is row cv_row(J, li) of x; a job visits its own rows only.  Every job has its own a, v, r,
-// sums, moments, record, two iterates and slice of U; its centres and scales are its training set's; its grids (state
-// workgroups, row chunks) are those newton_run would choose for n_t rows, so its arithmetic is the same whichever other
-// jobs share the launch.  The host sends one CvCmd per job and round.
-enum CvAction { kCvIdle = 0, kCvStep, kCvHalve, kCvStart };
-
-struct CvCmd {
-  int32_t action;          // CvAction; kCvStart: publish the path's start and evaluate it
-  int32_t cur;             // which of the job's two iterates is the current one (the other holds the candidate)
-  int32_t slot;            // >= 0: the current iterate is the answer for this lambda: store it into U[slot] first
-  int32_t ridge;
-  double l2, l1;           // this lambda's penalties
-};
-
-struct CvJob {
-  int64_t a0, a1, b0, b1;  // the rows of the training set
-  int64_t n_t;
-  int64_t rows_per_chunk;  // dense x: dense_rows_per_chunk(n_t, pairs)
-  int32_t set;             // the training set: whose centres and scales
-  int32_t state_blocks, chunks, pad;
-};
-
-__device__ __forceinline__ int64_t cv_row(const CvJob& J, int64_t li) {
-  const int64_t la = J.a1 - J.a0;
-  return li < la ? J.a0 + li : J.b0 + (li - la);
-}
+// A job is one (mix, training set), its command, its rows (cv_row) and its record as newton_cv_device.hpp has them.  Every
+// job has its own a, v, r, sums, moments, record, two iterates and slice of U; its centres and scales are its training
+// set's; its grids (state workgroups, row chunks) are those newton_run would choose for n_t rows, so its arithmetic is
+// the same whichever other jobs share the launch.
 
 // newton_state_kernel for the job blockIdx.y; workgroup b of the job leaves its sums in partial[job][3 b ..]
 template <bool kSparse>
@@ -1192,21 +1166,6 @@ struct CvGeometry {
   }
 };
 
-// what the host knows of a job between two rounds: newton_run's local variables
-struct CvJobState {
-  int l = 0, cur = 0, halved = 0, action = kCvStart, slot = -1;
-  unsigned steps = 0;
-  bool negligible = false;
-  double objective = 0.0, candidate = 0.0, loss = 0.0, half_sq = 0.0, abs1 = 0.0;
-};
-
-struct CvPinned {
-  void* p = nullptr;
-  ~CvPinned() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-
 }  // namespace
 
 size_t newton_cv_workspace_bytes(int64_t n, int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix) {
@@ -1240,19 +1199,7 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
   }
   CvGeometry geo(p, sparse, n_t.data(), G, pb.n_mix);
   const int jobs = (int)geo.jobs.size();
-  for (int job = 0; job < jobs; ++job) {
-    CvJob& J = geo.jobs[(size_t)job];
-    const int t = J.set;
-    if (pb.train_on_rest) {
-      J.a0 = 0;
-      J.a1 = pb.start[t];
-      J.b0 = pb.start[t + 1];
-      J.b1 = n;
-    } else {
-      J.a0 = pb.start[t];
-      J.a1 = J.b0 = J.b1 = pb.start[t + 1];
-    }
-  }
+  for (CvJob& J : geo.jobs) cv_job_rows(J, pb.start, n, pb.train_on_rest);
   const int64_t nnz = sparse ? pb.colptr[p] : 0;
 
   SGD_HIP_TRY(hipSetDevice(pb.device));
@@ -1353,13 +1300,7 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
     bool any_step = false, any_blend = false;
     for (int job = 0; job < jobs; ++job) {
       const CvJobState& s = state[(size_t)job];
-      CvCmd& c = cmd[job];
-      c.action = s.action;
-      c.cur = s.cur;
-      c.slot = s.slot;
-      c.ridge = pb.ridge[job / G] ? 1 : 0;
-      c.l2 = c.l1 = 0.0;
-      if (s.action == kCvStep) penalties(job, s.l, &c.l2, &c.l1);
+      cv_command(cmd[job], s, pb.ridge[job / G] != 0, [&](int l, double* al, double* be) { penalties(job, l, al, be); });
       any_step |= s.action == kCvStep;
       any_blend |= s.action == kCvHalve || s.action == kCvStart;
     }
@@ -1408,67 +1349,12 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
       out->state_ms += ms;
     }
 
-    for (int job = 0; job < jobs; ++job) {
-      CvJobState& s = state[(size_t)job];
-      const int did = s.action;
-      s.slot = -1;
-      if (did == kCvIdle) continue;
-      const double* rec = rec_all + (size_t)job * kRecLen;
-      out->passes[(size_t)job] += 1.0;
-      double al, be;
-      penalties(job, s.l, &al, &be);
-      if (did == kCvStart) {           // the path's start: w = 0, b = b0
-        s.loss = rec[kRecLoss];
-        s.half_sq = rec[kRecHalfSq];
-        s.abs1 = rec[kRecAbs];
-        s.objective = s.loss + al * s.half_sq + be * s.abs1;
-        s.steps = 0;
-        s.action = kCvStep;
-        continue;
-      }
-      if (did == kCvStep) {
-        out->sweeps += rec[kRecSweeps];
-        s.negligible = rec[kRecNegligible] != 0.0;
-        s.halved = 0;
-      } else {
-        out->halvings[(size_t)job] += 1.0;
-        s.negligible = false;          // (the inner solve said so of the whole step, not of a part of it)
-      }
-      s.candidate = rec[kRecLoss] + al * rec[kRecHalfSq] + be * rec[kRecAbs];
-      // (a candidate whose objective is not a number counts as one that rose)
-      if (s.halved < kNewtonMaxHalvings && rec[kRecChange] > 0.0 &&
-          !(s.candidate <= s.objective + kNewtonObjectiveSlack * fabs(s.objective))) {
-        ++s.halved;
-        s.action = kCvHalve;
-        continue;
-      }
-      s.cur ^= 1;                      // accepted: the candidate is the iterate
-      s.objective = s.candidate;
-      s.loss = rec[kRecLoss];
-      s.half_sq = rec[kRecHalfSq];
-      s.abs1 = rec[kRecAbs];
-      ++s.steps;
-      out->steps[(size_t)job] += 1.0;
-      const double change = rec[kRecChange], size = rec[kRecSize];
-      const bool all_zero = size == 0.0 && change == 0.0;
-      const bool no_change = size != 0.0 && change / size <= pb.tol;
-      const bool converged = rec[kRecInnerConverged] != 0.0 && (all_zero || no_change || s.negligible);
-      s.action = kCvStep;
-      if (converged || s.steps >= pb.max_iter) {
-        const size_t at = (size_t)job * (size_t)L + (size_t)s.l;
-        out->loss[at] = s.loss;
-        out->unconverged[at] = converged ? 0 : 1;
-        s.slot = s.l++;
-        s.steps = 0;
-        if (s.l == L) {
-          s.action = kCvIdle;
-          --live;
-        } else {
-          penalties(job, s.l, &al, &be);
-          s.objective = s.loss + al * s.half_sq + be * s.abs1;
-        }
-      }
-    }
+    for (int job = 0; job < jobs; ++job)
+      if (cv_job_advance(state[(size_t)job], rec_all + (size_t)job * kRecLen, L, pb.max_iter, pb.tol,
+                         [&](int l, double* al, double* be) { penalties(job, l, al, be); }, out->loss.data() + (size_t)job * (size_t)L,
+                         out->unconverged.data() + (size_t)job * (size_t)L, &out->passes[(size_t)job], &out->steps[(size_t)job],
+                         &out->halvings[(size_t)job], &out->sweeps))
+        --live;
   }
   out->u.resize((size_t)jobs * (size_t)L * (size_t)P);
   SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), d_U, sizeof(double) * out->u.size(), hipMemcpyDeviceToHost, st));

@@ -26,7 +26,10 @@ round over all of them (csrc/newton.hip: newton_cv_run).
 cv_sgdnet_mcovariance() is the mgaussian CV whose fits are sgdnet_mcovariance(); its fold_fits="batched" runs all fold fits
 through cv_mcovariance_fits -> sgdnet_cv_mcovariance_*: the group moments of the K responses from one pass, every training
 set pooled from them, one workgroup per path (csrc/covariance.hip: mcovariance_cv_run).
-_cv() is the body the three CVs share; they differ in the fit they inject.
+
+cv_sgdnet_mnewton() is the multinomial CV whose fits are sgdnet_mnewton(); its fold_fits="batched" runs all fold fits through
+cv_mnewton_fits -> sgdnet_cv_mnewton_*: the multinomial Newton loops of all jobs in lock-step (csrc/mnewton.hip: mnewton_cv_run).
+_cv() is the body the four CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -35,8 +38,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_NEWTON, MODES, check, dptr
-from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_newton
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODES, check, dptr
+from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -143,15 +146,39 @@ def cv_mcovariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=
                              standardize_response=standardize_response, device=device)
 
 
+def cv_mnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                    thresh=0.001, device=0):
+    """Every fold fit of a multinomial cross-validation in multinomial Newton mode from one native call, all of them
+    advancing in lock-step.
+
+    The arguments are cv_covariance_fits's; y holds K >= 2 classes and is encoded once, over all samples, as sgdnet()
+    encodes a multinomial response (so a fold's class codes are the whole data's; a training set without a row of some
+    class is refused).  Returns a list of SgdnetFit, alpha-major: entry a * nfolds + j is sgdnet_mnewton(x[T], y[T],
+    alpha=alpha[a], lambda_=lambda_[a]) for the training set T of fold j, in the shapes sgdnet_mnewton returns (a0 (K, n_lambda)
+    with its class mean removed, beta a list of K (p, n_lambda) arrays); its diagnostics hold the job's Newton steps and
+    halvings over the path ("steps", "halvings")."""
+    y_arr = np.asarray(y)
+    if y_arr.ndim > 1 and y_arr.shape[1] > 1:
+        raise ValueError("response for multinomial regression must be one-dimensional.")
+    levels, _, codes = _levels(y_arr)
+    if levels.size == 1:
+        raise ValueError("only one class in response.")
+    return _native_fold_fits(x, np.ascontiguousarray(codes), foldid, alpha, lambda_, train_on, family="multinomial",
+                             classnames=[str(v) for v in levels], maxit=maxit, standardize=standardize, intercept=intercept,
+                             thresh=thresh, device=device, n_classes=int(levels.size))
+
+
 def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, classnames, maxit, standardize, intercept, thresh,
-                      device, standardize_response=False):
+                      device, standardize_response=False, n_classes=1):
     """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*),
-    cv_newton_fits (binomial: sgdnet_cv_newton_*) and cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*); y_enc: the
-    response as the backend takes it (mgaussian: n x K, column-major)."""
+    cv_newton_fits (binomial: sgdnet_cv_newton_*), cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*) and cv_mnewton_fits
+    (multinomial: sgdnet_cv_mnewton_*, n_classes classes); y_enc: the response as the backend takes it (mgaussian: n x K,
+    column-major)."""
     import scipy.sparse as sp
 
-    newton, multi = family == "binomial", family == "mgaussian"
-    K = y_enc.shape[1] if multi else 1
+    mnewton = family == "multinomial"
+    newton, multi = family == "binomial" or mnewton, family == "mgaussian" or mnewton     # (the Newton loop; K columns of output)
+    K = y_enc.shape[1] if family == "mgaussian" else n_classes
     if train_on not in ("fold", "rest"):
         raise ValueError("train_on must be 'fold' or 'rest'")
     if not all(isinstance(v, (bool, np.bool_)) for v in (intercept, standardize)):
@@ -184,25 +211,27 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
     ctl.standardize_response = int(bool(standardize_response))
     ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, K
-    ctl.mode, ctl.device = (MODE_NEWTON if newton else MODE_MCOVARIANCE if multi else MODES["covariance"]), int(device)
+    ctl.mode = MODE_MNEWTON if mnewton else MODE_NEWTON if newton else MODE_MCOVARIANCE if multi else MODES["covariance"]
+    ctl.device = int(device)
     jobs = A * G
     a0 = np.zeros((jobs, nl, K) if multi else (jobs, nl))
-    beta = np.zeros((jobs, nl, p, K) if multi else (jobs, nl, p))      # (mgaussian: entry (k, j) at k + j K)
+    beta = np.zeros((jobs, nl, p, K) if multi else (jobs, nl, p))      # (K columns: entry (k, j) at k + j K)
     dev_ratio = np.zeros((jobs, nl))
     rcodes = np.zeros((jobs, nl))
     nulldev = np.zeros(jobs)
     npasses = np.zeros(jobs)
     steps, halvings = np.zeros(jobs), np.zeros(jobs)
     if newton:
-        res = _lib.CvNewtonResult(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev), dptr(npasses), dptr(steps),
-                                  dptr(halvings))
+        res = (_lib.CvMNewtonResult if mnewton else _lib.CvNewtonResult)(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev),
+                                                                         dptr(npasses), dptr(steps), dptr(halvings))
     else:
         res = (_lib.CvMcovResult if multi else _lib.CvCovResult)(dptr(a0), dptr(beta), dptr(dev_ratio), dptr(rcodes), dptr(nulldev),
                                                                  dptr(npasses))
     tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
             dptr(lam), C.byref(res))
     L = _lib.load()
-    stem = "sgdnet_cv_newton" if newton else "sgdnet_cv_mcovariance" if multi else "sgdnet_cv_covariance"
+    stem = ("sgdnet_cv_mnewton" if mnewton else "sgdnet_cv_newton" if newton else "sgdnet_cv_mcovariance" if multi
+            else "sgdnet_cv_covariance")
     if sp.issparse(x):
         xs = sp.csc_matrix(x, dtype=np.float64)
         xs.sort_indices()
@@ -225,8 +254,10 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
         for j in range(G):
             job = a * G + j
             dfmat = None
-            if multi:                                             # the shapes _fit() returns for mgaussian
+            if multi:                                             # the shapes _fit() returns for mgaussian and multinomial
                 a0_job = a0[job].T.copy()                         # (K, n_lambda)
+                if mnewton:                                       # (as _fit() does: R/sgdnet.R:409-410)
+                    a0_job = a0_job - a0_job.mean(axis=0, keepdims=True)
                 b = [beta[job, :, :, k].T.copy() for k in range(K)]
                 df = (sum(b) != 0).sum(axis=0)
                 dfmat = np.vstack([(np.abs(bk) > 0).sum(axis=0) for bk in b])
@@ -236,7 +267,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
                 df = (b != 0).sum(axis=0)
             fits.append(SgdnetFit(a0=a0_job, beta=b, lambda_=lam[a].copy(), dev_ratio=dev_ratio[job].copy(),
                                   df=df, nulldev=float(nulldev[job]), npasses=float(npasses[job]),
-                                  alpha=float(alphas[a]), offset=False, classnames=classnames, grouped=multi,
+                                  alpha=float(alphas[a]), offset=False, classnames=classnames, grouped=family == "mgaussian",
                                   nobs=int(n - counts[j] if train_on == "rest" else counts[j]), family=family,
                                   dfmat=dfmat, return_codes=rcodes[job].copy(), draws_used=0,
                                   diagnostics=dict(steps=float(steps[job]), halvings=float(halvings[job])) if newton else {}))
@@ -327,8 +358,31 @@ def cv_sgdnet_mcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, t
                train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
 
 
+def cv_sgdnet_mnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                      train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                      standardize=True, intercept=True, thresh=0.001):
+    """cv_sgdnet(family="multinomial") with every fit a sgdnet_mnewton(): the fold ids, the scoring, the generator and the
+    returned CvSgdnet are cv_sgdnet's.  fold_fits="separate" (the default) runs one sgdnet_mnewton per fold;
+    "batched" runs all fold fits of all alphas through ONE native call (cv_mnewton_fits) with the full fits' lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_mnewton(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio, device=dev,
+                              **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_mnewton_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="multinomial", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
 def _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, *, family, devices, rng, seed, train_on, densify, fit_one, batched_fits):
-    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton() and cv_sgdnet_mcovariance(): the full fits, the fold ids, the fold fits, the scores
+    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance() and cv_sgdnet_mnewton(): the full fits, the fold ids, the fold fits, the scores
     and the summary.  fit_one(x, y, lambda, alpha, device, seed, rng, sequential) is a fit; batched_fits(x, y, foldid, alpha,
     lambdas, device), where given, returns every fold fit from one call (alpha-major), else the folds are fitted one by one."""
     import scipy.sparse as sp
