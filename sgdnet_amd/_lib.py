@@ -41,6 +41,7 @@ EXPORTS = [
     "sgdnet_mnewton_max_features", "sgdnet_mnewton_probe", "sgdnet_wcovariance_max_features",
     "sgdnet_wnewton_max_features", "sgdnet_wmcovariance_max_features", "sgdnet_wmnewton_max_features",
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
+    "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -142,7 +143,7 @@ class MNewtonProbe(C.Structure):
 
 
 class CvCovResult(C.Structure):
-    """sgdnet_cv_cov_result: caller-allocated outputs of sgdnet_cv_covariance_*, job-major (job = alpha * n_groups + group)."""
+    """sgdnet_cv_cov_result: caller-allocated outputs of sgdnet_cv_covariance_* and sgdnet_cv_wcovariance_*, job-major (job = alpha * n_groups + group)."""
     _fields_ = [("a0", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)), ("dev_ratio", C.POINTER(C.c_double)),
                 ("return_codes", C.POINTER(C.c_double)), ("nulldev", C.POINTER(C.c_double)), ("npasses", C.POINTER(C.c_double))]
 
@@ -282,6 +283,8 @@ def load():
                 C.POINTER(C.c_double), C.POINTER(CvCovResult)]
     L.sgdnet_cv_covariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_covariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
+    L.sgdnet_cv_wcovariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
+    L.sgdnet_cv_wcovariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvNewtonResult)]
     L.sgdnet_cv_newton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_newton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail

@@ -52,6 +52,11 @@
 //              and the scale kernel are wide_cd_device.hpp's, shared with newton.hip; the geometry is wide_layout.hpp's.
 //              wmcovariance_run (SGDNET_MODE_WMCOVARIANCE) is the same step for the K responses: cov_wide_group_path_kernel
 //              runs cov_group_path_kernel's block descent over the list, one 16-byte read of a column serving all K.
+//              wcovariance_cv_run: the folds of the wide mode.  The group moments pass above (p + 2 columns, the wide row
+//              chunks cut at the groups' ends); wcov_cv_stats_kernel (per T: s, d, scales, means, penalties) and
+//              wcov_cv_assemble_kernel (per column and T) do cov_assemble_kernel's pooling and re-centring straight into
+//              every training set's S_T, diag S_T and c~_T in global memory; cov_wide_cv_path_kernel, a second entry around
+//              cov_wide_path_kernel's body, takes its job (mix, T) from blockIdx.x: one workgroup, one CU, per job.
 //
 // No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
@@ -677,13 +682,14 @@ __device__ __forceinline__ double cov_coord_new_w(double sjj, double wj, double 
 //            again, and the lambda is done when it adds nothing.
 // max_iter bounds the list sweeps of one lambda.  g[k] is updated by one lane from the same words in the same order
 // whatever kWidth is: both widths give the same bits.
+// The body of two entries, below: cov_wide_path_kernel (one fit) and cov_wide_cv_path_kernel (a job of a cross-validation).
 template <int kWidth, bool kPrefetch>
-__global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
-                                                                const double* __restrict__ ct, int p, int ld,
-                                                                const double* __restrict__ alpha, const double* __restrict__ beta,
-                                                                int n_lambda, int ridge, unsigned max_iter, double tol,
-                                                                double* __restrict__ W, double* __restrict__ G,
-                                                                int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+__device__ __forceinline__ void cov_wide_path_body(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                   const double* __restrict__ ct, int p, int ld,
+                                                   const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                   int n_lambda, int ridge, unsigned max_iter, double tol,
+                                                   double* __restrict__ W, double* __restrict__ G,
+                                                   int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kCovLdsBytes];
   const int lane = threadIdx.x;
   double* g = reinterpret_cast<double*>(lds);
@@ -843,6 +849,37 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
   }
 }
 
+// One fit: a grid of 1.  The entry the single fit has always had, around the shared body.
+template <int kWidth, bool kPrefetch>
+__global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                                const double* __restrict__ ct, int p, int ld,
+                                                                const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                int n_lambda, int ridge, unsigned max_iter, double tol,
+                                                                double* __restrict__ W, double* __restrict__ G,
+                                                                int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+  cov_wide_path_body<kWidth, kPrefetch>(S, Sd, ct, p, ld, alpha, beta, n_lambda, ridge, max_iter, tol, W, G, sweeps_out, unconverged);
+}
+
+// The same path over jobs (wcovariance_cv_run).  blockIdx.x = job, as in cov_path_kernel: its training set is job % n_sets
+// (S, diag S and c~ per set: strides ld p, p and p; a set's S is read-only and shared by its mixes), its penalties, functor
+// and outputs are the job's own.  The pointers are offset once, here at the entry, and the body is the single fit's: a
+// second entry rather than more arguments to the first, because with the job's arguments the single fit's <1024, ahead>
+// instance took one more VGPR (profiles/cv_wcovariance.txt has the registers of all eight).  The kernel declares the
+// CU's whole LDS: one job runs per CU, the others queue.
+template <int kWidth, bool kPrefetch>
+__global__ __launch_bounds__(kWidth) void cov_wide_cv_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                                   const double* __restrict__ ct, int p, int ld, int n_sets,
+                                                                   const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                   int n_lambda, const int32_t* __restrict__ ridge_jobs,
+                                                                   unsigned max_iter, double tol, double* __restrict__ W,
+                                                                   double* __restrict__ G, int32_t* __restrict__ sweeps_out,
+                                                                   int32_t* __restrict__ unconverged) {
+  const size_t job = blockIdx.x, set = job % (size_t)n_sets, at = job * (size_t)n_lambda;
+  cov_wide_path_body<kWidth, kPrefetch>(S + set * (size_t)ld * (size_t)p, Sd + set * (size_t)p, ct + set * (size_t)p, p, ld, alpha + at,
+                                        beta + at, n_lambda, ridge_jobs[job], max_iter, tol, W + at * (size_t)p, G + at * (size_t)p,
+                                        sweeps_out + at, unconverged + at);
+}
+
 // The wide path kernel's workgroup and whether it requests the next column ahead: all four instances give the same bits;
 // profiles/wcovariance_path.txt has the path kernel's time for each at p = 198, 1000, 2000 and 4000 (100 lambdas):
 //   lanes, ahead      p = 198     1000     2000     4000
@@ -856,6 +893,107 @@ __global__ __launch_bounds__(kWidth) void cov_wide_path_kernel(const double* __r
 // its column.  So: 256 lanes up to 512 features, 1024 beyond (wide_layout.hpp: wide_cd_width); ahead beyond 1536 (between
 // the two measurements).
 constexpr bool wcov_path_ahead(int p) { return p > 1536; }
+
+// ---- the folds of wide covariance mode (wcovariance_cv_run): cov_assemble_kernel's work, written in the wide layout ----
+// cov_assemble_kernel is one workgroup per training set with the sums s and the shifts d in static LDS sized for 198
+// features; at 4531 features a set's matrix is 20 M entries and the two vectors 72.5 KB.  So the work is cut in two, and s
+// and d live in GLOBAL memory (2 G (p + 1) doubles, read through L2 by the second kernel; no dynamic LDS, no attribute):
+//   wcov_cv_stats_kernel     blockIdx.x = training set T: everything of size p or smaller
+//   wcov_cv_assemble_kernel  blockIdx.x = column j, blockIdx.y = T: column j of S_T, diag S_T and c~_T
+// No G x (p + 1)^2 re-centred matrix is written in between: a column of S_T comes straight from row j of the group moments.
+
+// The (p + 2) x (p + 2) moments of training set T about the common centre: group T alone, or (rest) the total less group T.
+struct WcovSet {
+  const double* Ct;
+  const double* total;
+  int Pa, rest;
+  __device__ __forceinline__ double operator()(int j, int k) const {
+    const double v = Ct[(size_t)j * Pa + k];
+    return rest ? total[(size_t)j * Pa + k] - v : v;
+  }
+};
+
+// cov_assemble_kernel's re-centring of entry (j, k), j <= k, from the entry c about the common centre, T's sums of deviations
+// s and its shifts d: the operands come in the order of the smaller index first, so that (j, k) and (k, j) give the same bits
+// (the moments are symmetric bit for bit: cov_reduce_kernel and cov_sparse_pair_kernel store every entry twice)
+__device__ __forceinline__ double wcov_recentred(double c, double sj, double dj, double sk, double dk, double nT) {
+  return c - dj * sk - dk * sj + nT * dj * dk;
+}
+
+// blockIdx.x = training set T.  From the group moments to what is per T or per job and of size p or smaller, as
+// cov_assemble_kernel leaves it (the same expressions):
+//   s, d   G x (p + 1): T's sums of deviations about the common centre and its shifts d = t - a (0 where not centred)
+//   scale  G x p      mean  G x (p + 1): t (0 where the features are not centred), mean_T(y)
+//   tstat  3 x G: n_T | sd_T(y) (0 -> 1) | y~'y~         alpha, beta  jobs x n_lambda, job = mix * G + T      ridge  jobs
+// Every lane computes sd_T(y) itself from the same four words: nothing is staged and no barrier is needed.
+__global__ __launch_bounds__(kBlock) void wcov_cv_stats_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
+                                                                const double* __restrict__ mu, int n_groups, int p, int rest, int centre,
+                                                                int standardize, const double* __restrict__ mix,
+                                                                const double* __restrict__ lambda, int n_mix, int n_lambda,
+                                                                double* __restrict__ s, double* __restrict__ d, double* __restrict__ scale,
+                                                                double* __restrict__ mean, double* __restrict__ tstat,
+                                                                double* __restrict__ alpha, double* __restrict__ beta,
+                                                                int32_t* __restrict__ ridge) {
+  const int t = blockIdx.x, tid = threadIdx.x, P1 = p + 1, Pa = p + 2;
+  const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
+  const double nT = C(p + 1, p + 1);
+  const double sy = C(p, p + 1), dy = sy / nT;
+  const double qy = wcov_recentred(C(p, p), sy, dy, sy, dy, nT);
+  const double var_y = qy / nT;
+  const double sd_y = var_y > 0.0 ? sqrt(var_y) : 1.0;
+  for (int j = tid; j < P1; j += kBlock) {
+    const double sj = C(j, p + 1), dj = (j == p || centre) ? sj / nT : 0.0;
+    s[(size_t)t * P1 + j] = sj;
+    d[(size_t)t * P1 + j] = dj;
+    if (j < p) {
+      const double v = wcov_recentred(C(j, j), sj, dj, sj, dj, nT) / nT;
+      scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+      mean[(size_t)t * P1 + j] = centre ? mu[j] + dj : 0.0;
+    }
+  }
+  if (tid == 0) {
+    mean[(size_t)t * P1 + p] = mu[p + 1] + dy;
+    tstat[t] = nT;
+    tstat[n_groups + t] = sd_y;
+    tstat[2 * n_groups + t] = qy / sd_y / sd_y;
+  }
+  for (int e = tid; e < n_mix * n_lambda; e += kBlock) {
+    const int a = e / n_lambda, l = e - a * n_lambda;
+    const size_t at = ((size_t)a * n_groups + t) * n_lambda + l;
+    alpha[at] = (1.0 - mix[a]) * lambda[e] / sd_y;
+    beta[at] = mix[a] * lambda[e] / sd_y;
+    if (l == 0) ridge[(size_t)a * n_groups + t] = mix[a] == 0.0 ? 1 : 0;
+  }
+}
+
+// blockIdx.x = column j < p, blockIdx.y = training set T.  Column j of S_T = M^T / n_T / (sd sd') in the layout
+// cov_wide_path_kernel reads (leading dimension ld, rows p .. ld - 1 the zero pad; set stride ld p), diag S_T and
+// c~_T,j = M^T[j, y] / sd_T(y) / n_T / sd_j: the arithmetic of cov_assemble_kernel followed by wide_scale_kernel's.  The
+// moments are read along row j (coalesced; row j is column j bit for bit); s, d and scale come from wcov_cv_stats_kernel.
+__global__ __launch_bounds__(kBlock) void wcov_cv_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
+                                                                   const double* __restrict__ s, const double* __restrict__ d,
+                                                                   const double* __restrict__ scale, const double* __restrict__ tstat,
+                                                                   int n_groups, int p, int ld, int rest, double* __restrict__ S,
+                                                                   double* __restrict__ Sd, double* __restrict__ ct) {
+  const int j = blockIdx.x, t = blockIdx.y, P1 = p + 1, Pa = p + 2;
+  const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
+  s += (size_t)t * P1;
+  d += (size_t)t * P1;
+  scale += (size_t)t * p;
+  const double nT = tstat[t], sd_y = tstat[n_groups + t];
+  const double sj = s[j], dj = d[j], fj = scale[j];
+  double* col = S + ((size_t)t * p + j) * (size_t)ld;
+  for (int k = threadIdx.x; k < ld; k += kBlock) {
+    double v = 0.0;
+    if (k < p) {
+      const double c = C(j, k), sk = s[k], dk = d[k], fk = scale[k];
+      v = k >= j ? wcov_recentred(c, sj, dj, sk, dk, nT) / nT / (fj * fk) : wcov_recentred(c, sk, dk, sj, dj, nT) / nT / (fk * fj);
+    }
+    col[k] = v;
+    if (k == j) Sd[(size_t)t * p + j] = v;
+  }
+  if (threadIdx.x == 0) ct[(size_t)t * p + j] = wcov_recentred(C(j, p), sj, dj, s[p], d[p], nT) / sd_y / nT / fj;
+}
 
 // ---- wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): cov_group_path_kernel's problem, S in global memory ----
 
@@ -1521,6 +1659,201 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
   SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
   SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
   SGD_HIP_TRY(hipStreamSynchronize(st));
+  out->n_train.assign(tstat.begin(), tstat.begin() + G);
+  out->y_scale.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
+  out->yy.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
+  return SGDNET_OK;
+}
+
+int64_t wcov_cv_row_chunks(int64_t n, int64_t p, const int64_t* count, int n_groups) {
+  const int64_t rows_per_chunk = wide_rows_per_chunk(n, p + 2, kTileRows);
+  int64_t chunks = 0;
+  for (int g = 0; g < n_groups; ++g) chunks += (count[g] + rows_per_chunk - 1) / rows_per_chunk;
+  return chunks;
+}
+
+// covariance_cv_run beyond kCovMaxFeatures features: the same group moments pass (the wide mode's row chunks),
+// wcov_cv_stats_kernel and wcov_cv_assemble_kernel instead of cov_assemble_kernel, cov_wide_cv_path_kernel over the jobs.
+int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, int width) {
+  const int64_t n = pb.n;
+  const int p = (int)pb.p, P1 = p + 1, Pa = p + 2, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
+  const bool sparse = pb.x_dense == nullptr;
+  if (n <= 0 || p <= 0 || pb.p > kWcovMaxFeatures || L <= 0 || G <= 0 || A_mix <= 0 || !pb.fold || !pb.y || !pb.mix || !pb.lambda ||
+      (pb.train_on_rest && G < 2) || (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("wcovariance_cv_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  if (width == 0) width = wide_cd_width(p);
+  if (width != kWideNarrow && width != kWideFull) {
+    set_error("wcovariance_cv_run: the path kernel's workgroup is %d or %d lanes, not %d", kWideNarrow, kWideFull, width);
+    return SGDNET_EINVAL;
+  }
+  const size_t jobs = (size_t)A_mix * (size_t)G;
+
+  // dense x: the rows sorted by group (stable) and cut into chunks of the size one wide fit of n rows over p + 2 columns
+  // would use, none across a group's end: the summation order is a function of (n, p, fold) alone
+  const int64_t pairs = wide_tile_pairs(Pa);
+  std::vector<int64_t> perm, chunk_begin;
+  std::vector<int32_t> group_chunk;
+  if (!sparse) {
+    std::vector<int64_t> start((size_t)G + 1, 0);
+    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
+    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
+    perm.resize((size_t)n);
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
+    const int64_t rows_per_chunk = wide_rows_per_chunk(n, Pa, kTileRows);
+    group_chunk.assign((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
+      if (chunk_begin.size() > (size_t)kCovMaxRowChunks) {
+        set_error("mode = wcovariance needs the rows of the groups in at most %d chunks: %d groups of %lld rows", kCovMaxRowChunks, G,
+                  (long long)n);
+        return SGDNET_EUNSUPPORTED;
+      }
+      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
+    }
+    chunk_begin.push_back(n);
+  }
+  if (sparse && G > kCovMaxRowChunks) {       // (the pair kernel's gridDim.z, the assembly's gridDim.y)
+    set_error("mode = wcovariance needs at most %d groups of sparse rows: %d groups", kCovMaxRowChunks, G);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
+  if (wcov_cv_bytes(G, p, (int64_t)chunks) > kWcovCvBytes) {
+    set_error("mode = wcovariance needs the moments and the scaled matrices of the groups within %zu bytes: %d groups of %d features are %zu bytes",
+              kWcovCvBytes, G, p, wcov_cv_bytes(G, p, (int64_t)chunks));
+    return SGDNET_EUNSUPPORTED;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+  const size_t Melems = (size_t)Pa * (size_t)Pa;      // (at most 4533^2 = 20 548 089: cov_total_kernel's int)
+  const int ld = (int)wide_leading_dim(p);
+
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P1 : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
+  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
+  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
+  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)Pa);
+  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
+  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
+  const size_t o_total = A.reserve(sizeof(double) * Melems);
+  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
+  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  const size_t o_s = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
+  const size_t o_d = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
+  const size_t o_S = A.reserve(sizeof(double) * (size_t)G * (size_t)ld * (size_t)p);
+  const size_t o_Sd = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_ct = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
+  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
+  const size_t o_alpha = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_beta = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
+  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
+  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
+  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Events ev;
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
+  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  hipStream_t st = ev.st;
+  double* d_x = A.at<double>(o_x);
+  double* d_y = A.at<double>(o_y);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_Mg = A.at<double>(o_Mg);
+  double* d_tstat = A.at<double>(o_tstat);
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)P1, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
+
+  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
+  if (sparse) {
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, 1,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_group_response_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_y, A.at<int32_t>(o_fold), d_mu, n, p, d_Mg);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
+                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, 1, A.at<int32_t>(o_fold), d_Mg);
+  } else {
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, 1, Pa,
+                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
+  }
+  if (pb.train_on_rest)
+    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
+                       A.at<double>(o_total));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  const int rest = pb.train_on_rest ? 1 : 0;
+  hipLaunchKernelGGL(wcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p, rest,
+                     pb.centre ? 1 : 0, pb.standardize ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_s),
+                     A.at<double>(o_d), A.at<double>(o_scale), A.at<double>(o_mean), d_tstat, A.at<double>(o_alpha), A.at<double>(o_beta),
+                     A.at<int32_t>(o_ridge));
+  hipLaunchKernelGGL(wcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total),
+                     A.at<double>(o_s), A.at<double>(o_d), A.at<double>(o_scale), d_tstat, G, p, ld, rest, A.at<double>(o_S),
+                     A.at<double>(o_Sd), A.at<double>(o_ct));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  static const int ahead = exp_env_int("SGDNET_WCOV_PREFETCH", -1);     // (0 / 1, as in wcovariance_run)
+  const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
+  const auto kernel = width == kWideNarrow ? (prefetch ? cov_wide_cv_path_kernel<kWideNarrow, true> : cov_wide_cv_path_kernel<kWideNarrow, false>)
+                                           : (prefetch ? cov_wide_cv_path_kernel<kWideFull, true> : cov_wide_cv_path_kernel<kWideFull, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
+                     ld, G, A.at<double>(o_alpha), A.at<double>(o_beta), L, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol, A.at<double>(o_W),
+                     A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+
+  std::vector<double> tstat(3 * (size_t)G), ct((size_t)G * (size_t)p);
+  out->mean.resize((size_t)G * (size_t)P1);
+  out->scale.resize((size_t)G * (size_t)p);
+  out->c.resize(jobs * (size_t)p);
+  out->w.resize(jobs * (size_t)L * (size_t)p);
+  out->g.resize(jobs * (size_t)L * (size_t)p);
+  out->sweeps.resize(jobs * (size_t)L);
+  out->unconverged.resize(jobs * (size_t)L);
+  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
+  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
+  SGD_HIP_TRY(fetch(ct.data(), o_ct, sizeof(double) * ct.size()));
+  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
+  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
+  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
+  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
+  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
+  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  for (size_t job = 0; job < jobs; ++job)      // c~ is the training set's: every mix of a set gets its copy
+    std::copy(ct.begin() + (job % (size_t)G) * (size_t)p, ct.begin() + (job % (size_t)G + 1) * (size_t)p, out->c.begin() + job * (size_t)p);
   out->n_train.assign(tstat.begin(), tstat.begin() + G);
   out->y_scale.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
   out->yy.assign(tstat.begin() + 2 * (size_t)G, tstat.end());

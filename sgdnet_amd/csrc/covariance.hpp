@@ -205,6 +205,33 @@ struct CovarianceCvResult {
 // the caller's business (driver_direct.cpp: fit_cv_covariance).
 int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out);
 
+// ---- the same in wide covariance mode (SGDNET_MODE_WCOVARIANCE): beyond kCovMaxFeatures features ----
+// The same group moments (over p + 2 columns; dense x: row chunks by wide_rows_per_chunk, cut at the groups' ends), pooled
+// and re-centred per training set straight into the scaled Gram matrices S_T in global memory (leading dimension
+// wide_leading_dim(p), set stride ld p), and cov_wide_path_kernel's path over the jobs: one workgroup, one CU, per job.
+//
+// The budget, in doubles: the group moments G (p + 2)^2, their total (p + 2)^2, the dense partial tiles chunks x
+// wide_tile_pairs(p + 2) x 256 (none for sparse x) and the scaled matrices G ld p -- x and the per-job outputs are not
+// counted.  At the feature limit a group is 164.4 + 82.9 + 164.7 MB (one chunk per group from 1024 tile pairs on):
+// a 10-fold CV takes 4.28 GB and a 20-fold 8.40 GB of the 16 GiB; at p = 1000 a group is 20.2 MB and 849 groups fit.
+constexpr size_t kWcovCvBytes = (size_t)16 << 30;
+constexpr size_t wcov_cv_bytes(int64_t G, int64_t p, int64_t chunks) {
+  return sizeof(double) * ((size_t)(G + 1) * (size_t)(p + 2) * (size_t)(p + 2) + (size_t)chunks * (size_t)wide_tile_pairs(p + 2) * 256 +
+                           (size_t)G * (size_t)wide_leading_dim(p) * (size_t)p);
+}
+static_assert(wcov_cv_bytes(10, kWcovMaxFeatures, 10) <= kWcovCvBytes, "a 10-fold CV at the feature limit fits");
+static_assert(wcov_cv_bytes(10, kWcovMaxFeatures, 10) / 10000000 == 428 && wcov_cv_bytes(20, kWcovMaxFeatures, 20) / 10000000 == 840,
+              "the examples above");
+static_assert(wcov_cv_bytes(849, 1000, 849) <= kWcovCvBytes && wcov_cv_bytes(850, 1000, 850) > kWcovCvBytes, "the examples above");
+
+// The row chunks of the dense group moments pass (gridDim.y): count[g] rows in group g, none across a group's end.
+int64_t wcov_cv_row_chunks(int64_t n, int64_t p, const int64_t* count, int n_groups);
+
+// Group moments + stats and assembly + wide path kernel over the jobs.  p <= kWcovMaxFeatures, the budget above, at most
+// kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business (driver_direct.cpp:
+// fit_cv_wcovariance).  width as in wcovariance_run.
+int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, int width = 0);
+
 // ---- the same for K responses (SGDNET_MODE_MCOVARIANCE) ----
 // The augmented rows are [x - a | y_1 - a_y1 .. y_K - a_yK | 1]: per group a (p + K + 1) x (p + K + 1) moment matrix, the
 // response-by-response block included (a training set's y~'y~ and null deviance come from its diagonal).

@@ -4,7 +4,7 @@
 //   fit_direct          the stage behind the plan (driver.cpp: fit_common calls it once plan_fit accepted the fit): the
 //                       problem every mode fills the same way, the kernels' run, and per lambda the deviance and the way
 //                       back to the scale of the data
-//   fit_cv_covariance   every fold fit of a cross-validation in one launch       (sgdnet_cv_covariance_*)
+//   fit_cv_covariance   every fold fit of a cross-validation in one launch       (sgdnet_cv_covariance_*, sgdnet_cv_wcovariance_*)
 //   fit_cv_mcovariance  the same for the K responses of an mgaussian fit         (sgdnet_cv_mcovariance_*)
 //   fit_cv_newton       every fold fit through the Newton loop in lock-step      (sgdnet_cv_newton_*)
 //   fit_cv_mnewton      the same through the multinomial Newton loop             (sgdnet_cv_mnewton_*)
@@ -301,32 +301,37 @@ int validate_mixes(int n_alpha, const double* alphas, int L, const double* lambd
 // moments over T (prepare_response), the features centred (and scaled) by theirs, the penalties of regularization_path
 // in the units of that response.  The device assembles all of it from the group moments; what is left for the host is
 // the way back to the scale of the data (rescale_values) and the deviance from the quadratic form, per job.
+// wide: SGDNET_MODE_WCOVARIANCE, the same stage around wcovariance_cv_run (the stage behind sgdnet_cv_wcovariance_*): its own
+// feature limit and byte budget, and no way from one to the other -- each refuses by its own name.
 int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                      int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_cov_result* out) {
+                      int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_cov_result* out, bool wide = false) {
   const int64_t n = pb.n, p = pb.p;
+  const char* entry = wide ? "sgdnet_cv_wcovariance" : "sgdnet_cv_covariance";
+  const char* mode = wide ? "wcovariance" : "covariance";
   if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !pb.y ||
       !fold || !alphas || !lambdas) {
-    set_error("sgdnet_cv_covariance: null pointer");
+    set_error("%s: null pointer", entry);
     return SGDNET_EINVAL;
   }
   if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
       (train_on_rest && n_groups < 2)) {
-    set_error("sgdnet_cv_covariance: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    set_error("%s: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)", entry);
     return SGDNET_EINVAL;
   }
   const int L = ctl->n_lambda;
+  const int limit = wide ? kWcovMaxFeatures : kCovMaxFeatures;
   const char* what = nullptr;
   if (ctl->family != SGDNET_GAUSSIAN) what = "family = gaussian";
-  else if (p > kCovMaxFeatures) what = "no more features than sgdnet_covariance_max_features()";
+  else if (p > limit) what = wide ? "no more features than sgdnet_wcovariance_max_features()" : "no more features than sgdnet_covariance_max_features()";
   else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
   else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
   if (what) {
-    set_error("mode = covariance needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)p,
-              kCovMaxFeatures, ctl->n_gpus, ctl->debug);
+    set_error("mode = %s needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", mode, what, ctl->family, (long long)p, limit,
+              ctl->n_gpus, ctl->debug);
     return SGDNET_EUNSUPPORTED;
   }
   const size_t moment_bytes = (size_t)n_groups * (size_t)(p + 2) * (size_t)(p + 2) * sizeof(double);
-  if (moment_bytes > kCovGroupMomentBytes) {
+  if (!wide && moment_bytes > kCovGroupMomentBytes) {
     set_error("mode = covariance needs the group moments within %zu bytes: %d groups x (%lld + 2)^2 doubles are %zu bytes",
               kCovGroupMomentBytes, n_groups, (long long)p, moment_bytes);
     return SGDNET_EUNSUPPORTED;
@@ -334,7 +339,24 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
   std::vector<int64_t> count;
   int rc = count_groups(fold, n, n_groups, count);
   if (!rc) rc = validate_mixes(n_alpha, alphas, L, lambdas);
-  if (!rc) rc = check_device(ctl->device);
+  if (rc) return rc;
+  if (wide) {
+    // the limits of wcovariance_cv_run that need no device: its grid dimensions and its byte budget
+    const bool sparse = pb.x_dense == nullptr;
+    const int64_t chunks = sparse ? 0 : wcov_cv_row_chunks(n, p, count.data(), n_groups);
+    if (chunks > kCovMaxRowChunks || n_groups > kCovMaxRowChunks) {
+      set_error("mode = wcovariance needs at most %d groups and (dense x) row chunks: %d groups, %lld chunks of %lld rows", kCovMaxRowChunks,
+                n_groups, (long long)chunks, (long long)n);
+      return SGDNET_EUNSUPPORTED;
+    }
+    const size_t bytes = wcov_cv_bytes(n_groups, p, chunks);
+    if (bytes > kWcovCvBytes) {
+      set_error("mode = wcovariance needs the moments and the scaled matrices of the groups within %zu bytes: %d groups of %lld features are %zu bytes",
+                kWcovCvBytes, n_groups, (long long)p, bytes);
+      return SGDNET_EUNSUPPORTED;
+    }
+  }
+  rc = check_device(ctl->device);
   if (rc) return rc;
   PhaseTimer pt;
   const bool intercept = ctl->intercept != 0;
@@ -351,12 +373,13 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   CovarianceCvResult cr;
-  rc = covariance_cv_run(pb, &cr);
+  rc = wide ? wcovariance_cv_run(pb, &cr, option(kOptWcovarianceWidth)) : covariance_cv_run(pb, &cr);
   if (rc) return rc;
   if (pt.on)
-    fprintf(stderr, "[sgdnet]   cv covariance: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", cr.moments_ms,
+    fprintf(stderr, "[sgdnet]   cv %s: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", mode, cr.moments_ms,
             cr.assemble_ms, n_alpha * n_groups, cr.path_ms);
 
+  // per job, both modes alike: the way back to the scale of the data and the deviance from the quadratic form
   const size_t P = (size_t)p, P1 = P + 1;
   for (int a = 0; a < n_alpha; ++a)
     for (int t = 0; t < n_groups; ++t) {
@@ -388,7 +411,7 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
       out->nulldev[job] = yy * ys * ys;
       out->npasses[job] = n_sweeps;
     }
-  pt.mark("cv covariance (all folds)");
+  pt.mark(wide ? "cv wcovariance (all folds)" : "cv covariance (all folds)");
   return SGDNET_OK;
 }
 
@@ -1055,6 +1078,40 @@ int sgdnet_cv_covariance_sparse(const sgdnet_csc* x, const double* y, const int3
   pb.values = x->values;
   pb.y = y;
   return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_wcovariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                                int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                sgdnet_cv_cov_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_wcovariance_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  CovarianceCvProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  pb.y = y;
+  return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
+}
+
+int sgdnet_cv_wcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                 const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                 sgdnet_cv_cov_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_wcovariance_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  CovarianceCvProblem pb;
+  pb.n = x->n_rows;
+  pb.p = x->n_cols;
+  pb.colptr = x->colptr;
+  pb.rowidx = x->rowidx;
+  pb.values = x->values;
+  pb.y = y;
+  return fit_cv_covariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
 }
 
 int sgdnet_cv_mcovariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,

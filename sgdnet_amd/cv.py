@@ -29,7 +29,12 @@ set pooled from them, one workgroup per path (csrc/covariance.hip: mcovariance_c
 
 cv_sgdnet_mnewton() is the multinomial CV whose fits are sgdnet_mnewton(); its fold_fits="batched" runs all fold fits through
 cv_mnewton_fits -> sgdnet_cv_mnewton_*: the multinomial Newton loops of all jobs in lock-step (csrc/mnewton.hip: mnewton_cv_run).
-_cv() is the body the four CVs share; they differ in the fit they inject.
+
+cv_sgdnet_wcovariance() is the gaussian CV whose fits are sgdnet_wcovariance() (beyond covariance mode's 198 features); its
+fold_fits="batched" runs all fold fits through cv_wcovariance_fits -> sgdnet_cv_wcovariance_*: the group moments from one pass,
+every training set's scaled Gram matrix pooled from them into device memory, one workgroup -- one compute unit -- per path
+(csrc/covariance.hip: wcovariance_cv_run).
+_cv() is the body the five CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -38,8 +43,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODES, check, dptr
-from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODES, check, dptr
+from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -108,6 +113,18 @@ def cv_covariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1
                              standardize=standardize, intercept=intercept, thresh=thresh, device=device)
 
 
+def cv_wcovariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                        thresh=0.001, device=0):
+    """Every fold fit of a gaussian cross-validation in wide covariance mode from one native call.
+
+    The arguments are cv_covariance_fits's, for up to wcovariance_max_features() features.  Returns a list of SgdnetFit,
+    alpha-major: entry a * nfolds + j is sgdnet_wcovariance(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a]) for the
+    training set T of fold j (the same optimum, return codes and npasses; not the same bits)."""
+    y_enc = np.ascontiguousarray(np.asarray(y), dtype=np.float64).reshape(-1)
+    return _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, family="gaussian", classnames=None, maxit=maxit,
+                             standardize=standardize, intercept=intercept, thresh=thresh, device=device, wide=True)
+
+
 def cv_newton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
                    thresh=0.001, device=0):
     """Every fold fit of a binomial cross-validation in Newton mode from one native call, all of them advancing in lock-step.
@@ -169,8 +186,9 @@ def cv_mnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000
 
 
 def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, classnames, maxit, standardize, intercept, thresh,
-                      device, standardize_response=False, n_classes=1):
+                      device, standardize_response=False, n_classes=1, wide=False):
     """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*),
+    cv_wcovariance_fits (gaussian, wide: sgdnet_cv_wcovariance_*),
     cv_newton_fits (binomial: sgdnet_cv_newton_*), cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*) and cv_mnewton_fits
     (multinomial: sgdnet_cv_mnewton_*, n_classes classes); y_enc: the response as the backend takes it (mgaussian: n x K,
     column-major)."""
@@ -211,7 +229,8 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
     ctl.standardize_response = int(bool(standardize_response))
     ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, K
-    ctl.mode = MODE_MNEWTON if mnewton else MODE_NEWTON if newton else MODE_MCOVARIANCE if multi else MODES["covariance"]
+    ctl.mode = (MODE_MNEWTON if mnewton else MODE_NEWTON if newton else MODE_MCOVARIANCE if multi else MODE_WCOVARIANCE if wide
+                else MODES["covariance"])
     ctl.device = int(device)
     jobs = A * G
     a0 = np.zeros((jobs, nl, K) if multi else (jobs, nl))
@@ -231,7 +250,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
             dptr(lam), C.byref(res))
     L = _lib.load()
     stem = ("sgdnet_cv_mnewton" if mnewton else "sgdnet_cv_newton" if newton else "sgdnet_cv_mcovariance" if multi
-            else "sgdnet_cv_covariance")
+            else "sgdnet_cv_wcovariance" if wide else "sgdnet_cv_covariance")
     if sp.issparse(x):
         xs = sp.csc_matrix(x, dtype=np.float64)
         xs.sort_indices()
@@ -334,6 +353,29 @@ def cv_sgdnet_newton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_m
                train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
 
 
+def cv_sgdnet_wcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                          train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                          standardize=True, intercept=True, thresh=0.001):
+    """cv_sgdnet(family="gaussian") with every fit a sgdnet_wcovariance(): the fold ids, the scoring, the generator and the
+    returned CvSgdnet are cv_sgdnet's.  fold_fits="separate" (the default) runs one sgdnet_wcovariance per fold;
+    "batched" runs all fold fits of all alphas through ONE native call (cv_wcovariance_fits) with the full fits' lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_wcovariance(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio,
+                                  device=dev, **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_wcovariance_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="gaussian", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
 def cv_sgdnet_mcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
                           train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
                           standardize=True, intercept=True, thresh=0.001, standardize_response=False):
@@ -382,7 +424,7 @@ def cv_sgdnet_mnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_
 
 
 def _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, *, family, devices, rng, seed, train_on, densify, fit_one, batched_fits):
-    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance() and cv_sgdnet_mnewton(): the full fits, the fold ids, the fold fits, the scores
+    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance(), cv_sgdnet_mnewton() and cv_sgdnet_wcovariance(): the full fits, the fold ids, the fold fits, the scores
     and the summary.  fit_one(x, y, lambda, alpha, device, seed, rng, sequential) is a fit; batched_fits(x, y, foldid, alpha,
     lambdas, device), where given, returns every fold fit from one call (alpha-major), else the folds are fitted one by one."""
     import scipy.sparse as sp
