@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width, sgdnet_cv_mnewton_*, sgdnet_cv_wcovariance_* (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width, sgdnet_cv_mnewton_*, sgdnet_cv_wcovariance_*, sgdnet_cv_wmcovariance_* (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -991,6 +991,36 @@ int sgdnet_cv_wcovariance_dense(const double* x, int64_t n, int64_t p, const dou
 int sgdnet_cv_wcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
                                  const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
                                  sgdnet_cv_cov_result* out);
+
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in wide multi-response covariance mode (additions only;   */
+/* the ABI version stays): sgdnet_cv_mcovariance_* beyond                      */
+/* sgdnet_mcovariance_max_features(n_classes) features.  The arguments and the */
+/* result are those of sgdnet_cv_mcovariance_*; job (alpha a, group g) is by   */
+/* definition sgdnet_fit_*(x[T], y[T]) in SGDNET_MODE_WMCOVARIANCE with        */
+/* elasticnet_mix = alphas[a] and the user lambdas lambdas[a][.]: the same     */
+/* optimum, return codes and npasses (list sweeps), not the same bits.  One    */
+/* pass over x leaves the (p + K + 1)^2 moments of every group, every training */
+/* set's scaled Gram matrix and c~ are pooled from them into global memory,    */
+/* and the n_alpha * n_groups paths run one workgroup -- one compute unit --   */
+/* each; jobs beyond the compute units queue (sgdnet_amd/csrc/covariance.hip:  */
+/* wmcovariance_cv_run).  The option wmcovariance_width applies as in one fit  */
+/* (another value: SGDNET_EINVAL).                                             */
+/* SGDNET_EUNSUPPORTED ("mode = wmcovariance needs ..."): a family other than  */
+/* mgaussian, n_classes < 2, more than                                         */
+/* sgdnet_wmcovariance_max_features(n_classes) features, n_gpus > 1, debug,    */
+/* more than 65 535 groups (dense x: row chunks), or more than 16 GiB of group */
+/* moments, partial tiles, scaled matrices and c~ -- a 10-fold CV at the limit */
+/* of two responses takes 2.9 GB of it; the message gives the bytes.  There is */
+/* no fall-back to sgdnet_cv_mcovariance_*, to SAGA or to separate fits.       */
+/* SGDNET_EINVAL: the cases of sgdnet_cv_mcovariance_*.                        */
+/* ------------------------------------------------------------------------ */
+int sgdnet_cv_wmcovariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                                 int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                                 const double* lambdas, sgdnet_cv_mcov_result* out);
+int sgdnet_cv_wmcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                  const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                  sgdnet_cv_mcov_result* out);
 
 #ifdef __cplusplus
 }

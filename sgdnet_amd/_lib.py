@@ -41,7 +41,7 @@ EXPORTS = [
     "sgdnet_mnewton_max_features", "sgdnet_mnewton_probe", "sgdnet_wcovariance_max_features",
     "sgdnet_wnewton_max_features", "sgdnet_wmcovariance_max_features", "sgdnet_wmnewton_max_features",
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
-    "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse",
+    "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse", "sgdnet_cv_wmcovariance_dense", "sgdnet_cv_wmcovariance_sparse",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -156,7 +156,7 @@ class CvNewtonResult(C.Structure):
 
 
 class CvMcovResult(C.Structure):
-    """sgdnet_cv_mcov_result: caller-allocated outputs of sgdnet_cv_mcovariance_*, job-major (job = alpha * n_groups + group);
+    """sgdnet_cv_mcov_result: caller-allocated outputs of sgdnet_cv_mcovariance_* and sgdnet_cv_wmcovariance_*, job-major (job = alpha * n_groups + group);
     a0 is jobs x L x K and beta jobs x L x (K x p with entry (k, j) at k + j K)."""
     _fields_ = [("a0", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)), ("dev_ratio", C.POINTER(C.c_double)),
                 ("return_codes", C.POINTER(C.c_double)), ("nulldev", C.POINTER(C.c_double)), ("npasses", C.POINTER(C.c_double))]
@@ -291,6 +291,8 @@ def load():
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvMcovResult)]
     L.sgdnet_cv_mcovariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_mcovariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
+    L.sgdnet_cv_wmcovariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
+    L.sgdnet_cv_wmcovariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvMNewtonResult)]
     L.sgdnet_cv_mnewton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_mnewton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail

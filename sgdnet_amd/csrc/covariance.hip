@@ -57,6 +57,9 @@
 //              wcov_cv_assemble_kernel (per column and T) do cov_assemble_kernel's pooling and re-centring straight into
 //              every training set's S_T, diag S_T and c~_T in global memory; cov_wide_cv_path_kernel, a second entry around
 //              cov_wide_path_kernel's body, takes its job (mix, T) from blockIdx.x: one workgroup, one CU, per job.
+//              wmcovariance_cv_run: the same for the K responses.  The group moments of mcovariance_cv_run (p + K + 1
+//              columns, the wide row chunks), wmcov_cv_stats_kernel and wmcov_cv_assemble_kernel for mcov_assemble_kernel's
+//              pooling, and cov_wide_group_cv_path_kernel, a second entry around cov_wide_group_path_kernel's body.
 //
 // No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K, nnz, fold): the same input gives the
 // same bits (the contract of gradient.hip).
@@ -1039,13 +1042,15 @@ __global__ __launch_bounds__(kBlock) void cov_wide_group_scale_kernel(const doub
 //            sweeps; then the screen runs again, and the lambda is done when it adds nothing.
 // max_iter bounds the list sweeps of one lambda.  Every entry of g is updated by one lane from the same words in the same
 // order whatever kWidth is: both widths give the same bits.
+// The body of two entries, below: cov_wide_group_path_kernel (one fit) and cov_wide_group_cv_path_kernel (a job of a
+// cross-validation).
 template <int kWidth>
-__global__ __launch_bounds__(kWidth) void cov_wide_group_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
-                                                                      const double* __restrict__ ct, int p, int K, int ld,
-                                                                      const double* __restrict__ alpha, const double* __restrict__ beta,
-                                                                      int n_lambda, int ridge, unsigned max_iter, double tol,
-                                                                      double* __restrict__ W, double* __restrict__ G,
-                                                                      int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+__device__ __forceinline__ void cov_wide_group_path_body(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                         const double* __restrict__ ct, int p, int K, int ld,
+                                                         const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                         int n_lambda, int ridge, unsigned max_iter, double tol,
+                                                         double* __restrict__ W, double* __restrict__ G,
+                                                         int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kCovLdsBytes];
   const int lane = threadIdx.x, pe = p + (p & 1), slots = pe / 2, pK = p * K;
   double* g = reinterpret_cast<double*>(lds);
@@ -1202,6 +1207,135 @@ __global__ __launch_bounds__(kWidth) void cov_wide_group_path_kernel(const doubl
       unconverged[l] = converged ? 0 : 1;
     }
   }
+}
+
+// One fit: a grid of 1.  The entry the single fit has always had, around the shared body.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void cov_wide_group_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                                      const double* __restrict__ ct, int p, int K, int ld,
+                                                                      const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                      int n_lambda, int ridge, unsigned max_iter, double tol,
+                                                                      double* __restrict__ W, double* __restrict__ G,
+                                                                      int32_t* __restrict__ sweeps_out, int32_t* __restrict__ unconverged) {
+  cov_wide_group_path_body<kWidth>(S, Sd, ct, p, K, ld, alpha, beta, n_lambda, ridge, max_iter, tol, W, G, sweeps_out, unconverged);
+}
+
+// The same path over jobs (wmcovariance_cv_run).  blockIdx.x = job, as in cov_wide_cv_path_kernel: its training set is
+// job % n_sets (S, diag S and c~ per set: strides ld p, p and p K; read-only and shared by the set's mixes), its penalties,
+// functor and outputs are the job's own.  The pointers are offset once, here at the entry, and the body is the single
+// fit's; a second entry for the reason cov_wide_cv_path_kernel is one.  The kernel declares the CU's whole LDS: one job
+// runs per CU, the others queue.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void cov_wide_group_cv_path_kernel(const double* __restrict__ S, const double* __restrict__ Sd,
+                                                                         const double* __restrict__ ct, int p, int K, int ld, int n_sets,
+                                                                         const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                                         int n_lambda, const int32_t* __restrict__ ridge_jobs,
+                                                                         unsigned max_iter, double tol, double* __restrict__ W,
+                                                                         double* __restrict__ G, int32_t* __restrict__ sweeps_out,
+                                                                         int32_t* __restrict__ unconverged) {
+  const size_t job = blockIdx.x, set = job % (size_t)n_sets, at = job * (size_t)n_lambda, pK = (size_t)p * (size_t)K;
+  cov_wide_group_path_body<kWidth>(S + set * (size_t)ld * (size_t)p, Sd + set * (size_t)p, ct + set * pK, p, K, ld, alpha + at, beta + at,
+                                   n_lambda, ridge_jobs[job], max_iter, tol, W + at * pK, G + at * pK, sweeps_out + at, unconverged + at);
+}
+
+// ---- the folds of wide multi-response mode (wmcovariance_cv_run): mcov_assemble_kernel's work, written in the wide layout ----
+// mcov_assemble_kernel is one workgroup per training set with the sums s and the shifts d of the p + K columns in dynamic
+// LDS and a G x p x (p + K) re-centred matrix for its output; at 3709 features neither belongs there.  As for one response
+// (wcov_cv_stats_kernel, wcov_cv_assemble_kernel) the work is cut in two, s and d live in GLOBAL memory, and a column of S_T
+// comes straight from row j of the group moments:
+//   wmcov_cv_stats_kernel     blockIdx.x = training set T: everything of size p + K or smaller
+//   wmcov_cv_assemble_kernel  blockIdx.x = column j, blockIdx.y = T: column j of S_T, diag S_T and row j of c~_T
+// WcovSet and wcov_recentred are shared with them: the moments are (p + K + 1) x (p + K + 1) here.
+
+// blockIdx.x = training set T.  mcov_assemble_kernel's expressions for what is per T or per job:
+//   s, d   G x (p + K): T's sums of deviations about the common centre and its shifts (every response; a feature only when centred)
+//   scale  G x p      mean  G x (p + K): as mcov_assemble_kernel leaves it      ysd  G x K: the divisors of the responses
+//   tstat  3 x G: n_T | y~'y~ | the null deviance, both summed in the order r = 0 .. K - 1
+//   l2, l1  jobs x n_lambda, job = mix * G + T      ridge  jobs
+// Lane 0 forms yy and the null deviance from the moments themselves: nothing is staged and no barrier is needed.
+__global__ __launch_bounds__(kBlock) void wmcov_cv_stats_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
+                                                                 const double* __restrict__ mu, int n_groups, int p, int K, int rest,
+                                                                 int centre, int standardize, int standardize_response,
+                                                                 const double* __restrict__ mix, const double* __restrict__ lambda,
+                                                                 int n_mix, int n_lambda, double* __restrict__ s, double* __restrict__ d,
+                                                                 double* __restrict__ scale, double* __restrict__ mean,
+                                                                 double* __restrict__ ysd, double* __restrict__ tstat,
+                                                                 double* __restrict__ l2, double* __restrict__ l1,
+                                                                 int32_t* __restrict__ ridge) {
+  const int t = blockIdx.x, tid = threadIdx.x, nc = p + K, Pa = nc + 1;
+  const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
+  const double nT = C(nc, nc);
+  // the sd response r is divided by (1 without standardize_response; a constant response: 0 -> 1), from its re-centred square q
+  auto sd_y = [&](double q) -> double {
+    if (!standardize_response) return 1.0;
+    const double v = q / nT;
+    return v > 0.0 ? sqrt(v) : 1.0;
+  };
+  for (int j = tid; j < nc; j += kBlock) {
+    const double sj = C(j, nc), dj = (j >= p || centre) ? sj / nT : 0.0;
+    s[(size_t)t * nc + j] = sj;
+    d[(size_t)t * nc + j] = dj;
+    const double q = wcov_recentred(C(j, j), sj, dj, sj, dj, nT);
+    if (j < p) {
+      const double v = q / nT;
+      scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+      mean[(size_t)t * nc + j] = centre ? mu[j] + dj : 0.0;
+    } else {
+      ysd[(size_t)t * K + (j - p)] = sd_y(q);
+      mean[(size_t)t * nc + j] = standardize_response ? 0.0 : mu[j + K] + dj;
+    }
+  }
+  if (tid == 0) {
+    double yy = 0.0, nulldev = 0.0;
+    for (int r = 0; r < K; ++r) {
+      const double sr = C(p + r, nc), dr = sr / nT;
+      const double q = wcov_recentred(C(p + r, p + r), sr, dr, sr, dr, nT), sd = sd_y(q);
+      nulldev += q;
+      yy += q / sd / sd;
+    }
+    tstat[t] = nT;
+    tstat[n_groups + t] = yy;
+    tstat[2 * n_groups + t] = nulldev;
+  }
+  for (int e = tid; e < n_mix * n_lambda; e += kBlock) {
+    const int a = e / n_lambda, l = e - a * n_lambda;
+    const size_t at = ((size_t)a * n_groups + t) * n_lambda + l;
+    l2[at] = (1.0 - mix[a]) * lambda[e];
+    l1[at] = mix[a] * lambda[e];
+    if (l == 0) ridge[(size_t)a * n_groups + t] = mix[a] == 0.0 ? 1 : 0;
+  }
+}
+
+// blockIdx.x = column j < p, blockIdx.y = training set T.  Column j of S_T = M^T / n_T / (sd sd') in the layout
+// cov_wide_group_path_kernel reads (leading dimension ld, rows p .. ld - 1 the zero pad; set stride ld p), diag S_T and
+// c~_T[j, r] = M^T[j, p + r] / sd_y(r) / n_T / sd_j at j K + r (set stride p K): the arithmetic of mcov_assemble_kernel
+// followed by cov_wide_group_scale_kernel's.  The moments are read along row j (coalesced; row j is column j bit for bit);
+// s, d, scale and the responses' divisors come from wmcov_cv_stats_kernel.
+__global__ __launch_bounds__(kBlock) void wmcov_cv_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
+                                                                    const double* __restrict__ s, const double* __restrict__ d,
+                                                                    const double* __restrict__ scale, const double* __restrict__ ysd,
+                                                                    const double* __restrict__ tstat, int p, int K, int ld, int rest,
+                                                                    double* __restrict__ S, double* __restrict__ Sd, double* __restrict__ ct) {
+  const int j = blockIdx.x, t = blockIdx.y, nc = p + K, Pa = nc + 1;
+  const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
+  s += (size_t)t * nc;
+  d += (size_t)t * nc;
+  scale += (size_t)t * p;
+  ysd += (size_t)t * K;
+  const double nT = tstat[t];
+  const double sj = s[j], dj = d[j], fj = scale[j];
+  double* col = S + ((size_t)t * p + j) * (size_t)ld;
+  for (int k = threadIdx.x; k < ld; k += kBlock) {
+    double v = 0.0;
+    if (k < p) {
+      const double c = C(j, k), sk = s[k], dk = d[k], fk = scale[k];
+      v = k >= j ? wcov_recentred(c, sj, dj, sk, dk, nT) / nT / (fj * fk) : wcov_recentred(c, sk, dk, sj, dj, nT) / nT / (fk * fj);
+    }
+    col[k] = v;
+    if (k == j) Sd[(size_t)t * p + j] = v;
+  }
+  for (int r = threadIdx.x; r < K; r += kBlock)
+    ct[((size_t)t * p + j) * K + r] = wcov_recentred(C(j, p + r), sj, dj, s[p + r], d[p + r], nT) / ysd[r] / nT / fj;
 }
 
 // The wide group kernel's workgroup: both widths give the same bits; profiles/wmcovariance_path.txt has the path kernel's
@@ -2028,6 +2162,205 @@ int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out)
   SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
   SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
   SGD_HIP_TRY(hipStreamSynchronize(st));
+  out->n_train.assign(tstat.begin(), tstat.begin() + G);
+  out->yy.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
+  out->nulldev.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
+  SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
+  return SGDNET_OK;
+}
+
+int64_t wmcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups) {
+  const int64_t rows_per_chunk = wide_rows_per_chunk(n, p + K + 1, kTileRows);
+  int64_t chunks = 0;
+  for (int g = 0; g < n_groups; ++g) chunks += (count[g] + rows_per_chunk - 1) / rows_per_chunk;
+  return chunks;
+}
+
+// mcovariance_cv_run beyond mcov_max_features(K) features: the same group moments pass (the wide mode's row chunks),
+// wmcov_cv_stats_kernel and wmcov_cv_assemble_kernel instead of mcov_assemble_kernel, cov_wide_group_cv_path_kernel over
+// the jobs.
+int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, int width) {
+  const int64_t n = pb.n;
+  const int K = pb.K;
+  const bool sparse = pb.x_dense == nullptr;
+  if (n <= 0 || pb.p <= 0 || K < 1 || pb.p > wmcov_max_features(K) || pb.n_lambda <= 0 || pb.n_groups <= 0 || pb.n_mix <= 0 || !pb.fold ||
+      !pb.y || !pb.mix || !pb.lambda || (pb.train_on_rest && pb.n_groups < 2) || (!sparse && pb.colptr) ||
+      (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("wmcovariance_cv_run: invalid problem");
+    return SGDNET_EINVAL;
+  }
+  const int p = (int)pb.p, nc = p + K, Pa = nc + 1, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
+  if (width == 0) width = wmcov_path_width(p);
+  if (width != kWideNarrow && width != kWideFull) {
+    set_error("wmcovariance_cv_run: the path kernel's workgroup is %d or %d lanes, not %d", kWideNarrow, kWideFull, width);
+    return SGDNET_EINVAL;
+  }
+  const size_t jobs = (size_t)A_mix * (size_t)G, pK = (size_t)p * (size_t)K;
+
+  // dense x: the rows sorted by group (stable) and cut into chunks of the size one wide fit of n rows over p + K + 1 columns
+  // would use, none across a group's end: the summation order is a function of (n, p, K, fold) alone
+  const int64_t pairs = wide_tile_pairs(Pa);
+  std::vector<int64_t> perm, chunk_begin;
+  std::vector<int32_t> group_chunk;
+  if (!sparse) {
+    std::vector<int64_t> start((size_t)G + 1, 0);
+    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
+    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
+    perm.resize((size_t)n);
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
+    const int64_t rows_per_chunk = wide_rows_per_chunk(n, Pa, kTileRows);
+    group_chunk.assign((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
+      if (chunk_begin.size() > (size_t)kCovMaxRowChunks) {
+        set_error("mode = wmcovariance needs the rows of the groups in at most %d chunks: %d groups of %lld rows", kCovMaxRowChunks, G,
+                  (long long)n);
+        return SGDNET_EUNSUPPORTED;
+      }
+      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
+    }
+    chunk_begin.push_back(n);
+  }
+  if (G > kCovMaxRowChunks) {       // (the pair kernel's gridDim.z, the assembly's gridDim.y)
+    set_error("mode = wmcovariance needs at most %d groups: %d groups", kCovMaxRowChunks, G);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
+  if (wmcov_cv_bytes(G, p, K, (int64_t)chunks) > kWcovCvBytes) {
+    set_error("mode = wmcovariance needs the moments and the scaled matrices of the groups within %zu bytes: %d groups of %d features and %d responses are %zu bytes",
+              kWcovCvBytes, G, p, K, wmcov_cv_bytes(G, p, K, (int64_t)chunks));
+    return SGDNET_EUNSUPPORTED;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+
+  const int64_t nnz = sparse ? pb.colptr[p] : 0;
+  const int32_t* no_rows = nullptr;
+  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
+  const size_t Melems = (size_t)Pa * (size_t)Pa;      // (at most 4533^2 = 20 548 089: cov_total_kernel's int, covariance.hpp)
+  const int ld = (int)wide_leading_dim(p);
+
+  Arena A;
+  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
+  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
+  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
+  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
+  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
+  const size_t o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
+  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(nc + K));      // the features' centres | the responses' sums | their means
+  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
+  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
+  const size_t o_total = A.reserve(sizeof(double) * Melems);
+  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
+  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  const size_t o_s = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
+  const size_t o_d = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
+  const size_t o_S = A.reserve(sizeof(double) * (size_t)G * (size_t)ld * (size_t)p);
+  const size_t o_Sd = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_ct = A.reserve(sizeof(double) * (size_t)G * pK);
+  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
+  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
+  const size_t o_ysd = A.reserve(sizeof(double) * (size_t)G * (size_t)K);
+  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
+  const size_t o_l2 = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_l1 = A.reserve(sizeof(double) * jobs * (size_t)L);
+  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
+  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
+  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
+  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Events ev;
+  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
+  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  hipStream_t st = ev.st;
+  double* d_x = A.at<double>(o_x);
+  double* d_y = A.at<double>(o_y);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_Mg = A.at<double>(o_Mg);
+  double* d_tstat = A.at<double>(o_tstat);
+  if (sparse) {
+    if (nnz > 0) {
+      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)(p + 1), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+  } else {
+    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
+    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
+  }
+  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n * (size_t)K, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
+  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
+
+  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
+  if (sparse) {
+    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, K,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
+    hipLaunchKernelGGL(cov_group_responses_kernel, dim3((unsigned)K, (unsigned)K, (unsigned)G), dim3(kBlock), 0, st, d_y,
+                       A.at<int32_t>(o_fold), d_mu, n, p, K, d_Mg);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
+                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, K, A.at<int32_t>(o_fold), d_Mg);
+  } else {
+    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, K,
+                       pb.centre ? 1 : 0, d_mu);
+    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, Pa,
+                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
+  }
+  if (pb.train_on_rest)
+    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
+                       A.at<double>(o_total));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  const int rest = pb.train_on_rest ? 1 : 0;
+  hipLaunchKernelGGL(wmcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p, K, rest,
+                     pb.centre ? 1 : 0, pb.standardize ? 1 : 0, pb.standardize_response ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda),
+                     A_mix, L, A.at<double>(o_s), A.at<double>(o_d), A.at<double>(o_scale), A.at<double>(o_mean), A.at<double>(o_ysd), d_tstat,
+                     A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
+  hipLaunchKernelGGL(wmcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total),
+                     A.at<double>(o_s), A.at<double>(o_d), A.at<double>(o_scale), A.at<double>(o_ysd), d_tstat, p, K, ld, rest,
+                     A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  const auto kernel = width == kWideNarrow ? cov_wide_group_cv_path_kernel<kWideNarrow> : cov_wide_group_cv_path_kernel<kWideFull>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
+                     K, ld, G, A.at<double>(o_l2), A.at<double>(o_l1), L, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol, A.at<double>(o_W),
+                     A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+
+  std::vector<double> tstat(3 * (size_t)G), ct((size_t)G * pK);
+  out->mean.resize((size_t)G * (size_t)nc);
+  out->scale.resize((size_t)G * (size_t)p);
+  out->c.resize(jobs * pK);
+  out->w.resize(jobs * (size_t)L * pK);
+  out->g.resize(jobs * (size_t)L * pK);
+  out->sweeps.resize(jobs * (size_t)L);
+  out->unconverged.resize(jobs * (size_t)L);
+  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
+  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
+  SGD_HIP_TRY(fetch(ct.data(), o_ct, sizeof(double) * ct.size()));
+  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
+  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
+  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
+  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
+  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
+  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
+  for (size_t job = 0; job < jobs; ++job)      // c~ is the training set's: every mix of a set gets its copy
+    std::copy(ct.begin() + (job % (size_t)G) * pK, ct.begin() + (job % (size_t)G + 1) * pK, out->c.begin() + job * pK);
   out->n_train.assign(tstat.begin(), tstat.begin() + G);
   out->yy.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
   out->nulldev.assign(tstat.begin() + 2 * (size_t)G, tstat.end());

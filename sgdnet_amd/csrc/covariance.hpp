@@ -289,4 +289,36 @@ int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, in
 // (driver_direct.cpp: fit_cv_mcovariance).
 int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out);
 
+// ---- the same in wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): beyond mcov_max_features(K) features ----
+// The same group moments over Pa = p + K + 1 columns (dense x: row chunks by wide_rows_per_chunk, cut at the groups' ends),
+// pooled and re-centred per training set straight into the scaled Gram matrices S_T (leading dimension wide_leading_dim(p),
+// set stride ld p) and c~_T (p x K, entry (j, r) at j K + r) in global memory, and cov_wide_group_path_kernel's path over
+// the jobs: one workgroup, one CU, per job.
+//
+// The budget, in doubles: the group moments and their total (G + 1) Pa^2, the dense partial tiles chunks x
+// wide_tile_pairs(Pa) x 256 (none for sparse x), the scaled matrices G ld p and c~ G p K -- x and the per-job outputs are
+// not counted.  It is held within kWcovCvBytes.  At the limit of K = 2 (3709 features) a 10-fold CV takes 2.87 GB and a
+// 20-fold 5.63 GB; at the limit of K = 10 (950) a 10-fold takes 0.19 GB; at p = 1000, K = 2 a group is 20.3 MB and 847
+// groups fit.
+constexpr size_t wmcov_cv_bytes(int64_t G, int64_t p, int64_t K, int64_t chunks) {
+  return sizeof(double) * ((size_t)(G + 1) * (size_t)(p + K + 1) * (size_t)(p + K + 1) + (size_t)chunks * (size_t)wide_tile_pairs(p + K + 1) * 256 +
+                           (size_t)G * (size_t)wide_leading_dim(p) * (size_t)p + (size_t)G * (size_t)p * (size_t)K);
+}
+static_assert(wmcov_cv_bytes(10, wmcov_max_features(2), 2, 10) <= kWcovCvBytes && wmcov_cv_bytes(10, wmcov_max_features(10), 10, 10) <= kWcovCvBytes,
+              "a 10-fold CV at the feature limits of K = 2 and K = 10 fits");
+static_assert(wmcov_cv_bytes(10, 3709, 2, 10) / 10000000 == 286 && wmcov_cv_bytes(20, 3709, 2, 20) / 10000000 == 562 &&
+              wmcov_cv_bytes(10, 950, 10, 10) / 10000000 == 19, "the examples above");
+static_assert(wmcov_cv_bytes(847, 1000, 2, 847) <= kWcovCvBytes && wmcov_cv_bytes(848, 1000, 2, 848) > kWcovCvBytes, "the examples above");
+// wmcov_fits keeps p + K <= kWcovMaxFeatures + 1, so Pa <= 4533 and Pa^2 = 20 548 089 at most: cov_total_kernel's int
+static_assert((int64_t)(kWcovMaxFeatures + 2) * (kWcovMaxFeatures + 2) <= 2147483647, "Pa^2 fits cov_total_kernel's int");
+
+// The row chunks of the dense group moments pass (gridDim.y): count[g] rows in group g, none across a group's end.
+int64_t wmcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups);
+
+// Group moments + stats and assembly + wide group path kernel over the jobs.  p <= wmcov_max_features(K), the budget above,
+// at most kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business
+// (driver_direct.cpp: fit_cv_mcovariance, wide).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule
+// of covariance.hip (wmcov_path_width); both give the same bits.  pb.width is not read.
+int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, int width = 0);
+
 }  // namespace sgdnet

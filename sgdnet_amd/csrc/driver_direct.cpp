@@ -5,7 +5,7 @@
 //                       problem every mode fills the same way, the kernels' run, and per lambda the deviance and the way
 //                       back to the scale of the data
 //   fit_cv_covariance   every fold fit of a cross-validation in one launch       (sgdnet_cv_covariance_*, sgdnet_cv_wcovariance_*)
-//   fit_cv_mcovariance  the same for the K responses of an mgaussian fit         (sgdnet_cv_mcovariance_*)
+//   fit_cv_mcovariance  the same for the K responses of an mgaussian fit         (sgdnet_cv_mcovariance_*, sgdnet_cv_wmcovariance_*)
 //   fit_cv_newton       every fold fit through the Newton loop in lock-step      (sgdnet_cv_newton_*)
 //   fit_cv_mnewton      the same through the multinomial Newton loop             (sgdnet_cv_mnewton_*)
 //   the probes          one outer step of the Newton modes, everything copied back (sgdnet_newton_probe_*, sgdnet_mnewton_probe)
@@ -421,34 +421,38 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
 // mgaussian has y_scale = 1), the null model's intercepts b0_r = mean_T(y~_r) subtracted, the penalties (1 - mix) lambda and
 // mix lambda.  The device assembles all of it from the group moments; the host is left with the way back to the scale of
 // the features (rescale_values) and the deviance from the quadratic form, per job.
+// wide: SGDNET_MODE_WMCOVARIANCE, the same stage around wmcovariance_cv_run (the stage behind sgdnet_cv_wmcovariance_*): its own
+// feature limit and byte budget, and no way from one to the other -- each refuses by its own name.
 int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                       int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mcov_result* out) {
+                       int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mcov_result* out, bool wide = false) {
   const int64_t n = pb.n, p = pb.p;
+  const char* entry = wide ? "sgdnet_cv_wmcovariance" : "sgdnet_cv_mcovariance";
+  const char* mode = wide ? "wmcovariance" : "mcovariance";
   if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !pb.y ||
       !fold || !alphas || !lambdas) {
-    set_error("sgdnet_cv_mcovariance: null pointer");
+    set_error("%s: null pointer", entry);
     return SGDNET_EINVAL;
   }
   if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
       (train_on_rest && n_groups < 2)) {
-    set_error("sgdnet_cv_mcovariance: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    set_error("%s: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)", entry);
     return SGDNET_EINVAL;
   }
   const int L = ctl->n_lambda, K = ctl->n_classes;
-  const int limit = mcov_max_features(K);
+  const int limit = wide ? wmcov_max_features(K) : mcov_max_features(K);
   const char* what = nullptr;
   if (ctl->family != SGDNET_MGAUSSIAN) what = "family = mgaussian";
   else if (K < 2) what = "at least two responses (n_classes >= 2)";
-  else if (p > limit) what = "no more features than sgdnet_mcovariance_max_features(n_classes)";
+  else if (p > limit) what = wide ? "no more features than sgdnet_wmcovariance_max_features(n_classes)" : "no more features than sgdnet_mcovariance_max_features(n_classes)";
   else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
   else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
   if (what) {
-    set_error("mode = mcovariance needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, K,
+    set_error("mode = %s needs %s: family %d, n_classes %d, %lld features (limit %d), n_gpus %d, debug %d", mode, what, ctl->family, K,
               (long long)p, limit, ctl->n_gpus, ctl->debug);
     return SGDNET_EUNSUPPORTED;
   }
   const size_t moment_bytes = mcov_group_moment_bytes(n_groups, p, K);
-  if (moment_bytes > kCovGroupMomentBytes) {
+  if (!wide && moment_bytes > kCovGroupMomentBytes) {
     set_error("mode = mcovariance needs the group moments within %zu bytes: %d groups x (%lld + %d + 1)^2 doubles are %zu bytes",
               kCovGroupMomentBytes, n_groups, (long long)p, K, moment_bytes);
     return SGDNET_EUNSUPPORTED;
@@ -458,11 +462,20 @@ int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, cons
   if (!rc) rc = validate_mixes(n_alpha, alphas, L, lambdas);
   if (rc) return rc;
   const bool sparse = pb.x_dense == nullptr;
-  const int64_t chunks = sparse ? n_groups : mcov_cv_row_chunks(n, p, K, count.data(), n_groups);
+  const int64_t chunks = sparse ? n_groups
+                                : (wide ? wmcov_cv_row_chunks(n, p, K, count.data(), n_groups) : mcov_cv_row_chunks(n, p, K, count.data(), n_groups));
   if (chunks > kCovMaxRowChunks) {
-    set_error("mode = mcovariance needs at most %d %s: %d groups of %lld rows are %lld", kCovMaxRowChunks,
+    set_error("mode = %s needs at most %d %s: %d groups of %lld rows are %lld", mode, kCovMaxRowChunks,
               sparse ? "groups of sparse rows" : "row chunks of the groups", n_groups, (long long)n, (long long)chunks);
     return SGDNET_EUNSUPPORTED;
+  }
+  if (wide) {      // the byte budget of wmcovariance_cv_run (sparse x has no partial tiles)
+    const size_t bytes = wmcov_cv_bytes(n_groups, p, K, sparse ? 0 : chunks);
+    if (bytes > kWcovCvBytes) {
+      set_error("mode = wmcovariance needs the moments and the scaled matrices of the groups within %zu bytes: %d groups of %lld features and %d responses are %zu bytes",
+                kWcovCvBytes, n_groups, (long long)p, K, bytes);
+      return SGDNET_EUNSUPPORTED;
+    }
   }
   rc = check_device(ctl->device);
   if (rc) return rc;
@@ -485,12 +498,13 @@ int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, cons
   static const int width = exp_env_int("SGDNET_MCOV_WIDTH", 0);     // (64 or 256 lanes, as fit_mcovariance takes it)
   pb.width = width;
   McovarianceCvResult cr;
-  rc = mcovariance_cv_run(pb, &cr);
+  rc = wide ? wmcovariance_cv_run(pb, &cr, option(kOptWmcovarianceWidth)) : mcovariance_cv_run(pb, &cr);
   if (rc) return rc;
   if (pt.on)
-    fprintf(stderr, "[sgdnet]   cv mcovariance: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", cr.moments_ms,
+    fprintf(stderr, "[sgdnet]   cv %s: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", mode, cr.moments_ms,
             cr.assemble_ms, n_alpha * n_groups, cr.path_ms);
 
+  // per job, both modes alike: the way back to the scale of the data and the deviance from the quadratic form
   const size_t P = (size_t)p, Ks = (size_t)K, pK = P * Ks;
   std::vector<double> xbb(Ks);
   for (int a = 0; a < n_alpha; ++a)
@@ -525,7 +539,7 @@ int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, cons
       out->nulldev[job] = cr.nulldev[(size_t)t];
       out->npasses[job] = n_sweeps;
     }
-  pt.mark("cv mcovariance (all folds)");
+  pt.mark(wide ? "cv wmcovariance (all folds)" : "cv mcovariance (all folds)");
   return SGDNET_OK;
 }
 
@@ -1146,6 +1160,40 @@ int sgdnet_cv_mcovariance_sparse(const sgdnet_csc* x, const double* y, const int
   pb.values = x->values;
   pb.y = y;
   return fit_cv_mcovariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_wmcovariance_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                                 int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                 sgdnet_cv_mcov_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_wmcovariance_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  McovarianceCvProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  pb.y = y;
+  return fit_cv_mcovariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
+}
+
+int sgdnet_cv_wmcovariance_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                                  const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                                  sgdnet_cv_mcov_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_wmcovariance_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  McovarianceCvProblem pb;
+  pb.n = x->n_rows;
+  pb.p = x->n_cols;
+  pb.colptr = x->colptr;
+  pb.rowidx = x->rowidx;
+  pb.values = x->values;
+  pb.y = y;
+  return fit_cv_mcovariance(pb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
 }
 
 int sgdnet_cv_newton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,

@@ -34,7 +34,12 @@ cv_sgdnet_wcovariance() is the gaussian CV whose fits are sgdnet_wcovariance() (
 fold_fits="batched" runs all fold fits through cv_wcovariance_fits -> sgdnet_cv_wcovariance_*: the group moments from one pass,
 every training set's scaled Gram matrix pooled from them into device memory, one workgroup -- one compute unit -- per path
 (csrc/covariance.hip: wcovariance_cv_run).
-_cv() is the body the five CVs share; they differ in the fit they inject.
+
+cv_sgdnet_wmcovariance() is the mgaussian CV whose fits are sgdnet_wmcovariance() (beyond mcovariance mode's feature limit); its
+fold_fits="batched" runs all fold fits through cv_wmcovariance_fits -> sgdnet_cv_wmcovariance_*: the group moments of the K
+responses from one pass, every training set's scaled Gram matrix and c~ pooled from them into device memory, one workgroup --
+one compute unit -- per path (csrc/covariance.hip: wmcovariance_cv_run).
+_cv() is the body the six CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -43,8 +48,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODES, check, dptr
-from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODES, check, dptr
+from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -163,6 +168,24 @@ def cv_mcovariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=
                              standardize_response=standardize_response, device=device)
 
 
+def cv_wmcovariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                         thresh=0.001, standardize_response=False, device=0):
+    """Every fold fit of an mgaussian cross-validation in wide multi-response covariance mode from one native call.
+
+    The arguments are cv_mcovariance_fits's, for up to wmcovariance_max_features(K) features.  Returns a list of SgdnetFit,
+    alpha-major: entry a * nfolds + j is sgdnet_wmcovariance(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a],
+    standardize_response=standardize_response) for the training set T of fold j (the same optimum, return codes and
+    npasses; not the same bits)."""
+    y_arr = np.asarray(y)
+    if y_arr.ndim != 2 or y_arr.shape[1] < 2:
+        raise ValueError("response for multivariate Gaussian regression must not be one-dimensional; try family = 'gaussian'.")
+    if y_arr.dtype.kind not in "fiub":
+        raise ValueError("non-numeric response.")
+    return _native_fold_fits(x, np.asfortranarray(y_arr, dtype=np.float64), foldid, alpha, lambda_, train_on, family="mgaussian",
+                             classnames=None, maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh,
+                             standardize_response=standardize_response, device=device, wide=True)
+
+
 def cv_mnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
                     thresh=0.001, device=0):
     """Every fold fit of a multinomial cross-validation in multinomial Newton mode from one native call, all of them
@@ -188,7 +211,7 @@ def cv_mnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000
 def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, classnames, maxit, standardize, intercept, thresh,
                       device, standardize_response=False, n_classes=1, wide=False):
     """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*),
-    cv_wcovariance_fits (gaussian, wide: sgdnet_cv_wcovariance_*),
+    cv_wcovariance_fits (gaussian, wide: sgdnet_cv_wcovariance_*), cv_wmcovariance_fits (mgaussian, wide: sgdnet_cv_wmcovariance_*),
     cv_newton_fits (binomial: sgdnet_cv_newton_*), cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*) and cv_mnewton_fits
     (multinomial: sgdnet_cv_mnewton_*, n_classes classes); y_enc: the response as the backend takes it (mgaussian: n x K,
     column-major)."""
@@ -229,8 +252,8 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
     ctl.standardize_response = int(bool(standardize_response))
     ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, K
-    ctl.mode = (MODE_MNEWTON if mnewton else MODE_NEWTON if newton else MODE_MCOVARIANCE if multi else MODE_WCOVARIANCE if wide
-                else MODES["covariance"])
+    ctl.mode = (MODE_MNEWTON if mnewton else MODE_NEWTON if newton else (MODE_WMCOVARIANCE if wide else MODE_MCOVARIANCE) if multi
+                else MODE_WCOVARIANCE if wide else MODES["covariance"])
     ctl.device = int(device)
     jobs = A * G
     a0 = np.zeros((jobs, nl, K) if multi else (jobs, nl))
@@ -249,7 +272,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
             dptr(lam), C.byref(res))
     L = _lib.load()
-    stem = ("sgdnet_cv_mnewton" if mnewton else "sgdnet_cv_newton" if newton else "sgdnet_cv_mcovariance" if multi
+    stem = ("sgdnet_cv_mnewton" if mnewton else "sgdnet_cv_newton" if newton else ("sgdnet_cv_wmcovariance" if wide else "sgdnet_cv_mcovariance") if multi
             else "sgdnet_cv_wcovariance" if wide else "sgdnet_cv_covariance")
     if sp.issparse(x):
         xs = sp.csc_matrix(x, dtype=np.float64)
@@ -400,6 +423,30 @@ def cv_sgdnet_mcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, t
                train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
 
 
+def cv_sgdnet_wmcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                           train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                           standardize=True, intercept=True, thresh=0.001, standardize_response=False):
+    """cv_sgdnet(family="mgaussian") with every fit a sgdnet_wmcovariance(): cv_sgdnet_mcovariance() beyond its feature
+    limit, up to wmcovariance_max_features(K) features.  fold_fits="separate" (the default) runs one sgdnet_wmcovariance per
+    fold; "batched" runs all fold fits of all alphas through ONE native call (cv_wmcovariance_fits) with the full fits'
+    lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh, standardize_response=standardize_response)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_wmcovariance(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio,
+                                   device=dev, **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_wmcovariance_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="mgaussian", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
 def cv_sgdnet_mnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
                       train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
                       standardize=True, intercept=True, thresh=0.001):
@@ -424,7 +471,7 @@ def cv_sgdnet_mnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_
 
 
 def _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, *, family, devices, rng, seed, train_on, densify, fit_one, batched_fits):
-    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance(), cv_sgdnet_mnewton() and cv_sgdnet_wcovariance(): the full fits, the fold ids, the fold fits, the scores
+    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance(), cv_sgdnet_mnewton(), cv_sgdnet_wcovariance() and cv_sgdnet_wmcovariance(): the full fits, the fold ids, the fold fits, the scores
     and the summary.  fit_one(x, y, lambda, alpha, device, seed, rng, sequential) is a fit; batched_fits(x, y, foldid, alpha,
     lambdas, device), where given, returns every fold fit from one call (alpha-major), else the folds are fitted one by one."""
     import scipy.sparse as sp
