@@ -771,6 +771,87 @@ typedef struct sgdnet_mnewton_probe_io {
 
 int sgdnet_mnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_mnewton_probe_io* io);
 
+/* The wide Newton modes (SGDNET_MODE_WNEWTON, SGDNET_MODE_WMNEWTON), one outer step pass by pass (additions only; the ABI
+ * version stays).  Dense x only: a wide fit expands sparse x before anything is computed from it.  The probes go through
+ * the host steps a wide fit goes through (setup and upload, publish at t = 1, state pass, moments pass on the wide
+ * modes' row chunks, scale kernel, list solve, blend at t): the same kernels on the same grids in the same order, every
+ * output copied back; H, Hd and q are copied between the scale kernel and the solve.  Tests compare each with an exact
+ * reference (tests/test_gpu_wnewton_passes.py, tests/test_gpu_wmnewton_passes.py).  The fields the narrow probes have
+ * mean what they mean there; count = p + 1 (wnewton) or Q = K (p + 1) (wmnewton) coordinates.
+ * SGDNET_EINVAL: a missing input, n or p < 1, K < 2, max_sweeps = 0, a width other than 0 / 256 / 1024.
+ * SGDNET_EUNSUPPORTED ("mode = wnewton needs ..." / "mode = wmnewton needs ..."): more than sgdnet_wnewton_max_features()
+ * / sgdnet_wmnewton_max_features(K) features.  Both are decided before any HIP call. */
+typedef struct sgdnet_wnewton_probe_io {
+  /* inputs (sgdnet_newton_probe) */
+  const double* y;
+  const double* scale;
+  const double* u_cur;
+  const double* u;
+  double   t;
+  double   l2, l1, tol;
+  int      centre, ridge, fit_intercept;
+  unsigned max_sweeps;
+  int      width;          /* lanes of the list solve's workgroup: 256 or 1024; 0: the rule a fit follows */
+  /* outputs (sgdnet_newton_probe) */
+  double*  mean;
+  double*  pub_u;
+  double*  pub_a;
+  double   pub_rec[4];
+  double*  blend_u;
+  double*  blend_a;
+  double   blend_rec[4];
+  double*  v;
+  double*  r;
+  double   loss, V, R;
+  double*  M;
+  double*  cd_u;
+  double*  cd_a;
+  double   cd_rec[8];
+  /* outputs of the scale kernel */
+  int      ld;             /* the leading dimension of H: count rounded up to a multiple of 16                 */
+  double*  H;              /* ld x count, column-major as the kernel wrote it: H[k + ld j], the rows count .. ld - 1
+                              (the zero pad) included                                                          */
+  double*  Hd;             /* count: diag H                                                                    */
+  double*  q;              /* count: the right-hand side                                                       */
+} sgdnet_wnewton_probe_io;
+
+int sgdnet_wnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_wnewton_probe_io* io);
+
+typedef struct sgdnet_wmnewton_probe_io {
+  /* inputs (sgdnet_mnewton_probe_io) */
+  const double* y;
+  int      K;
+  const double* scale;
+  const double* u_cur;
+  const double* u;
+  double   t;
+  double   l2, l1, tol;
+  int      centre, ridge, fit_intercept;
+  unsigned max_sweeps;
+  int      width;          /* lanes of the list solve's workgroup: 256 or 1024; 0: the rule a fit follows */
+  /* outputs (sgdnet_mnewton_probe_io) */
+  double*  mean;
+  double*  pub_u;
+  double*  pub_a;
+  double   pub_rec[4];
+  double*  blend_u;
+  double*  blend_a;
+  double   blend_rec[4];
+  double*  mu;
+  double   loss;
+  double*  M;
+  double*  cd_u;
+  double*  cd_a;
+  double   cd_rec[8];
+  /* outputs of the scale kernel (sgdnet_wnewton_probe_io) */
+  int      ld;
+  double*  H;
+  double*  Hd;
+  double*  q;
+} sgdnet_wmnewton_probe_io;
+
+int sgdnet_wmnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_wmnewton_probe_io* io);
+
 /* ------------------------------------------------------------------------ */
 /* Cross-validation in covariance mode (additions only; the ABI version      */
 /* stays): every fold fit of every elastic-net mix in ONE call.  Rows carry a */

@@ -42,6 +42,7 @@ EXPORTS = [
     "sgdnet_wnewton_max_features", "sgdnet_wmcovariance_max_features", "sgdnet_wmnewton_max_features",
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
     "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse", "sgdnet_cv_wmcovariance_dense", "sgdnet_cv_wmcovariance_sparse",
+    "sgdnet_wnewton_probe", "sgdnet_wmnewton_probe",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -140,6 +141,25 @@ class MNewtonProbe(C.Structure):
                 ("blend_u", _D), ("blend_a", _D), ("blend_rec", C.c_double * 4),
                 ("mu", _D), ("loss", C.c_double),
                 ("M", _D), ("cd_u", _D), ("cd_a", _D), ("cd_rec", C.c_double * 8)]
+
+
+class WNewtonProbe(C.Structure):
+    """sgdnet_wnewton_probe_io (diagnostics): NewtonProbe's fields with the list solve's width and what the scale kernel wrote."""
+    _D = C.POINTER(C.c_double)
+    _fields_ = [("y", _D), ("scale", _D), ("u_cur", _D), ("u", _D),
+                ("t", C.c_double), ("l2", C.c_double), ("l1", C.c_double), ("tol", C.c_double),
+                ("centre", C.c_int), ("ridge", C.c_int), ("fit_intercept", C.c_int), ("max_sweeps", C.c_uint), ("width", C.c_int),
+                ("mean", _D), ("pub_u", _D), ("pub_a", _D), ("pub_rec", C.c_double * 4),
+                ("blend_u", _D), ("blend_a", _D), ("blend_rec", C.c_double * 4),
+                ("v", _D), ("r", _D), ("loss", C.c_double), ("V", C.c_double), ("R", C.c_double),
+                ("M", _D), ("cd_u", _D), ("cd_a", _D), ("cd_rec", C.c_double * 8),
+                ("ld", C.c_int), ("H", _D), ("Hd", _D), ("q", _D)]
+
+
+class WMNewtonProbe(C.Structure):
+    """sgdnet_wmnewton_probe_io (diagnostics): MNewtonProbe's fields (width: 256 or 1024) and what the scale kernel wrote."""
+    _D = C.POINTER(C.c_double)
+    _fields_ = MNewtonProbe._fields_ + [("ld", C.c_int), ("H", _D), ("Hd", _D), ("q", _D)]
 
 
 class CvCovResult(C.Structure):
@@ -303,6 +323,8 @@ def load():
     L.sgdnet_wcovariance_max_features.argtypes = []
     L.sgdnet_wnewton_max_features.argtypes = []
     L.sgdnet_mnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(MNewtonProbe)]
+    L.sgdnet_wnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(WNewtonProbe)]
+    L.sgdnet_wmnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(WMNewtonProbe)]
     _lib = L
     return L
 

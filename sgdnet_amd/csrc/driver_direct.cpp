@@ -1354,4 +1354,68 @@ int sgdnet_mnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdn
   return mnewton_probe_checked(pb, device, io, "sgdnet_mnewton_probe");
 }
 
+// ---- diagnostics: one outer step of the wide Newton modes (newton.hip: wnewton_probe, mnewton.hip: wmnewton_probe) ----
+// Every refusal is decided before any HIP call; the limits by the names the plan refuses them by (fit_plan.hpp).
+
+int sgdnet_wnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_wnewton_probe_io* io) {
+  if (!x || n <= 0 || p <= 0) {
+    set_error("sgdnet_wnewton_probe: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  if (!io || !io->y || !io->scale || !io->u_cur || !io->u || io->max_sweeps == 0 ||
+      (io->width != 0 && io->width != kWideNarrow && io->width != kWideFull)) {
+    set_error("sgdnet_wnewton_probe: invalid argument");
+    return SGDNET_EINVAL;
+  }
+  if (p > kWnewtonMaxFeatures) {
+    set_error("mode = wnewton needs no more features than sgdnet_wnewton_max_features(): %lld features (limit %d)", (long long)p,
+              kWnewtonMaxFeatures);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const int rc = check_device(device);
+  if (rc) return rc;
+  NewtonProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  pb.y = io->y;
+  pb.centre = io->centre != 0;
+  pb.scale = io->scale;
+  pb.device = device;
+  pb.n_lambda = 1;
+  return wnewton_probe(pb, io);
+}
+
+int sgdnet_wmnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_wmnewton_probe_io* io) {
+  if (!x || n <= 0 || p <= 0) {
+    set_error("sgdnet_wmnewton_probe: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  if (!io || !io->y || !io->scale || !io->u_cur || !io->u || io->K < 2 || io->max_sweeps == 0 ||
+      (io->width != 0 && io->width != kWideNarrow && io->width != kWideFull)) {
+    set_error("sgdnet_wmnewton_probe: invalid argument");
+    return SGDNET_EINVAL;
+  }
+  const int limit = wmnewton_max_features(io->K);
+  if (p > limit) {
+    set_error("mode = wmnewton needs no more features than sgdnet_wmnewton_max_features(n_classes): n_classes %d, %lld features (limit %d)",
+              io->K, (long long)p, limit);
+    return SGDNET_EUNSUPPORTED;
+  }
+  const int rc = check_device(device);
+  if (rc) return rc;
+  MNewtonProblem pb;
+  pb.n = n;
+  pb.p = p;
+  pb.x_dense = x;
+  pb.K = io->K;
+  pb.y = io->y;
+  pb.centre = io->centre != 0;
+  pb.scale = io->scale;
+  pb.fit_intercept = io->fit_intercept != 0;
+  pb.device = device;
+  pb.n_lambda = 1;
+  return wmnewton_probe(pb, io);
+}
+
 }  // extern "C"

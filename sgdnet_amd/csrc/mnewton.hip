@@ -825,17 +825,28 @@ struct MNewtonDevice {
     return SGDNET_OK;
   }
 
+  // wide: H, diag H and q from d_M (timed: up to the event 4)
+  int wide_scale() {
+    hipLaunchKernelGGL(mnewton_wide_scale_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, d_M, d_scale, p, K, ld, (double)n, d_H, d_Hd, d_q);
+    SGD_HIP_TRY(hipGetLastError());
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
+    return SGDNET_OK;
+  }
+
+  // wide: the list solve on d_H, d_Hd and d_q about d_cur
+  int wide_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
+    const auto kernel = width == kWideNarrow ? mnewton_wide_cd_kernel<kWideNarrow> : mnewton_wide_cd_kernel<kWideFull>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, K, ld, d_cur, al, be, ridge ? 1 : 0,
+                       fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+
   // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
   int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
-    if (wide) {                          // scale (timed: up to the event 4), then the solve on H about d_cur
-      hipLaunchKernelGGL(mnewton_wide_scale_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, d_M, d_scale, p, K, ld, (double)n, d_H, d_Hd, d_q);
-      SGD_HIP_TRY(hipGetLastError());
-      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
-      const auto kernel = width == kWideNarrow ? mnewton_wide_cd_kernel<kWideNarrow> : mnewton_wide_cd_kernel<kWideFull>;
-      hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, K, ld, d_cur, al, be, ridge ? 1 : 0,
-                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
-      SGD_HIP_TRY(hipGetLastError());
-      return SGDNET_OK;
+    if (wide) {                          // scale, then the solve on H about d_cur
+      const int rc = wide_scale();
+      return rc ? rc : wide_solve(al, be, ridge, fit_intercept, max_sweeps, tol);
     }
     if (width == 256)
       hipLaunchKernelGGL(mnewton_cd_kernel<256>, dim3(1), dim3(256), 0, st, d_M, d_scale, p, K, (double)n, d_cur, al, be, ridge ? 1 : 0,
@@ -1148,9 +1159,14 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is
 // taken at the candidate io->u; the moments are those of that state; the inner solve runs on them about io->u_cur.
-int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io) {
+// wide (sgdnet_wmnewton_probe): the steps of a wide fit, and what the scale kernel wrote is copied between it and the solve.
+namespace {
+
+template <class IO>
+int mnewton_probe_steps(const MNewtonProblem& pb, IO* io, bool wide, int width, double* H_out, double* Hd_out, double* q_out) {
   MNewtonDevice D;
-  int rc = D.setup(pb, io->u_cur, io->u, false, io->width);
+  D.wide = wide;
+  int rc = D.setup(pb, io->u_cur, io->u, false, width);
   if (rc) return rc;
   hipStream_t st = D.st;
   const size_t Q = (size_t)D.Q;
@@ -1172,13 +1188,34 @@ int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io) {
   if ((rc = D.moments())) return rc;
   if (io->M)
     SGD_HIP_TRY(hipMemcpyAsync(io->M, D.d_M, sizeof(double) * (size_t)D.class_pairs * (size_t)D.nc * (size_t)D.nc, hipMemcpyDeviceToHost, st));
-  if ((rc = D.inner_solve(io->l2, io->ridge ? 0.0 : io->l1, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol)) ||
-      (rc = fetch(io->cd_u, io->cd_a, io->cd_rec, 0, kRecLen)))
-    return rc;
+  const double be = io->ridge ? 0.0 : io->l1;
+  if (wide) {
+    if ((rc = D.wide_scale())) return rc;
+    if (H_out) SGD_HIP_TRY(hipMemcpyAsync(H_out, D.d_H, sizeof(double) * (size_t)D.ld * Q, hipMemcpyDeviceToHost, st));
+    if (Hd_out) SGD_HIP_TRY(hipMemcpyAsync(Hd_out, D.d_Hd, sizeof(double) * Q, hipMemcpyDeviceToHost, st));
+    if (q_out) SGD_HIP_TRY(hipMemcpyAsync(q_out, D.d_q, sizeof(double) * Q, hipMemcpyDeviceToHost, st));
+    rc = D.wide_solve(io->l2, be, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol);
+  } else {
+    rc = D.inner_solve(io->l2, be, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol);
+  }
+  if (rc || (rc = fetch(io->cd_u, io->cd_a, io->cd_rec, 0, kRecLen))) return rc;
   // the candidate again, blended with the iterate at the caller's t
   SGD_HIP_TRY(hipMemcpyAsync(D.d_cand, io->u, sizeof(double) * Q, hipMemcpyHostToDevice, st));
   if ((rc = D.publish(io->t)) || (rc = fetch(io->blend_u, io->blend_a, io->blend_rec, kRecHalfSq, 4))) return rc;
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io) {
+  return mnewton_probe_steps(pb, io, false, io->width, nullptr, nullptr, nullptr);
+}
+
+int wmnewton_probe(const MNewtonProblem& pb, sgdnet_wmnewton_probe_io* io) {
+  const int64_t Q = (int64_t)pb.K * (pb.p + 1);
+  const int width = io->width != 0 ? io->width : wmnewton_cd_width((int)std::min<int64_t>(Q, kWmnewtonMaxCoordinates));
+  io->ld = (int)wide_leading_dim(Q);
+  return mnewton_probe_steps(pb, io, true, width, io->H, io->Hd, io->q);
 }
 
 }  // namespace sgdnet

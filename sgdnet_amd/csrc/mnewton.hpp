@@ -215,5 +215,7 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
 // Diagnostics (include/sgdnet_hip.h: sgdnet_mnewton_probe): one outer step through the host steps mnewton_run takes, every
 // output copied back.  pb: n, p, K, x_dense, y, centre, scale, device and n_lambda = 1; the rest is read from io.
 int mnewton_probe(const MNewtonProblem& pb, sgdnet_mnewton_probe_io* io);
+// sgdnet_wmnewton_probe: the same through the host steps wmnewton_run takes (io->width checked by the caller)
+int wmnewton_probe(const MNewtonProblem& pb, sgdnet_wmnewton_probe_io* io);
 
 }  // namespace sgdnet

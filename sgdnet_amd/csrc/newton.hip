@@ -972,17 +972,28 @@ struct NewtonDevice {
     return SGDNET_OK;
   }
 
+  // wide: H, diag H and q from d_M (timed: up to the event 4)
+  int wide_scale() {
+    hipLaunchKernelGGL(wide_scale_kernel, dim3((unsigned)P), dim3(kBlock), 0, st, d_M, d_scale, p, p + 2, ld, (double)n, d_H, d_Hd, d_q);
+    SGD_HIP_TRY(hipGetLastError());
+    if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
+    return SGDNET_OK;
+  }
+
+  // wide: the list solve on d_H, d_Hd and d_q about d_cur
+  int wide_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
+    const auto kernel = width == kWideNarrow ? newton_wide_cd_kernel<kWideNarrow> : newton_wide_cd_kernel<kWideFull>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, ld, d_cur, al, be, ridge ? 1 : 0,
+                       fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+    SGD_HIP_TRY(hipGetLastError());
+    return SGDNET_OK;
+  }
+
   // the inner solve on d_M about d_cur: the candidate into d_cand and d_a, its record into d_rec
   int inner_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
-    if (wide) {                          // scale (timed: up to the event 4), then the solve on H about d_cur
-      hipLaunchKernelGGL(wide_scale_kernel, dim3((unsigned)P), dim3(kBlock), 0, st, d_M, d_scale, p, p + 2, ld, (double)n, d_H, d_Hd, d_q);
-      SGD_HIP_TRY(hipGetLastError());
-      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
-      const auto kernel = width == kWideNarrow ? newton_wide_cd_kernel<kWideNarrow> : newton_wide_cd_kernel<kWideFull>;
-      hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, ld, d_cur, al, be, ridge ? 1 : 0,
-                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
-      SGD_HIP_TRY(hipGetLastError());
-      return SGDNET_OK;
+    if (wide) {                          // scale, then the solve on H about d_cur
+      const int rc = wide_scale();
+      return rc ? rc : wide_solve(al, be, ridge, fit_intercept, max_sweeps, tol);
     }
     hipLaunchKernelGGL(newton_cd_kernel, dim3(1), dim3(64), 0, st, d_M, d_scale, p, (double)n, d_cur, al, be, ridge ? 1 : 0,
                        fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
@@ -1096,13 +1107,19 @@ int wnewton_run(const NewtonProblem& pb, bool timed, NewtonResult* out, int widt
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is
 // taken at the candidate io->u; the moments are those of that state; the inner solve runs on them about io->u_cur.
-int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io) {
+// wide (sgdnet_wnewton_probe): the steps of a wide fit, and what the scale kernel wrote is copied between it and the solve.
+namespace {
+
+template <class IO>
+int newton_probe_steps(const NewtonProblem& pb, IO* io, bool wide, int width, double* H_out, double* Hd_out, double* q_out) {
   const int p = (int)pb.p, P = p + 1, nc = p + 2;
   const int64_t n = pb.n;
   const bool sparse = pb.x_dense == nullptr;
   const int32_t* no_rows = nullptr;
   const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
   NewtonDevice D;
+  D.wide = wide;
+  D.width = width;
   int rc = D.setup(pb, cols, io->u_cur, io->u, false);
   if (rc) return rc;
   hipStream_t st = D.st;
@@ -1126,15 +1143,33 @@ int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io) {
   if (io->r) SGD_HIP_TRY(hipMemcpyAsync(io->r, D.d_r, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
   if ((rc = D.moments())) return rc;
   if (io->M) SGD_HIP_TRY(hipMemcpyAsync(io->M, D.d_M, sizeof(double) * (size_t)nc * (size_t)nc, hipMemcpyDeviceToHost, st));
-  if ((rc = D.inner_solve(io->l2, io->ridge ? 0.0 : io->l1, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol)) ||
-      (rc = fetch(io->cd_u, io->cd_a, io->cd_rec, 0, kRecLen)))
-    return rc;
+  const double be = io->ridge ? 0.0 : io->l1;
+  if (wide) {
+    if ((rc = D.wide_scale())) return rc;
+    if (H_out) SGD_HIP_TRY(hipMemcpyAsync(H_out, D.d_H, sizeof(double) * (size_t)D.ld * (size_t)P, hipMemcpyDeviceToHost, st));
+    if (Hd_out) SGD_HIP_TRY(hipMemcpyAsync(Hd_out, D.d_Hd, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+    if (q_out) SGD_HIP_TRY(hipMemcpyAsync(q_out, D.d_q, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+    rc = D.wide_solve(io->l2, be, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol);
+  } else {
+    rc = D.inner_solve(io->l2, be, io->ridge != 0, io->fit_intercept != 0, io->max_sweeps, io->tol);
+  }
+  if (rc || (rc = fetch(io->cd_u, io->cd_a, io->cd_rec, 0, kRecLen))) return rc;
   io->V = sums[0];
   io->R = sums[1];
   // the candidate again, blended with the iterate at the caller's t
   SGD_HIP_TRY(hipMemcpyAsync(D.d_cand, io->u, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
   if ((rc = D.publish(io->t)) || (rc = fetch(io->blend_u, io->blend_a, io->blend_rec, kRecHalfSq, 4))) return rc;
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io) { return newton_probe_steps(pb, io, false, 0, nullptr, nullptr, nullptr); }
+
+int wnewton_probe(const NewtonProblem& pb, sgdnet_wnewton_probe_io* io) {
+  const int width = io->width != 0 ? io->width : wide_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures));
+  io->ld = (int)wide_leading_dim(pb.p + 1);
+  return newton_probe_steps(pb, io, true, width, io->H, io->Hd, io->q);
 }
 
 namespace {

@@ -158,5 +158,7 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out);
 // Diagnostics (include/sgdnet_hip.h: sgdnet_newton_probe_*): one outer step through the host steps newton_run takes, every
 // output copied back.  pb: x, y, centre, scale, device and n_lambda = 1; the rest comes from io.  The caller has checked both.
 int newton_probe(const NewtonProblem& pb, sgdnet_newton_probe* io);
+// sgdnet_wnewton_probe: the same through the host steps wnewton_run takes (dense x; io->width checked by the caller)
+int wnewton_probe(const NewtonProblem& pb, sgdnet_wnewton_probe_io* io);
 
 }  // namespace sgdnet

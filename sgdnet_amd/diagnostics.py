@@ -1,6 +1,7 @@
 """Diagnostics (include/sgdnet_hip.h "Diagnostics"): what a fit's once-per-fit device setup passes
 (sgdnet_amd/csrc/setup_device.hip) and the passes of one outer step of Newton mode (sgdnet_amd/csrc/newton.hip) and of
-multinomial Newton mode (sgdnet_amd/csrc/mnewton.hip) leave on the device, copied back pass by pass.  Used by the tests; a fit never calls these."""
+multinomial Newton mode (sgdnet_amd/csrc/mnewton.hip), narrow and wide, leave on the device, copied back pass by pass.
+Used by the tests; a fit never calls these."""
 import ctypes as C
 from types import SimpleNamespace
 
@@ -137,6 +138,71 @@ def mnewton_probe(x, y, K, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0, 
     for name in ("mean", "mu", "M", "pub_u", "pub_a", "blend_u", "blend_a", "cd_u", "cd_a"):
         setattr(pr, name, dptr(getattr(o, name)))
     check(_lib.load().sgdnet_mnewton_probe(dptr(x), n, p, int(device), C.byref(pr)))
+    o.loss = pr.loss
+    o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
+    o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
+    o.cd_rec = dict(zip(NEWTON_REC, pr.cd_rec))
+    return o
+
+
+def wnewton_probe(x, y, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0, ridge=False, fit_intercept=True,
+                  max_sweeps=1000, tol=1e-7, width=0, device=0):
+    """One outer step of wide Newton mode, pass by pass (sgdnet_wnewton_probe; dense x only).  The arguments and the fields
+    of newton_probe; width: lanes of the list solve, 256 or 1024 (0: the rule a fit follows).  Added: ld; H (p + 1, ld):
+    row j is column j of the matrix as wide_scale_kernel wrote it, H[j, k] = H_kj, the zero pad k >= p + 1 included; Hd
+    (p + 1,): its diagonal; q (p + 1,): the right-hand side.  They are copied between the scale kernel and the solve."""
+    x = np.asfortranarray(np.asarray(x, dtype=np.float64))
+    n, p = x.shape
+    P = p + 1
+    ld = (P + 15) // 16 * 16
+    ins = [np.ascontiguousarray(a, dtype=np.float64).reshape(k) for a, k in ((y, n), (scale, p), (u_cur, P), (u, P))]
+    o = SimpleNamespace(mean=np.empty(p), v=np.empty(n), r=np.empty(n), M=np.empty((p + 2, p + 2)),
+                        H=np.empty((P, ld)), Hd=np.empty(P), q=np.empty(P),
+                        **{f"{s}_{w}": np.empty(P) for s in ("pub", "blend", "cd") for w in ("u", "a")})
+    pr = _lib.WNewtonProbe()
+    pr.y, pr.scale, pr.u_cur, pr.u = (dptr(a) for a in ins)
+    pr.width = int(width)
+    pr.t, pr.l2, pr.l1, pr.tol = float(t), float(l2), float(l1), float(tol)
+    pr.centre, pr.ridge, pr.fit_intercept, pr.max_sweeps = int(bool(centre)), int(bool(ridge)), int(bool(fit_intercept)), int(max_sweeps)
+    for name in ("mean", "v", "r", "M", "H", "Hd", "q", "pub_u", "pub_a", "blend_u", "blend_a", "cd_u", "cd_a"):
+        setattr(pr, name, dptr(getattr(o, name)))
+    check(_lib.load().sgdnet_wnewton_probe(dptr(x), n, p, int(device), C.byref(pr)))
+    if pr.ld != ld:
+        raise RuntimeError(f"sgdnet_wnewton_probe: leading dimension {pr.ld}, the binding allocated {ld}")
+    o.ld = pr.ld
+    o.loss, o.V, o.R = pr.loss, pr.V, pr.R
+    o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
+    o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
+    o.cd_rec = dict(zip(NEWTON_REC, pr.cd_rec))
+    return o
+
+
+def wmnewton_probe(x, y, K, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0, ridge=False, fit_intercept=True,
+                   max_sweeps=1000, tol=1e-7, width=0, device=0):
+    """One outer step of wide multinomial Newton mode, pass by pass (sgdnet_wmnewton_probe; dense x only).  The arguments and
+    the fields of mnewton_probe; width: lanes of the list solve, 256 or 1024 (0: the rule a fit follows).  Added: ld; H
+    (Q, ld): row c is column c of the joint matrix as mnewton_wide_scale_kernel wrote it, the zero pad included; Hd (Q,):
+    its diagonal; q (Q,): the right-hand side.  They are copied between the scale kernel and the solve."""
+    x = np.asfortranarray(np.asarray(x, dtype=np.float64))
+    n, p = x.shape
+    K = int(K)
+    Q, pairs = max(K, 0) * (p + 1), max(K, 0) * (max(K, 0) + 1) // 2
+    ld = (Q + 15) // 16 * 16
+    ins = [np.ascontiguousarray(a, dtype=np.float64).reshape(k) for a, k in ((y, n), (scale, p), (u_cur, Q), (u, Q))]
+    o = SimpleNamespace(mean=np.empty(p), mu=np.empty((n, max(K, 0)), order="F"), M=np.empty((pairs, p + 2, p + 2)),
+                        H=np.empty((Q, ld)), Hd=np.empty(Q), q=np.empty(Q),
+                        **{f"{s}_{w}": np.empty(Q) for s in ("pub", "blend", "cd") for w in ("u", "a")})
+    pr = _lib.WMNewtonProbe()
+    pr.y, pr.scale, pr.u_cur, pr.u = (dptr(a) for a in ins)
+    pr.K, pr.width = K, int(width)
+    pr.t, pr.l2, pr.l1, pr.tol = float(t), float(l2), float(l1), float(tol)
+    pr.centre, pr.ridge, pr.fit_intercept, pr.max_sweeps = int(bool(centre)), int(bool(ridge)), int(bool(fit_intercept)), int(max_sweeps)
+    for name in ("mean", "mu", "M", "H", "Hd", "q", "pub_u", "pub_a", "blend_u", "blend_a", "cd_u", "cd_a"):
+        setattr(pr, name, dptr(getattr(o, name)))
+    check(_lib.load().sgdnet_wmnewton_probe(dptr(x), n, p, int(device), C.byref(pr)))
+    if pr.ld != ld:
+        raise RuntimeError(f"sgdnet_wmnewton_probe: leading dimension {pr.ld}, the binding allocated {ld}")
+    o.ld = pr.ld
     o.loss = pr.loss
     o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
     o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
