@@ -852,6 +852,46 @@ typedef struct sgdnet_wmnewton_probe_io {
 
 int sgdnet_wmnewton_probe(const double* x, int64_t n, int64_t p, int device, sgdnet_wmnewton_probe_io* io);
 
+/* The covariance family (sgdnet_amd/csrc/covariance.hip), stage by stage.  The probes go through the host functions a fit
+ * goes through (one fit: covariance_run, wcovariance_run, mcovariance_run, wmcovariance_run; a cross-validation: the stage
+ * behind sgdnet_cv_*covariance_* and its covariance_cv_run, wcovariance_cv_run, mcovariance_cv_run, wmcovariance_cv_run)
+ * with a tap: the same kernels on the same grids with the same arguments, and behind the stages, before the path kernel
+ * is launched, device-to-host copies of what they left.  tests/test_gpu_covariance_passes.py and
+ * tests/test_gpu_cv_covariance_passes.py compare each with an exact reference.  The result is a set of named arrays of
+ * doubles (int32 fields are converted), owned by the library until sgdnet_cov_probe_free.
+ *
+ * exactly one of x_dense (n x p column-major) and x_sparse is given.  wide = 0: the narrow form (SGDNET_MODE_COVARIANCE /
+ * _MCOVARIANCE), 1: the wide form (_WCOVARIANCE / _WMCOVARIANCE).
+ *
+ * sgdnet_covariance_probe: y n x K column-major as the driver would hand it over (preprocessed), scale p, one mix and
+ * n_lambda lambdas (the penalties (1 - mix) lambda and mix lambda; mix = 0 is the ridge functor).  multi = 0 is the
+ * one-response form (K must be 1), 1 the K-response form.  SGDNET_EUNSUPPORTED, in the plan's words ("mode = covariance
+ * needs no more features than sgdnet_covariance_max_features(): ..."): more features than the mode's limit.
+ * SGDNET_EINVAL: a missing input, a mix outside [0, 1].  Fields, P = p + K:
+ *   mu   one response: p + 2 -- the centres (0 where not centred), the response's sum, its mean.  K responses: P -- the
+ *        centres and the K sums
+ *   M    P x P, symmetric bit for bit.  Sparse x: the response-by-response block (rows and columns >= p) is NOT DEFINED
+ *        (nothing writes it, nothing reads it)
+ *   wide: ld (1); S p x ld, row j = column j of the scaled matrix, the zero pad k >= p included; Sd p; ct p x K
+ *   narrow: c p x K, the path kernel's c~
+ * sgdnet_cv_covariance_probe: the arguments of sgdnet_cv_*covariance_* (family gaussian: one response; mgaussian:
+ * n_classes responses, y n x K column-major), refused in the same words with the same codes.  Fields, Pa = p + K + 1:
+ *   mu   one response: p + 2 (as above).  mgaussian: p + 2 K -- the centres, the K sums, the K means
+ *   Mg   G x Pa x Pa;  total  Pa x Pa (train_on_rest only)
+ *   scale G x p;  mean G x (p + K);  tstat 3 x G;  pen_a, pen_b jobs x n_lambda (alpha | beta, or l2 | l1);  ridge jobs
+ *   narrow: Mt  G x (p + 1) x (p + 1) (one response) or G x p x (p + K)
+ *   wide:   ld (1);  s, d G x (p + K);  ysd G x K (mgaussian);  S G x p x ld;  Sd G x p;  ct G x p x K */
+typedef struct sgdnet_cov_probe sgdnet_cov_probe;
+int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
+                            const double* scale, int centre, int wide, int multi, double mix, int n_lambda,
+                            const double* lambda, int device, sgdnet_cov_probe** out);
+int sgdnet_cv_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y,
+                               const int32_t* fold, int n_groups, int train_on_rest, const sgdnet_control* ctl, int wide,
+                               int n_alpha, const double* alphas, const double* lambdas, sgdnet_cov_probe** out);
+/* the number of doubles of field `name` and, through data, where they are; -1: no such field */
+int64_t sgdnet_cov_probe_field(const sgdnet_cov_probe* probe, const char* name, const double** data);
+void sgdnet_cov_probe_free(sgdnet_cov_probe* probe);
+
 /* ------------------------------------------------------------------------ */
 /* Cross-validation in covariance mode (additions only; the ABI version      */
 /* stays): every fold fit of every elastic-net mix in ONE call.  Rows carry a */

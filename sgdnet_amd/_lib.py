@@ -43,6 +43,7 @@ EXPORTS = [
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
     "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse", "sgdnet_cv_wmcovariance_dense", "sgdnet_cv_wmcovariance_sparse",
     "sgdnet_wnewton_probe", "sgdnet_wmnewton_probe",
+    "sgdnet_covariance_probe", "sgdnet_cv_covariance_probe", "sgdnet_cov_probe_field", "sgdnet_cov_probe_free",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -325,6 +326,15 @@ def load():
     L.sgdnet_mnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(MNewtonProbe)]
     L.sgdnet_wnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(WNewtonProbe)]
     L.sgdnet_wmnewton_probe.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(WMNewtonProbe)]
+    _D, _I = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    L.sgdnet_covariance_probe.argtypes = [_D, C.POINTER(Csc), C.c_int64, C.c_int64, _D, C.c_int, _D, C.c_int, C.c_int, C.c_int,
+                                          C.c_double, C.c_int, _D, C.c_int, C.POINTER(C.c_void_p)]
+    L.sgdnet_cv_covariance_probe.argtypes = [_D, C.POINTER(Csc), C.c_int64, C.c_int64, _D, _I, C.c_int, C.c_int, C.POINTER(Control),
+                                             C.c_int, C.c_int, _D, _D, C.POINTER(C.c_void_p)]
+    L.sgdnet_cov_probe_field.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(_D)]
+    L.sgdnet_cov_probe_field.restype = C.c_int64
+    L.sgdnet_cov_probe_free.argtypes = [C.c_void_p]
+    L.sgdnet_cov_probe_free.restype = None
     _lib = L
     return L
 

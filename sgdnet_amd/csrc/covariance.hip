@@ -301,6 +301,20 @@ __global__ __launch_bounds__(kBlock) void cov_total_kernel(const double* __restr
   total[e] = s;
 }
 
+// Is a column (a feature or a response) constant on training set T?  (DESIGN.md 4.5 has the derivation.)  Its re-centred
+// square q = C_jj - 2 d_j s_j + n_T d_j^2 is formed about the WHOLE-data centre: for a column that is constant on T and not on
+// the data, C_jj, d_j s_j and n_T d_j^2 are each n_T (c - a)^2 and q is their rounding noise, of either sign.  "q > 0" cannot
+// tell that from a variance; the bound of that noise can.  With every deviation on T the same double, C_jj and s_j are sums of
+// n_T equal terms (rest: less a group, out of a total of G terms), each within gamma_(n_T + G) of its magnitude a_c, a_s
+// (rest: |total| + |group|), and the expression adds three products and three sums of them:
+//   |q| <= (n_T + G + 8) 2^-52 (a_c + 2 |d| a_s + n_T d^2)        (2^-52 = 2 u: the factor 2 pays for the second-order terms)
+// A column at or below that is constant: scale 1, and exact zeros in what the path kernel reads, as the separate fit on x[T]
+// has them.  n_summed: G with rest, 0 without.
+__device__ __forceinline__ bool cov_constant_on_set(double q, double a_c, double a_s, double d, double nT, int n_summed) {
+  const double tol = (nT + (double)n_summed + 8.0) * 0x1p-52 * (a_c + 2.0 * fabs(d) * a_s + nT * d * d);
+  return !(q > tol);
+}
+
 // blockIdx.x = training set T: group T alone, or (rest) the total less group T.  From the (p + 2) x (p + 2) moments about the
 // common centre a to what cov_path_kernel reads for x[T], y[T] as fit_covariance (driver_direct.cpp) / prepare_response (driver.cpp) would
 // prepare them: the cross-products about T's own means t = a + d, the y column divided by sd_T(y), the features' sd over T,
@@ -315,11 +329,16 @@ __global__ __launch_bounds__(kBlock) void cov_assemble_kernel(const double* __re
                                                                double* __restrict__ tstat, double* __restrict__ alpha,
                                                                double* __restrict__ beta, int32_t* __restrict__ ridge) {
   __shared__ double s[kCovMaxFeatures + 1], d[kCovMaxFeatures + 1];
+  __shared__ int cst[kCovMaxFeatures + 1];      // the column is constant on T (cov_constant_on_set)
   const int t = blockIdx.x, tid = threadIdx.x, P1 = p + 1, Pa = p + 2;
   const double* Ct = Mg + (size_t)t * Pa * Pa;
   auto C = [&](int j, int k) -> double {
     const double v = Ct[(size_t)j * Pa + k];
     return rest ? total[(size_t)j * Pa + k] - v : v;
+  };
+  auto magnitude = [&](int j, int k) -> double {
+    const double v = fabs(Ct[(size_t)j * Pa + k]);
+    return rest ? fabs(total[(size_t)j * Pa + k]) + v : v;
   };
   const double nT = C(p + 1, p + 1);
   for (int j = tid; j < P1; j += kBlock) {
@@ -328,25 +347,28 @@ __global__ __launch_bounds__(kBlock) void cov_assemble_kernel(const double* __re
   }
   __syncthreads();
   auto recentred = [&](int j, int k) -> double { return C(j, k) - d[j] * s[k] - d[k] * s[j] + nT * d[j] * d[k]; };
+  for (int j = tid; j < P1; j += kBlock)
+    cst[j] = cov_constant_on_set(recentred(j, j), magnitude(j, j), magnitude(j, p + 1), d[j], nT, rest ? n_groups : 0) ? 1 : 0;
+  __syncthreads();
   const double var_y = recentred(p, p) / nT;
-  const double sd_y = var_y > 0.0 ? sqrt(var_y) : 1.0;
+  const double sd_y = cst[p] ? 1.0 : sqrt(var_y);
   for (int e = tid; e < P1 * P1; e += kBlock) {
     const int j = e / P1, k = e - j * P1;
     double m = recentred(j, k);
     if (j == p) m /= sd_y;
     if (k == p) m /= sd_y;
-    Mt[(size_t)t * P1 * P1 + e] = m;
+    Mt[(size_t)t * P1 * P1 + e] = (cst[j] || cst[k]) ? 0.0 : m;
   }
   for (int j = tid; j < p; j += kBlock) {
     const double v = recentred(j, j) / nT;
-    scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+    scale[(size_t)t * p + j] = (standardize && !cst[j]) ? sqrt(v) : 1.0;
     mean[(size_t)t * P1 + j] = centre ? mu[j] + d[j] : 0.0;
   }
   if (tid == 0) {
     mean[(size_t)t * P1 + p] = mu[p + 1] + d[p];
     tstat[t] = nT;
     tstat[n_groups + t] = sd_y;
-    tstat[2 * n_groups + t] = recentred(p, p) / sd_y / sd_y;
+    tstat[2 * n_groups + t] = cst[p] ? 0.0 : recentred(p, p) / sd_y / sd_y;
   }
   for (int e = tid; e < n_mix * n_lambda; e += kBlock) {
     const int a = e / n_lambda, l = e - a * n_lambda;
@@ -366,7 +388,8 @@ __global__ __launch_bounds__(kBlock) void cov_assemble_kernel(const double* __re
 //          SEES THEM (the null model's intercepts: mean_T(y_r), or 0 on the standardised scale)
 //   tstat  3 x G: n_T | y~'y~ = sum_r y~_r'y~_r | the null deviance of y[T] as it came = sum_r |y_r - mean_T(y_r)|^2, both in
 //          the order r = 0 .. K - 1           l2, l1  jobs x n_lambda, job = mix * G + T      ridge  jobs
-// The staging arrays (the sums s and the shifts d of the p + K columns) are 2 (p + K) doubles of dynamic LDS.
+// The staging arrays (the sums s and the shifts d of the p + K columns, then their constant-on-T flags) are 2 (p + K) doubles
+// and p + K ints of dynamic LDS.
 __global__ __launch_bounds__(kBlock) void mcov_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
                                                                 const double* __restrict__ mu, int n_groups, int p, int K, int rest,
                                                                 int centre, int standardize, int standardize_response,
@@ -379,10 +402,15 @@ __global__ __launch_bounds__(kBlock) void mcov_assemble_kernel(const double* __r
   const int t = blockIdx.x, tid = threadIdx.x, nc = p + K, Pa = nc + 1;
   double* s = staged;
   double* d = staged + nc;
+  int* cst = reinterpret_cast<int*>(staged + 2 * nc);      // the column is constant on T (cov_constant_on_set)
   const double* Ct = Mg + (size_t)t * Pa * Pa;
   auto C = [&](int j, int k) -> double {
     const double v = Ct[(size_t)j * Pa + k];
     return rest ? total[(size_t)j * Pa + k] - v : v;
+  };
+  auto magnitude = [&](int j, int k) -> double {
+    const double v = fabs(Ct[(size_t)j * Pa + k]);
+    return rest ? fabs(total[(size_t)j * Pa + k]) + v : v;
   };
   const double nT = C(nc, nc);
   for (int j = tid; j < nc; j += kBlock) {
@@ -391,28 +419,30 @@ __global__ __launch_bounds__(kBlock) void mcov_assemble_kernel(const double* __r
   }
   __syncthreads();
   auto recentred = [&](int j, int k) -> double { return C(j, k) - d[j] * s[k] - d[k] * s[j] + nT * d[j] * d[k]; };
-  // the sd response r is divided by (1 without standardize_response; a constant response: 0 -> 1)
+  for (int j = tid; j < nc; j += kBlock)
+    cst[j] = cov_constant_on_set(recentred(j, j), magnitude(j, j), magnitude(j, nc), d[j], nT, rest ? n_groups : 0) ? 1 : 0;
+  __syncthreads();
+  // the sd response r is divided by (1 without standardize_response; a response constant on T: 1)
   auto sd_y = [&](int r) -> double {
-    if (!standardize_response) return 1.0;
-    const double v = recentred(p + r, p + r) / nT;
-    return v > 0.0 ? sqrt(v) : 1.0;
+    if (!standardize_response || cst[p + r]) return 1.0;
+    return sqrt(recentred(p + r, p + r) / nT);
   };
   for (int e = tid; e < p * nc; e += kBlock) {
     const int j = e / nc, k = e - j * nc;
     double m = recentred(j, k);
     if (k >= p) m /= sd_y(k - p);
-    Mt[(size_t)t * p * nc + e] = m;
+    Mt[(size_t)t * p * nc + e] = (cst[j] || cst[k]) ? 0.0 : m;
   }
   for (int j = tid; j < p; j += kBlock) {
     const double v = recentred(j, j) / nT;
-    scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+    scale[(size_t)t * p + j] = (standardize && !cst[j]) ? sqrt(v) : 1.0;
     mean[(size_t)t * nc + j] = centre ? mu[j] + d[j] : 0.0;
   }
   for (int r = tid; r < K; r += kBlock) mean[(size_t)t * nc + p + r] = standardize_response ? 0.0 : mu[nc + r] + d[p + r];
   if (tid == 0) {
     double yy = 0.0, nulldev = 0.0;
     for (int r = 0; r < K; ++r) {
-      const double q = recentred(p + r, p + r), sd = sd_y(r);
+      const double q = cst[p + r] ? 0.0 : recentred(p + r, p + r), sd = sd_y(r);
       nulldev += q;
       yy += q / sd / sd;
     }
@@ -914,6 +944,11 @@ struct WcovSet {
     const double v = Ct[(size_t)j * Pa + k];
     return rest ? total[(size_t)j * Pa + k] - v : v;
   }
+  // the magnitude its rounding is relative to (cov_constant_on_set)
+  __device__ __forceinline__ double magnitude(int j, int k) const {
+    const double v = fabs(Ct[(size_t)j * Pa + k]);
+    return rest ? fabs(total[(size_t)j * Pa + k]) + v : v;
+  }
 };
 
 // cov_assemble_kernel's re-centring of entry (j, k), j <= k, from the entry c about the common centre, T's sums of deviations
@@ -926,6 +961,7 @@ __device__ __forceinline__ double wcov_recentred(double c, double sj, double dj,
 // blockIdx.x = training set T.  From the group moments to what is per T or per job and of size p or smaller, as
 // cov_assemble_kernel leaves it (the same expressions):
 //   s, d   G x (p + 1): T's sums of deviations about the common centre and its shifts d = t - a (0 where not centred)
+//   cst    G x (p + 1): the column is constant on T (cov_constant_on_set): scale 1, zeros in S_T and c~_T
 //   scale  G x p      mean  G x (p + 1): t (0 where the features are not centred), mean_T(y)
 //   tstat  3 x G: n_T | sd_T(y) (0 -> 1) | y~'y~         alpha, beta  jobs x n_lambda, job = mix * G + T      ridge  jobs
 // Every lane computes sd_T(y) itself from the same four words: nothing is staged and no barrier is needed.
@@ -933,24 +969,27 @@ __global__ __launch_bounds__(kBlock) void wcov_cv_stats_kernel(const double* __r
                                                                 const double* __restrict__ mu, int n_groups, int p, int rest, int centre,
                                                                 int standardize, const double* __restrict__ mix,
                                                                 const double* __restrict__ lambda, int n_mix, int n_lambda,
-                                                                double* __restrict__ s, double* __restrict__ d, double* __restrict__ scale,
-                                                                double* __restrict__ mean, double* __restrict__ tstat,
-                                                                double* __restrict__ alpha, double* __restrict__ beta,
-                                                                int32_t* __restrict__ ridge) {
+                                                                double* __restrict__ s, double* __restrict__ d, int32_t* __restrict__ cst,
+                                                                double* __restrict__ scale, double* __restrict__ mean,
+                                                                double* __restrict__ tstat, double* __restrict__ alpha,
+                                                                double* __restrict__ beta, int32_t* __restrict__ ridge) {
   const int t = blockIdx.x, tid = threadIdx.x, P1 = p + 1, Pa = p + 2;
   const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
+  const int n_summed = rest ? n_groups : 0;
   const double nT = C(p + 1, p + 1);
   const double sy = C(p, p + 1), dy = sy / nT;
   const double qy = wcov_recentred(C(p, p), sy, dy, sy, dy, nT);
-  const double var_y = qy / nT;
-  const double sd_y = var_y > 0.0 ? sqrt(var_y) : 1.0;
+  const bool cst_y = cov_constant_on_set(qy, C.magnitude(p, p), C.magnitude(p, p + 1), dy, nT, n_summed);
+  const double sd_y = cst_y ? 1.0 : sqrt(qy / nT);
   for (int j = tid; j < P1; j += kBlock) {
     const double sj = C(j, p + 1), dj = (j == p || centre) ? sj / nT : 0.0;
     s[(size_t)t * P1 + j] = sj;
     d[(size_t)t * P1 + j] = dj;
+    const double q = wcov_recentred(C(j, j), sj, dj, sj, dj, nT);
+    const bool cj = cov_constant_on_set(q, C.magnitude(j, j), C.magnitude(j, p + 1), dj, nT, n_summed);
+    cst[(size_t)t * P1 + j] = cj ? 1 : 0;
     if (j < p) {
-      const double v = wcov_recentred(C(j, j), sj, dj, sj, dj, nT) / nT;
-      scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+      scale[(size_t)t * p + j] = (standardize && !cj) ? sqrt(q / nT) : 1.0;
       mean[(size_t)t * P1 + j] = centre ? mu[j] + dj : 0.0;
     }
   }
@@ -958,7 +997,7 @@ __global__ __launch_bounds__(kBlock) void wcov_cv_stats_kernel(const double* __r
     mean[(size_t)t * P1 + p] = mu[p + 1] + dy;
     tstat[t] = nT;
     tstat[n_groups + t] = sd_y;
-    tstat[2 * n_groups + t] = qy / sd_y / sd_y;
+    tstat[2 * n_groups + t] = cst_y ? 0.0 : qy / sd_y / sd_y;
   }
   for (int e = tid; e < n_mix * n_lambda; e += kBlock) {
     const int a = e / n_lambda, l = e - a * n_lambda;
@@ -975,27 +1014,29 @@ __global__ __launch_bounds__(kBlock) void wcov_cv_stats_kernel(const double* __r
 // moments are read along row j (coalesced; row j is column j bit for bit); s, d and scale come from wcov_cv_stats_kernel.
 __global__ __launch_bounds__(kBlock) void wcov_cv_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
                                                                    const double* __restrict__ s, const double* __restrict__ d,
-                                                                   const double* __restrict__ scale, const double* __restrict__ tstat,
-                                                                   int n_groups, int p, int ld, int rest, double* __restrict__ S,
-                                                                   double* __restrict__ Sd, double* __restrict__ ct) {
+                                                                   const int32_t* __restrict__ cst, const double* __restrict__ scale,
+                                                                   const double* __restrict__ tstat, int n_groups, int p, int ld, int rest,
+                                                                   double* __restrict__ S, double* __restrict__ Sd, double* __restrict__ ct) {
   const int j = blockIdx.x, t = blockIdx.y, P1 = p + 1, Pa = p + 2;
   const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
   s += (size_t)t * P1;
   d += (size_t)t * P1;
+  cst += (size_t)t * P1;
   scale += (size_t)t * p;
   const double nT = tstat[t], sd_y = tstat[n_groups + t];
   const double sj = s[j], dj = d[j], fj = scale[j];
+  const bool cj = cst[j] != 0;
   double* col = S + ((size_t)t * p + j) * (size_t)ld;
   for (int k = threadIdx.x; k < ld; k += kBlock) {
     double v = 0.0;
-    if (k < p) {
+    if (k < p && !cj && !cst[k]) {
       const double c = C(j, k), sk = s[k], dk = d[k], fk = scale[k];
       v = k >= j ? wcov_recentred(c, sj, dj, sk, dk, nT) / nT / (fj * fk) : wcov_recentred(c, sk, dk, sj, dj, nT) / nT / (fk * fj);
     }
     col[k] = v;
     if (k == j) Sd[(size_t)t * p + j] = v;
   }
-  if (threadIdx.x == 0) ct[(size_t)t * p + j] = wcov_recentred(C(j, p), sj, dj, s[p], d[p], nT) / sd_y / nT / fj;
+  if (threadIdx.x == 0) ct[(size_t)t * p + j] = (cj || cst[p]) ? 0.0 : wcov_recentred(C(j, p), sj, dj, s[p], d[p], nT) / sd_y / nT / fj;
 }
 
 // ---- wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): cov_group_path_kernel's problem, S in global memory ----
@@ -1249,6 +1290,7 @@ __global__ __launch_bounds__(kWidth) void cov_wide_group_cv_path_kernel(const do
 
 // blockIdx.x = training set T.  mcov_assemble_kernel's expressions for what is per T or per job:
 //   s, d   G x (p + K): T's sums of deviations about the common centre and its shifts (every response; a feature only when centred)
+//   cst    G x (p + K): the column is constant on T (cov_constant_on_set): scale / divisor 1, zeros in S_T and c~_T
 //   scale  G x p      mean  G x (p + K): as mcov_assemble_kernel leaves it      ysd  G x K: the divisors of the responses
 //   tstat  3 x G: n_T | y~'y~ | the null deviance, both summed in the order r = 0 .. K - 1
 //   l2, l1  jobs x n_lambda, job = mix * G + T      ridge  jobs
@@ -1258,30 +1300,28 @@ __global__ __launch_bounds__(kBlock) void wmcov_cv_stats_kernel(const double* __
                                                                  int centre, int standardize, int standardize_response,
                                                                  const double* __restrict__ mix, const double* __restrict__ lambda,
                                                                  int n_mix, int n_lambda, double* __restrict__ s, double* __restrict__ d,
-                                                                 double* __restrict__ scale, double* __restrict__ mean,
+                                                                 int32_t* __restrict__ cst, double* __restrict__ scale, double* __restrict__ mean,
                                                                  double* __restrict__ ysd, double* __restrict__ tstat,
                                                                  double* __restrict__ l2, double* __restrict__ l1,
                                                                  int32_t* __restrict__ ridge) {
   const int t = blockIdx.x, tid = threadIdx.x, nc = p + K, Pa = nc + 1;
   const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
   const double nT = C(nc, nc);
-  // the sd response r is divided by (1 without standardize_response; a constant response: 0 -> 1), from its re-centred square q
-  auto sd_y = [&](double q) -> double {
-    if (!standardize_response) return 1.0;
-    const double v = q / nT;
-    return v > 0.0 ? sqrt(v) : 1.0;
-  };
+  const int n_summed = rest ? n_groups : 0;
+  // the sd response r is divided by (1 without standardize_response; a response constant on T: 1), from its re-centred square q
+  auto sd_y = [&](double q, bool constant) -> double { return (!standardize_response || constant) ? 1.0 : sqrt(q / nT); };
   for (int j = tid; j < nc; j += kBlock) {
     const double sj = C(j, nc), dj = (j >= p || centre) ? sj / nT : 0.0;
     s[(size_t)t * nc + j] = sj;
     d[(size_t)t * nc + j] = dj;
     const double q = wcov_recentred(C(j, j), sj, dj, sj, dj, nT);
+    const bool cj = cov_constant_on_set(q, C.magnitude(j, j), C.magnitude(j, nc), dj, nT, n_summed);
+    cst[(size_t)t * nc + j] = cj ? 1 : 0;
     if (j < p) {
-      const double v = q / nT;
-      scale[(size_t)t * p + j] = standardize ? (v > 0.0 ? sqrt(v) : 1.0) : 1.0;
+      scale[(size_t)t * p + j] = (standardize && !cj) ? sqrt(q / nT) : 1.0;
       mean[(size_t)t * nc + j] = centre ? mu[j] + dj : 0.0;
     } else {
-      ysd[(size_t)t * K + (j - p)] = sd_y(q);
+      ysd[(size_t)t * K + (j - p)] = sd_y(q, cj);
       mean[(size_t)t * nc + j] = standardize_response ? 0.0 : mu[j + K] + dj;
     }
   }
@@ -1289,7 +1329,9 @@ __global__ __launch_bounds__(kBlock) void wmcov_cv_stats_kernel(const double* __
     double yy = 0.0, nulldev = 0.0;
     for (int r = 0; r < K; ++r) {
       const double sr = C(p + r, nc), dr = sr / nT;
-      const double q = wcov_recentred(C(p + r, p + r), sr, dr, sr, dr, nT), sd = sd_y(q);
+      const double qr = wcov_recentred(C(p + r, p + r), sr, dr, sr, dr, nT);
+      const bool cr = cov_constant_on_set(qr, C.magnitude(p + r, p + r), C.magnitude(p + r, nc), dr, nT, n_summed);
+      const double q = cr ? 0.0 : qr, sd = sd_y(qr, cr);
       nulldev += q;
       yy += q / sd / sd;
     }
@@ -1313,21 +1355,24 @@ __global__ __launch_bounds__(kBlock) void wmcov_cv_stats_kernel(const double* __
 // s, d, scale and the responses' divisors come from wmcov_cv_stats_kernel.
 __global__ __launch_bounds__(kBlock) void wmcov_cv_assemble_kernel(const double* __restrict__ Mg, const double* __restrict__ total,
                                                                     const double* __restrict__ s, const double* __restrict__ d,
-                                                                    const double* __restrict__ scale, const double* __restrict__ ysd,
-                                                                    const double* __restrict__ tstat, int p, int K, int ld, int rest,
-                                                                    double* __restrict__ S, double* __restrict__ Sd, double* __restrict__ ct) {
+                                                                    const int32_t* __restrict__ cst, const double* __restrict__ scale,
+                                                                    const double* __restrict__ ysd, const double* __restrict__ tstat, int p, int K,
+                                                                    int ld, int rest, double* __restrict__ S, double* __restrict__ Sd,
+                                                                    double* __restrict__ ct) {
   const int j = blockIdx.x, t = blockIdx.y, nc = p + K, Pa = nc + 1;
   const WcovSet C{Mg + (size_t)t * Pa * Pa, total, Pa, rest};
   s += (size_t)t * nc;
   d += (size_t)t * nc;
+  cst += (size_t)t * nc;
   scale += (size_t)t * p;
   ysd += (size_t)t * K;
   const double nT = tstat[t];
   const double sj = s[j], dj = d[j], fj = scale[j];
+  const bool cj = cst[j] != 0;
   double* col = S + ((size_t)t * p + j) * (size_t)ld;
   for (int k = threadIdx.x; k < ld; k += kBlock) {
     double v = 0.0;
-    if (k < p) {
+    if (k < p && !cj && !cst[k]) {
       const double c = C(j, k), sk = s[k], dk = d[k], fk = scale[k];
       v = k >= j ? wcov_recentred(c, sj, dj, sk, dk, nT) / nT / (fj * fk) : wcov_recentred(c, sk, dk, sj, dj, nT) / nT / (fk * fj);
     }
@@ -1335,7 +1380,7 @@ __global__ __launch_bounds__(kBlock) void wmcov_cv_assemble_kernel(const double*
     if (k == j) Sd[(size_t)t * p + j] = v;
   }
   for (int r = threadIdx.x; r < K; r += kBlock)
-    ct[((size_t)t * p + j) * K + r] = wcov_recentred(C(j, p + r), sj, dj, s[p + r], d[p + r], nT) / ysd[r] / nT / fj;
+    ct[((size_t)t * p + j) * K + r] = (cj || cst[p + r]) ? 0.0 : wcov_recentred(C(j, p + r), sj, dj, s[p + r], d[p + r], nT) / ysd[r] / nT / fj;
 }
 
 // The wide group kernel's workgroup: both widths give the same bits; profiles/wmcovariance_path.txt has the path kernel's
@@ -1359,10 +1404,25 @@ struct Events {
   }
 };
 
+// Diagnostics (covariance.hpp: CovTap): `count` doubles (words) at dev, copied behind whatever the stream holds so far.
+// Nothing happens without a tap.  The vectors live in the tap's maps, so they stay where they are until the stream is drained.
+hipError_t tap_f64(CovTap* tap, const char* name, const double* dev, size_t count, hipStream_t st) {
+  if (!tap) return hipSuccess;
+  std::vector<double>& v = tap->f64[name];
+  v.resize(count);
+  return count ? hipMemcpyAsync(v.data(), dev, sizeof(double) * count, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+hipError_t tap_i32(CovTap* tap, const char* name, const int32_t* dev, size_t count, hipStream_t st) {
+  if (!tap) return hipSuccess;
+  std::vector<int32_t>& v = tap->i32[name];
+  v.resize(count);
+  return count ? hipMemcpyAsync(v.data(), dev, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
 // covariance_run and wcovariance_run: the same uploads, moments pass and downloads around two path kernels.
 // wide: S goes to global memory (wide_scale_kernel) and cov_wide_path_kernel<width> runs the path; the dense row
 // chunks follow wide_row_chunks.  Not wide: exactly the launches covariance mode has always made.
-int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int width) {
+int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int width, CovTap* tap) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, P1 = p + 1, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
@@ -1444,11 +1504,16 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)P1 + 1, st));
+  SGD_HIP_TRY(tap_f64(tap, "M", d_M, (size_t)P1 * (size_t)P1, st));
   if (wide) {
     hipLaunchKernelGGL(wide_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, P1, ld, (double)n,
                        A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
     SGD_HIP_TRY(hipGetLastError());
     SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+    SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)ld * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_c), (size_t)p, st));
     static const int ahead = exp_env_int("SGDNET_WCOV_PREFETCH", -1);     // (0 / 1: profiles/wcovariance_path.txt)
     const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
     const auto kernel = width == kWideNarrow ? (prefetch ? cov_wide_path_kernel<kWideNarrow, true> : cov_wide_path_kernel<kWideNarrow, false>)
@@ -1490,10 +1555,10 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
 
 }  // namespace
 
-int covariance_run(const CovarianceProblem& pb, CovarianceResult* out) { return cov_run(pb, out, false, 0); }
+int covariance_run(const CovarianceProblem& pb, CovarianceResult* out, CovTap* tap) { return cov_run(pb, out, false, 0, tap); }
 
-int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width) {
-  return cov_run(pb, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)));
+int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width, CovTap* tap) {
+  return cov_run(pb, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)), tap);
 }
 
 
@@ -1502,7 +1567,7 @@ namespace {
 // mcovariance_run and wmcovariance_run: the same uploads, moments pass and downloads around two path kernels.
 // wide: S and c~ go to global memory (cov_wide_group_scale_kernel) and cov_wide_group_path_kernel<width> runs the path; the
 // dense row chunks follow wide_row_chunks.  Not wide: exactly the launches mcovariance mode has always made.
-int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, int width) {
+int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, int width, CovTap* tap) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, K = pb.K, nc = p + K, L = pb.n_lambda;
   const bool sparse = pb.x_dense == nullptr;
@@ -1585,11 +1650,16 @@ int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, in
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)nc, st));
+  SGD_HIP_TRY(tap_f64(tap, "M", d_M, (size_t)nc * (size_t)nc, st));
   if (wide) {
     hipLaunchKernelGGL(cov_wide_group_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, K, ld, (double)n,
                        A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
     SGD_HIP_TRY(hipGetLastError());
     SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+    SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)ld * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_c), pK, st));
     const auto kernel = width == kWideNarrow ? cov_wide_group_path_kernel<kWideNarrow> : cov_wide_group_path_kernel<kWideFull>;
     hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c), p, K, ld,
                        A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
@@ -1632,14 +1702,14 @@ int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, in
 
 }  // namespace
 
-int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width) { return mcov_run(pb, out, false, width); }
+int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width, CovTap* tap) { return mcov_run(pb, out, false, width, tap); }
 
-int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width) {
-  return mcov_run(pb, out, true, width != 0 ? width : wmcov_path_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)));
+int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width, CovTap* tap) {
+  return mcov_run(pb, out, true, width != 0 ? width : wmcov_path_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)), tap);
 }
 
 
-int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
+int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, CovTap* tap) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, P1 = p + 1, Pa = p + 2, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
   const bool sparse = pb.x_dense == nullptr;
@@ -1769,6 +1839,18 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out) {
                      A.at<double>(o_beta), A.at<int32_t>(o_ridge));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  if (tap) {
+    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)Pa, st));
+    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
+    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(tap_f64(tap, "Mt", A.at<double>(o_Mt), (size_t)G * (size_t)P1 * (size_t)P1, st));
+    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)P1, st));
+    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_alpha), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_beta), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+  }
   hipLaunchKernelGGL(cov_path_kernel, dim3((unsigned)jobs), dim3(64), 0, st, A.at<double>(o_Mt), A.at<double>(o_scale), p, G, 0.0,
                      d_tstat, A.at<double>(o_alpha), A.at<double>(o_beta), L, 0, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol,
                      A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
@@ -1811,7 +1893,7 @@ int64_t wcov_cv_row_chunks(int64_t n, int64_t p, const int64_t* count, int n_gro
 
 // covariance_cv_run beyond kCovMaxFeatures features: the same group moments pass (the wide mode's row chunks),
 // wcov_cv_stats_kernel and wcov_cv_assemble_kernel instead of cov_assemble_kernel, cov_wide_cv_path_kernel over the jobs.
-int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, int width) {
+int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, int width, CovTap* tap) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, P1 = p + 1, Pa = p + 2, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
   const bool sparse = pb.x_dense == nullptr;
@@ -1887,6 +1969,7 @@ int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, i
   const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
   const size_t o_s = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
   const size_t o_d = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
+  const size_t o_cst = A.reserve(sizeof(int32_t) * (size_t)G * (size_t)P1);
   const size_t o_S = A.reserve(sizeof(double) * (size_t)G * (size_t)ld * (size_t)p);
   const size_t o_Sd = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
   const size_t o_ct = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
@@ -1951,13 +2034,29 @@ int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, i
   const int rest = pb.train_on_rest ? 1 : 0;
   hipLaunchKernelGGL(wcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p, rest,
                      pb.centre ? 1 : 0, pb.standardize ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_s),
-                     A.at<double>(o_d), A.at<double>(o_scale), A.at<double>(o_mean), d_tstat, A.at<double>(o_alpha), A.at<double>(o_beta),
-                     A.at<int32_t>(o_ridge));
+                     A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), A.at<double>(o_mean), d_tstat, A.at<double>(o_alpha),
+                     A.at<double>(o_beta), A.at<int32_t>(o_ridge));
   hipLaunchKernelGGL(wcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total),
-                     A.at<double>(o_s), A.at<double>(o_d), A.at<double>(o_scale), d_tstat, G, p, ld, rest, A.at<double>(o_S),
-                     A.at<double>(o_Sd), A.at<double>(o_ct));
+                     A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), d_tstat, G, p, ld, rest,
+                     A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  if (tap) {
+    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)Pa, st));
+    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
+    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(tap_f64(tap, "s", A.at<double>(o_s), (size_t)G * (size_t)P1, st));
+    SGD_HIP_TRY(tap_f64(tap, "d", A.at<double>(o_d), (size_t)G * (size_t)P1, st));
+    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)P1, st));
+    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_alpha), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_beta), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+    SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)G * (size_t)ld * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)G * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_ct), (size_t)G * (size_t)p, st));
+  }
   static const int ahead = exp_env_int("SGDNET_WCOV_PREFETCH", -1);     // (0 / 1, as in wcovariance_run)
   const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
   const auto kernel = width == kWideNarrow ? (prefetch ? cov_wide_cv_path_kernel<kWideNarrow, true> : cov_wide_cv_path_kernel<kWideNarrow, false>)
@@ -2007,7 +2106,7 @@ int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, in
 
 // covariance_cv_run for K responses: the same group moments with the columns p .. p + K - 1 the responses and column p + K the
 // ones, mcov_assemble_kernel, and cov_group_path_kernel over the jobs.
-int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out) {
+int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, CovTap* tap) {
   const int64_t n = pb.n;
   const int p = (int)pb.p, K = pb.K, nc = p + K, Pa = nc + 1, L = pb.n_lambda, G = pb.n_groups, A_mix = pb.n_mix;
   const bool sparse = pb.x_dense == nullptr;
@@ -2130,13 +2229,25 @@ int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out)
   if (pb.train_on_rest)
     hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
                        A.at<double>(o_total));
-  // (2 (p + K) doubles of LDS: the moment budget keeps p + K + 1 below 2897, so below 64 KiB)
-  hipLaunchKernelGGL(mcov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), sizeof(double) * 2 * (size_t)nc, st, d_Mg, A.at<double>(o_total),
+  // (20 (p + K) bytes of LDS: the moment budget keeps p + K + 1 below 2897, so below 57 920 bytes of the 64 KiB)
+  hipLaunchKernelGGL(mcov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), (sizeof(double) * 2 + sizeof(int)) * (size_t)nc, st, d_Mg, A.at<double>(o_total),
                      d_mu, G, p, K, pb.train_on_rest ? 1 : 0, pb.centre ? 1 : 0, pb.standardize ? 1 : 0, pb.standardize_response ? 1 : 0,
                      A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_Mt), A.at<double>(o_scale),
                      A.at<double>(o_mean), d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  if (tap) {
+    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)(nc + K), st));
+    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
+    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(tap_f64(tap, "Mt", A.at<double>(o_Mt), (size_t)G * (size_t)p * (size_t)nc, st));
+    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)nc, st));
+    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_l2), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_l1), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+  }
   const auto kernel = width == kMcovNarrow ? cov_group_path_kernel<kMcovNarrow> : cov_group_path_kernel<kMcovWide>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_Mt), A.at<double>(o_scale), p, K, G, 0.0,
                      d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), L, 0, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol,
@@ -2181,7 +2292,7 @@ int64_t wmcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, i
 // mcovariance_cv_run beyond mcov_max_features(K) features: the same group moments pass (the wide mode's row chunks),
 // wmcov_cv_stats_kernel and wmcov_cv_assemble_kernel instead of mcov_assemble_kernel, cov_wide_group_cv_path_kernel over
 // the jobs.
-int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, int width) {
+int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, int width, CovTap* tap) {
   const int64_t n = pb.n;
   const int K = pb.K;
   const bool sparse = pb.x_dense == nullptr;
@@ -2259,6 +2370,7 @@ int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out
   const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
   const size_t o_s = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
   const size_t o_d = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
+  const size_t o_cst = A.reserve(sizeof(int32_t) * (size_t)G * (size_t)nc);
   const size_t o_S = A.reserve(sizeof(double) * (size_t)G * (size_t)ld * (size_t)p);
   const size_t o_Sd = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
   const size_t o_ct = A.reserve(sizeof(double) * (size_t)G * pK);
@@ -2327,13 +2439,30 @@ int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out
   const int rest = pb.train_on_rest ? 1 : 0;
   hipLaunchKernelGGL(wmcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p, K, rest,
                      pb.centre ? 1 : 0, pb.standardize ? 1 : 0, pb.standardize_response ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda),
-                     A_mix, L, A.at<double>(o_s), A.at<double>(o_d), A.at<double>(o_scale), A.at<double>(o_mean), A.at<double>(o_ysd), d_tstat,
-                     A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
+                     A_mix, L, A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), A.at<double>(o_mean),
+                     A.at<double>(o_ysd), d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
   hipLaunchKernelGGL(wmcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total),
-                     A.at<double>(o_s), A.at<double>(o_d), A.at<double>(o_scale), A.at<double>(o_ysd), d_tstat, p, K, ld, rest,
+                     A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), A.at<double>(o_ysd), d_tstat, p, K, ld, rest,
                      A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  if (tap) {
+    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)(nc + K), st));
+    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
+    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(tap_f64(tap, "s", A.at<double>(o_s), (size_t)G * (size_t)nc, st));
+    SGD_HIP_TRY(tap_f64(tap, "d", A.at<double>(o_d), (size_t)G * (size_t)nc, st));
+    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)nc, st));
+    SGD_HIP_TRY(tap_f64(tap, "ysd", A.at<double>(o_ysd), (size_t)G * (size_t)K, st));
+    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_l2), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_l1), jobs * (size_t)L, st));
+    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+    SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)G * (size_t)ld * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)G * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_ct), (size_t)G * pK, st));
+  }
   const auto kernel = width == kWideNarrow ? cov_wide_group_cv_path_kernel<kWideNarrow> : cov_wide_group_cv_path_kernel<kWideFull>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
                      K, ld, G, A.at<double>(o_l2), A.at<double>(o_l1), L, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol, A.at<double>(o_W),

@@ -4,6 +4,8 @@
 
 #include <stdint.h>
 
+#include <map>
+#include <string>
 #include <vector>
 
 #include "direct_problem.hpp"
@@ -28,6 +30,14 @@ constexpr int kCovMaxFeatures = cov_max_features();
 static_assert(kCovMaxFeatures == 198, "the LDS budget of the path kernel (see above)");
 static_assert(kCovMaxFeatures >= 64, "include/sgdnet_hip.h promises at least 64 features");
 
+// Diagnostics (include/sgdnet_hip.h: sgdnet_covariance_probe, sgdnet_cv_covariance_probe).  A run that is handed a tap appends,
+// behind the stages that wrote them and before the path kernel is launched, device-to-host copies of what those stages
+// left, under the names the header lists.  A fit passes null: not a launch, a grid or an argument differs.
+struct CovTap {
+  std::map<std::string, std::vector<double>> f64;
+  std::map<std::string, std::vector<int32_t>> i32;
+};
+
 struct CovarianceProblem : DirectProblem {      // max_iter: coordinate sweeps per lambda
   const double* y = nullptr;           // n: the response as the solvers see it (centred and scaled by the driver)
 };
@@ -43,7 +53,7 @@ struct CovarianceResult {
 };
 
 // Moments pass + path kernel (covariance.hip).  p <= kCovMaxFeatures is the caller's business (plan_fit).
-int covariance_run(const CovarianceProblem& pb, CovarianceResult* out);
+int covariance_run(const CovarianceProblem& pb, CovarianceResult* out, CovTap* tap = nullptr);
 
 // ---- wide covariance mode (SGDNET_MODE_WCOVARIANCE): the same path with S in global memory ----
 // cov_wide_path_kernel is ONE workgroup that keeps, for the whole lambda path, in its LDS
@@ -73,7 +83,7 @@ static_assert(wide_row_chunks(1 << 30, 2) * wide_tile_pairs(2) * 256 * 8 <= kWco
 // Moments pass + wide_scale_kernel + cov_wide_path_kernel (covariance.hip).  p <= kWcovMaxFeatures is the caller's
 // business (plan_fit).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule of wide_layout.hpp
 // (wide_cd_width); both give the same bits.
-int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width = 0);
+int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int width = 0, CovTap* tap = nullptr);
 
 // ---- several responses (SGDNET_MODE_MCOVARIANCE): the mgaussian group-lasso path ----
 // cov_group_path_kernel keeps the same packed triangle S (one Gram matrix serves all K responses) and c~, w and the
@@ -111,7 +121,7 @@ struct McovarianceResult {
 
 // Moments pass + cov_group_path_kernel (covariance.hip).  p <= mcov_max_features(K) is the caller's business (plan_fit).
 // width: lanes of the path kernel's workgroup (64 or 256), 0 = the rule of covariance.hip (mcov_path_width)
-int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0);
+int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0, CovTap* tap = nullptr);
 
 // ---- wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): the mgaussian path with S in global memory ----
 // cov_wide_group_path_kernel is ONE workgroup that keeps, for the whole lambda path, in its LDS
@@ -155,7 +165,7 @@ static_assert(wmcov_max_features(1) + 1 <= kWcovMaxFeatures + 1 && wmcov_max_fea
 // Moments pass + cov_wide_group_scale_kernel + cov_wide_group_path_kernel (covariance.hip).  p <= wmcov_max_features(K) is
 // the caller's business (plan_fit).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule of
 // covariance.hip (wmcov_path_width: 256 up to 1024 features); both give the same bits.
-int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0);
+int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width = 0, CovTap* tap = nullptr);
 
 // ---- cross-validation: every (training set, elastic-net mix) path of one x in one launch ----
 // Rows carry a group id fold[i] in [0, G).  One pass leaves, per group and about ONE centre a (the whole-data column
@@ -203,7 +213,7 @@ struct CovarianceCvResult {
 
 // Group moments + assembly + path kernel over the jobs.  p <= kCovMaxFeatures, the budget above and valid fold ids are
 // the caller's business (driver_direct.cpp: fit_cv_covariance).
-int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out);
+int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, CovTap* tap = nullptr);
 
 // ---- the same in wide covariance mode (SGDNET_MODE_WCOVARIANCE): beyond kCovMaxFeatures features ----
 // The same group moments (over p + 2 columns; dense x: row chunks by wide_rows_per_chunk, cut at the groups' ends), pooled
@@ -230,7 +240,7 @@ int64_t wcov_cv_row_chunks(int64_t n, int64_t p, const int64_t* count, int n_gro
 // Group moments + stats and assembly + wide path kernel over the jobs.  p <= kWcovMaxFeatures, the budget above, at most
 // kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business (driver_direct.cpp:
 // fit_cv_wcovariance).  width as in wcovariance_run.
-int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, int width = 0);
+int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, int width = 0, CovTap* tap = nullptr);
 
 // ---- the same for K responses (SGDNET_MODE_MCOVARIANCE) ----
 // The augmented rows are [x - a | y_1 - a_y1 .. y_K - a_yK | 1]: per group a (p + K + 1) x (p + K + 1) moment matrix, the
@@ -241,7 +251,7 @@ int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, i
 // = 1).  A job is (mix, T) as above and runs cov_group_path_kernel, one workgroup and one CU's LDS each.
 //
 // The budget: G (p + K + 1)^2 doubles within kCovGroupMomentBytes, so p + K + 1 <= 2896 whatever G is and the assembly's
-// staging (2 (p + K) doubles of LDS) stays below 64 KiB.  At K = 96, p = 63 a 10-fold CV takes 2.0 MB of it.
+// staging (2 (p + K) doubles and p + K ints of LDS) stays below 64 KiB.  At K = 96, p = 63 a 10-fold CV takes 2.0 MB of it.
 constexpr size_t mcov_group_moment_bytes(int64_t G, int64_t p, int64_t K) {
   return (size_t)G * (size_t)(p + K + 1) * (size_t)(p + K + 1) * sizeof(double);
 }
@@ -287,7 +297,7 @@ int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, in
 // Group moments + assembly + path kernel over the jobs.  p <= mcov_max_features(K), the budget above, at most
 // kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business
 // (driver_direct.cpp: fit_cv_mcovariance).
-int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out);
+int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, CovTap* tap = nullptr);
 
 // ---- the same in wide multi-response mode (SGDNET_MODE_WMCOVARIANCE): beyond mcov_max_features(K) features ----
 // The same group moments over Pa = p + K + 1 columns (dense x: row chunks by wide_rows_per_chunk, cut at the groups' ends),
@@ -319,6 +329,6 @@ int64_t wmcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, i
 // at most kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business
 // (driver_direct.cpp: fit_cv_mcovariance, wide).  width: lanes of the path kernel's workgroup (256 or 1024), 0 = the rule
 // of covariance.hip (wmcov_path_width); both give the same bits.  pb.width is not read.
-int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, int width = 0);
+int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out, int width = 0, CovTap* tap = nullptr);
 
 }  // namespace sgdnet

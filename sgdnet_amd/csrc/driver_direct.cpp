@@ -304,7 +304,8 @@ int validate_mixes(int n_alpha, const double* alphas, int L, const double* lambd
 // wide: SGDNET_MODE_WCOVARIANCE, the same stage around wcovariance_cv_run (the stage behind sgdnet_cv_wcovariance_*): its own
 // feature limit and byte budget, and no way from one to the other -- each refuses by its own name.
 int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                      int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_cov_result* out, bool wide = false) {
+                      int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_cov_result* out, bool wide = false,
+                      CovTap* tap = nullptr) {
   const int64_t n = pb.n, p = pb.p;
   const char* entry = wide ? "sgdnet_cv_wcovariance" : "sgdnet_cv_covariance";
   const char* mode = wide ? "wcovariance" : "covariance";
@@ -373,7 +374,7 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   CovarianceCvResult cr;
-  rc = wide ? wcovariance_cv_run(pb, &cr, option(kOptWcovarianceWidth)) : covariance_cv_run(pb, &cr);
+  rc = wide ? wcovariance_cv_run(pb, &cr, option(kOptWcovarianceWidth), tap) : covariance_cv_run(pb, &cr, tap);
   if (rc) return rc;
   if (pt.on)
     fprintf(stderr, "[sgdnet]   cv %s: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", mode, cr.moments_ms,
@@ -424,7 +425,8 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
 // wide: SGDNET_MODE_WMCOVARIANCE, the same stage around wmcovariance_cv_run (the stage behind sgdnet_cv_wmcovariance_*): its own
 // feature limit and byte budget, and no way from one to the other -- each refuses by its own name.
 int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                       int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mcov_result* out, bool wide = false) {
+                       int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mcov_result* out, bool wide = false,
+                       CovTap* tap = nullptr) {
   const int64_t n = pb.n, p = pb.p;
   const char* entry = wide ? "sgdnet_cv_wmcovariance" : "sgdnet_cv_mcovariance";
   const char* mode = wide ? "wmcovariance" : "mcovariance";
@@ -498,7 +500,7 @@ int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, cons
   static const int width = exp_env_int("SGDNET_MCOV_WIDTH", 0);     // (64 or 256 lanes, as fit_mcovariance takes it)
   pb.width = width;
   McovarianceCvResult cr;
-  rc = wide ? wmcovariance_cv_run(pb, &cr, option(kOptWmcovarianceWidth)) : mcovariance_cv_run(pb, &cr);
+  rc = wide ? wmcovariance_cv_run(pb, &cr, option(kOptWmcovarianceWidth), tap) : mcovariance_cv_run(pb, &cr, tap);
   if (rc) return rc;
   if (pt.on)
     fprintf(stderr, "[sgdnet]   cv %s: group moments %.3f ms, assembly %.3f ms, path kernel (%d jobs) %.3f ms\n", mode, cr.moments_ms,
@@ -1417,5 +1419,175 @@ int sgdnet_wmnewton_probe(const double* x, int64_t n, int64_t p, int device, sgd
   pb.n_lambda = 1;
   return wmnewton_probe(pb, io);
 }
+
+}  // extern "C"
+
+// ---- diagnostics: the covariance family stage by stage (covariance.hpp: CovTap) ----
+// The handle is the tap itself with its int32 fields converted, so that one getter serves every field.
+
+struct sgdnet_cov_probe {
+  CovTap tap;
+};
+
+namespace {
+
+// x for a probe: exactly one of the two forms, validated as the fit entry points validate theirs
+template <class Problem>
+int cov_probe_matrix(Problem& pb, const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const char* who) {
+  if ((x_dense != nullptr) == (x_sparse != nullptr)) {
+    set_error("%s: invalid matrix", who);
+    return SGDNET_EINVAL;
+  }
+  if (x_dense) {
+    pb.n = n;
+    pb.p = p;
+    pb.x_dense = x_dense;
+    return SGDNET_OK;
+  }
+  if (x_sparse->n_rows <= 0 || x_sparse->n_cols <= 0 || !x_sparse->colptr || !x_sparse->rowidx || !x_sparse->values) {
+    set_error("%s: invalid matrix", who);
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x_sparse)) || (rc = validate_rowidx(x_sparse))) return rc;
+  pb.n = x_sparse->n_rows;
+  pb.p = x_sparse->n_cols;
+  pb.colptr = x_sparse->colptr;
+  pb.rowidx = x_sparse->rowidx;
+  pb.values = x_sparse->values;
+  return SGDNET_OK;
+}
+
+// the feature limit of a mode, refused by the name the plan (fit_plan.hpp) refuses it by
+int cov_probe_limit(int64_t p, bool wide, bool multi, int K) {
+  const int limit = multi ? (wide ? wmcov_max_features(K) : mcov_max_features(K)) : (wide ? kWcovMaxFeatures : kCovMaxFeatures);
+  if (p <= limit) return SGDNET_OK;
+  const char* mode = multi ? (wide ? "wmcovariance" : "mcovariance") : (wide ? "wcovariance" : "covariance");
+  set_error("mode = %s needs no more features than sgdnet_%s_max_features(%s): %lld features (limit %d)", mode, mode,
+            multi ? "n_classes" : "", (long long)p, limit);
+  return SGDNET_EUNSUPPORTED;
+}
+
+int cov_probe_finish(int rc, sgdnet_cov_probe* h, int ld, sgdnet_cov_probe** out) {
+  if (rc) {
+    delete h;
+    return rc;
+  }
+  for (const auto& f : h->tap.i32) h->tap.f64[f.first].assign(f.second.begin(), f.second.end());
+  if (ld > 0) h->tap.f64["ld"].assign(1, (double)ld);
+  *out = h;
+  return SGDNET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
+                            const double* scale, int centre, int wide, int multi, double mix, int n_lambda, const double* lambda,
+                            int device, sgdnet_cov_probe** out) {
+  if (!out || !y || !scale || !lambda || n_lambda <= 0 || K < 1 || (!multi && K != 1) || !(mix >= 0.0 && mix <= 1.0)) {
+    set_error("sgdnet_covariance_probe: invalid argument");
+    return SGDNET_EINVAL;
+  }
+  std::vector<double> l2((size_t)n_lambda), l1((size_t)n_lambda);
+  for (int l = 0; l < n_lambda; ++l) {
+    l2[(size_t)l] = (1.0 - mix) * lambda[l];
+    l1[(size_t)l] = mix * lambda[l];
+  }
+  auto fill = [&](DirectProblem& pb) {
+    pb.centre = centre != 0;
+    pb.scale = scale;
+    pb.device = device;
+    pb.n_lambda = n_lambda;
+    pb.alpha = l2.data();
+    pb.beta = l1.data();
+    pb.ridge = mix == 0.0;
+    pb.max_iter = 1000;
+    pb.tol = 1e-7;
+  };
+  int rc;
+  sgdnet_cov_probe* h = new sgdnet_cov_probe;
+  if (multi) {
+    McovarianceProblem pb;
+    if ((rc = cov_probe_matrix(pb, x_dense, x_sparse, n, p, "sgdnet_covariance_probe")) || (rc = cov_probe_limit(pb.p, wide != 0, true, K)) ||
+        (rc = check_device(device)))
+      return cov_probe_finish(rc, h, 0, out);
+    fill(pb);
+    pb.K = K;
+    pb.y = y;
+    McovarianceResult res;
+    rc = wide ? wmcovariance_run(pb, &res, 0, &h->tap) : mcovariance_run(pb, &res, 0, &h->tap);
+    if (!rc && !wide) h->tap.f64["c"] = res.c;
+    return cov_probe_finish(rc, h, wide ? (int)wide_leading_dim(pb.p) : 0, out);
+  }
+  CovarianceProblem pb;
+  if ((rc = cov_probe_matrix(pb, x_dense, x_sparse, n, p, "sgdnet_covariance_probe")) || (rc = cov_probe_limit(pb.p, wide != 0, false, 1)) ||
+      (rc = check_device(device)))
+    return cov_probe_finish(rc, h, 0, out);
+  fill(pb);
+  pb.y = y;
+  CovarianceResult res;
+  rc = wide ? wcovariance_run(pb, &res, 0, &h->tap) : covariance_run(pb, &res, &h->tap);
+  if (!rc && !wide) h->tap.f64["c"] = res.c;
+  return cov_probe_finish(rc, h, wide ? (int)wide_leading_dim(pb.p) : 0, out);
+}
+
+int sgdnet_cv_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y,
+                               const int32_t* fold, int n_groups, int train_on_rest, const sgdnet_control* ctl, int wide, int n_alpha,
+                               const double* alphas, const double* lambdas, sgdnet_cov_probe** out) {
+  if (!out || !ctl) {
+    set_error("sgdnet_cv_covariance_probe: null pointer");
+    return SGDNET_EINVAL;
+  }
+  const bool multi = ctl->family == SGDNET_MGAUSSIAN;
+  const char* who = multi ? (wide ? "sgdnet_cv_wmcovariance" : "sgdnet_cv_mcovariance") : (wide ? "sgdnet_cv_wcovariance" : "sgdnet_cv_covariance");
+  int rc;
+  sgdnet_cov_probe* h = new sgdnet_cov_probe;
+  McovarianceCvProblem mpb;
+  CovarianceCvProblem cpb;
+  if ((rc = multi ? cov_probe_matrix(mpb, x_dense, x_sparse, n, p, who) : cov_probe_matrix(cpb, x_dense, x_sparse, n, p, who)))
+    return cov_probe_finish(rc, h, 0, out);
+  const int64_t P = multi ? mpb.p : cpb.p;       // (validated: the sparse matrix's own count)
+  // the stage's own outputs: sized only where the stage's checks of the sizes and of the feature limit will pass (it refuses
+  // the rest before it writes)
+  const int K = multi ? ctl->n_classes : 1;
+  const int limit = K < 1 ? 0 : multi ? (wide ? wmcov_max_features(K) : mcov_max_features(K)) : (wide ? kWcovMaxFeatures : kCovMaxFeatures);
+  const bool sized = n_groups > 0 && n_alpha > 0 && ctl->n_lambda > 0 && P > 0 && P <= limit;
+  const size_t jobs = sized ? (size_t)n_alpha * (size_t)n_groups : 1, L = sized ? (size_t)ctl->n_lambda : 1;
+  const size_t Ks = sized ? (size_t)K : 1, Ps = sized ? (size_t)P : 1;
+  std::vector<double> a0, beta, dev, codes, nulldev, npasses;
+  try {
+    a0.resize(jobs * L * Ks);
+    beta.resize(jobs * L * Ps * Ks);
+    dev.resize(jobs * L);
+    codes.resize(jobs * L);
+    nulldev.resize(jobs);
+    npasses.resize(jobs);
+  } catch (const std::exception&) {
+    set_error("%s: the probe could not allocate its result buffers", who);
+    return cov_probe_finish(SGDNET_ENOMEM, h, 0, out);
+  }
+  if (multi) {
+    mpb.y = y;
+    sgdnet_cv_mcov_result res{a0.data(), beta.data(), dev.data(), codes.data(), nulldev.data(), npasses.data()};
+    rc = fit_cv_mcovariance(mpb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, &res, wide != 0, &h->tap);
+    return cov_probe_finish(rc, h, wide ? (int)wide_leading_dim(mpb.p) : 0, out);
+  }
+  cpb.y = y;
+  sgdnet_cv_cov_result res{a0.data(), beta.data(), dev.data(), codes.data(), nulldev.data(), npasses.data()};
+  rc = fit_cv_covariance(cpb, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, &res, wide != 0, &h->tap);
+  return cov_probe_finish(rc, h, wide ? (int)wide_leading_dim(cpb.p) : 0, out);
+}
+
+int64_t sgdnet_cov_probe_field(const sgdnet_cov_probe* probe, const char* name, const double** data) {
+  if (!probe || !name) return -1;
+  const auto it = probe->tap.f64.find(name);
+  if (it == probe->tap.f64.end()) return -1;
+  if (data) *data = it->second.data();
+  return (int64_t)it->second.size();
+}
+
+void sgdnet_cov_probe_free(sgdnet_cov_probe* probe) { delete probe; }
 
 }  // extern "C"

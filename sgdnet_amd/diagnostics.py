@@ -1,6 +1,7 @@
 """Diagnostics (include/sgdnet_hip.h "Diagnostics"): what a fit's once-per-fit device setup passes
 (sgdnet_amd/csrc/setup_device.hip) and the passes of one outer step of Newton mode (sgdnet_amd/csrc/newton.hip) and of
-multinomial Newton mode (sgdnet_amd/csrc/mnewton.hip), narrow and wide, leave on the device, copied back pass by pass.
+multinomial Newton mode (sgdnet_amd/csrc/mnewton.hip), narrow and wide, and the stages of the covariance family
+(sgdnet_amd/csrc/covariance.hip), one fit or a cross-validation, leave on the device, copied back pass by pass.
 Used by the tests; a fit never calls these."""
 import ctypes as C
 from types import SimpleNamespace
@@ -207,4 +208,108 @@ def wmnewton_probe(x, y, K, scale, u_cur, u, t=0.5, centre=True, l2=0.0, l1=0.0,
     o.pub_rec = dict(zip(NEWTON_REC[1:5], pr.pub_rec))
     o.blend_rec = dict(zip(NEWTON_REC[1:5], pr.blend_rec))
     o.cd_rec = dict(zip(NEWTON_REC, pr.cd_rec))
+    return o
+
+
+def _csc_of(x):
+    """(Csc, the arrays it points into): the CSC slots of a scipy.sparse x as they are (row order within a column included)"""
+    n, p = x.shape
+    keep = (np.ascontiguousarray(x.indptr, dtype=np.int32), np.ascontiguousarray(x.indices, dtype=np.int32),
+            np.ascontiguousarray(x.data, dtype=np.float64))
+    csc = _lib.Csc()
+    csc.n_rows, csc.n_cols = n, p
+    csc.colptr = keep[0].ctypes.data_as(C.POINTER(C.c_int32))
+    csc.rowidx = keep[1].ctypes.data_as(C.POINTER(C.c_int32))
+    csc.values = dptr(keep[2])
+    return csc, keep
+
+
+def _cov_fields(handle, shapes):
+    """the named arrays of a sgdnet_cov_probe, copied and shaped; the handle is freed"""
+    L = _lib.load()
+    o = SimpleNamespace()
+    try:
+        for name, shape in shapes.items():
+            data = C.POINTER(C.c_double)()
+            count = L.sgdnet_cov_probe_field(handle, name.encode(), C.byref(data))
+            if count < 0:
+                continue
+            a = np.ctypeslib.as_array(data, shape=(count,)).copy() if count else np.empty(0)
+            if name == "ld":
+                o.ld = int(a[0])
+                continue
+            want = shape(o) if callable(shape) else shape
+            if int(np.prod(want)) != count:
+                raise RuntimeError(f"sgdnet_cov_probe: field {name} has {count} doubles, the binding expected {want}")
+            setattr(o, name, a.reshape(want))
+    finally:
+        L.sgdnet_cov_probe_free(handle)
+    return o
+
+
+def covariance_probe(x, y, scale, mix, lambda_, *, wide=False, multi=None, centre=True, device=0):
+    """One fit of the covariance family stage by stage (sgdnet_covariance_probe).  x: (n, p) array or scipy.sparse CSC (its
+    slots go to the library as they are); y: (n,) or (n, K) as the driver would hand it over; scale: (p,); multi: the
+    K-response form (default: K > 1).  Returns mu, M (P, P) with P = p + K, and c (p, K) (narrow) or ld, S (p, ld), Sd (p,),
+    ct (p, K) (wide); include/sgdnet_hip.h says which entries of M are defined."""
+    sparse = hasattr(x, "tocsc")
+    n, p = x.shape
+    y = np.asfortranarray(np.asarray(y, dtype=np.float64).reshape(n, -1))
+    K = y.shape[1]
+    multi = K > 1 if multi is None else bool(multi)
+    scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(p)
+    lam = np.ascontiguousarray(lambda_, dtype=np.float64).reshape(-1)
+    handle = C.c_void_p()
+    L = _lib.load()
+    tail = (dptr(y), K, dptr(scale), int(bool(centre)), int(bool(wide)), int(multi), float(mix), lam.size, dptr(lam), int(device),
+            C.byref(handle))
+    if sparse:
+        csc, keep = _csc_of(x)
+        check(L.sgdnet_covariance_probe(None, C.byref(csc), n, p, *tail))
+    else:
+        xd = np.asfortranarray(np.asarray(x, dtype=np.float64))
+        check(L.sgdnet_covariance_probe(dptr(xd), None, n, p, *tail))
+    P = p + K
+    return _cov_fields(handle, {"ld": (1,), "mu": (P if multi else p + 2,), "M": (P, P), "c": (p, K), "S": lambda o: (p, o.ld),
+                                "Sd": (p,), "ct": (p, K)})
+
+
+def cv_covariance_probe(x, y, fold, n_groups, alphas, lambdas, *, train_on="fold", wide=False, intercept=True, standardize=True,
+                        standardize_response=False, family=None, n_classes=None, maxit=1000, thresh=1e-7, n_gpus=0, debug=0,
+                        device=0):
+    """A cross-validation of the covariance family stage by stage (sgdnet_cv_covariance_probe): the arguments of
+    sgdnet_cv_*covariance_*.  fold: group ids 0 .. n_groups - 1; alphas: (A,); lambdas: (A, L).  y (n,): gaussian; (n, K):
+    mgaussian (family and n_classes override what y's shape says, for the refusals).  Returns mu, Mg (G, Pa, Pa), total
+    (Pa, Pa; train_on = "rest"), scale (G, p), mean (G, p + K), tstat (3, G), pen_a and pen_b (A, G, L), ridge (A, G), and Mt
+    (narrow) or ld, s, d (G, p + K), ysd (G, K; mgaussian), S (G, p, ld), Sd (G, p), ct (G, p, K) (wide)."""
+    sparse = hasattr(x, "tocsc")
+    n, p = x.shape
+    y = np.asarray(y, dtype=np.float64)
+    multi = y.ndim == 2
+    y = np.asfortranarray(y.reshape(n, -1))
+    K = y.shape[1]
+    fold = np.ascontiguousarray(fold, dtype=np.int32).reshape(-1)
+    alphas = np.ascontiguousarray(np.atleast_1d(alphas), dtype=np.float64)
+    lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(alphas.size, -1))
+    A, nl, G = alphas.size, lam.shape[1], int(n_groups)
+    ctl = _lib.Control()
+    ctl.family = _lib.FAMILIES[family or ("mgaussian" if multi else "gaussian")]
+    ctl.intercept, ctl.standardize, ctl.standardize_response = int(intercept), int(standardize), int(bool(standardize_response))
+    ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, int(K if n_classes is None else n_classes)
+    ctl.n_gpus, ctl.debug, ctl.device = int(n_gpus), int(debug), int(device)
+    handle = C.c_void_p()
+    L = _lib.load()
+    tail = (dptr(y), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), int(bool(wide)), A,
+            dptr(alphas), dptr(lam), C.byref(handle))
+    if sparse:
+        csc, keep = _csc_of(x)
+        check(L.sgdnet_cv_covariance_probe(None, C.byref(csc), n, p, *tail))
+    else:
+        xd = np.asfortranarray(np.asarray(x, dtype=np.float64))
+        check(L.sgdnet_cv_covariance_probe(dptr(xd), None, n, p, *tail))
+    Pa = p + K + 1
+    o = _cov_fields(handle, {"ld": (1,), "mu": (p + 2 * K if multi else p + 2,), "Mg": (G, Pa, Pa), "total": (Pa, Pa),
+                             "Mt": (G, p, p + K) if multi else (G, p + 1, p + 1), "scale": (G, p), "mean": (G, p + K), "tstat": (3, G),
+                             "pen_a": (A, G, nl), "pen_b": (A, G, nl), "ridge": (A, G), "s": (G, p + K), "d": (G, p + K), "ysd": (G, K),
+                             "S": lambda o: (G, p, o.ld), "Sd": (G, p), "ct": (G, p, K)})
     return o
