@@ -856,8 +856,9 @@ int sgdnet_wmnewton_probe(const double* x, int64_t n, int64_t p, int device, sgd
  * goes through (one fit: covariance_run, wcovariance_run, mcovariance_run, wmcovariance_run; a cross-validation: the stage
  * behind sgdnet_cv_*covariance_* and its covariance_cv_run, wcovariance_cv_run, mcovariance_cv_run, wmcovariance_cv_run)
  * with a tap: the same kernels on the same grids with the same arguments, and behind the stages, before the path kernel
- * is launched, device-to-host copies of what they left.  tests/test_gpu_covariance_passes.py and
- * tests/test_gpu_cv_covariance_passes.py compare each with an exact reference.  The result is a set of named arrays of
+ * is launched, device-to-host copies of what they left; then, behind the path kernel, of what it wrote.
+ * tests/test_gpu_covariance_passes.py and tests/test_gpu_cv_covariance_passes.py compare each stage with an exact
+ * reference, tests/test_gpu_covariance_path_passes.py and tests/test_gpu_cv_covariance_path_passes.py the path kernels.  The result is a set of named arrays of
  * doubles (int32 fields are converted), owned by the library until sgdnet_cov_probe_free.
  *
  * exactly one of x_dense (n x p column-major) and x_sparse is given.  wide = 0: the narrow form (SGDNET_MODE_COVARIANCE /
@@ -874,14 +875,25 @@ int sgdnet_wmnewton_probe(const double* x, int64_t n, int64_t p, int device, sgd
  *        (nothing writes it, nothing reads it)
  *   wide: ld (1); S p x ld, row j = column j of the scaled matrix, the zero pad k >= p included; Sd p; ct p x K
  *   narrow: c p x K, the path kernel's c~
+ *   the path kernel's own: W, G n_lambda x p x K (the coefficients and the gradient S w - c~ of the standardised problem
+ *        at the end of every lambda), sweeps, unconverged n_lambda, and tol (1), max_iter (1) as the kernel got them
+ * sgdnet_covariance_path_probe: the same with the stopping rule and the path kernel's workgroup chosen.  tol and max_iter
+ * (the list sweeps of one lambda) go to the kernel as they are; width = 0 is the rule a fit follows, otherwise 64 or 256
+ * (multi and not wide) or 256 or 1024 (wide).  SGDNET_EINVAL, before any HIP call: any other width, max_iter = 0.
+ * sgdnet_covariance_probe is this entry with tol = 1e-7, max_iter = 1000, width = 0.
  * sgdnet_cv_covariance_probe: the arguments of sgdnet_cv_*covariance_* (family gaussian: one response; mgaussian:
  * n_classes responses, y n x K column-major), refused in the same words with the same codes.  Fields, Pa = p + K + 1:
  *   mu   one response: p + 2 (as above).  mgaussian: p + 2 K -- the centres, the K sums, the K means
  *   Mg   G x Pa x Pa;  total  Pa x Pa (train_on_rest only)
  *   scale G x p;  mean G x (p + K);  tstat 3 x G;  pen_a, pen_b jobs x n_lambda (alpha | beta, or l2 | l1);  ridge jobs
  *   narrow: Mt  G x (p + 1) x (p + 1) (one response) or G x p x (p + K)
- *   wide:   ld (1);  s, d G x (p + K);  ysd G x K (mgaussian);  S G x p x ld;  Sd G x p;  ct G x p x K */
+ *   wide:   ld (1);  s, d G x (p + K);  ysd G x K (mgaussian);  S G x p x ld;  Sd G x p;  ct G x p x K
+ *   the path kernel's own: W, G jobs x n_lambda x p x K, sweeps, unconverged jobs x n_lambda, tol (1), max_iter (1) */
 typedef struct sgdnet_cov_probe sgdnet_cov_probe;
+int sgdnet_covariance_path_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
+                                 const double* scale, int centre, int wide, int multi, double mix, int n_lambda,
+                                 const double* lambda, int device, double tol, unsigned max_iter, int width,
+                                 sgdnet_cov_probe** out);
 int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
                             const double* scale, int centre, int wide, int multi, double mix, int n_lambda,
                             const double* lambda, int device, sgdnet_cov_probe** out);

@@ -43,7 +43,7 @@ EXPORTS = [
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
     "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse", "sgdnet_cv_wmcovariance_dense", "sgdnet_cv_wmcovariance_sparse",
     "sgdnet_wnewton_probe", "sgdnet_wmnewton_probe",
-    "sgdnet_covariance_probe", "sgdnet_cv_covariance_probe", "sgdnet_cov_probe_field", "sgdnet_cov_probe_free",
+    "sgdnet_covariance_probe", "sgdnet_covariance_path_probe", "sgdnet_cv_covariance_probe", "sgdnet_cov_probe_field", "sgdnet_cov_probe_free",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
 MEASURES = {"deviance": 0, "mse": 1, "mae": 2, "class": 3, "auc": 4}
@@ -329,6 +329,9 @@ def load():
     _D, _I = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     L.sgdnet_covariance_probe.argtypes = [_D, C.POINTER(Csc), C.c_int64, C.c_int64, _D, C.c_int, _D, C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.c_int, _D, C.c_int, C.POINTER(C.c_void_p)]
+    L.sgdnet_covariance_path_probe.argtypes = [_D, C.POINTER(Csc), C.c_int64, C.c_int64, _D, C.c_int, _D, C.c_int, C.c_int, C.c_int,
+                                               C.c_double, C.c_int, _D, C.c_int, C.c_double, C.c_uint, C.c_int,
+                                               C.POINTER(C.c_void_p)]
     L.sgdnet_cv_covariance_probe.argtypes = [_D, C.POINTER(Csc), C.c_int64, C.c_int64, _D, _I, C.c_int, C.c_int, C.POINTER(Control),
                                              C.c_int, C.c_int, _D, _D, C.POINTER(C.c_void_p)]
     L.sgdnet_cov_probe_field.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(_D)]

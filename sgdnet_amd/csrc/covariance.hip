@@ -1418,6 +1418,19 @@ hipError_t tap_i32(CovTap* tap, const char* name, const int32_t* dev, size_t cou
   v.resize(count);
   return count ? hipMemcpyAsync(v.data(), dev, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st) : hipSuccess;
 }
+// Behind the path kernel: the four buffers it wrote (coefs = jobs x L x p x K doubles, paths = jobs x L words) and the
+// stopping rule it was handed
+hipError_t tap_path(CovTap* tap, const double* W, const double* G, size_t coefs, const int32_t* sweeps, const int32_t* unconverged,
+                    size_t paths, double tol, unsigned max_iter, hipStream_t st) {
+  if (!tap) return hipSuccess;
+  tap->f64["tol"].assign(1, tol);
+  tap->f64["max_iter"].assign(1, (double)max_iter);
+  hipError_t e;
+  if ((e = tap_f64(tap, "W", W, coefs, st)) != hipSuccess || (e = tap_f64(tap, "G", G, coefs, st)) != hipSuccess ||
+      (e = tap_i32(tap, "sweeps", sweeps, paths, st)) != hipSuccess)
+    return e;
+  return tap_i32(tap, "unconverged", unconverged, paths, st);
+}
 
 // covariance_run and wcovariance_run: the same uploads, moments pass and downloads around two path kernels.
 // wide: S goes to global memory (wide_scale_kernel) and cov_wide_path_kernel<width> runs the path; the dense row
@@ -1528,6 +1541,8 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), (size_t)L * (size_t)p, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
+                       (size_t)L, pb.tol, pb.max_iter, st));
 
   out->mean.resize((size_t)P1);
   out->c.resize((size_t)p);
@@ -1676,6 +1691,8 @@ int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, in
                        A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), (size_t)L * pK, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
+                       (size_t)L, pb.tol, pb.max_iter, st));
 
   out->mean.resize((size_t)p);
   out->c.resize(pK);
@@ -1856,6 +1873,8 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, Co
                      A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * (size_t)p, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
+                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
 
   std::vector<double> tstat(3 * (size_t)G);
   out->mean.resize((size_t)G * (size_t)P1);
@@ -2066,6 +2085,8 @@ int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, i
                      A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * (size_t)p, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
+                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
 
   std::vector<double> tstat(3 * (size_t)G), ct((size_t)G * (size_t)p);
   out->mean.resize((size_t)G * (size_t)P1);
@@ -2254,6 +2275,8 @@ int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out,
                      A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * pK, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
+                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
 
   std::vector<double> tstat(3 * (size_t)G);
   out->mean.resize((size_t)G * (size_t)nc);
@@ -2469,6 +2492,8 @@ int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out
                      A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * pK, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
+                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
 
   std::vector<double> tstat(3 * (size_t)G), ct((size_t)G * pK);
   out->mean.resize((size_t)G * (size_t)nc);

@@ -30,9 +30,11 @@ constexpr int kCovMaxFeatures = cov_max_features();
 static_assert(kCovMaxFeatures == 198, "the LDS budget of the path kernel (see above)");
 static_assert(kCovMaxFeatures >= 64, "include/sgdnet_hip.h promises at least 64 features");
 
-// Diagnostics (include/sgdnet_hip.h: sgdnet_covariance_probe, sgdnet_cv_covariance_probe).  A run that is handed a tap appends,
-// behind the stages that wrote them and before the path kernel is launched, device-to-host copies of what those stages
-// left, under the names the header lists.  A fit passes null: not a launch, a grid or an argument differs.
+// Diagnostics (include/sgdnet_hip.h: sgdnet_covariance_path_probe, sgdnet_cv_covariance_probe).  A run that is handed a tap
+// appends, behind the stages that wrote them and before the path kernel is launched, device-to-host copies of what those
+// stages left, under the names the header lists; and, once the path kernel has been enqueued, of the four buffers it
+// wrote (W, G, sweeps, unconverged: the device buffers themselves, in the kernel's layout), with the tol and max_iter the
+// kernel was handed.  A fit passes null: not a launch, a grid or an argument differs, with a tap or without.
 struct CovTap {
   std::map<std::string, std::vector<double>> f64;
   std::map<std::string, std::vector<int32_t>> i32;

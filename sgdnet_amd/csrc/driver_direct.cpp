@@ -1483,11 +1483,17 @@ int cov_probe_finish(int rc, sgdnet_cov_probe* h, int ld, sgdnet_cov_probe** out
 
 extern "C" {
 
-int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
-                            const double* scale, int centre, int wide, int multi, double mix, int n_lambda, const double* lambda,
-                            int device, sgdnet_cov_probe** out) {
+int sgdnet_covariance_path_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
+                                 const double* scale, int centre, int wide, int multi, double mix, int n_lambda, const double* lambda,
+                                 int device, double tol, unsigned max_iter, int width, sgdnet_cov_probe** out) {
   if (!out || !y || !scale || !lambda || n_lambda <= 0 || K < 1 || (!multi && K != 1) || !(mix >= 0.0 && mix <= 1.0)) {
     set_error("sgdnet_covariance_probe: invalid argument");
+    return SGDNET_EINVAL;
+  }
+  // the path kernel's workgroup: 0 is the rule a fit follows; the one-response narrow kernel has one width only
+  const bool width_ok = width == 0 || (wide ? (width == 256 || width == 1024) : (multi && (width == 64 || width == 256)));
+  if (!width_ok || max_iter == 0) {
+    set_error("sgdnet_covariance_path_probe: invalid argument");
     return SGDNET_EINVAL;
   }
   std::vector<double> l2((size_t)n_lambda), l1((size_t)n_lambda);
@@ -1503,8 +1509,8 @@ int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, i
     pb.alpha = l2.data();
     pb.beta = l1.data();
     pb.ridge = mix == 0.0;
-    pb.max_iter = 1000;
-    pb.tol = 1e-7;
+    pb.max_iter = max_iter;
+    pb.tol = tol;
   };
   int rc;
   sgdnet_cov_probe* h = new sgdnet_cov_probe;
@@ -1517,7 +1523,7 @@ int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, i
     pb.K = K;
     pb.y = y;
     McovarianceResult res;
-    rc = wide ? wmcovariance_run(pb, &res, 0, &h->tap) : mcovariance_run(pb, &res, 0, &h->tap);
+    rc = wide ? wmcovariance_run(pb, &res, width, &h->tap) : mcovariance_run(pb, &res, width, &h->tap);
     if (!rc && !wide) h->tap.f64["c"] = res.c;
     return cov_probe_finish(rc, h, wide ? (int)wide_leading_dim(pb.p) : 0, out);
   }
@@ -1528,9 +1534,16 @@ int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, i
   fill(pb);
   pb.y = y;
   CovarianceResult res;
-  rc = wide ? wcovariance_run(pb, &res, 0, &h->tap) : covariance_run(pb, &res, &h->tap);
+  rc = wide ? wcovariance_run(pb, &res, width, &h->tap) : covariance_run(pb, &res, &h->tap);
   if (!rc && !wide) h->tap.f64["c"] = res.c;
   return cov_probe_finish(rc, h, wide ? (int)wide_leading_dim(pb.p) : 0, out);
+}
+
+int sgdnet_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y, int K,
+                            const double* scale, int centre, int wide, int multi, double mix, int n_lambda, const double* lambda,
+                            int device, sgdnet_cov_probe** out) {
+  return sgdnet_covariance_path_probe(x_dense, x_sparse, n, p, y, K, scale, centre, wide, multi, mix, n_lambda, lambda, device, 1e-7, 1000, 0,
+                                      out);
 }
 
 int sgdnet_cv_covariance_probe(const double* x_dense, const sgdnet_csc* x_sparse, int64_t n, int64_t p, const double* y,

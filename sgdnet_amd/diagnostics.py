@@ -238,6 +238,8 @@ def _cov_fields(handle, shapes):
             if name == "ld":
                 o.ld = int(a[0])
                 continue
+            if name in ("sweeps", "unconverged", "max_iter"):
+                a = a.astype(np.int64)
             want = shape(o) if callable(shape) else shape
             if int(np.prod(want)) != count:
                 raise RuntimeError(f"sgdnet_cov_probe: field {name} has {count} doubles, the binding expected {want}")
@@ -247,11 +249,13 @@ def _cov_fields(handle, shapes):
     return o
 
 
-def covariance_probe(x, y, scale, mix, lambda_, *, wide=False, multi=None, centre=True, device=0):
-    """One fit of the covariance family stage by stage (sgdnet_covariance_probe).  x: (n, p) array or scipy.sparse CSC (its
+def covariance_probe(x, y, scale, mix, lambda_, *, wide=False, multi=None, centre=True, device=0, tol=1e-7, max_sweeps=1000, width=0):
+    """One fit of the covariance family stage by stage (sgdnet_covariance_path_probe).  x: (n, p) array or scipy.sparse CSC (its
     slots go to the library as they are); y: (n,) or (n, K) as the driver would hand it over; scale: (p,); multi: the
     K-response form (default: K > 1).  Returns mu, M (P, P) with P = p + K, and c (p, K) (narrow) or ld, S (p, ld), Sd (p,),
-    ct (p, K) (wide); include/sgdnet_hip.h says which entries of M are defined."""
+    ct (p, K) (wide); include/sgdnet_hip.h says which entries of M are defined.  The path kernel ran with tol and
+    max_sweeps in a workgroup of `width` lanes (0: the rule a fit follows) and left W, G (L, p, K), sweeps, unconverged (L,
+    integers), and tol, max_iter as it got them."""
     sparse = hasattr(x, "tocsc")
     n, p = x.shape
     y = np.asfortranarray(np.asarray(y, dtype=np.float64).reshape(n, -1))
@@ -262,16 +266,17 @@ def covariance_probe(x, y, scale, mix, lambda_, *, wide=False, multi=None, centr
     handle = C.c_void_p()
     L = _lib.load()
     tail = (dptr(y), K, dptr(scale), int(bool(centre)), int(bool(wide)), int(multi), float(mix), lam.size, dptr(lam), int(device),
-            C.byref(handle))
+            float(tol), int(max_sweeps), int(width), C.byref(handle))
     if sparse:
         csc, keep = _csc_of(x)
-        check(L.sgdnet_covariance_probe(None, C.byref(csc), n, p, *tail))
+        check(L.sgdnet_covariance_path_probe(None, C.byref(csc), n, p, *tail))
     else:
         xd = np.asfortranarray(np.asarray(x, dtype=np.float64))
-        check(L.sgdnet_covariance_probe(dptr(xd), None, n, p, *tail))
-    P = p + K
+        check(L.sgdnet_covariance_path_probe(dptr(xd), None, n, p, *tail))
+    P, nl = p + K, lam.size
     return _cov_fields(handle, {"ld": (1,), "mu": (P if multi else p + 2,), "M": (P, P), "c": (p, K), "S": lambda o: (p, o.ld),
-                                "Sd": (p,), "ct": (p, K)})
+                                "Sd": (p,), "ct": (p, K), "W": (nl, p, K), "G": (nl, p, K), "sweeps": (nl,), "unconverged": (nl,),
+                                "tol": (1,), "max_iter": (1,)})
 
 
 def cv_covariance_probe(x, y, fold, n_groups, alphas, lambdas, *, train_on="fold", wide=False, intercept=True, standardize=True,
@@ -281,7 +286,8 @@ def cv_covariance_probe(x, y, fold, n_groups, alphas, lambdas, *, train_on="fold
     sgdnet_cv_*covariance_*.  fold: group ids 0 .. n_groups - 1; alphas: (A,); lambdas: (A, L).  y (n,): gaussian; (n, K):
     mgaussian (family and n_classes override what y's shape says, for the refusals).  Returns mu, Mg (G, Pa, Pa), total
     (Pa, Pa; train_on = "rest"), scale (G, p), mean (G, p + K), tstat (3, G), pen_a and pen_b (A, G, L), ridge (A, G), and Mt
-    (narrow) or ld, s, d (G, p + K), ysd (G, K; mgaussian), S (G, p, ld), Sd (G, p), ct (G, p, K) (wide)."""
+    (narrow) or ld, s, d (G, p + K), ysd (G, K; mgaussian), S (G, p, ld), Sd (G, p), ct (G, p, K) (wide); and what the path
+    kernel wrote: W, G (A, G, L, p, K), sweeps, unconverged (A, G, L; integers), with tol and max_iter as it got them."""
     sparse = hasattr(x, "tocsc")
     n, p = x.shape
     y = np.asarray(y, dtype=np.float64)
@@ -311,5 +317,6 @@ def cv_covariance_probe(x, y, fold, n_groups, alphas, lambdas, *, train_on="fold
     o = _cov_fields(handle, {"ld": (1,), "mu": (p + 2 * K if multi else p + 2,), "Mg": (G, Pa, Pa), "total": (Pa, Pa),
                              "Mt": (G, p, p + K) if multi else (G, p + 1, p + 1), "scale": (G, p), "mean": (G, p + K), "tstat": (3, G),
                              "pen_a": (A, G, nl), "pen_b": (A, G, nl), "ridge": (A, G), "s": (G, p + K), "d": (G, p + K), "ysd": (G, K),
-                             "S": lambda o: (G, p, o.ld), "Sd": (G, p), "ct": (G, p, K)})
+                             "S": lambda o: (G, p, o.ld), "Sd": (G, p), "ct": (G, p, K), "W": (A, G, nl, p, K), "G": (A, G, nl, p, K),
+                             "sweeps": (A, G, nl), "unconverged": (A, G, nl), "tol": (1,), "max_iter": (1,)})
     return o
