@@ -1402,6 +1402,13 @@ struct Events {
       if (v) (void)hipEventDestroy(v);
     if (st) (void)hipStreamDestroy(st);
   }
+  // the run's own non-blocking stream and the four events its phases are timed between
+  hipError_t open() {
+    hipError_t err = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    for (hipEvent_t& v : e)
+      if (err == hipSuccess) err = hipEventCreate(&v);
+    return err;
+  }
 };
 
 // Diagnostics (covariance.hpp: CovTap): `count` doubles (words) at dev, copied behind whatever the stream holds so far.
@@ -1432,7 +1439,154 @@ hipError_t tap_path(CovTap* tap, const double* W, const double* G, size_t coefs,
   return tap_i32(tap, "unconverged", unconverged, paths, st);
 }
 
-// covariance_run and wcovariance_run: the same uploads, moments pass and downloads around two path kernels.
+// `count` values at offset off of the arena into v, behind whatever the stream holds so far
+template <class T>
+hipError_t download(const Arena& A, size_t off, size_t count, std::vector<T>* v, hipStream_t st) {
+  v->resize(count);
+  return count ? hipMemcpyAsync(v->data(), A.base + off, sizeof(T) * count, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+static_assert(kTileRows == kMomentTileRows && kTileCols == 16, "group_rows.hpp and wide_layout.hpp count these tiles");
+
+// The moments stage of all six runs: the inputs on the device (x sparse or dense, y as n x K, the parameter vectors of the
+// mode), the centres mu, the dense pass's partial tiles and the moment matrices, and the launches from the ones to the others.
+//   a fit (G = 0):  one ncols x ncols matrix over ncols = p + K columns, plain row chunks of the n rows;
+//   a CV (G > 0):   one per group over ncols = p + K + 1 columns (the last: the ones), and their total; dense x reads its
+//                   rows through a GroupRows, sparse x takes a row's group from fold.
+// responses: the K response columns of the mcovariance modes (false: the one response of the covariance modes).  The CV form
+// alone tells them apart: cov_group_response_kernel against cov_response_centre_kernel + cov_group_responses_kernel, and mu of
+// p + 2 against p + 2 K entries (the features' centres | the responses' sums | their means).
+struct Moments {
+  struct Param {
+    size_t off;
+    const double* host;
+    size_t count;
+  };
+  const int64_t n;
+  const int p, K, G, ncols, pairs, centre;
+  const bool sparse, responses;
+  const int64_t nnz, rows_per_chunk;     // (rows_per_chunk: what the tile kernel is handed, 0 with a GroupRows)
+  const size_t chunks, mu_len, M_elems;
+  const AscendingColumns cols;
+  const double* const x_dense;
+  const int32_t* const colptr;
+  const double* const y;
+  const int32_t* const fold;
+  const GroupRows* const rows;
+  std::vector<Param> params;
+  size_t o_x = 0, o_colptr = 0, o_rowidx = 0, o_fold = 0, o_perm = 0, o_cbegin = 0, o_gchunk = 0, o_y = 0, o_mu = 0, o_part = 0, o_M = 0, o_total = 0;
+
+  // pb: any of the four problems, validated.  A CV hands over its groups: fold and, for dense x, the rows by group.
+  template <class Problem>
+  Moments(const Problem& pb, int K_, bool responses_, bool wide, int G_ = 0, const int32_t* fold_ = nullptr, const GroupRows* rows_ = nullptr)
+      : n(pb.n), p((int)pb.p), K(K_), G(G_), ncols(p + K + (G ? 1 : 0)), pairs((int)wide_tile_pairs(ncols)), centre(pb.centre ? 1 : 0),
+        sparse(pb.x_dense == nullptr), responses(responses_), nnz(sparse ? pb.colptr[p] : 0),
+        rows_per_chunk(G ? 0 : cov_rows_per_chunk(n, ncols, wide)),
+        chunks(sparse ? 0 : (G ? rows_->chunks() : (size_t)((n + rows_per_chunk - 1) / rows_per_chunk))),
+        mu_len((size_t)(G && responses ? p + 2 * K : p + K + 1)), M_elems((size_t)ncols * (size_t)ncols),
+        cols(sparse ? pb.colptr : (const int32_t*)nullptr, pb.rowidx, pb.values, sparse ? p : 0), x_dense(pb.x_dense), colptr(pb.colptr),
+        y(pb.y), fold(fold_), rows(sparse ? nullptr : rows_) {}
+
+  void reserve(Arena& A) {
+    o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
+    o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
+    o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
+    o_fold = A.reserve(sparse && G ? sizeof(int32_t) * (size_t)n : 0);
+    o_perm = A.reserve(rows ? sizeof(int64_t) * (size_t)n : 0);
+    o_cbegin = A.reserve(rows ? sizeof(int64_t) * (chunks + 1) : 0);
+    o_gchunk = A.reserve(rows ? sizeof(int32_t) * ((size_t)G + 1) : 0);
+    o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
+    o_mu = A.reserve(sizeof(double) * mu_len);
+    o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
+    o_M = A.reserve(sizeof(double) * (size_t)(G ? G : 1) * M_elems);
+    o_total = A.reserve(G ? sizeof(double) * M_elems : 0);
+  }
+  // a parameter vector of the mode (scale, the penalties, the mixes, ...): reserved here, uploaded behind y in this order
+  size_t param(Arena& A, const double* host, size_t count) {
+    params.push_back({A.reserve(sizeof(double) * count), host, count});
+    return params.back().off;
+  }
+
+  hipError_t upload(const Arena& A, hipStream_t st) const {
+    hipError_t e = hipSuccess;
+    auto up = [&](size_t off, const void* src, size_t bytes) {
+      if (e == hipSuccess && bytes) e = hipMemcpyAsync(A.base + off, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    if (sparse) {
+      up(o_x, cols.values, sizeof(double) * (size_t)nnz);
+      up(o_rowidx, cols.rowidx, sizeof(int32_t) * (size_t)nnz);
+      up(o_colptr, colptr, sizeof(int32_t) * (size_t)(p + 1));
+      if (G) up(o_fold, fold, sizeof(int32_t) * (size_t)n);
+    } else {
+      up(o_x, x_dense, sizeof(double) * (size_t)(n * (int64_t)p));
+      if (rows) {
+        up(o_perm, rows->perm.data(), sizeof(int64_t) * (size_t)n);
+        up(o_cbegin, rows->chunk_begin.data(), sizeof(int64_t) * (chunks + 1));
+        up(o_gchunk, rows->group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1));
+      }
+    }
+    up(o_y, y, sizeof(double) * (size_t)n * (size_t)K);
+    for (const Param& q : params) up(q.off, q.host, sizeof(double) * q.count);
+    return e;
+  }
+
+  // mu and the moment matrix at o_M.  The caller asks hipGetLastError.
+  void launch_fit(const Arena& A, hipStream_t st) const {
+    const double* d_x = A.at<double>(o_x);
+    const double* d_y = A.at<double>(o_y);
+    double* d_mu = A.at<double>(o_mu);
+    const int32_t* none = nullptr;
+    if (sparse) {
+      hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)ncols), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, K, centre, d_mu);
+      hipLaunchKernelGGL(cov_sparse_pair_kernel<false>, dim3((unsigned)p, (unsigned)ncols), dim3(kBlock), 0, st, A.at<int32_t>(o_colptr),
+                         A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, K, none, A.at<double>(o_M));
+    } else {
+      hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)ncols), dim3(kBlock), 0, st, d_x, none, d_y, n, p, K, centre, d_mu);
+      hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, ncols,
+                         rows_per_chunk, (const int64_t*)nullptr, (const int64_t*)nullptr, A.at<double>(o_part));
+      hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks, none, ncols,
+                         A.at<double>(o_M));
+    }
+  }
+  // the CV form (below, before the CV runs): mu and the groups' matrices at o_M; their total, for a CV that trains on the
+  // rest; a CV's taps of what this stage left
+  void launch_cv(const Arena& A, hipStream_t st) const;
+  void launch_total(const Arena& A, hipStream_t st) const;
+  hipError_t tap_cv(const Arena& A, CovTap* tap, bool rest, hipStream_t st) const;
+};
+
+// What a path kernel writes over `jobs` jobs of L lambdas and pK coefficients each: W, G, sweeps, unconverged and, where the
+// kernel leaves c~ per job (own_c: the narrow kernels and the wide fits' scale kernels), c
+struct PathOut {
+  const size_t coefs, paths, c_len;
+  const bool own_c;
+  const size_t o_W, o_G, o_c, o_sweeps, o_unconv;
+  PathOut(Arena& A, size_t jobs, int L, size_t pK, bool own_c_)
+      : coefs(jobs * (size_t)L * pK), paths(jobs * (size_t)L), c_len(jobs * pK), own_c(own_c_), o_W(A.reserve(sizeof(double) * coefs)),
+        o_G(A.reserve(sizeof(double) * coefs)), o_c(A.reserve(own_c ? sizeof(double) * c_len : 0)), o_sweeps(A.reserve(sizeof(int32_t) * paths)),
+        o_unconv(A.reserve(sizeof(int32_t) * paths)) {}
+  // behind the path kernel: the tap's copies of the four buffers, then the result's (R: any of the four results; c is only
+  // sized where it is not the kernel's own)
+  template <class R>
+  hipError_t fetch(const Arena& A, CovTap* tap, double tol, unsigned max_iter, R* out, hipStream_t st) const {
+    // every vector is sized before the first copy: a copy into pageable memory waits for the path kernel, and zero-filling
+    // W and G (120 MB each in a wide 50-job CV) belongs in that wait, not behind it
+    out->c.resize(c_len);
+    out->w.resize(coefs);
+    out->g.resize(coefs);
+    out->sweeps.resize(paths);
+    out->unconverged.resize(paths);
+    hipError_t e = tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), coefs, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv), paths, tol, max_iter, st);
+    if (e == hipSuccess && own_c) e = download(A, o_c, c_len, &out->c, st);
+    if (e == hipSuccess) e = download(A, o_W, coefs, &out->w, st);
+    if (e == hipSuccess) e = download(A, o_G, coefs, &out->g, st);
+    if (e == hipSuccess) e = download(A, o_sweeps, paths, &out->sweeps, st);
+    if (e == hipSuccess) e = download(A, o_unconv, paths, &out->unconverged, st);
+    return e;
+  }
+};
+
+// covariance_run and wcovariance_run: the moments stage and the path outputs around two path kernels.
 // wide: S goes to global memory (wide_scale_kernel) and cov_wide_path_kernel<width> runs the path; the dense row
 // chunks follow wide_row_chunks.  Not wide: exactly the launches covariance mode has always made.
 int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int width, CovTap* tap) {
@@ -1446,118 +1600,123 @@ int cov_run(const CovarianceProblem& pb, CovarianceResult* out, bool wide, int w
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
 
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-  const int32_t* rowidx = cols.rowidx;
-  const double* values = cols.values;
-
-  // dense x: the tile pairs and the row chunks (a function of n and p alone)
-  const int T = (P1 + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t rows_per_chunk = wide ? wide_rows_per_chunk(n, P1, kTileRows) : dense_rows_per_chunk(n, pairs);
-  const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-
   Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P1 : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(P1 + 1));     // (the last entry: mean of y, for the group moments)
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
-  const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
-  const size_t o_M = A.reserve(sizeof(double) * (size_t)P1 * (size_t)P1);
+  Moments m(pb, 1, false, wide);
+  m.reserve(A);
+  const size_t o_scale = m.param(A, pb.scale, (size_t)p), o_alpha = m.param(A, pb.alpha, (size_t)L), o_beta = m.param(A, pb.beta, (size_t)L);
   const int ld = (int)wide_leading_dim(p);
   const size_t o_S = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)p : 0);
   const size_t o_Sd = A.reserve(wide ? sizeof(double) * (size_t)p : 0);
-  const size_t o_alpha = A.reserve(sizeof(double) * (size_t)L);
-  const size_t o_beta = A.reserve(sizeof(double) * (size_t)L);
-  const size_t o_W = A.reserve(sizeof(double) * (size_t)L * (size_t)p);
-  const size_t o_G = A.reserve(sizeof(double) * (size_t)L * (size_t)p);
-  const size_t o_c = A.reserve(sizeof(double) * (size_t)p);
-  const size_t o_sweeps = A.reserve(sizeof(int32_t) * (size_t)L);
-  const size_t o_unconv = A.reserve(sizeof(int32_t) * (size_t)L);
+  const PathOut po(A, 1, L, (size_t)p, true);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
   Events ev;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  SGD_HIP_TRY(ev.open());
   hipStream_t st = ev.st;
-  double* d_x = A.at<double>(o_x);
-  int32_t* d_colptr = A.at<int32_t>(o_colptr);
-  int32_t* d_rowidx = A.at<int32_t>(o_rowidx);
-  double* d_y = A.at<double>(o_y);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_M = A.at<double>(o_M);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)P1, hipMemcpyHostToDevice, st));
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_scale), pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_alpha), pb.alpha, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_beta), pb.beta, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, st));
-
+  double* d_M = A.at<double>(m.o_M);
+  SGD_HIP_TRY(m.upload(A, st));
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, 1, pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel<false>, dim3((unsigned)p, (unsigned)P1), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_y,
-                       d_mu, n, p, 1, (const int32_t*)nullptr, d_M);
-  } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, 1, P1,
-                       rows_per_chunk, (const int64_t*)nullptr, (const int64_t*)nullptr, A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                       (const int32_t*)nullptr, P1, d_M);
-  }
+  m.launch_fit(A, st);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)P1 + 1, st));
+  SGD_HIP_TRY(tap_f64(tap, "mu", A.at<double>(m.o_mu), (size_t)P1 + 1, st));     // (the last entry: mean of y)
   SGD_HIP_TRY(tap_f64(tap, "M", d_M, (size_t)P1 * (size_t)P1, st));
   if (wide) {
     hipLaunchKernelGGL(wide_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, P1, ld, (double)n,
-                       A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
+                       A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(po.o_c));
     SGD_HIP_TRY(hipGetLastError());
     SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
     SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)ld * (size_t)p, st));
     SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_c), (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(po.o_c), (size_t)p, st));
     static const int ahead = exp_env_int("SGDNET_WCOV_PREFETCH", -1);     // (0 / 1: profiles/wcovariance_path.txt)
     const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
     const auto kernel = width == kWideNarrow ? (prefetch ? cov_wide_path_kernel<kWideNarrow, true> : cov_wide_path_kernel<kWideNarrow, false>)
                                              : (prefetch ? cov_wide_path_kernel<kWideFull, true> : cov_wide_path_kernel<kWideFull, false>);
-    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c), p, ld,
-                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
-                       A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(po.o_c), p, ld,
+                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(po.o_W),
+                       A.at<double>(po.o_G), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
   } else {
     hipLaunchKernelGGL(cov_path_kernel, dim3(1), dim3(64), 0, st, d_M, A.at<double>(o_scale), p, 1, (double)n, (const double*)nullptr,
                        A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr, pb.max_iter, pb.tol,
-                       A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+                       A.at<double>(po.o_W), A.at<double>(po.o_G), A.at<double>(po.o_c), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
   }
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
-  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), (size_t)L * (size_t)p, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
-                       (size_t)L, pb.tol, pb.max_iter, st));
-
-  out->mean.resize((size_t)P1);
-  out->c.resize((size_t)p);
-  out->w.resize((size_t)L * (size_t)p);
-  out->g.resize((size_t)L * (size_t)p);
-  out->sweeps.resize((size_t)L);
-  out->unconverged.resize((size_t)L);
-  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), d_mu, sizeof(double) * (size_t)P1, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->c.data(), A.at<double>(o_c), sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->w.data(), A.at<double>(o_W), sizeof(double) * (size_t)L * (size_t)p, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->g.data(), A.at<double>(o_G), sizeof(double) * (size_t)L * (size_t)p, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->sweeps.data(), A.at<int32_t>(o_sweeps), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->unconverged.data(), A.at<int32_t>(o_unconv), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
+  SGD_HIP_TRY(po.fetch(A, tap, pb.tol, pb.max_iter, out, st));
+  SGD_HIP_TRY(download(A, m.o_mu, (size_t)p, &out->mean, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  out->mean.resize((size_t)p);     // (entry p was the response's sum)
+  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
+  if (wide) {
+    SGD_HIP_TRY(hipEventElapsedTime(&out->scale_ms, ev.e[1], ev.e[3]));
+    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[3], ev.e[2]));
+  } else {
+    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
+  }
+  return SGDNET_OK;
+}
+
+// mcovariance_run and wmcovariance_run: the same stages around two path kernels.
+// wide: S and c~ go to global memory (cov_wide_group_scale_kernel) and cov_wide_group_path_kernel<width> runs the path; the
+// dense row chunks follow wide_row_chunks.  Not wide: exactly the launches mcovariance mode has always made.
+int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, int width, CovTap* tap) {
+  const int64_t n = pb.n;
+  const int p = (int)pb.p, K = pb.K, nc = p + K, L = pb.n_lambda;
+  const bool sparse = pb.x_dense == nullptr;
+  const bool width_ok = wide ? (width == kWideNarrow || width == kWideFull) : (width == 0 || width == kMcovNarrow || width == kMcovWide);
+  if (n <= 0 || p <= 0 || K < 1 || pb.p > (wide ? wmcov_max_features(K) : mcov_max_features(K)) || L <= 0 || !pb.y || !width_ok ||
+      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
+    set_error("%s: invalid problem", wide ? "wmcovariance_run" : "mcovariance_run");
+    return SGDNET_EINVAL;
+  }
+  SGD_HIP_TRY(hipSetDevice(pb.device));
+  const size_t pK = (size_t)p * (size_t)K;
+  if (width == 0) width = mcov_path_width(pK);
+
+  Arena A;
+  Moments m(pb, K, true, wide);
+  m.reserve(A);
+  const size_t o_scale = m.param(A, pb.scale, (size_t)p), o_alpha = m.param(A, pb.alpha, (size_t)L), o_beta = m.param(A, pb.beta, (size_t)L);
+  const int ld = (int)wide_leading_dim(p);
+  const size_t o_S = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)p : 0);
+  const size_t o_Sd = A.reserve(wide ? sizeof(double) * (size_t)p : 0);
+  const PathOut po(A, 1, L, pK, true);
+  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+
+  Events ev;
+  SGD_HIP_TRY(ev.open());
+  hipStream_t st = ev.st;
+  double* d_M = A.at<double>(m.o_M);
+  SGD_HIP_TRY(m.upload(A, st));
+  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
+  m.launch_fit(A, st);
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
+  SGD_HIP_TRY(tap_f64(tap, "mu", A.at<double>(m.o_mu), (size_t)nc, st));
+  SGD_HIP_TRY(tap_f64(tap, "M", d_M, (size_t)nc * (size_t)nc, st));
+  if (wide) {
+    hipLaunchKernelGGL(cov_wide_group_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, K, ld, (double)n,
+                       A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(po.o_c));
+    SGD_HIP_TRY(hipGetLastError());
+    SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
+    SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)ld * (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)p, st));
+    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(po.o_c), pK, st));
+    const auto kernel = width == kWideNarrow ? cov_wide_group_path_kernel<kWideNarrow> : cov_wide_group_path_kernel<kWideFull>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(po.o_c), p, K, ld,
+                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(po.o_W),
+                       A.at<double>(po.o_G), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
+  } else {
+    const auto kernel = width == kMcovNarrow ? cov_group_path_kernel<kMcovNarrow> : cov_group_path_kernel<kMcovWide>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_M, A.at<double>(o_scale), p, K, 1, (double)n, (const double*)nullptr,
+                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr, pb.max_iter, pb.tol,
+                       A.at<double>(po.o_W), A.at<double>(po.o_G), A.at<double>(po.o_c), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
+  }
+  SGD_HIP_TRY(hipGetLastError());
+  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
+  SGD_HIP_TRY(po.fetch(A, tap, pb.tol, pb.max_iter, out, st));
+  SGD_HIP_TRY(download(A, m.o_mu, (size_t)p, &out->mean, st));
+  SGD_HIP_TRY(hipStreamSynchronize(st));
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   if (wide) {
     SGD_HIP_TRY(hipEventElapsedTime(&out->scale_ms, ev.e[1], ev.e[3]));
@@ -1576,155 +1735,98 @@ int wcovariance_run(const CovarianceProblem& pb, CovarianceResult* out, int widt
   return cov_run(pb, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)), tap);
 }
 
-
-namespace {
-
-// mcovariance_run and wmcovariance_run: the same uploads, moments pass and downloads around two path kernels.
-// wide: S and c~ go to global memory (cov_wide_group_scale_kernel) and cov_wide_group_path_kernel<width> runs the path; the
-// dense row chunks follow wide_row_chunks.  Not wide: exactly the launches mcovariance mode has always made.
-int mcov_run(const McovarianceProblem& pb, McovarianceResult* out, bool wide, int width, CovTap* tap) {
-  const int64_t n = pb.n;
-  const int p = (int)pb.p, K = pb.K, nc = p + K, L = pb.n_lambda;
-  const bool sparse = pb.x_dense == nullptr;
-  const bool width_ok = wide ? (width == kWideNarrow || width == kWideFull) : (width == 0 || width == kMcovNarrow || width == kMcovWide);
-  if (n <= 0 || p <= 0 || K < 1 || pb.p > (wide ? wmcov_max_features(K) : mcov_max_features(K)) || L <= 0 || !pb.y || !width_ok ||
-      (!sparse && pb.colptr) || (sparse && (!pb.colptr || !pb.rowidx || !pb.values))) {
-    set_error("%s: invalid problem", wide ? "wmcovariance_run" : "mcovariance_run");
-    return SGDNET_EINVAL;
-  }
-  SGD_HIP_TRY(hipSetDevice(pb.device));
-
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-
-  // dense x: the tile pairs and the row chunks (a function of n, p and K alone)
-  const int T = (nc + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  const int64_t rows_per_chunk = wide ? wide_rows_per_chunk(n, nc, kTileRows) : dense_rows_per_chunk(n, pairs);
-  const int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  const size_t pK = (size_t)p * (size_t)K;
-  if (width == 0) width = mcov_path_width(pK);
-
-  Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(nc + 1));
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
-  const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
-  const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
-  const int ld = (int)wide_leading_dim(p);
-  const size_t o_S = A.reserve(wide ? sizeof(double) * (size_t)ld * (size_t)p : 0);
-  const size_t o_Sd = A.reserve(wide ? sizeof(double) * (size_t)p : 0);
-  const size_t o_alpha = A.reserve(sizeof(double) * (size_t)L);
-  const size_t o_beta = A.reserve(sizeof(double) * (size_t)L);
-  const size_t o_W = A.reserve(sizeof(double) * (size_t)L * pK);
-  const size_t o_G = A.reserve(sizeof(double) * (size_t)L * pK);
-  const size_t o_c = A.reserve(sizeof(double) * pK);
-  const size_t o_sweeps = A.reserve(sizeof(int32_t) * (size_t)L);
-  const size_t o_unconv = A.reserve(sizeof(int32_t) * (size_t)L);
-  SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
-
-  Events ev;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
-  hipStream_t st = ev.st;
-  double* d_x = A.at<double>(o_x);
-  int32_t* d_colptr = A.at<int32_t>(o_colptr);
-  int32_t* d_rowidx = A.at<int32_t>(o_rowidx);
-  double* d_y = A.at<double>(o_y);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_M = A.at<double>(o_M);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(d_rowidx, cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(d_colptr, pb.colptr, sizeof(int32_t) * (size_t)(p + 1), hipMemcpyHostToDevice, st));
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n * (size_t)K, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_scale), pb.scale, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_alpha), pb.alpha, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_beta), pb.beta, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, st));
-
-  SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, K, pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel<false>, dim3((unsigned)p, (unsigned)nc), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_y,
-                       d_mu, n, p, K, (const int32_t*)nullptr, d_M);
-  } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, K,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, nc,
-                       rows_per_chunk, (const int64_t*)nullptr, (const int64_t*)nullptr, A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                       (const int32_t*)nullptr, nc, d_M);
-  }
-  SGD_HIP_TRY(hipGetLastError());
-  SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)nc, st));
-  SGD_HIP_TRY(tap_f64(tap, "M", d_M, (size_t)nc * (size_t)nc, st));
-  if (wide) {
-    hipLaunchKernelGGL(cov_wide_group_scale_kernel, dim3((unsigned)p), dim3(kBlock), 0, st, d_M, A.at<double>(o_scale), p, K, ld, (double)n,
-                       A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c));
-    SGD_HIP_TRY(hipGetLastError());
-    SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
-    SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)ld * (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_c), pK, st));
-    const auto kernel = width == kWideNarrow ? cov_wide_group_path_kernel<kWideNarrow> : cov_wide_group_path_kernel<kWideFull>;
-    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_c), p, K, ld,
-                       A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, pb.max_iter, pb.tol, A.at<double>(o_W),
-                       A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
-  } else if (width == kMcovNarrow)
-    hipLaunchKernelGGL(cov_group_path_kernel<kMcovNarrow>, dim3(1), dim3(kMcovNarrow), 0, st, d_M, A.at<double>(o_scale), p, K, 1, (double)n,
-                       (const double*)nullptr, A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr,
-                       pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps),
-                       A.at<int32_t>(o_unconv));
-  else
-    hipLaunchKernelGGL(cov_group_path_kernel<kMcovWide>, dim3(1), dim3(kMcovWide), 0, st, d_M, A.at<double>(o_scale), p, K, 1, (double)n,
-                       (const double*)nullptr, A.at<double>(o_alpha), A.at<double>(o_beta), L, pb.ridge ? 1 : 0, (const int32_t*)nullptr,
-                       pb.max_iter, pb.tol, A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps),
-                       A.at<int32_t>(o_unconv));
-  SGD_HIP_TRY(hipGetLastError());
-  SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
-  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), (size_t)L * pK, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
-                       (size_t)L, pb.tol, pb.max_iter, st));
-
-  out->mean.resize((size_t)p);
-  out->c.resize(pK);
-  out->w.resize((size_t)L * pK);
-  out->g.resize((size_t)L * pK);
-  out->sweeps.resize((size_t)L);
-  out->unconverged.resize((size_t)L);
-  SGD_HIP_TRY(hipMemcpyAsync(out->mean.data(), d_mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->c.data(), A.at<double>(o_c), sizeof(double) * pK, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->w.data(), A.at<double>(o_W), sizeof(double) * (size_t)L * pK, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->g.data(), A.at<double>(o_G), sizeof(double) * (size_t)L * pK, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->sweeps.data(), A.at<int32_t>(o_sweeps), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipMemcpyAsync(out->unconverged.data(), A.at<int32_t>(o_unconv), sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
-  SGD_HIP_TRY(hipStreamSynchronize(st));
-  SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
-  if (wide) {
-    SGD_HIP_TRY(hipEventElapsedTime(&out->scale_ms, ev.e[1], ev.e[3]));
-    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[3], ev.e[2]));
-  } else {
-    SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[1], ev.e[2]));
-  }
-  return SGDNET_OK;
-}
-
-}  // namespace
-
 int mcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width, CovTap* tap) { return mcov_run(pb, out, false, width, tap); }
 
 int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int width, CovTap* tap) {
   return mcov_run(pb, out, true, width != 0 ? width : wmcov_path_width((int)std::min<int64_t>(pb.p, kWcovMaxFeatures)), tap);
 }
 
+// ---- cross-validation: the CV form of the moments stage and what the four CV runs share besides ----
+namespace {
+
+void Moments::launch_cv(const Arena& A, hipStream_t st) const {
+  const double* d_x = A.at<double>(o_x);
+  const double* d_y = A.at<double>(o_y);
+  double* d_mu = A.at<double>(o_mu);
+  double* d_Mg = A.at<double>(o_M);
+  const int32_t* d_colptr = sparse ? A.at<int32_t>(o_colptr) : nullptr;
+  const int32_t* d_fold = A.at<int32_t>(o_fold);
+  if (sparse) hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)(p + K)), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, K, centre, d_mu);
+  else hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)(p + K)), dim3(kBlock), 0, st, d_x, d_colptr, d_y, n, p, K, centre, d_mu);
+  if (responses) hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
+  if (sparse) {
+    if (responses)
+      hipLaunchKernelGGL(cov_group_responses_kernel, dim3((unsigned)K, (unsigned)K, (unsigned)G), dim3(kBlock), 0, st, d_y, d_fold, d_mu, n, p, K,
+                         d_Mg);
+    else hipLaunchKernelGGL(cov_group_response_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_y, d_fold, d_mu, n, p, d_Mg);
+    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)ncols, (unsigned)G), dim3(kBlock), 0, st, d_colptr,
+                       A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, K, d_fold, d_Mg);
+  } else {
+    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, ncols,
+                       rows_per_chunk, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
+                       A.at<int32_t>(o_gchunk), ncols, d_Mg);
+  }
+}
+// the groups' matrices added in group order
+void Moments::launch_total(const Arena& A, hipStream_t st) const {
+  hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((M_elems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, A.at<double>(o_M), G, (int)M_elems,
+                     A.at<double>(o_total));
+}
+hipError_t Moments::tap_cv(const Arena& A, CovTap* tap, bool rest, hipStream_t st) const {
+  hipError_t e = tap_f64(tap, "mu", A.at<double>(o_mu), mu_len, st);
+  if (e == hipSuccess) e = tap_f64(tap, "Mg", A.at<double>(o_M), (size_t)G * M_elems, st);
+  if (e == hipSuccess && rest) e = tap_f64(tap, "total", A.at<double>(o_total), M_elems, st);
+  return e;
+}
+
+// What every CV assembly leaves besides its matrices: per training set scale (p), mean (nc = p + K) and tstat (three
+// vectors over the sets); per job the two penalties per lambda and the ridge flag
+struct CvSets {
+  const size_t G, jobs, scales, means, pens;
+  const size_t o_scale, o_mean, o_tstat, o_pen_a, o_pen_b, o_ridge;
+  CvSets(Arena& A, int G_, int n_mix, int L, int p, int nc)
+      : G((size_t)G_), jobs((size_t)n_mix * G), scales(G * (size_t)p), means(G * (size_t)nc), pens(jobs * (size_t)L),
+        o_scale(A.reserve(sizeof(double) * scales)), o_mean(A.reserve(sizeof(double) * means)), o_tstat(A.reserve(sizeof(double) * 3 * G)),
+        o_pen_a(A.reserve(sizeof(double) * pens)), o_pen_b(A.reserve(sizeof(double) * pens)), o_ridge(A.reserve(sizeof(int32_t) * jobs)) {}
+  hipError_t tap(const Arena& A, CovTap* tap, hipStream_t st) const {
+    hipError_t e = tap_f64(tap, "scale", A.at<double>(o_scale), scales, st);
+    if (e == hipSuccess) e = tap_f64(tap, "mean", A.at<double>(o_mean), means, st);
+    if (e == hipSuccess) e = tap_f64(tap, "tstat", A.at<double>(o_tstat), 3 * G, st);
+    if (e == hipSuccess) e = tap_f64(tap, "pen_a", A.at<double>(o_pen_a), pens, st);
+    if (e == hipSuccess) e = tap_f64(tap, "pen_b", A.at<double>(o_pen_b), pens, st);
+    if (e == hipSuccess) e = tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st);
+    return e;
+  }
+  template <class R>
+  hipError_t fetch(const Arena& A, R* out, std::vector<double>* tstat, hipStream_t st) const {
+    hipError_t e = download(A, o_tstat, 3 * G, tstat, st);
+    if (e == hipSuccess) e = download(A, o_mean, means, &out->mean, st);
+    if (e == hipSuccess) e = download(A, o_scale, scales, &out->scale, st);
+    return e;
+  }
+  // once the stream is drained: tstat's three vectors
+  void split(const std::vector<double>& tstat, std::vector<double>* a, std::vector<double>* b, std::vector<double>* c) const {
+    a->assign(tstat.begin(), tstat.begin() + G);
+    b->assign(tstat.begin() + G, tstat.begin() + 2 * G);
+    c->assign(tstat.begin() + 2 * G, tstat.end());
+  }
+};
+
+// the wide CV runs: c~ is the training set's (ct: G x len), every mix of a set gets its copy (c: jobs x len, job = mix G + T)
+void copy_to_jobs(const std::vector<double>& ct, size_t G, size_t len, std::vector<double>* c) {
+  for (size_t job = 0; job * len < c->size(); ++job) std::copy(ct.begin() + (job % G) * len, ct.begin() + (job % G + 1) * len, c->begin() + job * len);
+}
+
+// dense x of a CV: the rows by group, in chunks of the size one fit of n rows over ncols columns would use (the summation
+// order is a function of (n, ncols, fold) alone).  More than kCovMaxRowChunks chunks are refused by the mode's name.
+int cv_group_rows(const char* mode, const int32_t* fold, int64_t n, int G, int ncols, bool wide, GroupRows* rows) {
+  if (group_rows(fold, n, G, cov_rows_per_chunk(n, ncols, wide), kCovMaxRowChunks, rows)) return SGDNET_OK;
+  set_error("mode = %s needs the rows of the groups in at most %d chunks: %d groups of %lld rows", mode, kCovMaxRowChunks, G, (long long)n);
+  return SGDNET_EUNSUPPORTED;
+}
+
+}  // namespace
 
 int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, CovTap* tap) {
   const int64_t n = pb.n;
@@ -1737,177 +1839,59 @@ int covariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, Co
     return SGDNET_EINVAL;
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
-  const size_t jobs = (size_t)A_mix * (size_t)G;
-
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-
-  // dense x: the rows sorted by group (stable: a group's rows stay in row order) and cut into chunks of the size one
-  // fit of n rows would use, none across a group's end: the summation order is a function of (n, p, fold) alone
-  const int T = (Pa + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  std::vector<int64_t> perm, chunk_begin;
-  std::vector<int32_t> group_chunk;
-  if (!sparse) {
-    std::vector<int64_t> start((size_t)G + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
-    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
-    perm.resize((size_t)n);
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
-    const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
-    group_chunk.assign((size_t)G + 1, 0);
-    for (int g = 0; g < G; ++g) {
-      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
-      if (chunk_begin.size() > (size_t)kCovMaxRowChunks) {
-        set_error("mode = covariance needs the rows of the groups in at most %d chunks: %d groups of %lld rows", kCovMaxRowChunks, G,
-                  (long long)n);
-        return SGDNET_EUNSUPPORTED;
-      }
-      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
-    }
-    chunk_begin.push_back(n);
-  }
+  GroupRows rows;
+  if (!sparse)
+    if (const int rc = cv_group_rows("covariance", pb.fold, n, G, Pa, false, &rows)) return rc;
   if (sparse && G > kCovMaxRowChunks) {       // (the pair kernel's gridDim.z)
     set_error("mode = covariance needs at most %d groups of sparse rows: %d groups", kCovMaxRowChunks, G);
     return SGDNET_EUNSUPPORTED;
   }
-  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
-  const size_t Melems = (size_t)Pa * (size_t)Pa;
+  const int rest = pb.train_on_rest ? 1 : 0;
 
   Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P1 : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
-  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
-  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
-  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)Pa);
-  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
-  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
-  const size_t o_total = A.reserve(sizeof(double) * Melems);
-  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
-  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  Moments m(pb, 1, false, false, G, pb.fold, &rows);
+  m.reserve(A);
+  const size_t o_mix = m.param(A, pb.mix, (size_t)A_mix), o_lambda = m.param(A, pb.lambda, (size_t)A_mix * (size_t)L);
   const size_t o_Mt = A.reserve(sizeof(double) * (size_t)G * (size_t)P1 * (size_t)P1);
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
-  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
-  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
-  const size_t o_alpha = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_beta = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
-  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
-  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
-  const size_t o_c = A.reserve(sizeof(double) * jobs * (size_t)p);
-  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
-  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const CvSets sets(A, G, A_mix, L, p, P1);
+  const PathOut po(A, sets.jobs, L, (size_t)p, true);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
   Events ev;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  SGD_HIP_TRY(ev.open());
   hipStream_t st = ev.st;
-  double* d_x = A.at<double>(o_x);
-  double* d_y = A.at<double>(o_y);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_Mg = A.at<double>(o_Mg);
-  double* d_tstat = A.at<double>(o_tstat);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)P1, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
-
+  double* d_tstat = A.at<double>(sets.o_tstat);
+  SGD_HIP_TRY(m.upload(A, st));
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, 1,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_group_response_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_y, A.at<int32_t>(o_fold), d_mu, n, p, d_Mg);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
-                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, 1, A.at<int32_t>(o_fold), d_Mg);
-  } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, 1, Pa,
-                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
-  }
+  m.launch_cv(A, st);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  if (pb.train_on_rest)
-    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
-                       A.at<double>(o_total));
-  hipLaunchKernelGGL(cov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p,
-                     pb.train_on_rest ? 1 : 0, pb.centre ? 1 : 0, pb.standardize ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda),
-                     A_mix, L, A.at<double>(o_Mt), A.at<double>(o_scale), A.at<double>(o_mean), d_tstat, A.at<double>(o_alpha),
-                     A.at<double>(o_beta), A.at<int32_t>(o_ridge));
+  if (rest) m.launch_total(A, st);
+  hipLaunchKernelGGL(cov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, A.at<double>(m.o_M), A.at<double>(m.o_total),
+                     A.at<double>(m.o_mu), G, p, rest, pb.centre ? 1 : 0, pb.standardize ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda),
+                     A_mix, L, A.at<double>(o_Mt), A.at<double>(sets.o_scale), A.at<double>(sets.o_mean), d_tstat, A.at<double>(sets.o_pen_a),
+                     A.at<double>(sets.o_pen_b), A.at<int32_t>(sets.o_ridge));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
   if (tap) {
-    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)Pa, st));
-    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
-    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(m.tap_cv(A, tap, pb.train_on_rest, st));
     SGD_HIP_TRY(tap_f64(tap, "Mt", A.at<double>(o_Mt), (size_t)G * (size_t)P1 * (size_t)P1, st));
-    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)P1, st));
-    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_alpha), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_beta), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+    SGD_HIP_TRY(sets.tap(A, tap, st));
   }
-  hipLaunchKernelGGL(cov_path_kernel, dim3((unsigned)jobs), dim3(64), 0, st, A.at<double>(o_Mt), A.at<double>(o_scale), p, G, 0.0,
-                     d_tstat, A.at<double>(o_alpha), A.at<double>(o_beta), L, 0, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol,
-                     A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  hipLaunchKernelGGL(cov_path_kernel, dim3((unsigned)sets.jobs), dim3(64), 0, st, A.at<double>(o_Mt), A.at<double>(sets.o_scale), p, G, 0.0,
+                     d_tstat, A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b), L, 0, A.at<int32_t>(sets.o_ridge), pb.max_iter, pb.tol,
+                     A.at<double>(po.o_W), A.at<double>(po.o_G), A.at<double>(po.o_c), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
-  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * (size_t)p, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
-                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
-
-  std::vector<double> tstat(3 * (size_t)G);
-  out->mean.resize((size_t)G * (size_t)P1);
-  out->scale.resize((size_t)G * (size_t)p);
-  out->c.resize(jobs * (size_t)p);
-  out->w.resize(jobs * (size_t)L * (size_t)p);
-  out->g.resize(jobs * (size_t)L * (size_t)p);
-  out->sweeps.resize(jobs * (size_t)L);
-  out->unconverged.resize(jobs * (size_t)L);
-  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
-  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
-  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
-  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
-  SGD_HIP_TRY(fetch(out->c.data(), o_c, sizeof(double) * out->c.size()));
-  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
-  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
-  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
-  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  std::vector<double> tstat;
+  SGD_HIP_TRY(po.fetch(A, tap, pb.tol, pb.max_iter, out, st));
+  SGD_HIP_TRY(sets.fetch(A, out, &tstat, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  out->n_train.assign(tstat.begin(), tstat.begin() + G);
-  out->y_scale.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
-  out->yy.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  sets.split(tstat, &out->n_train, &out->y_scale, &out->yy);
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
   return SGDNET_OK;
-}
-
-int64_t wcov_cv_row_chunks(int64_t n, int64_t p, const int64_t* count, int n_groups) {
-  const int64_t rows_per_chunk = wide_rows_per_chunk(n, p + 2, kTileRows);
-  int64_t chunks = 0;
-  for (int g = 0; g < n_groups; ++g) chunks += (count[g] + rows_per_chunk - 1) / rows_per_chunk;
-  return chunks;
 }
 
 // covariance_cv_run beyond kCovMaxFeatures features: the same group moments pass (the wide mode's row chunks),
@@ -1926,152 +1910,61 @@ int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, i
     set_error("wcovariance_cv_run: the path kernel's workgroup is %d or %d lanes, not %d", kWideNarrow, kWideFull, width);
     return SGDNET_EINVAL;
   }
-  const size_t jobs = (size_t)A_mix * (size_t)G;
-
-  // dense x: the rows sorted by group (stable) and cut into chunks of the size one wide fit of n rows over p + 2 columns
-  // would use, none across a group's end: the summation order is a function of (n, p, fold) alone
-  const int64_t pairs = wide_tile_pairs(Pa);
-  std::vector<int64_t> perm, chunk_begin;
-  std::vector<int32_t> group_chunk;
-  if (!sparse) {
-    std::vector<int64_t> start((size_t)G + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
-    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
-    perm.resize((size_t)n);
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
-    const int64_t rows_per_chunk = wide_rows_per_chunk(n, Pa, kTileRows);
-    group_chunk.assign((size_t)G + 1, 0);
-    for (int g = 0; g < G; ++g) {
-      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
-      if (chunk_begin.size() > (size_t)kCovMaxRowChunks) {
-        set_error("mode = wcovariance needs the rows of the groups in at most %d chunks: %d groups of %lld rows", kCovMaxRowChunks, G,
-                  (long long)n);
-        return SGDNET_EUNSUPPORTED;
-      }
-      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
-    }
-    chunk_begin.push_back(n);
-  }
+  GroupRows rows;
+  if (!sparse)
+    if (const int rc = cv_group_rows("wcovariance", pb.fold, n, G, Pa, true, &rows)) return rc;
   if (sparse && G > kCovMaxRowChunks) {       // (the pair kernel's gridDim.z, the assembly's gridDim.y)
     set_error("mode = wcovariance needs at most %d groups of sparse rows: %d groups", kCovMaxRowChunks, G);
     return SGDNET_EUNSUPPORTED;
   }
-  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
-  if (wcov_cv_bytes(G, p, (int64_t)chunks) > kWcovCvBytes) {
+  if (wcov_cv_bytes(G, p, (int64_t)rows.chunks()) > kWcovCvBytes) {
     set_error("mode = wcovariance needs the moments and the scaled matrices of the groups within %zu bytes: %d groups of %d features are %zu bytes",
-              kWcovCvBytes, G, p, wcov_cv_bytes(G, p, (int64_t)chunks));
+              kWcovCvBytes, G, p, wcov_cv_bytes(G, p, (int64_t)rows.chunks()));
     return SGDNET_EUNSUPPORTED;
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
-
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-  const size_t Melems = (size_t)Pa * (size_t)Pa;      // (at most 4533^2 = 20 548 089: cov_total_kernel's int)
-  const int ld = (int)wide_leading_dim(p);
+  const int ld = (int)wide_leading_dim(p), rest = pb.train_on_rest ? 1 : 0;
 
   Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)P1 : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
-  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
-  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
-  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)Pa);
-  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
-  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
-  const size_t o_total = A.reserve(sizeof(double) * Melems);
-  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
-  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  Moments m(pb, 1, false, true, G, pb.fold, &rows);      // (Pa^2 is at most 4533^2 = 20 548 089: cov_total_kernel's int)
+  m.reserve(A);
+  const size_t o_mix = m.param(A, pb.mix, (size_t)A_mix), o_lambda = m.param(A, pb.lambda, (size_t)A_mix * (size_t)L);
   const size_t o_s = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
   const size_t o_d = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
   const size_t o_cst = A.reserve(sizeof(int32_t) * (size_t)G * (size_t)P1);
   const size_t o_S = A.reserve(sizeof(double) * (size_t)G * (size_t)ld * (size_t)p);
   const size_t o_Sd = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
   const size_t o_ct = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
-  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)P1);
-  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
-  const size_t o_alpha = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_beta = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
-  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
-  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * (size_t)p);
-  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
-  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const CvSets sets(A, G, A_mix, L, p, P1);
+  const PathOut po(A, sets.jobs, L, (size_t)p, false);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
   Events ev;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  SGD_HIP_TRY(ev.open());
   hipStream_t st = ev.st;
-  double* d_x = A.at<double>(o_x);
-  double* d_y = A.at<double>(o_y);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_Mg = A.at<double>(o_Mg);
-  double* d_tstat = A.at<double>(o_tstat);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)P1, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
-
+  double* d_Mg = A.at<double>(m.o_M);
+  double* d_total = A.at<double>(m.o_total);
+  double* d_tstat = A.at<double>(sets.o_tstat);
+  SGD_HIP_TRY(m.upload(A, st));
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, 1,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_group_response_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_y, A.at<int32_t>(o_fold), d_mu, n, p, d_Mg);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
-                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, 1, A.at<int32_t>(o_fold), d_Mg);
-  } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)P1), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, 1,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, 1, Pa,
-                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
-  }
-  if (pb.train_on_rest)
-    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
-                       A.at<double>(o_total));
+  m.launch_cv(A, st);
+  if (rest) m.launch_total(A, st);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  const int rest = pb.train_on_rest ? 1 : 0;
-  hipLaunchKernelGGL(wcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p, rest,
+  hipLaunchKernelGGL(wcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, d_total, A.at<double>(m.o_mu), G, p, rest,
                      pb.centre ? 1 : 0, pb.standardize ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_s),
-                     A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), A.at<double>(o_mean), d_tstat, A.at<double>(o_alpha),
-                     A.at<double>(o_beta), A.at<int32_t>(o_ridge));
-  hipLaunchKernelGGL(wcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total),
-                     A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), d_tstat, G, p, ld, rest,
-                     A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct));
+                     A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(sets.o_scale), A.at<double>(sets.o_mean), d_tstat,
+                     A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b), A.at<int32_t>(sets.o_ridge));
+  hipLaunchKernelGGL(wcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, d_total, A.at<double>(o_s),
+                     A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(sets.o_scale), d_tstat, G, p, ld, rest, A.at<double>(o_S),
+                     A.at<double>(o_Sd), A.at<double>(o_ct));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
   if (tap) {
-    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)Pa, st));
-    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
-    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(m.tap_cv(A, tap, pb.train_on_rest, st));
     SGD_HIP_TRY(tap_f64(tap, "s", A.at<double>(o_s), (size_t)G * (size_t)P1, st));
     SGD_HIP_TRY(tap_f64(tap, "d", A.at<double>(o_d), (size_t)G * (size_t)P1, st));
-    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)P1, st));
-    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_alpha), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_beta), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+    SGD_HIP_TRY(sets.tap(A, tap, st));
     SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)G * (size_t)ld * (size_t)p, st));
     SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)G * (size_t)p, st));
     SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_ct), (size_t)G * (size_t)p, st));
@@ -2080,49 +1973,22 @@ int wcovariance_cv_run(const CovarianceCvProblem& pb, CovarianceCvResult* out, i
   const bool prefetch = ahead < 0 ? wcov_path_ahead(p) : ahead != 0;
   const auto kernel = width == kWideNarrow ? (prefetch ? cov_wide_cv_path_kernel<kWideNarrow, true> : cov_wide_cv_path_kernel<kWideNarrow, false>)
                                            : (prefetch ? cov_wide_cv_path_kernel<kWideFull, true> : cov_wide_cv_path_kernel<kWideFull, false>);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
-                     ld, G, A.at<double>(o_alpha), A.at<double>(o_beta), L, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol, A.at<double>(o_W),
-                     A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)sets.jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
+                     ld, G, A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b), L, A.at<int32_t>(sets.o_ridge), pb.max_iter, pb.tol,
+                     A.at<double>(po.o_W), A.at<double>(po.o_G), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
-  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * (size_t)p, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
-                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
-
-  std::vector<double> tstat(3 * (size_t)G), ct((size_t)G * (size_t)p);
-  out->mean.resize((size_t)G * (size_t)P1);
-  out->scale.resize((size_t)G * (size_t)p);
-  out->c.resize(jobs * (size_t)p);
-  out->w.resize(jobs * (size_t)L * (size_t)p);
-  out->g.resize(jobs * (size_t)L * (size_t)p);
-  out->sweeps.resize(jobs * (size_t)L);
-  out->unconverged.resize(jobs * (size_t)L);
-  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
-  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
-  SGD_HIP_TRY(fetch(ct.data(), o_ct, sizeof(double) * ct.size()));
-  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
-  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
-  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
-  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
-  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
-  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  std::vector<double> tstat, ct;
+  SGD_HIP_TRY(po.fetch(A, tap, pb.tol, pb.max_iter, out, st));
+  SGD_HIP_TRY(sets.fetch(A, out, &tstat, st));
+  SGD_HIP_TRY(download(A, o_ct, (size_t)G * (size_t)p, &ct, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  for (size_t job = 0; job < jobs; ++job)      // c~ is the training set's: every mix of a set gets its copy
-    std::copy(ct.begin() + (job % (size_t)G) * (size_t)p, ct.begin() + (job % (size_t)G + 1) * (size_t)p, out->c.begin() + job * (size_t)p);
-  out->n_train.assign(tstat.begin(), tstat.begin() + G);
-  out->y_scale.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
-  out->yy.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  copy_to_jobs(ct, (size_t)G, (size_t)p, &out->c);
+  sets.split(tstat, &out->n_train, &out->y_scale, &out->yy);
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
   return SGDNET_OK;
-}
-
-int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups) {
-  const int64_t T = (p + K + 1 + kTileCols - 1) / kTileCols;
-  const int64_t rows_per_chunk = dense_rows_per_chunk(n, (int)(T * (T + 1) / 2));
-  int64_t chunks = 0;
-  for (int g = 0; g < n_groups; ++g) chunks += (count[g] + rows_per_chunk - 1) / rows_per_chunk;
-  return chunks;
 }
 
 // covariance_cv_run for K responses: the same group moments with the columns p .. p + K - 1 the responses and column p + K the
@@ -2138,178 +2004,64 @@ int mcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out,
     set_error("mcovariance_cv_run: invalid problem");
     return SGDNET_EINVAL;
   }
-  const size_t jobs = (size_t)A_mix * (size_t)G, pK = (size_t)p * (size_t)K;
+  const size_t pK = (size_t)p * (size_t)K;
   const int width = pb.width != 0 ? pb.width : mcov_path_width(pK);
-
-  // dense x: the rows sorted by group and cut into chunks, none across a group's end, as covariance_cv_run cuts them
-  const int T = (Pa + kTileCols - 1) / kTileCols, pairs = T * (T + 1) / 2;
-  std::vector<int64_t> perm, chunk_begin;
-  std::vector<int32_t> group_chunk;
-  if (!sparse) {
-    std::vector<int64_t> start((size_t)G + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
-    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
-    perm.resize((size_t)n);
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
-    const int64_t rows_per_chunk = dense_rows_per_chunk(n, pairs);
-    group_chunk.assign((size_t)G + 1, 0);
-    for (int g = 0; g < G; ++g) {
-      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
-      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
-    }
-    chunk_begin.push_back(n);
-  }
-  if ((sparse ? (size_t)G : chunk_begin.size() - 1) > (size_t)kCovMaxRowChunks) {     // (gridDim.y of the tile kernel, .z of the pair kernel)
+  // dense x: the rows by group as covariance_cv_run cuts them (gridDim.y of the tile kernel); sparse x: gridDim.z of the pair kernel
+  GroupRows rows;
+  if (sparse ? G > kCovMaxRowChunks : !group_rows(pb.fold, n, G, cov_rows_per_chunk(n, Pa, false), kCovMaxRowChunks, &rows)) {
     set_error("mcovariance_cv_run: more than %d row chunks or groups", kCovMaxRowChunks);
     return SGDNET_EINVAL;
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
-
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
-  const size_t Melems = (size_t)Pa * (size_t)Pa;
+  const int rest = pb.train_on_rest ? 1 : 0;
 
   Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
-  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
-  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
-  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(nc + K));      // the features' centres | the responses' sums | their means
-  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
-  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
-  const size_t o_total = A.reserve(sizeof(double) * Melems);
-  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
-  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  Moments m(pb, K, true, false, G, pb.fold, &rows);
+  m.reserve(A);
+  const size_t o_mix = m.param(A, pb.mix, (size_t)A_mix), o_lambda = m.param(A, pb.lambda, (size_t)A_mix * (size_t)L);
   const size_t o_Mt = A.reserve(sizeof(double) * (size_t)G * (size_t)p * (size_t)nc);
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
-  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
-  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
-  const size_t o_l2 = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_l1 = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
-  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
-  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
-  const size_t o_c = A.reserve(sizeof(double) * jobs * pK);
-  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
-  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const CvSets sets(A, G, A_mix, L, p, nc);      // (pen_a: the l2 strengths, pen_b: the group thresholds)
+  const PathOut po(A, sets.jobs, L, pK, true);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
   Events ev;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  SGD_HIP_TRY(ev.open());
   hipStream_t st = ev.st;
-  double* d_x = A.at<double>(o_x);
-  double* d_y = A.at<double>(o_y);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_Mg = A.at<double>(o_Mg);
-  double* d_tstat = A.at<double>(o_tstat);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)(p + 1), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n * (size_t)K, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
-
+  double* d_tstat = A.at<double>(sets.o_tstat);
+  SGD_HIP_TRY(m.upload(A, st));
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, K,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
-    hipLaunchKernelGGL(cov_group_responses_kernel, dim3((unsigned)K, (unsigned)K, (unsigned)G), dim3(kBlock), 0, st, d_y,
-                       A.at<int32_t>(o_fold), d_mu, n, p, K, d_Mg);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
-                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, K, A.at<int32_t>(o_fold), d_Mg);
-  } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, K,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, Pa,
-                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
-  }
+  m.launch_cv(A, st);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  if (pb.train_on_rest)
-    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
-                       A.at<double>(o_total));
+  if (rest) m.launch_total(A, st);
   // (20 (p + K) bytes of LDS: the moment budget keeps p + K + 1 below 2897, so below 57 920 bytes of the 64 KiB)
-  hipLaunchKernelGGL(mcov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), (sizeof(double) * 2 + sizeof(int)) * (size_t)nc, st, d_Mg, A.at<double>(o_total),
-                     d_mu, G, p, K, pb.train_on_rest ? 1 : 0, pb.centre ? 1 : 0, pb.standardize ? 1 : 0, pb.standardize_response ? 1 : 0,
-                     A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_Mt), A.at<double>(o_scale),
-                     A.at<double>(o_mean), d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
+  hipLaunchKernelGGL(mcov_assemble_kernel, dim3((unsigned)G), dim3(kBlock), (sizeof(double) * 2 + sizeof(int)) * (size_t)nc, st, A.at<double>(m.o_M),
+                     A.at<double>(m.o_total), A.at<double>(m.o_mu), G, p, K, rest, pb.centre ? 1 : 0, pb.standardize ? 1 : 0,
+                     pb.standardize_response ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda), A_mix, L, A.at<double>(o_Mt),
+                     A.at<double>(sets.o_scale), A.at<double>(sets.o_mean), d_tstat, A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b),
+                     A.at<int32_t>(sets.o_ridge));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
   if (tap) {
-    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)(nc + K), st));
-    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
-    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(m.tap_cv(A, tap, pb.train_on_rest, st));
     SGD_HIP_TRY(tap_f64(tap, "Mt", A.at<double>(o_Mt), (size_t)G * (size_t)p * (size_t)nc, st));
-    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)nc, st));
-    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_l2), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_l1), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+    SGD_HIP_TRY(sets.tap(A, tap, st));
   }
   const auto kernel = width == kMcovNarrow ? cov_group_path_kernel<kMcovNarrow> : cov_group_path_kernel<kMcovWide>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_Mt), A.at<double>(o_scale), p, K, G, 0.0,
-                     d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), L, 0, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol,
-                     A.at<double>(o_W), A.at<double>(o_G), A.at<double>(o_c), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)sets.jobs), dim3((unsigned)width), 0, st, A.at<double>(o_Mt), A.at<double>(sets.o_scale), p, K, G, 0.0,
+                     d_tstat, A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b), L, 0, A.at<int32_t>(sets.o_ridge), pb.max_iter, pb.tol,
+                     A.at<double>(po.o_W), A.at<double>(po.o_G), A.at<double>(po.o_c), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
-  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * pK, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
-                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
-
-  std::vector<double> tstat(3 * (size_t)G);
-  out->mean.resize((size_t)G * (size_t)nc);
-  out->scale.resize((size_t)G * (size_t)p);
-  out->c.resize(jobs * pK);
-  out->w.resize(jobs * (size_t)L * pK);
-  out->g.resize(jobs * (size_t)L * pK);
-  out->sweeps.resize(jobs * (size_t)L);
-  out->unconverged.resize(jobs * (size_t)L);
-  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
-  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
-  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
-  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
-  SGD_HIP_TRY(fetch(out->c.data(), o_c, sizeof(double) * out->c.size()));
-  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
-  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
-  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
-  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  std::vector<double> tstat;
+  SGD_HIP_TRY(po.fetch(A, tap, pb.tol, pb.max_iter, out, st));
+  SGD_HIP_TRY(sets.fetch(A, out, &tstat, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  out->n_train.assign(tstat.begin(), tstat.begin() + G);
-  out->yy.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
-  out->nulldev.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  sets.split(tstat, &out->n_train, &out->yy, &out->nulldev);
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));
   return SGDNET_OK;
-}
-
-int64_t wmcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups) {
-  const int64_t rows_per_chunk = wide_rows_per_chunk(n, p + K + 1, kTileRows);
-  int64_t chunks = 0;
-  for (int g = 0; g < n_groups; ++g) chunks += (count[g] + rows_per_chunk - 1) / rows_per_chunk;
-  return chunks;
 }
 
 // mcovariance_cv_run beyond mcov_max_features(K) features: the same group moments pass (the wide mode's row chunks),
@@ -2331,193 +2083,81 @@ int wmcovariance_cv_run(const McovarianceCvProblem& pb, McovarianceCvResult* out
     set_error("wmcovariance_cv_run: the path kernel's workgroup is %d or %d lanes, not %d", kWideNarrow, kWideFull, width);
     return SGDNET_EINVAL;
   }
-  const size_t jobs = (size_t)A_mix * (size_t)G, pK = (size_t)p * (size_t)K;
-
-  // dense x: the rows sorted by group (stable) and cut into chunks of the size one wide fit of n rows over p + K + 1 columns
-  // would use, none across a group's end: the summation order is a function of (n, p, K, fold) alone
-  const int64_t pairs = wide_tile_pairs(Pa);
-  std::vector<int64_t> perm, chunk_begin;
-  std::vector<int32_t> group_chunk;
-  if (!sparse) {
-    std::vector<int64_t> start((size_t)G + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++start[(size_t)pb.fold[i] + 1];
-    for (int g = 0; g < G; ++g) start[(size_t)g + 1] += start[(size_t)g];
-    perm.resize((size_t)n);
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) perm[(size_t)fill[(size_t)pb.fold[i]]++] = i;
-    const int64_t rows_per_chunk = wide_rows_per_chunk(n, Pa, kTileRows);
-    group_chunk.assign((size_t)G + 1, 0);
-    for (int g = 0; g < G; ++g) {
-      for (int64_t r = start[(size_t)g]; r < start[(size_t)g + 1]; r += rows_per_chunk) chunk_begin.push_back(r);
-      if (chunk_begin.size() > (size_t)kCovMaxRowChunks) {
-        set_error("mode = wmcovariance needs the rows of the groups in at most %d chunks: %d groups of %lld rows", kCovMaxRowChunks, G,
-                  (long long)n);
-        return SGDNET_EUNSUPPORTED;
-      }
-      group_chunk[(size_t)g + 1] = (int32_t)chunk_begin.size();
-    }
-    chunk_begin.push_back(n);
-  }
+  const size_t pK = (size_t)p * (size_t)K;
+  GroupRows rows;
+  if (!sparse)
+    if (const int rc = cv_group_rows("wmcovariance", pb.fold, n, G, Pa, true, &rows)) return rc;
   if (G > kCovMaxRowChunks) {       // (the pair kernel's gridDim.z, the assembly's gridDim.y)
     set_error("mode = wmcovariance needs at most %d groups: %d groups", kCovMaxRowChunks, G);
     return SGDNET_EUNSUPPORTED;
   }
-  const size_t chunks = sparse ? 0 : chunk_begin.size() - 1;
-  if (wmcov_cv_bytes(G, p, K, (int64_t)chunks) > kWcovCvBytes) {
+  if (wmcov_cv_bytes(G, p, K, (int64_t)rows.chunks()) > kWcovCvBytes) {
     set_error("mode = wmcovariance needs the moments and the scaled matrices of the groups within %zu bytes: %d groups of %d features and %d responses are %zu bytes",
-              kWcovCvBytes, G, p, K, wmcov_cv_bytes(G, p, K, (int64_t)chunks));
+              kWcovCvBytes, G, p, K, wmcov_cv_bytes(G, p, K, (int64_t)rows.chunks()));
     return SGDNET_EUNSUPPORTED;
   }
   SGD_HIP_TRY(hipSetDevice(pb.device));
-
-  const int64_t nnz = sparse ? pb.colptr[p] : 0;
-  const int32_t* no_rows = nullptr;
-  const AscendingColumns cols(sparse ? pb.colptr : no_rows, pb.rowidx, pb.values, sparse ? p : 0);
-  const size_t Melems = (size_t)Pa * (size_t)Pa;      // (at most 4533^2 = 20 548 089: cov_total_kernel's int, covariance.hpp)
-  const int ld = (int)wide_leading_dim(p);
+  const int ld = (int)wide_leading_dim(p), rest = pb.train_on_rest ? 1 : 0;
 
   Arena A;
-  const size_t o_x = A.reserve(sizeof(double) * (size_t)(sparse ? nnz : n * (int64_t)p));
-  const size_t o_colptr = A.reserve(sparse ? sizeof(int32_t) * (size_t)(p + 1) : 0);
-  const size_t o_rowidx = A.reserve(sparse ? sizeof(int32_t) * (size_t)nnz : 0);
-  const size_t o_fold = A.reserve(sparse ? sizeof(int32_t) * (size_t)n : 0);
-  const size_t o_perm = A.reserve(sparse ? 0 : sizeof(int64_t) * (size_t)n);
-  const size_t o_cbegin = A.reserve(sparse ? 0 : sizeof(int64_t) * (chunks + 1));
-  const size_t o_gchunk = A.reserve(sparse ? 0 : sizeof(int32_t) * ((size_t)G + 1));
-  const size_t o_y = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
-  const size_t o_mu = A.reserve(sizeof(double) * (size_t)(nc + K));      // the features' centres | the responses' sums | their means
-  const size_t o_part = A.reserve(sizeof(double) * chunks * (size_t)pairs * kBlock);
-  const size_t o_Mg = A.reserve(sizeof(double) * (size_t)G * Melems);
-  const size_t o_total = A.reserve(sizeof(double) * Melems);
-  const size_t o_mix = A.reserve(sizeof(double) * (size_t)A_mix);
-  const size_t o_lambda = A.reserve(sizeof(double) * (size_t)A_mix * (size_t)L);
+  Moments m(pb, K, true, true, G, pb.fold, &rows);      // (Pa^2 fits cov_total_kernel's int: covariance.hpp)
+  m.reserve(A);
+  const size_t o_mix = m.param(A, pb.mix, (size_t)A_mix), o_lambda = m.param(A, pb.lambda, (size_t)A_mix * (size_t)L);
   const size_t o_s = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
   const size_t o_d = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
   const size_t o_cst = A.reserve(sizeof(int32_t) * (size_t)G * (size_t)nc);
   const size_t o_S = A.reserve(sizeof(double) * (size_t)G * (size_t)ld * (size_t)p);
   const size_t o_Sd = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
   const size_t o_ct = A.reserve(sizeof(double) * (size_t)G * pK);
-  const size_t o_scale = A.reserve(sizeof(double) * (size_t)G * (size_t)p);
-  const size_t o_mean = A.reserve(sizeof(double) * (size_t)G * (size_t)nc);
   const size_t o_ysd = A.reserve(sizeof(double) * (size_t)G * (size_t)K);
-  const size_t o_tstat = A.reserve(sizeof(double) * 3 * (size_t)G);
-  const size_t o_l2 = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_l1 = A.reserve(sizeof(double) * jobs * (size_t)L);
-  const size_t o_ridge = A.reserve(sizeof(int32_t) * jobs);
-  const size_t o_W = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
-  const size_t o_G = A.reserve(sizeof(double) * jobs * (size_t)L * pK);
-  const size_t o_sweeps = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
-  const size_t o_unconv = A.reserve(sizeof(int32_t) * jobs * (size_t)L);
+  const CvSets sets(A, G, A_mix, L, p, nc);      // (pen_a: the l2 strengths, pen_b: the group thresholds)
+  const PathOut po(A, sets.jobs, L, pK, false);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
 
   Events ev;
-  SGD_HIP_TRY(hipStreamCreateWithFlags(&ev.st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev.e) SGD_HIP_TRY(hipEventCreate(&e));
+  SGD_HIP_TRY(ev.open());
   hipStream_t st = ev.st;
-  double* d_x = A.at<double>(o_x);
-  double* d_y = A.at<double>(o_y);
-  double* d_mu = A.at<double>(o_mu);
-  double* d_Mg = A.at<double>(o_Mg);
-  double* d_tstat = A.at<double>(o_tstat);
-  if (sparse) {
-    if (nnz > 0) {
-      SGD_HIP_TRY(hipMemcpyAsync(d_x, cols.values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
-      SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_rowidx), cols.rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    }
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_colptr), pb.colptr, sizeof(int32_t) * (size_t)(p + 1), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_fold), pb.fold, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-  } else {
-    SGD_HIP_TRY(hipMemcpyAsync(d_x, pb.x_dense, sizeof(double) * (size_t)(n * (int64_t)p), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_perm), perm.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int64_t>(o_cbegin), chunk_begin.data(), sizeof(int64_t) * (chunks + 1), hipMemcpyHostToDevice, st));
-    SGD_HIP_TRY(hipMemcpyAsync(A.at<int32_t>(o_gchunk), group_chunk.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, st));
-  }
-  SGD_HIP_TRY(hipMemcpyAsync(d_y, pb.y, sizeof(double) * (size_t)n * (size_t)K, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_mix), pb.mix, sizeof(double) * (size_t)A_mix, hipMemcpyHostToDevice, st));
-  SGD_HIP_TRY(hipMemcpyAsync(A.at<double>(o_lambda), pb.lambda, sizeof(double) * (size_t)A_mix * (size_t)L, hipMemcpyHostToDevice, st));
-
+  double* d_Mg = A.at<double>(m.o_M);
+  double* d_total = A.at<double>(m.o_total);
+  double* d_tstat = A.at<double>(sets.o_tstat);
+  SGD_HIP_TRY(m.upload(A, st));
   SGD_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (sparse) {
-    hipLaunchKernelGGL(cov_sum_kernel<true>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, A.at<int32_t>(o_colptr), d_y, n, p, K,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
-    hipLaunchKernelGGL(cov_group_responses_kernel, dim3((unsigned)K, (unsigned)K, (unsigned)G), dim3(kBlock), 0, st, d_y,
-                       A.at<int32_t>(o_fold), d_mu, n, p, K, d_Mg);
-    hipLaunchKernelGGL(cov_sparse_pair_kernel<true>, dim3((unsigned)p, (unsigned)Pa, (unsigned)G), dim3(kBlock), 0, st,
-                       A.at<int32_t>(o_colptr), A.at<int32_t>(o_rowidx), d_x, d_y, d_mu, n, p, K, A.at<int32_t>(o_fold), d_Mg);
-  } else {
-    hipLaunchKernelGGL(cov_sum_kernel<false>, dim3((unsigned)nc), dim3(kBlock), 0, st, d_x, (const int32_t*)nullptr, d_y, n, p, K,
-                       pb.centre ? 1 : 0, d_mu);
-    hipLaunchKernelGGL(cov_response_centre_kernel, dim3(1), dim3(kBlock), 0, st, d_mu, n, p, K);
-    hipLaunchKernelGGL(cov_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_y, d_mu, n, p, K, Pa,
-                       (int64_t)0, A.at<int64_t>(o_perm), A.at<int64_t>(o_cbegin), A.at<double>(o_part));
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)pairs, (unsigned)G), dim3(kBlock), 0, st, A.at<double>(o_part), (int)chunks,
-                       A.at<int32_t>(o_gchunk), Pa, d_Mg);
-  }
-  if (pb.train_on_rest)
-    hipLaunchKernelGGL(cov_total_kernel, dim3((unsigned)((Melems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_Mg, G, (int)Melems,
-                       A.at<double>(o_total));
+  m.launch_cv(A, st);
+  if (rest) m.launch_total(A, st);
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[1], st));
-  const int rest = pb.train_on_rest ? 1 : 0;
-  hipLaunchKernelGGL(wmcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total), d_mu, G, p, K, rest,
+  hipLaunchKernelGGL(wmcov_cv_stats_kernel, dim3((unsigned)G), dim3(kBlock), 0, st, d_Mg, d_total, A.at<double>(m.o_mu), G, p, K, rest,
                      pb.centre ? 1 : 0, pb.standardize ? 1 : 0, pb.standardize_response ? 1 : 0, A.at<double>(o_mix), A.at<double>(o_lambda),
-                     A_mix, L, A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), A.at<double>(o_mean),
-                     A.at<double>(o_ysd), d_tstat, A.at<double>(o_l2), A.at<double>(o_l1), A.at<int32_t>(o_ridge));
-  hipLaunchKernelGGL(wmcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, A.at<double>(o_total),
-                     A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(o_scale), A.at<double>(o_ysd), d_tstat, p, K, ld, rest,
+                     A_mix, L, A.at<double>(o_s), A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(sets.o_scale), A.at<double>(sets.o_mean),
+                     A.at<double>(o_ysd), d_tstat, A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b), A.at<int32_t>(sets.o_ridge));
+  hipLaunchKernelGGL(wmcov_cv_assemble_kernel, dim3((unsigned)p, (unsigned)G), dim3(kBlock), 0, st, d_Mg, d_total, A.at<double>(o_s),
+                     A.at<double>(o_d), A.at<int32_t>(o_cst), A.at<double>(sets.o_scale), A.at<double>(o_ysd), d_tstat, p, K, ld, rest,
                      A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[2], st));
   if (tap) {
-    SGD_HIP_TRY(tap_f64(tap, "mu", d_mu, (size_t)(nc + K), st));
-    SGD_HIP_TRY(tap_f64(tap, "Mg", d_Mg, (size_t)G * Melems, st));
-    if (pb.train_on_rest) SGD_HIP_TRY(tap_f64(tap, "total", A.at<double>(o_total), Melems, st));
+    SGD_HIP_TRY(m.tap_cv(A, tap, pb.train_on_rest, st));
     SGD_HIP_TRY(tap_f64(tap, "s", A.at<double>(o_s), (size_t)G * (size_t)nc, st));
     SGD_HIP_TRY(tap_f64(tap, "d", A.at<double>(o_d), (size_t)G * (size_t)nc, st));
-    SGD_HIP_TRY(tap_f64(tap, "scale", A.at<double>(o_scale), (size_t)G * (size_t)p, st));
-    SGD_HIP_TRY(tap_f64(tap, "mean", A.at<double>(o_mean), (size_t)G * (size_t)nc, st));
     SGD_HIP_TRY(tap_f64(tap, "ysd", A.at<double>(o_ysd), (size_t)G * (size_t)K, st));
-    SGD_HIP_TRY(tap_f64(tap, "tstat", d_tstat, 3 * (size_t)G, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_a", A.at<double>(o_l2), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_f64(tap, "pen_b", A.at<double>(o_l1), jobs * (size_t)L, st));
-    SGD_HIP_TRY(tap_i32(tap, "ridge", A.at<int32_t>(o_ridge), jobs, st));
+    SGD_HIP_TRY(sets.tap(A, tap, st));
     SGD_HIP_TRY(tap_f64(tap, "S", A.at<double>(o_S), (size_t)G * (size_t)ld * (size_t)p, st));
     SGD_HIP_TRY(tap_f64(tap, "Sd", A.at<double>(o_Sd), (size_t)G * (size_t)p, st));
     SGD_HIP_TRY(tap_f64(tap, "ct", A.at<double>(o_ct), (size_t)G * pK, st));
   }
   const auto kernel = width == kWideNarrow ? cov_wide_group_cv_path_kernel<kWideNarrow> : cov_wide_group_cv_path_kernel<kWideFull>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
-                     K, ld, G, A.at<double>(o_l2), A.at<double>(o_l1), L, A.at<int32_t>(o_ridge), pb.max_iter, pb.tol, A.at<double>(o_W),
-                     A.at<double>(o_G), A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)sets.jobs), dim3((unsigned)width), 0, st, A.at<double>(o_S), A.at<double>(o_Sd), A.at<double>(o_ct), p,
+                     K, ld, G, A.at<double>(sets.o_pen_a), A.at<double>(sets.o_pen_b), L, A.at<int32_t>(sets.o_ridge), pb.max_iter, pb.tol,
+                     A.at<double>(po.o_W), A.at<double>(po.o_G), A.at<int32_t>(po.o_sweeps), A.at<int32_t>(po.o_unconv));
   SGD_HIP_TRY(hipGetLastError());
   SGD_HIP_TRY(hipEventRecord(ev.e[3], st));
-  SGD_HIP_TRY(tap_path(tap, A.at<double>(o_W), A.at<double>(o_G), jobs * (size_t)L * pK, A.at<int32_t>(o_sweeps), A.at<int32_t>(o_unconv),
-                       jobs * (size_t)L, pb.tol, pb.max_iter, st));
-
-  std::vector<double> tstat(3 * (size_t)G), ct((size_t)G * pK);
-  out->mean.resize((size_t)G * (size_t)nc);
-  out->scale.resize((size_t)G * (size_t)p);
-  out->c.resize(jobs * pK);
-  out->w.resize(jobs * (size_t)L * pK);
-  out->g.resize(jobs * (size_t)L * pK);
-  out->sweeps.resize(jobs * (size_t)L);
-  out->unconverged.resize(jobs * (size_t)L);
-  auto fetch = [&](void* dst, size_t off, size_t bytes) { return hipMemcpyAsync(dst, A.base + off, bytes, hipMemcpyDeviceToHost, st); };
-  SGD_HIP_TRY(fetch(tstat.data(), o_tstat, sizeof(double) * tstat.size()));
-  SGD_HIP_TRY(fetch(ct.data(), o_ct, sizeof(double) * ct.size()));
-  SGD_HIP_TRY(fetch(out->mean.data(), o_mean, sizeof(double) * out->mean.size()));
-  SGD_HIP_TRY(fetch(out->scale.data(), o_scale, sizeof(double) * out->scale.size()));
-  SGD_HIP_TRY(fetch(out->w.data(), o_W, sizeof(double) * out->w.size()));
-  SGD_HIP_TRY(fetch(out->g.data(), o_G, sizeof(double) * out->g.size()));
-  SGD_HIP_TRY(fetch(out->sweeps.data(), o_sweeps, sizeof(int32_t) * out->sweeps.size()));
-  SGD_HIP_TRY(fetch(out->unconverged.data(), o_unconv, sizeof(int32_t) * out->unconverged.size()));
+  std::vector<double> tstat, ct;
+  SGD_HIP_TRY(po.fetch(A, tap, pb.tol, pb.max_iter, out, st));
+  SGD_HIP_TRY(sets.fetch(A, out, &tstat, st));
+  SGD_HIP_TRY(download(A, o_ct, (size_t)G * pK, &ct, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
-  for (size_t job = 0; job < jobs; ++job)      // c~ is the training set's: every mix of a set gets its copy
-    std::copy(ct.begin() + (job % (size_t)G) * pK, ct.begin() + (job % (size_t)G + 1) * pK, out->c.begin() + job * pK);
-  out->n_train.assign(tstat.begin(), tstat.begin() + G);
-  out->yy.assign(tstat.begin() + G, tstat.begin() + 2 * (size_t)G);
-  out->nulldev.assign(tstat.begin() + 2 * (size_t)G, tstat.end());
+  copy_to_jobs(ct, (size_t)G, pK, &out->c);
+  sets.split(tstat, &out->n_train, &out->yy, &out->nulldev);
   SGD_HIP_TRY(hipEventElapsedTime(&out->moments_ms, ev.e[0], ev.e[1]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->assemble_ms, ev.e[1], ev.e[2]));
   SGD_HIP_TRY(hipEventElapsedTime(&out->path_ms, ev.e[2], ev.e[3]));

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "direct_problem.hpp"
+#include "group_rows.hpp"
 #include "wide_layout.hpp"
 
 namespace sgdnet {
@@ -180,6 +181,8 @@ int wmcovariance_run(const McovarianceProblem& pb, McovarianceResult* out, int w
 // up to 524 288 at p = 2; a 10-fold CV at p = 198 takes 3.2 MB of it.
 constexpr size_t kCovGroupMomentBytes = (size_t)64 << 20;
 constexpr int kCovMaxRowChunks = 65535;   // the dense moments pass puts its row chunks (at least one per group) on gridDim.y
+// The chunks are group_rows.hpp's: group_row_chunks(count, G, cov_rows_per_chunk(n, p + K + 1, wide)) predicts what the
+// runs below launch from group_rows() at the same rows per chunk (one response: K = 1).
 
 struct CovarianceCvProblem {
   int64_t n = 0, p = 0;
@@ -236,9 +239,6 @@ static_assert(wcov_cv_bytes(10, kWcovMaxFeatures, 10) / 10000000 == 428 && wcov_
               "the examples above");
 static_assert(wcov_cv_bytes(849, 1000, 849) <= kWcovCvBytes && wcov_cv_bytes(850, 1000, 850) > kWcovCvBytes, "the examples above");
 
-// The row chunks of the dense group moments pass (gridDim.y): count[g] rows in group g, none across a group's end.
-int64_t wcov_cv_row_chunks(int64_t n, int64_t p, const int64_t* count, int n_groups);
-
 // Group moments + stats and assembly + wide path kernel over the jobs.  p <= kWcovMaxFeatures, the budget above, at most
 // kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business (driver_direct.cpp:
 // fit_cv_wcovariance).  width as in wcovariance_run.
@@ -293,9 +293,6 @@ struct McovarianceCvResult {
   float moments_ms = 0.f, assemble_ms = 0.f, path_ms = 0.f;
 };
 
-// The row chunks of the dense group moments pass (gridDim.y): count[g] rows in group g, none across a group's end.
-int64_t mcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups);
-
 // Group moments + assembly + path kernel over the jobs.  p <= mcov_max_features(K), the budget above, at most
 // kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business
 // (driver_direct.cpp: fit_cv_mcovariance).
@@ -323,9 +320,6 @@ static_assert(wmcov_cv_bytes(10, 3709, 2, 10) / 10000000 == 286 && wmcov_cv_byte
 static_assert(wmcov_cv_bytes(847, 1000, 2, 847) <= kWcovCvBytes && wmcov_cv_bytes(848, 1000, 2, 848) > kWcovCvBytes, "the examples above");
 // wmcov_fits keeps p + K <= kWcovMaxFeatures + 1, so Pa <= 4533 and Pa^2 = 20 548 089 at most: cov_total_kernel's int
 static_assert((int64_t)(kWcovMaxFeatures + 2) * (kWcovMaxFeatures + 2) <= 2147483647, "Pa^2 fits cov_total_kernel's int");
-
-// The row chunks of the dense group moments pass (gridDim.y): count[g] rows in group g, none across a group's end.
-int64_t wmcov_cv_row_chunks(int64_t n, int64_t p, int K, const int64_t* count, int n_groups);
 
 // Group moments + stats and assembly + wide group path kernel over the jobs.  p <= wmcov_max_features(K), the budget above,
 // at most kCovMaxRowChunks row chunks (dense) or groups (sparse) and valid fold ids are the caller's business

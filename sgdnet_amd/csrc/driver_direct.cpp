@@ -344,7 +344,7 @@ int fit_cv_covariance(CovarianceCvProblem& pb, const sgdnet_control* ctl, const 
   if (wide) {
     // the limits of wcovariance_cv_run that need no device: its grid dimensions and its byte budget
     const bool sparse = pb.x_dense == nullptr;
-    const int64_t chunks = sparse ? 0 : wcov_cv_row_chunks(n, p, count.data(), n_groups);
+    const int64_t chunks = sparse ? 0 : group_row_chunks(count.data(), n_groups, cov_rows_per_chunk(n, p + 2, true));
     if (chunks > kCovMaxRowChunks || n_groups > kCovMaxRowChunks) {
       set_error("mode = wcovariance needs at most %d groups and (dense x) row chunks: %d groups, %lld chunks of %lld rows", kCovMaxRowChunks,
                 n_groups, (long long)chunks, (long long)n);
@@ -464,8 +464,7 @@ int fit_cv_mcovariance(McovarianceCvProblem& pb, const sgdnet_control* ctl, cons
   if (!rc) rc = validate_mixes(n_alpha, alphas, L, lambdas);
   if (rc) return rc;
   const bool sparse = pb.x_dense == nullptr;
-  const int64_t chunks = sparse ? n_groups
-                                : (wide ? wmcov_cv_row_chunks(n, p, K, count.data(), n_groups) : mcov_cv_row_chunks(n, p, K, count.data(), n_groups));
+  const int64_t chunks = sparse ? n_groups : group_row_chunks(count.data(), n_groups, cov_rows_per_chunk(n, p + K + 1, wide));
   if (chunks > kCovMaxRowChunks) {
     set_error("mode = %s needs at most %d %s: %d groups of %lld rows are %lld", mode, kCovMaxRowChunks,
               sparse ? "groups of sparse rows" : "row chunks of the groups", n_groups, (long long)n, (long long)chunks);
