@@ -35,7 +35,7 @@ extern "C" {
 /* 2: sgdnet_control carries losses_sink / losses_ctx, sgdnet_set_option exists.  3: sgdnet_auc_*_rng, the option
  * exact_row_registers, sgdnet_solver_rng_layout (additions only).  4: sgdnet_control ends with n_gpus / devices
  * (a fit sharded over the GPUs of a node), sgdnet_solver_link_peers, the option fused_epoch.  5: sgdnet_gradient_sparse /
- * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width, sgdnet_cv_mnewton_*, sgdnet_cv_wcovariance_*, sgdnet_cv_wmcovariance_* (additions only).  A caller compiled against
+ * _dense (additions only).  6: SGDNET_MODE_COVARIANCE, sgdnet_covariance_max_features, later sgdnet_cv_covariance_*, SGDNET_MODE_NEWTON, sgdnet_newton_max_features and sgdnet_cv_newton_*, SGDNET_MODE_MCOVARIANCE and sgdnet_mcovariance_max_features, SGDNET_MODE_MNEWTON and sgdnet_mnewton_max_features, sgdnet_mnewton_probe, SGDNET_MODE_WCOVARIANCE, sgdnet_wcovariance_max_features and the option wcovariance_width, SGDNET_MODE_WNEWTON, sgdnet_wnewton_max_features and the option wnewton_width, SGDNET_MODE_WMCOVARIANCE, sgdnet_wmcovariance_max_features and the option wmcovariance_width, sgdnet_cv_mnewton_*, sgdnet_cv_wcovariance_*, sgdnet_cv_wmcovariance_*, sgdnet_cv_wnewton_* (additions only).  A caller compiled against
  * another version must not pass its structs: the shim and the Python binding compare sgdnet_abi_version()
  * with this constant when they load the library. */
 #define SGDNET_ABI_VERSION 6
@@ -991,6 +991,45 @@ int sgdnet_cv_newton_dense(const double* x, int64_t n, int64_t p, const double* 
 int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
                             sgdnet_cv_newton_result* out);
+
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in wide Newton mode (additions only; the ABI version     */
+/* stays): sgdnet_cv_newton_* beyond its 198 features.  The arguments and the */
+/* result are those of sgdnet_cv_newton_*.  Job (alpha a, group g) is by      */
+/* definition sgdnet_fit_*(x[T], y[T]) in SGDNET_MODE_WNEWTON with            */
+/* elasticnet_mix = alphas[a] and the user lambdas lambdas[a][.]: the same    */
+/* preprocessed problem, stopping rule, constants and accept / halve rule;    */
+/* return_codes and npasses mean what they mean there.  What the jobs share:  */
+/* x and y, sorted by group and uploaded once, every launch of a round, the   */
+/* round's one command upload and one record readback.  What they do not: H   */
+/* depends on the iterate, so every job keeps its own moments, its own        */
+/* H = M / n_T / (s s') in global memory, diag H and q, and its inner solve   */
+/* is one workgroup -- one compute unit -- of its own (sgdnet_amd/csrc/       */
+/* newton.hip: wnewton_cv_run).  A job's row chunks are those a single fit    */
+/* takes for its rows: the same input gives the same bits, a job's bits do    */
+/* not depend on which other jobs share the call, and both widths of the      */
+/* inner solve ("wnewton_width") give the same bits.  Sparse x is expanded to */
+/* the dense copy a single fit makes: a sparse call gives the bits of the     */
+/* dense call on the same matrix.                                             */
+/* SGDNET_EUNSUPPORTED ("mode = wnewton needs ..."): a family other than      */
+/* binomial, more than sgdnet_wnewton_max_features() features, n_gpus > 1,    */
+/* debug, more than 65 535 jobs, a sparse x whose dense copy is above 1 GiB,  */
+/* or a workspace -- per job 2 n_rows + (n_features + 2)^2 + row chunks x     */
+/* tile pairs x 256 + H + the answers, about 2.5 (n_features + 2)^2 doubles   */
+/* -- above 16 GiB (which holds 5 mixes x 10 folds up to 4110 features and    */
+/* 25 jobs at the feature limit).  There is no fall-back to                   */
+/* sgdnet_cv_newton_* or to separate fits.                                    */
+/* SGDNET_EINVAL: the cases of sgdnet_cv_newton_*, and a "wnewton_width"      */
+/* that is neither 0, 256 nor 1024.                                           */
+/* ------------------------------------------------------------------------ */
+typedef sgdnet_cv_newton_result sgdnet_cv_wnewton_result;
+
+int sgdnet_cv_wnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                            int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                            const double* lambdas, sgdnet_cv_wnewton_result* out);
+int sgdnet_cv_wnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                             sgdnet_cv_wnewton_result* out);
 
 /* ------------------------------------------------------------------------ */
 /* Cross-validation in multi-response covariance mode (additions only; the    */

@@ -8,7 +8,7 @@ from ._lib import LIB_PATH, SgdnetError, load  # noqa: F401
 from .api import SgdnetFit, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance, sgdnet_wmnewton, sgdnet_wnewton  # noqa: F401
 from .cv import (CvSgdnet, cv_covariance_fits, cv_mcovariance_fits, cv_mnewton_fits, cv_newton_fits, cv_sgdnet,  # noqa: F401
                  cv_sgdnet_mcovariance, cv_sgdnet_mnewton, cv_sgdnet_newton, cv_sgdnet_wcovariance, cv_sgdnet_wmcovariance, cv_wcovariance_fits,
-                 cv_wmcovariance_fits)
+                 cv_wmcovariance_fits, cv_sgdnet_wnewton, cv_wnewton_fits)
 from .kkt import (evaluation_intercepts, feature_moments, kkt, kkt_from_gradient, path_gradient,  # noqa: F401
                   response_moments)
 from .predict import coef, predict  # noqa: F401
@@ -25,4 +25,4 @@ __all__ = ["sgdnet", "SgdnetFit", "SagaSolver", "RRng", "auto_batch", "SgdnetErr
            "sgdnet_wnewton", "wnewton_max_features", "sgdnet_wmcovariance", "wmcovariance_max_features",
            "sgdnet_wmnewton", "wmnewton_max_features", "cv_mcovariance_fits", "cv_sgdnet_mcovariance",
            "cv_mnewton_fits", "cv_sgdnet_mnewton", "cv_wcovariance_fits", "cv_sgdnet_wcovariance",
-           "cv_wmcovariance_fits", "cv_sgdnet_wmcovariance"]
+           "cv_wmcovariance_fits", "cv_sgdnet_wmcovariance", "cv_wnewton_fits", "cv_sgdnet_wnewton"]

@@ -42,7 +42,7 @@ EXPORTS = [
     "sgdnet_wnewton_max_features", "sgdnet_wmcovariance_max_features", "sgdnet_wmnewton_max_features",
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
     "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse", "sgdnet_cv_wmcovariance_dense", "sgdnet_cv_wmcovariance_sparse",
-    "sgdnet_wnewton_probe", "sgdnet_wmnewton_probe",
+    "sgdnet_wnewton_probe", "sgdnet_wmnewton_probe", "sgdnet_cv_wnewton_dense", "sgdnet_cv_wnewton_sparse",
     "sgdnet_covariance_probe", "sgdnet_covariance_path_probe", "sgdnet_cv_covariance_probe", "sgdnet_cov_probe_field", "sgdnet_cov_probe_free",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
@@ -309,6 +309,8 @@ def load():
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvNewtonResult)]
     L.sgdnet_cv_newton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_newton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
+    L.sgdnet_cv_wnewton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail     # (sgdnet_cv_wnewton_result is that struct)
+    L.sgdnet_cv_wnewton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvMcovResult)]
     L.sgdnet_cv_mcovariance_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_mcovariance_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail

@@ -626,30 +626,52 @@ struct CvNewtonMatrix {
   const double* values = nullptr;
 };
 
+//
+// wide (the stage behind sgdnet_cv_wnewton_*, newton.hip: wnewton_cv_run): every job is fit_newton in SGDNET_MODE_WNEWTON on
+// x[T], y[T].  The same steps with the wide mode's feature limit and its own workspace bound; sparse x is expanded to the dense
+// copy a single wnewton fit makes (driver.cpp: fit_sparse_impl; entries stored twice add up) before anything is computed
+// from it and goes the dense way, so a sparse call gives the dense call's bits.  Every refusal is decided before the first
+// HIP call; there is no fall-back to the narrow loop or to separate fits.
 int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                  int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_newton_result* out) {
+                  int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_newton_result* out, bool wide = false) {
   const int64_t n = X.n, p = X.p;
+  const char* const who = wide ? "sgdnet_cv_wnewton" : "sgdnet_cv_newton";
+  const char* const mode = wide ? "wnewton" : "newton";
   if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !out->steps ||
       !out->halvings || !y || !fold || !alphas || !lambdas) {
-    set_error("sgdnet_cv_newton: null pointer");
+    set_error("%s: null pointer", who);
     return SGDNET_EINVAL;
   }
   if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
       (train_on_rest && n_groups < 2)) {
-    set_error("sgdnet_cv_newton: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    set_error("%s: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)", who);
     return SGDNET_EINVAL;
   }
   const int L = ctl->n_lambda, G = n_groups;
-  const bool sparse = X.dense == nullptr, rest = train_on_rest != 0;
+  // (wide: x is read dense whichever way it came)
+  const bool expand = wide && X.dense == nullptr, sparse = !wide && X.dense == nullptr, rest = train_on_rest != 0;
+  const int limit = wide ? kWnewtonMaxFeatures : kNewtonMaxFeatures;
   const char* what = nullptr;
   if (ctl->family != SGDNET_BINOMIAL) what = "family = binomial";
-  else if (p > kNewtonMaxFeatures) what = "no more features than sgdnet_newton_max_features()";
+  else if (p > limit) what = wide ? "no more features than sgdnet_wnewton_max_features()" : "no more features than sgdnet_newton_max_features()";
   else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
   else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
+  else if (expand && (double)n * (double)p * 8.0 > (double)kWnewtonDenseCopyBytes)
+    what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
+  if (what && wide) {
+    set_error("mode = wnewton needs %s: family %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)n,
+              (long long)p, limit, ctl->n_gpus, ctl->debug);
+    return SGDNET_EUNSUPPORTED;
+  }
   if (what) {
     set_error("mode = newton needs %s: family %d, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family, (long long)p,
               kNewtonMaxFeatures, ctl->n_gpus, ctl->debug);
     return SGDNET_EUNSUPPORTED;
+  }
+  const int width = wide ? option(kOptWnewtonWidth) : 0;
+  if (width != 0 && width != kWideNarrow && width != kWideFull) {
+    set_error("%s: the option wnewton_width is %d; the inner solve runs on 256 or 1024 lanes (0: the rule)", who, width);
+    return SGDNET_EINVAL;
   }
   int rc = validate_response(ctl, y, n);
   if (rc) return rc;
@@ -687,12 +709,19 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
     }
   }
   if ((int64_t)n_alpha * G > kNewtonCvMaxJobs) {
-    set_error("mode = newton needs no more than %lld jobs in one cross-validation call: %d mixes x %d groups", (long long)kNewtonCvMaxJobs,
+    set_error("mode = %s needs no more than %lld jobs in one cross-validation call: %d mixes x %d groups", mode, (long long)kNewtonCvMaxJobs,
               n_alpha, G);
     return SGDNET_EUNSUPPORTED;
   }
-  const size_t workspace = newton_cv_workspace_bytes(n, p, sparse, n_t.data(), G, n_alpha);
-  if (workspace > kNewtonCvWorkspaceBytes) {
+  const size_t workspace = wide ? wnewton_cv_workspace_bytes(n, p, n_t.data(), G, n_alpha, L)
+                                : newton_cv_workspace_bytes(n, p, sparse, n_t.data(), G, n_alpha);
+  if (wide && workspace > kWnewtonCvBytes) {
+    set_error("mode = wnewton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of %lld rows and %lld features (per job the "
+              "moments, the row-chunk partials and H, about 2.5 (features + 2)^2 doubles) are %zu bytes", kWnewtonCvBytes, n_alpha, G,
+              (long long)n, (long long)p, workspace);
+    return SGDNET_EUNSUPPORTED;
+  }
+  if (!wide && workspace > kNewtonCvWorkspaceBytes) {
     set_error("mode = newton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of (2 x %lld rows + (%lld + 2)^2 moments%s) "
               "doubles are %zu bytes", kNewtonCvWorkspaceBytes, n_alpha, G, (long long)n, (long long)p, sparse ? "" : " + row-chunk partials",
               workspace);
@@ -752,13 +781,18 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
         }
       }
     }
+  } else if (expand) {
+    std::vector<double> expanded((size_t)(n * p), 0.0);
+    for (int64_t j = 0; j < p; ++j)
+      for (int64_t q = X.colptr[j]; q < X.colptr[j + 1]; ++q) expanded[(size_t)(X.rowidx[q] + j * n)] += X.values[q];
+    sorted_dense_moments(expanded.data(), n, p, G, to, start, xs, abar, s1, s2);
   } else {
     sorted_dense_moments(X.dense, n, p, G, to, start, xs, abar, s1, s2);
   }
   const bool centre = intercept || ctl->standardize != 0;
   std::vector<double> mean, scale;
   pooled_centres_and_scales(abar, s1, s2, n_t, rest, centre, ctl->standardize != 0, mean, scale);
-  pt.mark("cv newton: rows sorted, moments");
+  pt.mark(wide ? "cv wnewton: rows sorted, moments" : "cv newton: rows sorted, moments");
 
   // regularization_path for user lambdas and a binomial response (its y_scale is 1)
   std::vector<double> l2((size_t)n_alpha * (size_t)L), l1(l2.size());
@@ -799,7 +833,7 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   NewtonCvResult nr;
-  rc = newton_cv_run(pb, pt.on, &nr);
+  rc = wide ? wnewton_cv_run(pb, pt.on, &nr, width) : newton_cv_run(pb, pt.on, &nr);
   if (rc) return rc;
 
   const size_t P1 = P + 1;
@@ -830,11 +864,15 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
       most_steps = std::max(most_steps, nr.steps[job] + nr.halvings[job]);
       most_halvings = std::max(most_halvings, nr.halvings[job]);
     }
-  if (pt.on)
+  if (pt.on && wide)
+    fprintf(stderr, "[sgdnet]   cv wnewton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
+            "moments %.3f ms, scale %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings,
+            nr.sweeps, nr.moments_ms, nr.scale_ms, nr.cd_ms, nr.state_ms);
+  else if (pt.on)
     fprintf(stderr, "[sgdnet]   cv newton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
             "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
             nr.moments_ms, nr.cd_ms, nr.state_ms);
-  pt.mark("cv newton (all folds)");
+  pt.mark(wide ? "cv wnewton (all folds)" : "cv newton (all folds)");
   return SGDNET_OK;
 }
 
@@ -1227,6 +1265,38 @@ int sgdnet_cv_newton_sparse(const sgdnet_csc* x, const double* y, const int32_t*
   X.rowidx = x->rowidx;
   X.values = x->values;
   return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_wnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                            const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                            sgdnet_cv_wnewton_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_wnewton_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  CvNewtonMatrix X;
+  X.n = n;
+  X.p = p;
+  X.dense = x;
+  return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
+}
+
+int sgdnet_cv_wnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                             sgdnet_cv_wnewton_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_wnewton_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  CvNewtonMatrix X;
+  X.n = x->n_rows;
+  X.p = x->n_cols;
+  X.colptr = x->colptr;
+  X.rowidx = x->rowidx;
+  X.values = x->values;
+  return fit_cv_newton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
 }
 
 int sgdnet_cv_mnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,

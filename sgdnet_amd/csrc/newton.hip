@@ -47,6 +47,12 @@
 // newton_cv_* kernels are the kernels above with a job dimension, each job on its own rows, centres, scales and buffers;
 // the host keeps newton_run's state machine once per job, sends one command per job and round and reads all records
 // back in one copy.
+//
+// Wide cross-validation (wnewton_cv_run, include/sgdnet_hip.h: sgdnet_cv_wnewton_*): the same loop around the wide inner
+// solve, dense x only.  The state, finish, dense tile and reduce kernels are the narrow CV's on the row chunks wnewton_run
+// would choose for each job's rows; newton_cv_wide_scale_kernel, newton_cv_wide_cd_kernel and newton_cv_wide_blend_kernel are
+// the wide kernels with a job dimension, every job with its own H, diag H and q in global memory (H depends on the iterate:
+// nothing is pooled across jobs) and one workgroup -- one compute unit -- per job and round.
 #define SGDNET_DET_MATH
 #include <algorithm>
 #include <utility>
@@ -377,14 +383,14 @@ __device__ __forceinline__ double newton_coord_new_u(double hjj, double uj, doub
 //            it adds nothing.
 // max_sweeps bounds the list sweeps of the solve.  g[k] is updated by one lane from the same words in the same order
 // whatever kWidth is, and the candidate is published by the first wavefront alone: both widths give the same bits.
+// (the body of newton_wide_cd_kernel and of newton_cv_wide_cd_kernel, which runs it once per job; lds: the workgroup's
+// kWnewtonLdsBytes, aligned to 16)
 template <int kWidth>
-__global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __restrict__ H, const double* __restrict__ Hd,
-                                                                 const double* __restrict__ q, const double* __restrict__ scale, int p, int ld,
-                                                                 const double* __restrict__ u_cur, double al, double be, int ridge,
-                                                                 int fit_intercept, unsigned max_sweeps, double tol,
-                                                                 double* __restrict__ u_cand, double* __restrict__ a_cand,
-                                                                 double* __restrict__ rec) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kWnewtonLdsBytes];
+__device__ __forceinline__ void newton_wide_cd_solve(unsigned char* lds, const double* __restrict__ H, const double* __restrict__ Hd,
+                                                     const double* __restrict__ q, const double* __restrict__ scale, int p, int ld,
+                                                     const double* __restrict__ u_cur, double al, double be, int ridge, int fit_intercept,
+                                                     unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                     double* __restrict__ a_cand, double* __restrict__ rec) {
   const int lane = threadIdx.x, wave = lane >> 6, P = p + 1;
   double* g = reinterpret_cast<double*>(lds);
   double* u = g + P;
@@ -465,6 +471,17 @@ __global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __
       rec[kRecNegligible] = negligible ? 1.0 : 0.0;
     }
   }
+}
+
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void newton_wide_cd_kernel(const double* __restrict__ H, const double* __restrict__ Hd,
+                                                                 const double* __restrict__ q, const double* __restrict__ scale, int p, int ld,
+                                                                 const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                                 int fit_intercept, unsigned max_sweeps, double tol,
+                                                                 double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                                 double* __restrict__ rec) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kWnewtonLdsBytes];
+  newton_wide_cd_solve<kWidth>(lds, H, Hd, q, scale, p, ld, u_cur, al, be, ridge, fit_intercept, max_sweeps, tol, u_cand, a_cand, rec);
 }
 
 // The wide inner solve's workgroup.  Both instances give the same bits; profiles/wnewton_path.txt has the inner solves'
@@ -774,6 +791,74 @@ __global__ __launch_bounds__(64) void newton_cv_cd_kernel(const CvCmd* __restric
                   (double)jobs[job].n_t, u_cur, c.l2, c.l1, c.ridge, fit_intercept, max_sweeps, tol,
                   u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)P, a_all + (size_t)job * (size_t)P,
                   rec_all + (size_t)job * kRecLen);
+}
+
+// ---- wide cross-validation (wnewton_cv_run): the wide kernels with a job dimension ----
+// The state, finish, dense tile and reduce kernels are the ones above, on the row chunks wnewton_run would choose for n_t
+// rows (CvGeometry).  Every job has its own H (leading dimension ld = wide_leading_dim(P)), diag H and q.
+
+// wide_scale_kernel on a grid of (column, job): the job's M into its H, diag H and q, with its training set's scales and n_t
+__global__ __launch_bounds__(kBlock) void newton_cv_wide_scale_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                       const double* __restrict__ M_all, const double* __restrict__ scale_all,
+                                                                       int p, int ld, double* __restrict__ H_all, double* __restrict__ Hd_all,
+                                                                       double* __restrict__ q_all) {
+  const int job = blockIdx.y;
+  if (cmd[job].action != kCvStep) return;
+  const int j = blockIdx.x, P = p + 1, ncols = p + 2;
+  const double* __restrict__ M = M_all + (size_t)job * (size_t)ncols * (size_t)ncols;
+  const double* __restrict__ scale = scale_all + (size_t)jobs[job].set * (size_t)p;
+  double* __restrict__ A = H_all + (size_t)job * (size_t)ld * (size_t)P;
+  const double dn = (double)jobs[job].n_t;
+  const double sj = j < p ? scale[j] : 1.0;
+  for (int k = threadIdx.x; k < ld; k += kBlock) {
+    double v = 0.0;
+    if (k < P) {
+      const double sk = k < p ? scale[k] : 1.0;
+      v = k >= j ? M[(size_t)j * ncols + k] / dn / (sj * sk) : M[(size_t)k * ncols + j] / dn / (sk * sj);
+    }
+    A[(size_t)j * ld + k] = v;
+    if (k == j) Hd_all[(size_t)job * (size_t)P + j] = v;
+  }
+  if (threadIdx.x == 0) q_all[(size_t)job * (size_t)P + j] = M[(size_t)j * ncols + P] / dn / sj;
+}
+
+// newton_wide_blend_kernel for the job blockIdx.x: a halving (t = 1/2), or the path's start published as it is (t = 1)
+__global__ __launch_bounds__(64) void newton_cv_wide_blend_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                   const double* __restrict__ scale_all, int p, double* u_all,
+                                                                   double* __restrict__ a_all, double* __restrict__ rec_all) {
+  const int job = blockIdx.x, P = p + 1;
+  const CvCmd c = cmd[job];
+  if (c.action != kCvHalve && c.action != kCvStart) return;
+  const double* u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)P;
+  double* u_cand = u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)P;
+  publish_candidate(BlendedCandidate{u_cur, u_cand, c.action == kCvStart ? 1.0 : 0.5}, u_cur,
+                    scale_all + (size_t)jobs[job].set * (size_t)p, p, u_cand, a_all + (size_t)job * (size_t)P,
+                    rec_all + (size_t)job * kRecLen);
+}
+
+// newton_wide_cd_kernel for the job blockIdx.x: one workgroup per job, each declaring the whole LDS, so the jobs spread one
+// per CU (more jobs than CUs queue: no workgroup waits for another).  Before anything else it stores the current iterate
+// into U[slot] where the host says it answers a lambda.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void newton_cv_wide_cd_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                    const double* __restrict__ H_all, const double* __restrict__ Hd_all,
+                                                                    const double* __restrict__ q_all, const double* __restrict__ scale_all,
+                                                                    int p, int ld, int n_lambda, int fit_intercept, unsigned max_sweeps,
+                                                                    double tol, double* __restrict__ u_all, double* __restrict__ a_all,
+                                                                    double* __restrict__ rec_all, double* __restrict__ U_all) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kWnewtonLdsBytes];
+  const int job = blockIdx.x, P = p + 1;
+  const CvCmd c = cmd[job];
+  const double* __restrict__ u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)P;
+  if (c.slot >= 0) {
+    double* __restrict__ U = U_all + ((size_t)job * (size_t)n_lambda + (size_t)c.slot) * (size_t)P;
+    for (int k = threadIdx.x; k < P; k += kWidth) U[k] = u_cur[k];
+  }
+  if (c.action != kCvStep) return;
+  newton_wide_cd_solve<kWidth>(lds, H_all + (size_t)job * (size_t)ld * (size_t)P, Hd_all + (size_t)job * (size_t)P,
+                               q_all + (size_t)job * (size_t)P, scale_all + (size_t)jobs[job].set * (size_t)p, p, ld, u_cur, c.l2, c.l1,
+                               c.ridge, fit_intercept, max_sweeps, tol, u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)P,
+                               a_all + (size_t)job * (size_t)P, rec_all + (size_t)job * kRecLen);
 }
 
 struct Stream {
@@ -1174,11 +1259,12 @@ int wnewton_probe(const NewtonProblem& pb, sgdnet_wnewton_probe_io* io) {
 
 namespace {
 
-// the geometry of a call's jobs: a function of (n, p, the groups, the number of mixes) alone
+// the geometry of a call's jobs: a function of (n, p, the groups, the number of mixes) alone.  wide: the row chunks of a
+// job are those wnewton_run chooses for n_t rows (wide_layout.hpp), else newton_run's (dense_rows_per_chunk)
 struct CvGeometry {
   int pairs = 0, max_chunks = 0, max_state_blocks = 0;
   std::vector<CvJob> jobs;
-  CvGeometry(int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix) {
+  CvGeometry(int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix, bool wide = false) {
     const int nc = (int)p + 2, T = (nc + kTileCols - 1) / kTileCols;
     pairs = T * (T + 1) / 2;
     jobs.resize((size_t)n_sets * (size_t)n_mix);
@@ -1188,7 +1274,7 @@ struct CvGeometry {
         J = CvJob{};
         J.n_t = n_t[t];
         J.set = t;
-        J.rows_per_chunk = dense_rows_per_chunk(J.n_t, pairs);
+        J.rows_per_chunk = wide ? wide_rows_per_chunk(J.n_t, nc, kTileRows) : dense_rows_per_chunk(J.n_t, pairs);
         J.chunks = sparse ? 0 : (int32_t)((J.n_t + J.rows_per_chunk - 1) / J.rows_per_chunk);
         J.state_blocks = (int32_t)std::min<int64_t>(kStateMaxBlocks, (J.n_t + kBlock - 1) / kBlock);
         max_chunks = std::max(max_chunks, (int)J.chunks);
@@ -1207,20 +1293,36 @@ size_t newton_cv_workspace_bytes(int64_t n, int64_t p, bool sparse, const int64_
   return sizeof(double) * CvGeometry(p, sparse, n_t, n_sets, n_mix).workspace_doubles(n, p);
 }
 
+size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int n_sets, int n_mix, int n_lambda) {
+  int64_t max_chunks = 0;
+  for (int t = 0; t < n_sets; ++t) max_chunks = std::max(max_chunks, wnewton_row_chunks(n_t[t], p));
+  return wnewton_cv_bytes((int64_t)n_sets * n_mix, n, p, n_lambda, max_chunks);
+}
+
 // The lock-step loop.  A round: the commands go up in one copy, every kernel is launched once over all jobs (a job whose
 // command does not need a kernel leaves it at once), the records come back in one copy, and every job's state machine
 // moves exactly as newton_run moves its one: a step is (moments, inner solve, state pass at the candidate); a candidate
 // after which the objective rose is halved (blend, state pass) in the next round; an accepted candidate becomes the
 // current iterate by flipping `cur`; a lambda that is done names the slot of U its iterate goes to.  The loop ends
 // when every job has finished its last lambda; one last launch stores the iterates still owed.
-int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
+// newton_cv_run and wnewton_cv_run: one loop, one state machine per job.  wide: the jobs' row chunks follow wide_row_chunks,
+// newton_cv_wide_scale_kernel writes every stepping job's H, diag H and q to global memory, the inner solve is
+// newton_cv_wide_cd_kernel<width> and the blend has no array of kNewtonMaxFeatures + 1.  Not wide: exactly the launches the
+// Newton cross-validation has always made.
+namespace {
+
+static_assert(kTileRows == kWnewtonCvTileRows && kStateMaxBlocks == kWnewtonCvStateMaxBlocks && kRecLen == kWnewtonCvRecordDoubles &&
+              kBlock == 256, "newton.hpp: wnewton_cv_bytes counts these");
+
+int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, bool wide, int width) {
   const int p = (int)pb.p, P = p + 1, nc = p + 2, L = pb.n_lambda, G = pb.n_sets;
   const int64_t n = pb.n;
   const bool sparse = pb.x_dense == nullptr;
-  if (n <= 0 || p <= 0 || p > kNewtonMaxFeatures || L <= 0 || G <= 0 || pb.n_mix <= 0 || !pb.y || !pb.start || !pb.mean || !pb.scale ||
-      !pb.b0 || !pb.l2 || !pb.l1 || !pb.ridge || pb.max_iter == 0 || (sparse && (!pb.colptr || !pb.rowidx || !pb.values || !pb.cut)) ||
-      (int64_t)G * pb.n_mix > kNewtonCvMaxJobs) {
-    set_error("newton_cv_run: invalid problem");
+  if (n <= 0 || pb.p <= 0 || pb.p > (wide ? kWnewtonMaxFeatures : kNewtonMaxFeatures) || L <= 0 || G <= 0 || pb.n_mix <= 0 || !pb.y ||
+      !pb.start || !pb.mean || !pb.scale || !pb.b0 || !pb.l2 || !pb.l1 || !pb.ridge || pb.max_iter == 0 ||
+      (sparse && (!pb.colptr || !pb.rowidx || !pb.values || !pb.cut)) || (int64_t)G * pb.n_mix > kNewtonCvMaxJobs ||
+      (wide && (sparse || (width != kWideNarrow && width != kWideFull)))) {
+    set_error("%s: invalid problem", wide ? "wnewton_cv_run" : "newton_cv_run");
     return SGDNET_EINVAL;
   }
   std::vector<int64_t> n_t((size_t)G);
@@ -1228,12 +1330,12 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
     const int64_t own = pb.start[t + 1] - pb.start[t];
     n_t[(size_t)t] = pb.train_on_rest ? n - own : own;
     if (own <= 0 || n_t[(size_t)t] <= 0) {
-      set_error("newton_cv_run: empty training set %d", t);
+      set_error("%s: empty training set %d", wide ? "wnewton_cv_run" : "newton_cv_run", t);
       return SGDNET_EINVAL;
     }
   }
-  CvGeometry geo(p, sparse, n_t.data(), G, pb.n_mix);
-  const int jobs = (int)geo.jobs.size();
+  CvGeometry geo(p, sparse, n_t.data(), G, pb.n_mix, wide);
+  const int jobs = (int)geo.jobs.size(), ld = (int)wide_leading_dim(P);
   for (CvJob& J : geo.jobs) cv_job_rows(J, pb.start, n, pb.train_on_rest);
   const int64_t nnz = sparse ? pb.colptr[p] : 0;
 
@@ -1258,7 +1360,11 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
   const size_t o_u = A.reserve(sizeof(double) * 2 * (size_t)P * (size_t)jobs);
   const size_t o_a = A.reserve(sizeof(double) * (size_t)P * (size_t)jobs);
   const size_t o_U = A.reserve(sizeof(double) * (size_t)jobs * (size_t)L * (size_t)P);
+  const size_t o_H = A.reserve(wide ? sizeof(double) * (size_t)jobs * (size_t)ld * (size_t)P : 0);
+  const size_t o_Hd = A.reserve(wide ? sizeof(double) * (size_t)jobs * (size_t)P : 0);
+  const size_t o_q = A.reserve(wide ? sizeof(double) * (size_t)jobs * (size_t)P : 0);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+  double *d_H = A.at<double>(o_H), *d_Hd = A.at<double>(o_Hd), *d_q = A.at<double>(o_q);
   double *d_x = A.at<double>(o_x), *d_y = A.at<double>(o_y), *d_mu = A.at<double>(o_mu), *d_scale = A.at<double>(o_scale),
          *d_v = A.at<double>(o_v), *d_r = A.at<double>(o_r), *d_part = A.at<double>(o_part), *d_M = A.at<double>(o_M),
          *d_partial = A.at<double>(o_partial), *d_sums = A.at<double>(o_sums), *d_rec = A.at<double>(o_rec), *d_u = A.at<double>(o_u),
@@ -1321,7 +1427,7 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
   out->halvings.assign((size_t)jobs, 0.0);
   out->sweeps = 0.0;
   out->rounds = 0;
-  out->moments_ms = out->cd_ms = out->state_ms = 0.f;
+  out->moments_ms = out->cd_ms = out->state_ms = out->scale_ms = 0.f;
 
   std::vector<CvJobState> state((size_t)jobs);
   const int centre = pb.centre ? 1 : 0, fit_intercept = pb.fit_intercept ? 1 : 0;
@@ -1354,10 +1460,22 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
     }
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
     // (the inner solve's kernel also stores the iterates owed to U: it runs in every round)
-    hipLaunchKernelGGL(newton_cv_cd_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_M, d_scale, p, L, fit_intercept,
-                       kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
-    if (any_blend)
-      hipLaunchKernelGGL(newton_cv_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, d_u, d_a, d_rec);
+    if (wide) {
+      if (any_step)
+        hipLaunchKernelGGL(newton_cv_wide_scale_kernel, dim3((unsigned)P, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs, d_M, d_scale,
+                           p, ld, d_H, d_Hd, d_q);
+      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
+      const auto kernel = width == kWideNarrow ? newton_cv_wide_cd_kernel<kWideNarrow> : newton_cv_wide_cd_kernel<kWideFull>;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, d_cmd, d_jobs, d_H, d_Hd, d_q, d_scale, p, ld, L,
+                         fit_intercept, kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
+      if (any_blend)
+        hipLaunchKernelGGL(newton_cv_wide_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, d_u, d_a, d_rec);
+    } else {
+      hipLaunchKernelGGL(newton_cv_cd_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_M, d_scale, p, L, fit_intercept,
+                         kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
+      if (any_blend)
+        hipLaunchKernelGGL(newton_cv_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, d_u, d_a, d_rec);
+    }
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
     if (live > 0) {
       if (sparse)
@@ -1378,7 +1496,11 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
       float ms = 0.f;
       SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[0], sx.e[1]));
       out->moments_ms += ms;
-      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[2]));
+      if (wide) {
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[4]));
+        out->scale_ms += ms;
+      }
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[wide ? 4 : 1], sx.e[2]));
       out->cd_ms += ms;
       SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
       out->state_ms += ms;
@@ -1395,6 +1517,14 @@ int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) {
   SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), d_U, sizeof(double) * out->u.size(), hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) { return newton_cv_loop(pb, timed, out, false, 0); }
+
+int wnewton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, int width) {
+  return newton_cv_loop(pb, timed, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures)));
 }
 
 }  // namespace sgdnet

@@ -147,6 +147,7 @@ struct NewtonCvResult {                // job-major
   double sweeps = 0.0;
   int rounds = 0;                      // rounds of the lock-step loop: launches shared by all jobs
   float moments_ms = 0.f, cd_ms = 0.f, state_ms = 0.f;   // (timed only)
+  float scale_ms = 0.f;                                  // wnewton_cv_run only: newton_cv_wide_scale_kernel
 };
 
 // the device memory the jobs of a call need (see above); n_t: the rows of each training set
@@ -154,6 +155,52 @@ size_t newton_cv_workspace_bytes(int64_t n, int64_t p, bool sparse, const int64_
 
 // The lock-step loop.  The caller has checked the sizes, the feature limit, the job count and the workspace.
 int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out);
+
+// ---- the same for the wide mode (newton.hip: wnewton_cv_run) ----
+// Job (mix a, training set t) = a * n_sets + t is wnewton_run on the rows of its training set: the lock-step loop above
+// around the wide inner solve, dense x only, one workgroup -- one compute unit -- per job and round.  H depends on the
+// iterate, so nothing is pooled across jobs: every job keeps its own, in doubles (P = p + 1, ld = wide_leading_dim(P)),
+//   v and r                        2 n
+//   the moments M                  (p + 2)^2
+//   the row chunks' partial tiles  max_chunks x wide_tile_pairs(p + 2) x 256   (max_chunks: the most chunks of a job, each
+//                                  job's being those wnewton_run takes for its n_t rows)
+//   H, diag H and q                ld P + 2 P
+//   the answers U                  n_lambda P
+//   the small vectors              the state pass's sums (3 x 1024 + 2), the record, both iterates and the state-pass form (3 P)
+// and once per call x and y (n p + n).  From 2000 features on a job is one chunk and about 2.5 (p + 2)^2 doubles.  With 100
+// lambdas and 2000 rows: 50 jobs (5 mixes x 10 folds) take 1.07 GB at p = 1000 and 9.21 GB at p = 3000; at the limit
+// p = 5819 a job is 0.68 GB (2.52 (p + 2)^2 doubles) and 25 jobs fit.  The bound is kWcovCvBytes's 16 GiB: the arithmetic
+// gives no reason for another -- it is an eighteenth of the card's 288 GB, and it holds the 50-job CV up to 4110 features.
+constexpr size_t kWnewtonCvBytes = (size_t)16 << 30;
+constexpr int kWnewtonCvTileRows = 64, kWnewtonCvStateMaxBlocks = 1024, kWnewtonCvRecordDoubles = 8;     // (newton.hip asserts them)
+// the row chunks wnewton_run takes for n rows
+constexpr int64_t wnewton_row_chunks(int64_t n, int64_t p) {
+  return (n + wide_rows_per_chunk(n, p + 2, kWnewtonCvTileRows) - 1) / wide_rows_per_chunk(n, p + 2, kWnewtonCvTileRows);
+}
+constexpr size_t wnewton_cv_bytes(int64_t jobs, int64_t n, int64_t p, int64_t n_lambda, int64_t max_chunks) {
+  return sizeof(double) * ((size_t)jobs * (2 * (size_t)n + (size_t)(p + 2) * (size_t)(p + 2) +
+                                           (size_t)max_chunks * (size_t)wide_tile_pairs(p + 2) * 256 +
+                                           (size_t)wide_leading_dim(p + 1) * (size_t)(p + 1) + 2 * (size_t)(p + 1) +
+                                           (size_t)n_lambda * (size_t)(p + 1) + 3 * (size_t)kWnewtonCvStateMaxBlocks + 2 +
+                                           (size_t)kWnewtonCvRecordDoubles + 3 * (size_t)(p + 1)) +
+                           (size_t)n * (size_t)p + (size_t)n);
+}
+static_assert(wnewton_row_chunks(2000, 1000) == 1 && wnewton_row_chunks(2000, 3000) == 1, "one chunk from 1024 tile pairs on");
+static_assert(wnewton_cv_bytes(50, 2000, 1000, 100, 1) / 10000000 == 107 && wnewton_cv_bytes(50, 2000, 3000, 100, 1) / 10000000 == 921,
+              "the examples above");
+static_assert((wnewton_cv_bytes(2, 2000, kWnewtonMaxFeatures, 100, 1) - wnewton_cv_bytes(1, 2000, kWnewtonMaxFeatures, 100, 1)) / 10000000 == 68,
+              "the examples above");
+static_assert(wnewton_cv_bytes(25, 2000, kWnewtonMaxFeatures, 100, 1) <= kWnewtonCvBytes &&
+              wnewton_cv_bytes(26, 2000, kWnewtonMaxFeatures, 100, 1) > kWnewtonCvBytes, "the examples above");
+static_assert(wnewton_cv_bytes(50, 2000, 4110, 100, 1) <= kWnewtonCvBytes && wnewton_cv_bytes(50, 2000, 4111, 100, 1) > kWnewtonCvBytes,
+              "the examples above");
+
+// the device memory the jobs of a call need (see above); n_t: the rows of each training set
+size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int n_sets, int n_mix, int n_lambda);
+
+// The lock-step loop around the wide inner solve: pb as newton_cv_run takes it, dense x only.  width as wnewton_run's.  The
+// caller has checked the sizes, the feature limit, the job count, the width and the workspace.
+int wnewton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, int width = 0);
 
 // Diagnostics (include/sgdnet_hip.h: sgdnet_newton_probe_*): one outer step through the host steps newton_run takes, every
 // output copied back.  pb: x, y, centre, scale, device and n_lambda = 1; the rest comes from io.  The caller has checked both.

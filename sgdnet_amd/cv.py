@@ -23,6 +23,11 @@ cv_sgdnet_newton() is the binomial CV whose fits are sgdnet_newton(); its fold_f
 cv_newton_fits -> sgdnet_cv_newton_*: the Newton loops of all jobs advance in lock-step, every kernel launched once per
 round over all of them (csrc/newton.hip: newton_cv_run).
 
+cv_sgdnet_wnewton() is the binomial CV whose fits are sgdnet_wnewton() (beyond Newton mode's 198 features); its
+fold_fits="batched" runs all fold fits through cv_wnewton_fits -> sgdnet_cv_wnewton_*: the same lock-step loop around the wide
+inner solve, every job with its own H in device memory and one workgroup -- one compute unit -- per job and round
+(csrc/newton.hip: wnewton_cv_run).
+
 cv_sgdnet_mcovariance() is the mgaussian CV whose fits are sgdnet_mcovariance(); its fold_fits="batched" runs all fold fits
 through cv_mcovariance_fits -> sgdnet_cv_mcovariance_*: the group moments of the K responses from one pass, every training
 set pooled from them, one workgroup per path (csrc/covariance.hip: mcovariance_cv_run).
@@ -39,7 +44,7 @@ cv_sgdnet_wmcovariance() is the mgaussian CV whose fits are sgdnet_wmcovariance(
 fold_fits="batched" runs all fold fits through cv_wmcovariance_fits -> sgdnet_cv_wmcovariance_*: the group moments of the K
 responses from one pass, every training set's scaled Gram matrix and c~ pooled from them into device memory, one workgroup --
 one compute unit -- per path (csrc/covariance.hip: wmcovariance_cv_run).
-_cv() is the body the six CVs share; they differ in the fit they inject.
+_cv() is the body the seven CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -48,8 +53,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODES, check, dptr
-from .api import SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance
+from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODE_WNEWTON, MODES, check, dptr
+from .api import (SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance,
+                  sgdnet_wnewton)
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -138,6 +144,25 @@ def cv_newton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000,
     a binomial response (so a fold's class codes are the whole data's).  Returns a list of SgdnetFit, alpha-major: entry
     a * nfolds + j is sgdnet_newton(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a]) for the training set T of fold j;
     its diagnostics hold the job's Newton steps and halvings over the path ("steps", "halvings")."""
+    return _binomial_fold_fits(x, y, foldid, alpha, lambda_, train_on, maxit=maxit, standardize=standardize, intercept=intercept,
+                               thresh=thresh, device=device, wide=False)
+
+
+def cv_wnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                    thresh=0.001, device=0):
+    """Every fold fit of a binomial cross-validation in wide Newton mode from one native call, all of them advancing in
+    lock-step.
+
+    The arguments are cv_newton_fits's, for up to wnewton_max_features() features.  Returns a list of SgdnetFit, alpha-major:
+    entry a * nfolds + j is sgdnet_wnewton(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a]) for the training set T of fold j
+    (the same optimum, return codes and npasses; not the same bits); its diagnostics hold the job's Newton steps and halvings
+    over the path ("steps", "halvings").  Sparse x gives the bits of the dense call on the same matrix."""
+    return _binomial_fold_fits(x, y, foldid, alpha, lambda_, train_on, maxit=maxit, standardize=standardize, intercept=intercept,
+                               thresh=thresh, device=device, wide=True)
+
+
+def _binomial_fold_fits(x, y, foldid, alpha, lambda_, train_on, *, maxit, standardize, intercept, thresh, device, wide):
+    """cv_newton_fits and cv_wnewton_fits: the response encoded once, over all samples"""
     y_arr = np.asarray(y)
     if y_arr.ndim > 1 and y_arr.shape[1] > 1:
         raise ValueError("response for binomial regression must be one-dimensional.")
@@ -148,7 +173,7 @@ def cv_newton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000,
         raise ValueError("only one class in response.")
     return _native_fold_fits(x, np.ascontiguousarray(codes), foldid, alpha, lambda_, train_on, family="binomial",
                              classnames=[str(v) for v in levels], maxit=maxit, standardize=standardize, intercept=intercept,
-                             thresh=thresh, device=device)
+                             thresh=thresh, device=device, wide=wide)
 
 
 def cv_mcovariance_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
@@ -212,7 +237,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
                       device, standardize_response=False, n_classes=1, wide=False):
     """Validation, the native call and the SgdnetFit list behind cv_covariance_fits (gaussian: sgdnet_cv_covariance_*),
     cv_wcovariance_fits (gaussian, wide: sgdnet_cv_wcovariance_*), cv_wmcovariance_fits (mgaussian, wide: sgdnet_cv_wmcovariance_*),
-    cv_newton_fits (binomial: sgdnet_cv_newton_*), cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*) and cv_mnewton_fits
+    cv_newton_fits (binomial: sgdnet_cv_newton_*), cv_wnewton_fits (binomial, wide: sgdnet_cv_wnewton_*), cv_mcovariance_fits (mgaussian: sgdnet_cv_mcovariance_*) and cv_mnewton_fits
     (multinomial: sgdnet_cv_mnewton_*, n_classes classes); y_enc: the response as the backend takes it (mgaussian: n x K,
     column-major)."""
     import scipy.sparse as sp
@@ -252,7 +277,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
     ctl.standardize_response = int(bool(standardize_response))
     ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, K
-    ctl.mode = (MODE_MNEWTON if mnewton else MODE_NEWTON if newton else (MODE_WMCOVARIANCE if wide else MODE_MCOVARIANCE) if multi
+    ctl.mode = (MODE_MNEWTON if mnewton else (MODE_WNEWTON if wide else MODE_NEWTON) if newton else (MODE_WMCOVARIANCE if wide else MODE_MCOVARIANCE) if multi
                 else MODE_WCOVARIANCE if wide else MODES["covariance"])
     ctl.device = int(device)
     jobs = A * G
@@ -272,7 +297,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
             dptr(lam), C.byref(res))
     L = _lib.load()
-    stem = ("sgdnet_cv_mnewton" if mnewton else "sgdnet_cv_newton" if newton else ("sgdnet_cv_wmcovariance" if wide else "sgdnet_cv_mcovariance") if multi
+    stem = ("sgdnet_cv_mnewton" if mnewton else ("sgdnet_cv_wnewton" if wide else "sgdnet_cv_newton") if newton else ("sgdnet_cv_wmcovariance" if wide else "sgdnet_cv_mcovariance") if multi
             else "sgdnet_cv_wcovariance" if wide else "sgdnet_cv_covariance")
     if sp.issparse(x):
         xs = sp.csc_matrix(x, dtype=np.float64)
@@ -376,6 +401,29 @@ def cv_sgdnet_newton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_m
                train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
 
 
+def cv_sgdnet_wnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                      train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                      standardize=True, intercept=True, thresh=0.001):
+    """cv_sgdnet(family="binomial") with every fit a sgdnet_wnewton(): cv_sgdnet_newton() beyond its feature limit, up to
+    wnewton_max_features() features.  fold_fits="separate" (the default) runs one sgdnet_wnewton per fold; "batched" runs all
+    fold fits of all alphas through ONE native call (cv_wnewton_fits) with the full fits' lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_wnewton(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio, device=dev,
+                              **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_wnewton_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="binomial", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
 def cv_sgdnet_wcovariance(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
                           train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
                           standardize=True, intercept=True, thresh=0.001):
@@ -471,7 +519,7 @@ def cv_sgdnet_mnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_
 
 
 def _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, *, family, devices, rng, seed, train_on, densify, fit_one, batched_fits):
-    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance(), cv_sgdnet_mnewton(), cv_sgdnet_wcovariance() and cv_sgdnet_wmcovariance(): the full fits, the fold ids, the fold fits, the scores
+    """The cross-validation behind cv_sgdnet(), cv_sgdnet_newton(), cv_sgdnet_mcovariance(), cv_sgdnet_mnewton(), cv_sgdnet_wnewton(), cv_sgdnet_wcovariance() and cv_sgdnet_wmcovariance(): the full fits, the fold ids, the fold fits, the scores
     and the summary.  fit_one(x, y, lambda, alpha, device, seed, rng, sequential) is a fit; batched_fits(x, y, foldid, alpha,
     lambdas, device), where given, returns every fold fit from one call (alpha-major), else the folds are fitted one by one."""
     import scipy.sparse as sp
