@@ -352,6 +352,12 @@ int sgdnet_wmnewton_max_features(int n_classes);
 /*                        on 256 or 1024 lanes by the library's rule; 256 or  */
 /*                        1024: on that many (same bits either way; any       */
 /*                        other value makes such a fit return SGDNET_EINVAL)  */
+/*   "wnewton_moments"    0 (default): SGDNET_MODE_WNEWTON's moments pass over */
+/*                        dense x is the tile kernel on the vector ALU; 1: the */
+/*                        f64 matrix-core kernel (same terms, the rows summed   */
+/*                        in another order: the same optimum, other last bits). */
+/*                        Read by sgdnet_wnewton_probe too; the other modes and */
+/*                        the cross-validation entry points ignore it           */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

@@ -63,6 +63,7 @@
 #include "moments_device.hpp"
 #include "newton.hpp"
 #include "newton_cv_device.hpp"
+#include "newton_mfma.hpp"
 #include "setup_device.hpp"
 #include "wide_cd_device.hpp"
 
@@ -886,6 +887,8 @@ struct NewtonDevice {
   bool wide = false;
   int width = 0, ld = 0;
   double *d_H = nullptr, *d_Hd = nullptr, *d_q = nullptr;
+  // wide, dense x and the option "wnewton_moments" = 1 (read in setup): the moments pass of newton_mfma.hip on its own row chunks
+  bool mfma = false;
   // dense x: the tile pairs and the row chunks (a function of n and p alone)
   int pairs = 0;
   int64_t rows_per_chunk = 0, chunks = 0;
@@ -930,7 +933,8 @@ struct NewtonDevice {
     const size_t o_r = A.reserve(sizeof(double) * (size_t)n);
     const size_t o_mu = A.reserve(sizeof(double) * (size_t)nc);          // cov_sum_kernel: the means, then the sum and the mean of y
     const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
-    const size_t o_part = A.reserve(sparse ? 0 : sizeof(double) * (size_t)(chunks * pairs * kBlock));
+    mfma = wide && !sparse && option(kOptWnewtonMoments) == 1;
+    const size_t o_part = A.reserve(sparse ? 0 : mfma ? (size_t)wide_mfma_partial_bytes(n, nc) : sizeof(double) * (size_t)(chunks * pairs * kBlock));
     const size_t o_M = A.reserve(sizeof(double) * (size_t)nc * (size_t)nc);
     const size_t o_partial = A.reserve(sizeof(double) * 3 * (size_t)state_blocks);
     const size_t o_sums = A.reserve(sizeof(double) * 2);
@@ -1046,6 +1050,8 @@ struct NewtonDevice {
     if (sparse) {
       hipLaunchKernelGGL(newton_sparse_pair_kernel, dim3((unsigned)p, (unsigned)nc), dim3(kBlock), 0, st, d_colptr, d_rowidx, d_x, d_v,
                          d_r, d_mu, d_sums, n, p, d_M);
+    } else if (mfma) {
+      wnewton_mfma_moments(d_x, d_v, d_r, d_mu, n, p, d_part, d_M, st);
     } else {
       hipLaunchKernelGGL(newton_dense_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks), dim3(kBlock), 0, st, d_x, d_v, d_r, d_mu, n,
                          p, rows_per_chunk, d_part);
@@ -1173,6 +1179,7 @@ int newton_loop(const NewtonProblem& pb, bool timed, NewtonResult* out, bool wid
   }
   out->passes = D.passes;
   out->state_ms = D.state_ms;
+  out->moments_kernel = sparse ? "newton_sparse_pair_kernel" : D.mfma ? "newton_mfma_tile_kernel" : "newton_dense_tile_kernel";
 
   out->mean.resize((size_t)p);
   out->u.resize((size_t)L * (size_t)P);

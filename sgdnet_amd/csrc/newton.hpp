@@ -70,6 +70,13 @@ constexpr int64_t kWnewtonPartialBytes = (int64_t)160 << 20;
 static_assert(wide_row_chunks(1 << 30, kWnewtonMaxFeatures + 2) == 1 &&
               wide_tile_pairs(kWnewtonMaxFeatures + 2) * 256 * 8 <= kWnewtonPartialBytes, "one chunk at the limit");
 static_assert(wide_row_chunks(1 << 30, 3) * wide_tile_pairs(3) * 256 * 8 <= kWnewtonPartialBytes, "1024 workgroups' tiles at most");
+// The matrix-core pass (the option "wnewton_moments" = 1; newton_mfma.hip) keeps a 64 x 64 partial tile per macro-tile pair
+// and row chunk in the same buffer: 64 MiB at most while there are chunks (2048 workgroups' tiles) and 137 MB at the
+// feature limit (91 macro tiles, 4186 pairs, one chunk).
+static_assert(wide_mfma_partial_bytes(1 << 30, kWnewtonMaxFeatures + 2) == (int64_t)4186 * 32768 &&
+              wide_mfma_partial_bytes(1 << 30, kWnewtonMaxFeatures + 2) <= kWnewtonPartialBytes, "one chunk at the limit");
+static_assert(wide_mfma_partial_bytes(1 << 30, 3) == (int64_t)64 << 20 && wide_mfma_partial_bytes(1 << 30, 2816) <= (int64_t)64 << 20,
+              "2048 workgroups' tiles at most");
 // Sparse x is expanded to a column-major dense copy by the driver (the sparse pair kernel launches p (p + 2) workgroups per
 // outer step); the copy stays within this many bytes.
 constexpr size_t kWnewtonDenseCopyBytes = (size_t)1 << 30;
@@ -90,6 +97,7 @@ struct NewtonResult {
   double sweeps = 0.0, halvings = 0.0; // (SGDNET_TRACE)
   float state_ms = 0.f, moments_ms = 0.f, cd_ms = 0.f;   // kernel times summed over the path (SGDNET_TRACE only: they cost a sync per step)
   float scale_ms = 0.f;                                  // wnewton_run only: wide_scale_kernel
+  const char* moments_kernel = "";                       // (SGDNET_TRACE) the kernel of the moments pass
 };
 
 // The Newton loop (newton.hip).  p <= kNewtonMaxFeatures is the caller's business (plan_fit).  timed: fill the *_ms fields.
@@ -97,7 +105,8 @@ int newton_run(const NewtonProblem& pb, bool timed, NewtonResult* out);
 
 // The same loop around the wide inner solve (newton.hip): dense x only, p <= kWnewtonMaxFeatures is the caller's business
 // (plan_fit).  width: lanes of the inner solve's workgroup (256 or 1024), 0 = the rule of wide_layout.hpp (wide_cd_width);
-// both give the same bits.
+// both give the same bits.  The option "wnewton_moments" chooses the kernel of the moments pass (0: newton_dense_tile_kernel,
+// 1: newton_mfma_tile_kernel); wnewton_probe reads it too, the other modes and the cross-validation do not.
 int wnewton_run(const NewtonProblem& pb, bool timed, NewtonResult* out, int width = 0);
 
 // ---- cross-validation: every fold fit of every mix through the Newton loop in lock-step (newton.hip: newton_cv_run) ----

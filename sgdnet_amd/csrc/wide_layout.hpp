@@ -41,5 +41,41 @@ constexpr int64_t wide_rows_per_chunk(int64_t n, int64_t ncols, int64_t tile_row
   return ((n + wide_row_chunks(n, ncols) - 1) / wide_row_chunks(n, ncols) + tile_rows - 1) / tile_rows * tile_rows;
 }
 
+// The matrix-core moments pass of wide Newton mode (newton_mfma.hip; the option "wnewton_moments" = 1) over ncols = p + 2
+// columns.  A workgroup owns a pair of macro tiles of kMfmaTileCols columns and steps through its rows in slabs of
+// kMfmaSlabRows; its partial tile is kMfmaTileCols^2 doubles (32 KiB).  The row chunks are a function of n and ncols alone:
+// as many as it takes to put 2048 workgroups on the GPU (256 CUs x 8 short ones balance better than x 4 long ones, and a
+// chunk's partial tile costs 32 KiB of traffic against the 128 columns x rows it read), none shorter than
+// kMfmaMinChunkRows, and ONE once two chunks of every macro-tile pair would be more than that (p + 2 > 2816).  Examples:
+//   p + 2 <= 64 (one pair): a chunk per 256 rows up to 2048 chunks -- 256 rows 1, 257 rows 2 (the second holds one row),
+//                           513 rows 3; beyond 524 288 rows the chunks grow instead
+//   20000 x 1000 (136 pairs): 15 chunks of 1344 rows (the last holds 1184), 2040 workgroups
+//   500 x 2000 (528 pairs):   3 chunks would be allowed, but 500 rows are 2 chunks of 256
+//   the limit p = 5819 (4186 pairs): one chunk whatever n is
+constexpr int kMfmaTileCols = 64, kMfmaSlabRows = 32, kMfmaMinChunkRows = 256, kMfmaWorkgroups = 2048;
+constexpr int64_t wide_mfma_tiles(int64_t ncols) { return (ncols + kMfmaTileCols - 1) / kMfmaTileCols; }
+constexpr int64_t wide_mfma_pairs(int64_t ncols) { return wide_mfma_tiles(ncols) * (wide_mfma_tiles(ncols) + 1) / 2; }
+// the rows of a chunk: n over the chunks the workgroup target allows, in whole slabs, at least kMfmaMinChunkRows
+constexpr int64_t wide_mfma_rows_per_chunk(int64_t n, int64_t ncols) {
+  const int64_t pairs = wide_mfma_pairs(ncols), cap = pairs >= kMfmaWorkgroups ? 1 : kMfmaWorkgroups / pairs;
+  const int64_t rows = ((n + cap - 1) / cap + kMfmaSlabRows - 1) / kMfmaSlabRows * kMfmaSlabRows;
+  return rows < kMfmaMinChunkRows ? kMfmaMinChunkRows : rows;
+}
+constexpr int64_t wide_mfma_row_chunks(int64_t n, int64_t ncols) {
+  return n < 1 ? 1 : (n + wide_mfma_rows_per_chunk(n, ncols) - 1) / wide_mfma_rows_per_chunk(n, ncols);
+}
+constexpr int64_t wide_mfma_partial_bytes(int64_t n, int64_t ncols) {
+  return wide_mfma_row_chunks(n, ncols) * wide_mfma_pairs(ncols) * kMfmaTileCols * kMfmaTileCols * 8;
+}
+static_assert(wide_mfma_row_chunks(1, 3) == 1 && wide_mfma_row_chunks(256, 9) == 1 && wide_mfma_row_chunks(257, 9) == 2 &&
+              wide_mfma_row_chunks(512, 9) == 2 && wide_mfma_row_chunks(513, 9) == 3, "a chunk per 256 rows at one pair");
+static_assert(wide_mfma_row_chunks(524288, 64) == 2048 && wide_mfma_rows_per_chunk(524289, 64) == 288 &&
+              wide_mfma_row_chunks(524289, 64) == 1821, "beyond 2048 chunks the chunks grow");
+static_assert(wide_mfma_pairs(1002) == 136 && wide_mfma_rows_per_chunk(20000, 1002) == 1344 && wide_mfma_row_chunks(20000, 1002) == 15,
+              "20000 x 1000");
+static_assert(wide_mfma_pairs(2002) == 528 && wide_mfma_row_chunks(500, 2002) == 2, "500 x 2000");
+static_assert(wide_mfma_pairs(2816) == 990 && wide_mfma_row_chunks(1 << 30, 2816) == 2 && wide_mfma_pairs(2817) == 1035 &&
+              wide_mfma_row_chunks(1 << 30, 2817) == 1, "one chunk from 1025 pairs on");
+
 #pragma GCC visibility pop
 }  // namespace sgdnet
