@@ -358,6 +358,15 @@ int sgdnet_wmnewton_max_features(int n_classes);
 /*                        in another order: the same optimum, other last bits). */
 /*                        Read by sgdnet_wnewton_probe too; the other modes and */
 /*                        the cross-validation entry points ignore it           */
+/*   "wmnewton_moments"   0 (default): SGDNET_MODE_WMNEWTON's class-pair moments */
+/*                        pass is the tile kernel on the vector ALU; 1: the f64 */
+/*                        matrix-core kernel, which stages the rows once for a  */
+/*                        group of class pairs (same terms, the rows summed in  */
+/*                        another order: the same optimum, other last bits).    */
+/*                        Sparse x goes through the same dense copy.  Read by   */
+/*                        sgdnet_wmnewton_probe too; SGDNET_MODE_MNEWTON, the   */
+/*                        other modes and the cross-validation entry points     */
+/*                        ignore it                                             */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

@@ -252,7 +252,8 @@ int fit_mnewton(const Features& X, const Response& R, const Path& path, const Fi
   }
   if (pt.on && wide)
     fprintf(stderr, "[sgdnet]   wmnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
-            "scale %.3f ms, inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.scale_ms, nr.cd_ms);
+            "scale %.3f ms, inner solves %.3f ms; moments by %s\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms,
+            nr.scale_ms, nr.cd_ms, nr.moments_kernel);
   else if (pt.on)
     fprintf(stderr, "[sgdnet]   mnewton: %.0f outer steps, %.0f state passes (%.0f after a halving), %.0f sweeps; state %.3f ms, moments %.3f ms, "
             "inner solves %.3f ms\n", n_steps, nr.passes, nr.halvings, nr.sweeps, nr.state_ms, nr.moments_ms, nr.cd_ms);

@@ -56,6 +56,7 @@
 #include "common.hpp"
 #include "device_math.hpp"
 #include "mnewton.hpp"
+#include "mnewton_mfma.hpp"
 #include "moments_device.hpp"
 #include "newton_cv_device.hpp"
 #include "wide_cd_device.hpp"
@@ -110,16 +111,7 @@ __global__ __launch_bounds__(kBlock) void mnewton_finish_kernel(const double* __
   if (threadIdx.x == 0) rec[kRecLoss] = s / (double)n;
 }
 
-// class pair c = 0 .. K (K + 1) / 2 - 1 -> (k, l), k <= l, row by row of the upper triangle
-__device__ __forceinline__ void class_pair(int c, int K, int* k, int* l) {
-  int kk = 0;
-  while (c >= K - kk) {
-    c -= K - kk;
-    ++kk;
-  }
-  *k = kk;
-  *l = kk + c;
-}
+// (class pair c -> (k, l), k <= l: mnewton.hpp's class_pair)
 __device__ __forceinline__ int class_pair_index(int k, int l, int K) { return k * K - k * (k - 1) / 2 + (l - k); }
 
 // newton_cv_dense_tile_kernel with the class pair blockIdx.z where that kernel has the job: entry (a, b), a <= b, of the
@@ -701,6 +693,8 @@ struct MNewtonDevice {
   bool wide = false;
   int ld = 0;
   double *d_H = nullptr, *d_Hd = nullptr, *d_q = nullptr;
+  // wide and the option "wmnewton_moments" = 1 (read in setup): the moments pass of mnewton_mfma.hip on its own row chunks
+  bool mfma = false;
   int pairs = 0;                       // the tile pairs and the row chunks (a function of n, p and K alone)
   int64_t rows_per_chunk = 0, chunks = 0;
   int state_blocks = 0;
@@ -740,7 +734,9 @@ struct MNewtonDevice {
     const size_t o_mu = A.reserve(sizeof(double) * (size_t)n * (size_t)K);
     const size_t o_m = A.reserve(sizeof(double) * (size_t)nc);           // cov_sum_kernel: the means, then the sum and the mean of y
     const size_t o_scale = A.reserve(sizeof(double) * (size_t)p);
-    const size_t o_part = A.reserve(sizeof(double) * (size_t)class_pairs * (size_t)chunks * (size_t)pairs * kBlock);
+    mfma = wide && option(kOptWmnewtonMoments) == 1;
+    const size_t o_part = A.reserve(mfma ? (size_t)wmnewton_mfma_partial_bytes(n, nc, K)
+                                         : sizeof(double) * (size_t)class_pairs * (size_t)chunks * (size_t)pairs * kBlock);
     const size_t o_M = A.reserve(sizeof(double) * (size_t)class_pairs * (size_t)nc * (size_t)nc);
     const size_t o_partial = A.reserve(sizeof(double) * (size_t)state_blocks);
     const size_t o_rec = A.reserve(sizeof(double) * kRecLen);
@@ -816,10 +812,14 @@ struct MNewtonDevice {
   // the moments pass: d_M from d_mu of the last state pass (timed: between the events 0 and 1)
   int moments() {
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
-    hipLaunchKernelGGL(mnewton_pair_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks, (unsigned)class_pairs), dim3(kBlock), 0, st, d_x,
-                       d_y, d_mu, d_m, n, p, K, rows_per_chunk, d_part);
-    hipLaunchKernelGGL(mnewton_pair_reduce_kernel, dim3((unsigned)pairs, (unsigned)class_pairs), dim3(kBlock), 0, st, d_part, (int)chunks,
-                       nc, d_M);
+    if (mfma) {
+      wmnewton_mfma_moments(d_x, d_y, d_mu, d_m, n, p, K, d_part, d_M, st);
+    } else {
+      hipLaunchKernelGGL(mnewton_pair_tile_kernel, dim3((unsigned)pairs, (unsigned)chunks, (unsigned)class_pairs), dim3(kBlock), 0, st, d_x,
+                         d_y, d_mu, d_m, n, p, K, rows_per_chunk, d_part);
+      hipLaunchKernelGGL(mnewton_pair_reduce_kernel, dim3((unsigned)pairs, (unsigned)class_pairs), dim3(kBlock), 0, st, d_part, (int)chunks,
+                         nc, d_M);
+    }
     SGD_HIP_TRY(hipGetLastError());
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
     return SGDNET_OK;
@@ -942,6 +942,7 @@ int mnewton_loop(const MNewtonProblem& pb, bool timed, MNewtonResult* out, bool 
   }
   out->passes = D.passes;
   out->state_ms = D.state_ms;
+  out->moments_kernel = D.mfma ? "mnewton_mfma_tile_kernel" : "mnewton_pair_tile_kernel";
 
   out->mean.resize((size_t)p);
   out->u.resize((size_t)L * (size_t)Q);

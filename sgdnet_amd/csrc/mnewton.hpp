@@ -106,6 +106,63 @@ static_assert(wmnewton_row_chunks((int64_t)1 << 40, 3, 2) * wmnewton_chunk_workg
 // Sparse x is expanded to a column-major dense copy by the driver, as for mnewton; the copy stays within this many bytes.
 constexpr size_t kWmnewtonDenseCopyBytes = (size_t)1 << 30;
 
+// class pair c = 0 .. K (K + 1) / 2 - 1 -> (k, l), k <= l, row by row of the upper triangle (the kernels call it too)
+constexpr void class_pair(int c, int K, int* k, int* l) {
+  int kk = 0;
+  while (c >= K - kk) {
+    c -= K - kk;
+    ++kk;
+  }
+  *k = kk;
+  *l = kk + c;
+}
+
+// The matrix-core class-pair moments pass of the wide mode (mnewton_mfma.hip; the option "wmnewton_moments" = 1).  A
+// workgroup owns a pair of 64-column macro tiles (wide_layout.hpp) for a GROUP of kWmnewtonMfmaGroup consecutive class
+// pairs: the slab of centred rows is staged once and weighted in registers pair by pair.  The last group of a K may be
+// partial: 3 pairs at K = 2, 1 of 55 at K = 10.  The row chunks follow wide_layout.hpp's wide_mfma_chunk_rows with macro
+// pairs x groups workgroups a chunk; every workgroup stores one 64 x 64 partial tile (32 KiB) per class pair of its group.
+//   K = 3 (one group), p + 2 <= 64: a chunk per 256 rows up to 2048 chunks, as wide_mfma_row_chunks
+//   20000 x 200, K = 10: 10 macro pairs x 10 groups, 20 chunks of 1024 rows (the last holds 544), 2000 workgroups
+//   500 x 2500, K = 2:   820 macro pairs x 1 group, 2 chunks of 256 rows
+constexpr int kWmnewtonMfmaGroup = 6;
+static_assert(kWmnewtonMfmaGroup >= 3 && kWmnewtonMfmaGroup * kMfmaSlabRows <= 256, "a lane of the workgroup per (pair, slab row) of the weight table");
+constexpr int64_t wmnewton_mfma_groups(int64_t K) { return (K * (K + 1) / 2 + kWmnewtonMfmaGroup - 1) / kWmnewtonMfmaGroup; }
+constexpr int64_t wmnewton_mfma_rows_per_chunk(int64_t n, int64_t ncols, int64_t K) {
+  return wide_mfma_chunk_rows(n, wide_mfma_pairs(ncols) * wmnewton_mfma_groups(K));
+}
+constexpr int64_t wmnewton_mfma_row_chunks(int64_t n, int64_t ncols, int64_t K) {
+  return n < 1 ? 1 : (n + wmnewton_mfma_rows_per_chunk(n, ncols, K) - 1) / wmnewton_mfma_rows_per_chunk(n, ncols, K);
+}
+constexpr int64_t wmnewton_mfma_partial_bytes(int64_t n, int64_t ncols, int64_t K) {
+  return wmnewton_mfma_row_chunks(n, ncols, K) * wide_mfma_pairs(ncols) * (K * (K + 1) / 2) * kMfmaTileCols * kMfmaTileCols * 8;
+}
+static_assert(wmnewton_mfma_groups(2) == 1 && wmnewton_mfma_groups(3) == 1 && wmnewton_mfma_groups(4) == 2 && wmnewton_mfma_groups(10) == 10 &&
+              wmnewton_mfma_groups(99) == 825, "groups of 6 class pairs");
+static_assert(wmnewton_mfma_row_chunks(256, 9, 2) == 1 && wmnewton_mfma_row_chunks(257, 9, 2) == 2 && wmnewton_mfma_row_chunks(513, 9, 2) == 3 &&
+              wmnewton_mfma_row_chunks(513, 129, 3) == 3, "a chunk per 256 rows while the workgroups are few");
+static_assert(wmnewton_mfma_rows_per_chunk(20000, 202, 10) == 1024 && wmnewton_mfma_row_chunks(20000, 202, 10) == 20, "20000 x 200, K = 10");
+static_assert(wide_mfma_pairs(2502) == 820 && wmnewton_mfma_row_chunks(500, 2502, 2) == 2, "500 x 2500, K = 2");
+// The partial tiles in bytes.  With several chunks there are at most kMfmaWorkgroups workgroups of at most a full group
+// each: 2048 x 6 x 32 KiB = 384 MiB, reached at K = 3 (one full group), p + 2 <= 64 and 524 288 rows or more.  With ONE
+// chunk the most at any K's feature limit is K = 90's: p = 63, 3 macro pairs x 4095 class pairs = 12 285 tiles, 402.6 MB,
+// just under that (K = 2's limit: 1081 x 3 tiles, 106 MB); fewer features at one chunk only have fewer macro pairs.
+// More than kWmnewtonPartialBytes, so the pass has a bound of its own: MNewtonDevice reserves by the pass it runs.
+constexpr int64_t kWmnewtonMfmaPartialBytes = (int64_t)384 << 20;
+constexpr int64_t wmnewton_mfma_limit_bytes(int K) { return wmnewton_mfma_partial_bytes((int64_t)1 << 40, wmnewton_max_features(K) + 2, K); }
+constexpr int wmnewton_mfma_limit_peak() {              // the K whose feature limit takes the most
+  int at = 2;
+  for (int K = 2; K <= kWmnewtonMaxClasses; ++K)
+    if (wmnewton_mfma_limit_bytes(K) > wmnewton_mfma_limit_bytes(at)) at = K;
+  return at;
+}
+static_assert(wmnewton_mfma_limit_peak() == 90 && wmnewton_mfma_limit_bytes(90) == (int64_t)12285 * 32768 &&
+              wmnewton_mfma_limit_bytes(90) <= kWmnewtonMfmaPartialBytes && wmnewton_mfma_limit_bytes(2) == (int64_t)3243 * 32768,
+              "the feature limits (see above)");
+static_assert((int64_t)kMfmaWorkgroups * kWmnewtonMfmaGroup * kMfmaTileCols * kMfmaTileCols * 8 == kWmnewtonMfmaPartialBytes &&
+              wmnewton_mfma_partial_bytes((int64_t)1 << 40, 3, 3) == kWmnewtonMfmaPartialBytes, "2048 workgroups' groups while there are chunks");
+static_assert(kWmnewtonMfmaPartialBytes > kWmnewtonPartialBytes, "(a bound of its own: see above)");
+
 struct MNewtonProblem : DirectProblem {         // x_dense only (sparse x: the driver's dense copy); max_iter: outer steps per lambda
   int K = 0;                           // classes
   const double* y = nullptr;           // n: class codes 0 .. K - 1
@@ -123,6 +180,7 @@ struct MNewtonResult {
   double sweeps = 0.0, halvings = 0.0; // (SGDNET_TRACE)
   float state_ms = 0.f, moments_ms = 0.f, cd_ms = 0.f;   // kernel times summed over the path (SGDNET_TRACE only: they cost a sync per step)
   float scale_ms = 0.f;                                  // wmnewton_run only: mnewton_wide_scale_kernel
+  const char* moments_kernel = "";                       // (SGDNET_TRACE) the kernel of the moments pass
 };
 
 // The Newton loop (mnewton.hip).  2 <= K and p <= mnewton_max_features(K) are the caller's business (plan_fit).
@@ -131,7 +189,9 @@ int mnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int wi
 
 // The same loop around the wide inner solve (mnewton.hip): 2 <= K <= 99 and p <= wmnewton_max_features(K) are the caller's
 // business (plan_fit).  width: lanes of the inner solve's workgroup (256 or 1024), 0 = the rule of mnewton.hip
-// (wmnewton_cd_width); both give the same bits.
+// (wmnewton_cd_width); both give the same bits.  The option "wmnewton_moments" chooses the kernel of the moments pass (0:
+// mnewton_pair_tile_kernel, 1: mnewton_mfma_tile_kernel); wmnewton_probe reads it too, mnewton_run and the cross-validation
+// do not.
 int wmnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int width = 0);
 
 // ---- cross-validation: every fold fit of every mix through the loop above in lock-step (mnewton.hip: mnewton_cv_run) ----

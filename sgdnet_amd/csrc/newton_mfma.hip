@@ -40,15 +40,6 @@ static_assert(kStride % 2 == 0 && (kStride / 2) % 16 == 1, "16-byte LDS loads: 1
 
 typedef double acc_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void macro_pair(int pair, int tiles, int& tI, int& tJ) {
-  tI = 0;
-  while (pair >= tiles - tI) {
-    pair -= tiles - tI;
-    ++tI;
-  }
-  tJ = tI + pair;
-}
-
 __global__ __launch_bounds__(kLanes) void newton_mfma_tile_kernel(const double* __restrict__ x, const double* __restrict__ v,
                                                                    const double* __restrict__ r, const double* __restrict__ mu,
                                                                    int64_t n, int p, int64_t rows_per_chunk, double* __restrict__ part) {

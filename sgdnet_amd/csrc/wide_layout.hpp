@@ -55,12 +55,23 @@ constexpr int64_t wide_rows_per_chunk(int64_t n, int64_t ncols, int64_t tile_row
 constexpr int kMfmaTileCols = 64, kMfmaSlabRows = 32, kMfmaMinChunkRows = 256, kMfmaWorkgroups = 2048;
 constexpr int64_t wide_mfma_tiles(int64_t ncols) { return (ncols + kMfmaTileCols - 1) / kMfmaTileCols; }
 constexpr int64_t wide_mfma_pairs(int64_t ncols) { return wide_mfma_tiles(ncols) * (wide_mfma_tiles(ncols) + 1) / 2; }
-// the rows of a chunk: n over the chunks the workgroup target allows, in whole slabs, at least kMfmaMinChunkRows
-constexpr int64_t wide_mfma_rows_per_chunk(int64_t n, int64_t ncols) {
-  const int64_t pairs = wide_mfma_pairs(ncols), cap = pairs >= kMfmaWorkgroups ? 1 : kMfmaWorkgroups / pairs;
+// macro-tile pair 0 .. wide_mfma_pairs - 1 -> (tI, tJ), tI <= tJ, row by row of the upper triangle (the kernels call it too)
+constexpr void macro_pair(int pair, int tiles, int& tI, int& tJ) {
+  tI = 0;
+  while (pair >= tiles - tI) {
+    pair -= tiles - tI;
+    ++tI;
+  }
+  tJ = tI + pair;
+}
+// the rows of a chunk: n over the chunks the workgroup target allows, in whole slabs, at least kMfmaMinChunkRows.
+// workgroups: those of ONE chunk (the macro-tile pairs; mnewton.hpp: times the class-pair groups)
+constexpr int64_t wide_mfma_chunk_rows(int64_t n, int64_t workgroups) {
+  const int64_t cap = workgroups >= kMfmaWorkgroups ? 1 : kMfmaWorkgroups / workgroups;
   const int64_t rows = ((n + cap - 1) / cap + kMfmaSlabRows - 1) / kMfmaSlabRows * kMfmaSlabRows;
   return rows < kMfmaMinChunkRows ? kMfmaMinChunkRows : rows;
 }
+constexpr int64_t wide_mfma_rows_per_chunk(int64_t n, int64_t ncols) { return wide_mfma_chunk_rows(n, wide_mfma_pairs(ncols)); }
 constexpr int64_t wide_mfma_row_chunks(int64_t n, int64_t ncols) {
   return n < 1 ? 1 : (n + wide_mfma_rows_per_chunk(n, ncols) - 1) / wide_mfma_rows_per_chunk(n, ncols);
 }
