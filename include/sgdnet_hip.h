@@ -367,6 +367,18 @@ int sgdnet_wmnewton_max_features(int n_classes);
 /*                        sgdnet_wmnewton_probe too; SGDNET_MODE_MNEWTON, the   */
 /*                        other modes and the cross-validation entry points     */
 /*                        ignore it                                             */
+/*   "cv_wnewton_moments" 0 (default): the moments pass of sgdnet_cv_wnewton_*   */
+/*                        is the tile kernel on the vector ALU, one job at a    */
+/*                        time; 1: the f64 matrix-core kernel, which stages the */
+/*                        rows of a training set once for a group of up to six  */
+/*                        mixes (same terms, the rows summed in another order:  */
+/*                        the same optimum, other last bits; a job's bits still */
+/*                        do not depend on the other jobs of the call).  Sparse */
+/*                        x goes through the same dense copy.  The jobs' partial */
+/*                        tiles are larger (64 x 64 per macro-tile pair and row */
+/*                        chunk) and count towards the same 16 GiB bound.  The  */
+/*                        narrow sgdnet_cv_newton_*, sgdnet_cv_mnewton_* and the */
+/*                        single fits ignore it                                 */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

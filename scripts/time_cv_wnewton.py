@@ -2,7 +2,7 @@
 """Wall time of a binomial cross-validation whose fits are sgdnet_wnewton(): fold fits one by one against
 fold_fits="batched" (profiles/cv_wnewton.txt).
 
-    python scripts/time_cv_wnewton.py --shape 2000x1000 [--timed N] [--warm W] [--out FILE]
+    python scripts/time_cv_wnewton.py --shape 2000x1000 [--timed N] [--warm W] [--out FILE] [--moments 0|1|both]
 
 One process times one shape, both routes in it, alternating (separate, batched, separate, ...): the separate route is
 cv_sgdnet_wnewton(fold_fits="separate"), one sgdnet_wnewton per fold, the code the mode had before it had a batched CV.
@@ -13,8 +13,12 @@ W warm-up rounds of both routes, then median / min / max of N timed calls each, 
 ends in a device synchronise).  Then the 50 fold fits alone (sa.cv_wnewton_fits with the full fits' lambdas), and one more
 such call under SGDNET_TRACE=1 for the library's line: jobs, rounds, the slowest job, sweeps, and the kernel times per phase
 (moments / scale / inner solves / state; hipEvent times, which cost nothing extra here: a round ends in a synchronise anyway).
-The mean held-out deviance over all folds, mixes and lambdas is printed per route to show both computed the same thing."""
+The mean held-out deviance over all folds, mixes and lambdas is printed per route to show both computed the same thing.
+--moments: the option "cv_wnewton_moments" the batched route runs under (0: the tile kernel, 1: newton_cv_mfma.hip).  "both"
+leaves the separate route out and times the batched CV and the fold fits alone under 0 and 1, alternating after the warm-up,
+with the library's line for each (profiles/cv_wnewton_mfma.txt)."""
 import argparse
+import hashlib
 import os
 import sys
 import tempfile
@@ -54,6 +58,7 @@ def main():
     ap.add_argument("--timed", type=int, default=3)
     ap.add_argument("--warm", type=int, default=1)
     ap.add_argument("--out", default=None, help="append the report to this file as well")
+    ap.add_argument("--moments", default="0", choices=["0", "1", "both"], help='the option "cv_wnewton_moments" of the batched route')
     args = ap.parse_args()
     n, p = (int(v) for v in args.shape.split("x"))
     sys.path.insert(0, ROOT)
@@ -65,7 +70,21 @@ def main():
     x, y = tn.problem(n, p, False)
     foldid = np.random.default_rng(0).permutation(np.arange(n) % NFOLDS) + 1
     kw = dict(alpha=ALPHAS, foldid=foldid, nlambda=NLAMBDA, train_on="rest")
-    routes = {r: (lambda r=r: sa.cv_sgdnet_wnewton(x, y, fold_fits=r, **kw)) for r in ("separate", "batched")}
+
+    def under(setting, f):
+        if args.moments == "0":            # (the default is left alone: a library from before the option runs too)
+            return f
+
+        def call():
+            with sa.option("cv_wnewton_moments", setting):
+                return f()
+        return call
+
+    if args.moments == "both":
+        routes = {"batched, moments = %d" % m: under(m, lambda: sa.cv_sgdnet_wnewton(x, y, fold_fits="batched", **kw)) for m in (0, 1)}
+    else:
+        routes = {"separate": lambda: sa.cv_sgdnet_wnewton(x, y, fold_fits="separate", **kw),
+                  "batched": under(int(args.moments), lambda: sa.cv_sgdnet_wnewton(x, y, fold_fits="batched", **kw))}
 
     report = []
 
@@ -87,24 +106,33 @@ def main():
     for r in routes:
         say("  %s %s: %s" % (r, head, stats(times[r])))
         say("     mean held-out deviance over all jobs and lambdas: %.12g" % np.mean([np.mean(m) for m in cv[r].cv_raw]))
-    lam = cv["batched"].lambda_
-    fits_only = lambda: sa.cv_wnewton_fits(x, y, foldid, ALPHAS, lam, train_on="rest")        # noqa: E731
-    t = []
+    lam = next(iter(cv.values())).lambda_
+    settings = (0, 1) if args.moments == "both" else (int(args.moments),)
+    only = {m: under(m, lambda: sa.cv_wnewton_fits(x, y, foldid, ALPHAS, lam, train_on="rest")) for m in settings}
+    t, fits = {m: [] for m in settings}, {}
     for i in range(args.warm + args.timed):
-        t0 = time.perf_counter()
-        fits = fits_only()
-        if i >= args.warm:
-            t.append(time.perf_counter() - t0)
-    say("  batched_fits_only %s: %s" % (head, stats(t)))
-    say("     unconverged lambdas over all jobs: %d; steps + halvings of the slowest job %d"
-        % (int(sum((f.return_codes != 0).sum() for f in fits)), max(f.diagnostics["steps"] + f.diagnostics["halvings"] for f in fits)))
-    _, lines = traced(fits_only)
-    for line in lines:
-        if "cv wnewton" in line:
-            say("    " + line.replace("[sgdnet]", "").strip())
-    med = {r: float(np.median(times[r])) for r in routes}
-    say("  %s: separate / batched (whole CV) = %.2f: batched is %s" % (args.shape, med["separate"] / med["batched"],
-                                                                     "faster" if med["batched"] < med["separate"] else "slower there"))
+        for m in settings:
+            t0 = time.perf_counter()
+            fits[m] = only[m]()
+            if i >= args.warm:
+                t[m].append(time.perf_counter() - t0)
+    for m in settings:
+        say("  batched_fits_only, moments = %d %s: %s" % (m, head, stats(t[m])))
+        say("     unconverged lambdas over all jobs: %d; steps + halvings of the slowest job %d"
+            % (int(sum((f.return_codes != 0).sum() for f in fits[m])),
+               max(f.diagnostics["steps"] + f.diagnostics["halvings"] for f in fits[m])))
+        say("     sha256 of every job's coefficients and intercepts: %s"
+            % hashlib.sha256(b"".join(f.beta.tobytes() + f.a0.tobytes() for f in fits[m])).hexdigest()[:16])
+        _, lines = traced(only[m])
+        for line in lines:
+            if "cv wnewton" in line:
+                say("    " + line.replace("[sgdnet]", "").strip())
+    if args.moments == "both":
+        say("  %s: fold fits alone, moments 0 / moments 1 = %.2f" % (args.shape, np.median(t[0]) / np.median(t[1])))
+    else:
+        med = {r: float(np.median(times[r])) for r in routes}
+        say("  %s: separate / batched (whole CV) = %.2f: batched is %s" % (args.shape, med["separate"] / med["batched"],
+                                                                         "faster" if med["batched"] < med["separate"] else "slower there"))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as fh:

@@ -675,6 +675,7 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
     set_error("%s: the option wnewton_width is %d; the inner solve runs on 256 or 1024 lanes (0: the rule)", who, width);
     return SGDNET_EINVAL;
   }
+  const bool mfma = wide && option(kOptCvWnewtonMoments) == 1;     // the moments pass of newton_cv_mfma.hip
   int rc = validate_response(ctl, y, n);
   if (rc) return rc;
   std::vector<int64_t> count, start, to;
@@ -715,7 +716,7 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
               n_alpha, G);
     return SGDNET_EUNSUPPORTED;
   }
-  const size_t workspace = wide ? wnewton_cv_workspace_bytes(n, p, n_t.data(), G, n_alpha, L)
+  const size_t workspace = wide ? wnewton_cv_workspace_bytes(n, p, n_t.data(), G, n_alpha, L, mfma)
                                 : newton_cv_workspace_bytes(n, p, sparse, n_t.data(), G, n_alpha);
   if (wide && workspace > kWnewtonCvBytes) {
     set_error("mode = wnewton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of %lld rows and %lld features (per job the "
@@ -835,7 +836,7 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   NewtonCvResult nr;
-  rc = wide ? wnewton_cv_run(pb, pt.on, &nr, width) : newton_cv_run(pb, pt.on, &nr);
+  rc = wide ? wnewton_cv_run(pb, pt.on, &nr, width, mfma) : newton_cv_run(pb, pt.on, &nr);
   if (rc) return rc;
 
   const size_t P1 = P + 1;
@@ -868,8 +869,8 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
     }
   if (pt.on && wide)
     fprintf(stderr, "[sgdnet]   cv wnewton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
-            "moments %.3f ms, scale %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings,
-            nr.sweeps, nr.moments_ms, nr.scale_ms, nr.cd_ms, nr.state_ms);
+            "moments %.3f ms (%s), scale %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings,
+            nr.sweeps, nr.moments_ms, mfma ? "newton_cv_mfma_tile_kernel" : "newton_cv_dense_tile_kernel", nr.scale_ms, nr.cd_ms, nr.state_ms);
   else if (pt.on)
     fprintf(stderr, "[sgdnet]   cv newton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
             "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,

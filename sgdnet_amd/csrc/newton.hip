@@ -63,6 +63,7 @@
 #include "moments_device.hpp"
 #include "newton.hpp"
 #include "newton_cv_device.hpp"
+#include "newton_cv_mfma.hpp"
 #include "newton_mfma.hpp"
 #include "setup_device.hpp"
 #include "wide_cd_device.hpp"
@@ -1267,13 +1268,16 @@ int wnewton_probe(const NewtonProblem& pb, sgdnet_wnewton_probe_io* io) {
 namespace {
 
 // the geometry of a call's jobs: a function of (n, p, the groups, the number of mixes) alone.  wide: the row chunks of a
-// job are those wnewton_run chooses for n_t rows (wide_layout.hpp), else newton_run's (dense_rows_per_chunk)
+// job are those wnewton_run chooses for n_t rows (wide_layout.hpp), else newton_run's (dense_rows_per_chunk).  mfma (wide
+// only): the chunks and the 64 x 64 partial tiles of the matrix-core pass (newton_cv_mfma.hip)
 struct CvGeometry {
   int pairs = 0, max_chunks = 0, max_state_blocks = 0;
+  size_t tile_doubles = kBlock;        // of one partial tile
   std::vector<CvJob> jobs;
-  CvGeometry(int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix, bool wide = false) {
+  CvGeometry(int64_t p, bool sparse, const int64_t* n_t, int n_sets, int n_mix, bool wide = false, bool mfma = false) {
     const int nc = (int)p + 2, T = (nc + kTileCols - 1) / kTileCols;
-    pairs = T * (T + 1) / 2;
+    pairs = mfma ? (int)wide_mfma_pairs(nc) : T * (T + 1) / 2;
+    if (mfma) tile_doubles = (size_t)kMfmaTileCols * kMfmaTileCols;
     jobs.resize((size_t)n_sets * (size_t)n_mix);
     for (int a = 0; a < n_mix; ++a)
       for (int t = 0; t < n_sets; ++t) {
@@ -1281,7 +1285,9 @@ struct CvGeometry {
         J = CvJob{};
         J.n_t = n_t[t];
         J.set = t;
-        J.rows_per_chunk = wide ? wide_rows_per_chunk(J.n_t, nc, kTileRows) : dense_rows_per_chunk(J.n_t, pairs);
+        J.rows_per_chunk = mfma   ? wide_mfma_rows_per_chunk(J.n_t, nc)
+                           : wide ? wide_rows_per_chunk(J.n_t, nc, kTileRows)
+                                  : dense_rows_per_chunk(J.n_t, pairs);
         J.chunks = sparse ? 0 : (int32_t)((J.n_t + J.rows_per_chunk - 1) / J.rows_per_chunk);
         J.state_blocks = (int32_t)std::min<int64_t>(kStateMaxBlocks, (J.n_t + kBlock - 1) / kBlock);
         max_chunks = std::max(max_chunks, (int)J.chunks);
@@ -1300,10 +1306,10 @@ size_t newton_cv_workspace_bytes(int64_t n, int64_t p, bool sparse, const int64_
   return sizeof(double) * CvGeometry(p, sparse, n_t, n_sets, n_mix).workspace_doubles(n, p);
 }
 
-size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int n_sets, int n_mix, int n_lambda) {
+size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int n_sets, int n_mix, int n_lambda, bool mfma) {
   int64_t max_chunks = 0;
-  for (int t = 0; t < n_sets; ++t) max_chunks = std::max(max_chunks, wnewton_row_chunks(n_t[t], p));
-  return wnewton_cv_bytes((int64_t)n_sets * n_mix, n, p, n_lambda, max_chunks);
+  for (int t = 0; t < n_sets; ++t) max_chunks = std::max(max_chunks, mfma ? wnewton_cv_mfma_row_chunks(n_t[t], p) : wnewton_row_chunks(n_t[t], p));
+  return wnewton_cv_bytes((int64_t)n_sets * n_mix, n, p, n_lambda, max_chunks, mfma);
 }
 
 // The lock-step loop.  A round: the commands go up in one copy, every kernel is launched once over all jobs (a job whose
@@ -1314,21 +1320,22 @@ size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int 
 // when every job has finished its last lambda; one last launch stores the iterates still owed.
 // newton_cv_run and wnewton_cv_run: one loop, one state machine per job.  wide: the jobs' row chunks follow wide_row_chunks,
 // newton_cv_wide_scale_kernel writes every stepping job's H, diag H and q to global memory, the inner solve is
-// newton_cv_wide_cd_kernel<width> and the blend has no array of kNewtonMaxFeatures + 1.  Not wide: exactly the launches the
-// Newton cross-validation has always made.
+// newton_cv_wide_cd_kernel<width> and the blend has no array of kNewtonMaxFeatures + 1.  mfma (wide only; the option
+// "cv_wnewton_moments" = 1): the moments pass of a round is newton_cv_mfma.hip's on its own row chunks, everything else in
+// the round as it is.  Not wide: exactly the launches the Newton cross-validation has always made.
 namespace {
 
 static_assert(kTileRows == kWnewtonCvTileRows && kStateMaxBlocks == kWnewtonCvStateMaxBlocks && kRecLen == kWnewtonCvRecordDoubles &&
               kBlock == 256, "newton.hpp: wnewton_cv_bytes counts these");
 
-int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, bool wide, int width) {
+int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, bool wide, int width, bool mfma) {
   const int p = (int)pb.p, P = p + 1, nc = p + 2, L = pb.n_lambda, G = pb.n_sets;
   const int64_t n = pb.n;
   const bool sparse = pb.x_dense == nullptr;
   if (n <= 0 || pb.p <= 0 || pb.p > (wide ? kWnewtonMaxFeatures : kNewtonMaxFeatures) || L <= 0 || G <= 0 || pb.n_mix <= 0 || !pb.y ||
       !pb.start || !pb.mean || !pb.scale || !pb.b0 || !pb.l2 || !pb.l1 || !pb.ridge || pb.max_iter == 0 ||
       (sparse && (!pb.colptr || !pb.rowidx || !pb.values || !pb.cut)) || (int64_t)G * pb.n_mix > kNewtonCvMaxJobs ||
-      (wide && (sparse || (width != kWideNarrow && width != kWideFull)))) {
+      (wide && (sparse || (width != kWideNarrow && width != kWideFull))) || (mfma && !wide)) {
     set_error("%s: invalid problem", wide ? "wnewton_cv_run" : "newton_cv_run");
     return SGDNET_EINVAL;
   }
@@ -1341,7 +1348,7 @@ int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, b
       return SGDNET_EINVAL;
     }
   }
-  CvGeometry geo(p, sparse, n_t.data(), G, pb.n_mix, wide);
+  CvGeometry geo(p, sparse, n_t.data(), G, pb.n_mix, wide, mfma);
   const int jobs = (int)geo.jobs.size(), ld = (int)wide_leading_dim(P);
   for (CvJob& J : geo.jobs) cv_job_rows(J, pb.start, n, pb.train_on_rest);
   const int64_t nnz = sparse ? pb.colptr[p] : 0;
@@ -1359,7 +1366,7 @@ int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, b
   const size_t o_cmd = A.reserve(sizeof(CvCmd) * (size_t)jobs);
   const size_t o_v = A.reserve(sizeof(double) * (size_t)jobs * (size_t)n);
   const size_t o_r = A.reserve(sizeof(double) * (size_t)jobs * (size_t)n);
-  const size_t o_part = A.reserve(sizeof(double) * (size_t)jobs * (size_t)geo.max_chunks * (size_t)geo.pairs * kBlock);
+  const size_t o_part = A.reserve(sizeof(double) * (size_t)jobs * (size_t)geo.max_chunks * (size_t)geo.pairs * geo.tile_doubles);
   const size_t o_M = A.reserve(sizeof(double) * (size_t)jobs * (size_t)nc * (size_t)nc);
   const size_t o_partial = A.reserve(sizeof(double) * (size_t)jobs * 3 * kStateMaxBlocks);
   const size_t o_sums = A.reserve(sizeof(double) * 2 * (size_t)jobs);
@@ -1458,6 +1465,8 @@ int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, b
       if (sparse) {
         hipLaunchKernelGGL(newton_cv_sparse_pair_kernel, dim3((unsigned)p, (unsigned)nc, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs,
                            d_cut, G, pb.train_on_rest ? 1 : 0, d_rowidx, d_x, d_v, d_r, d_mu, d_sums, n, p, d_M);
+      } else if (mfma) {
+        wnewton_cv_mfma_moments(d_cmd, d_jobs, d_x, d_v, d_r, d_mu, n, p, G, pb.n_mix, geo.max_chunks, d_part, d_M, st);
       } else {
         hipLaunchKernelGGL(newton_cv_dense_tile_kernel, dim3((unsigned)geo.pairs, (unsigned)geo.max_chunks, (unsigned)jobs), dim3(kBlock), 0,
                            st, d_cmd, d_jobs, d_x, d_v, d_r, d_mu, n, p, geo.max_chunks, d_part);
@@ -1528,10 +1537,10 @@ int newton_cv_loop(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, b
 
 }  // namespace
 
-int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) { return newton_cv_loop(pb, timed, out, false, 0); }
+int newton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out) { return newton_cv_loop(pb, timed, out, false, 0, false); }
 
-int wnewton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, int width) {
-  return newton_cv_loop(pb, timed, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures)));
+int wnewton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, int width, bool mfma) {
+  return newton_cv_loop(pb, timed, out, true, width != 0 ? width : wide_cd_width((int)std::min<int64_t>(pb.p, kWnewtonMaxFeatures)), mfma);
 }
 
 }  // namespace sgdnet

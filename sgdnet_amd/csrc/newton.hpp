@@ -186,9 +186,23 @@ constexpr int kWnewtonCvTileRows = 64, kWnewtonCvStateMaxBlocks = 1024, kWnewton
 constexpr int64_t wnewton_row_chunks(int64_t n, int64_t p) {
   return (n + wide_rows_per_chunk(n, p + 2, kWnewtonCvTileRows) - 1) / wide_rows_per_chunk(n, p + 2, kWnewtonCvTileRows);
 }
-constexpr size_t wnewton_cv_bytes(int64_t jobs, int64_t n, int64_t p, int64_t n_lambda, int64_t max_chunks) {
+// The matrix-core moments pass of the cross-validation (newton_cv_mfma.hip; the option "cv_wnewton_moments" = 1): a
+// workgroup serves a GROUP of up to kWnewtonCvMfmaGroup consecutive mixes of one training set (kG x 16 accumulator doubles a
+// lane: 192 accumulator registers of a lane's 512, no scratch, one wavefront a SIMD -- profiles/cv_wnewton_mfma.txt; the usual
+// 5 mixes are one group).  A job's row chunks are those a single fit with "wnewton_moments" = 1 takes for its n_t rows, and its partial tiles
+// are max_chunks x wide_mfma_pairs(p + 2) x 64 x 64 doubles in place of the 16-column form's (mfma below).  50 jobs of 1800
+// rows at p = 1000 keep 8 chunks x 136 pairs each: 2.64 GB in all against 1.07; from p + 2 > 2816 on a job is one chunk
+// and the two forms are the same size to the tile padding (at the limit 24 jobs fit within kWnewtonCvBytes, not 25).
+constexpr int kWnewtonCvMfmaGroup = 6;
+static_assert(kWnewtonCvMfmaGroup * kMfmaSlabRows <= 256, "a lane of the workgroup per (member, slab row) of the weight table");
+constexpr int64_t wnewton_cv_mfma_groups(int64_t n_mix) { return (n_mix + kWnewtonCvMfmaGroup - 1) / kWnewtonCvMfmaGroup; }
+constexpr int64_t wnewton_cv_mfma_row_chunks(int64_t n, int64_t p) { return wide_mfma_row_chunks(n, p + 2); }
+constexpr size_t wnewton_cv_partial_doubles(int64_t p, int64_t max_chunks, bool mfma) {
+  return (size_t)max_chunks * (mfma ? (size_t)wide_mfma_pairs(p + 2) * kMfmaTileCols * kMfmaTileCols : (size_t)wide_tile_pairs(p + 2) * 256);
+}
+constexpr size_t wnewton_cv_bytes(int64_t jobs, int64_t n, int64_t p, int64_t n_lambda, int64_t max_chunks, bool mfma = false) {
   return sizeof(double) * ((size_t)jobs * (2 * (size_t)n + (size_t)(p + 2) * (size_t)(p + 2) +
-                                           (size_t)max_chunks * (size_t)wide_tile_pairs(p + 2) * 256 +
+                                           wnewton_cv_partial_doubles(p, max_chunks, mfma) +
                                            (size_t)wide_leading_dim(p + 1) * (size_t)(p + 1) + 2 * (size_t)(p + 1) +
                                            (size_t)n_lambda * (size_t)(p + 1) + 3 * (size_t)kWnewtonCvStateMaxBlocks + 2 +
                                            (size_t)kWnewtonCvRecordDoubles + 3 * (size_t)(p + 1)) +
@@ -203,13 +217,22 @@ static_assert(wnewton_cv_bytes(25, 2000, kWnewtonMaxFeatures, 100, 1) <= kWnewto
               wnewton_cv_bytes(26, 2000, kWnewtonMaxFeatures, 100, 1) > kWnewtonCvBytes, "the examples above");
 static_assert(wnewton_cv_bytes(50, 2000, 4110, 100, 1) <= kWnewtonCvBytes && wnewton_cv_bytes(50, 2000, 4111, 100, 1) > kWnewtonCvBytes,
               "the examples above");
+// ... and with the matrix-core partial tiles: 8 chunks of 256 rows at 2000 x 1000 ("rest", 10 folds: 1800 rows), one at the limit
+static_assert(wnewton_cv_mfma_row_chunks(1800, 1000) == 8 && wnewton_cv_partial_doubles(1000, 8, true) == (size_t)8 * 136 * 4096 &&
+              wnewton_cv_bytes(50, 2000, 1000, 100, 8, true) / 10000000 == 264, "2000 x 1000 with the option cv_wnewton_moments");
+static_assert(wnewton_cv_mfma_row_chunks(1 << 30, kWnewtonMaxFeatures) == 1 &&
+              wnewton_cv_partial_doubles(kWnewtonMaxFeatures, 1, true) == (size_t)4186 * 4096 &&
+              wnewton_cv_bytes(24, 2000, kWnewtonMaxFeatures, 100, 1, true) <= kWnewtonCvBytes &&
+              wnewton_cv_bytes(25, 2000, kWnewtonMaxFeatures, 100, 1, true) > kWnewtonCvBytes, "the feature limit with the option: 24 jobs fit");
 
-// the device memory the jobs of a call need (see above); n_t: the rows of each training set
-size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int n_sets, int n_mix, int n_lambda);
+// the device memory the jobs of a call need (see above); n_t: the rows of each training set; mfma: the option "cv_wnewton_moments"
+size_t wnewton_cv_workspace_bytes(int64_t n, int64_t p, const int64_t* n_t, int n_sets, int n_mix, int n_lambda, bool mfma = false);
 
-// The lock-step loop around the wide inner solve: pb as newton_cv_run takes it, dense x only.  width as wnewton_run's.  The
-// caller has checked the sizes, the feature limit, the job count, the width and the workspace.
-int wnewton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, int width = 0);
+// The lock-step loop around the wide inner solve: pb as newton_cv_run takes it, dense x only.  width as wnewton_run's.  mfma:
+// the moments pass is newton_cv_mfma.hip's (the option "cv_wnewton_moments" = 1, read by the caller with the width), else
+// newton_cv_dense_tile_kernel + newton_cv_reduce_kernel.  The caller has checked the sizes, the feature limit, the job count,
+// the width and the workspace.
+int wnewton_cv_run(const NewtonCvProblem& pb, bool timed, NewtonCvResult* out, int width = 0, bool mfma = false);
 
 // Diagnostics (include/sgdnet_hip.h: sgdnet_newton_probe_*): one outer step through the host steps newton_run takes, every
 // output copied back.  pb: x, y, centre, scale, device and n_lambda = 1; the rest comes from io.  The caller has checked both.
