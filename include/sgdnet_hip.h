@@ -379,6 +379,17 @@ int sgdnet_wmnewton_max_features(int n_classes);
 /*                        chunk) and count towards the same 16 GiB bound.  The  */
 /*                        narrow sgdnet_cv_newton_*, sgdnet_cv_mnewton_* and the */
 /*                        single fits ignore it                                 */
+/*   "cv_wmnewton_moments" 0 (default): the class-pair moments pass of          */
+/*                        sgdnet_cv_wmnewton_* is the tile kernel on the vector */
+/*                        ALU, one (job, class pair) at a time; 1: the f64      */
+/*                        matrix-core kernel, which stages the rows of a        */
+/*                        training set once for a group of six (mix, class      */
+/*                        pair) members (same terms, the rows summed in another */
+/*                        order: the same optimum, other last bits; a job's     */
+/*                        bits still do not depend on the other jobs of the     */
+/*                        call).  The partial tiles are larger and count        */
+/*                        towards the same 16 GiB bound.  Read by those two     */
+/*                        entry points only                                     */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */
@@ -1162,6 +1173,39 @@ int sgdnet_cv_mnewton_dense(const double* x, int64_t n, int64_t p, const double*
 int sgdnet_cv_mnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
                              const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
                              sgdnet_cv_mnewton_result* out);
+
+/* ------------------------------------------------------------------------ */
+/* Cross-validation in wide multinomial Newton mode (additions only; the ABI */
+/* version stays): sgdnet_cv_mnewton_* beyond sgdnet_mnewton_max_features(K)  */
+/* features, up to sgdnet_wmnewton_max_features(K).  The arguments and the    */
+/* result are those of sgdnet_cv_mnewton_*.  Job (a, t) is by definition the  */
+/* SGDNET_MODE_WMNEWTON fit of the rows of training set t with alphas[a] and   */
+/* the user lambdas: the same lock-step loop around the wide inner solve, every */
+/* job with its own joint Hessian in device memory and one workgroup -- one     */
+/* compute unit -- per job and round (sgdnet_amd/csrc/mnewton.hip:              */
+/* wmnewton_cv_run).  Sparse x is expanded to the dense copy a single fit      */
+/* makes: a sparse call gives the dense call's bits.  The options               */
+/* "wmnewton_width" and "cv_wmnewton_moments" are read.  There is no fall-back */
+/* to the narrow loop or to separate fits.                                     */
+/* SGDNET_EUNSUPPORTED ("cv wmnewton needs ..."): the conditions of            */
+/* sgdnet_cv_mnewton_* with this mode's feature limit; more than 65 535 jobs,  */
+/* jobs x class pairs or (cv_wmnewton_moments = 1) groups x member groups; a   */
+/* dense copy of a sparse x above 1 GiB; or a workspace -- per job rows x K +  */
+/* K (K + 1) / 2 x ((n_features + 2)^2 + the row chunks' partial tiles) + H    */
+/* (K (n_features + 1))^2 + 1024 + (n_lambda + 5) x K (n_features + 1) + 8     */
+/* doubles, and x and y once -- above 16 GiB (which holds 5 mixes x 10 folds   */
+/* of 2000 x 1000 at 3 classes under either setting of the option, and 29      */
+/* jobs at 2 classes' feature limit).  SGDNET_EINVAL: as sgdnet_cv_mnewton_*,  */
+/* and a "wmnewton_width" other than 0, 256 or 1024.                           */
+/* ------------------------------------------------------------------------ */
+typedef sgdnet_cv_mnewton_result sgdnet_cv_wmnewton_result;
+
+int sgdnet_cv_wmnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups,
+                             int train_on_rest, const sgdnet_control* ctl, int n_alpha, const double* alphas,
+                             const double* lambdas, sgdnet_cv_wmnewton_result* out);
+int sgdnet_cv_wmnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                              const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                              sgdnet_cv_wmnewton_result* out);
 
 /* ------------------------------------------------------------------------ */
 /* Cross-validation in wide covariance mode (additions only; the ABI version */

@@ -43,6 +43,7 @@ EXPORTS = [
     "sgdnet_cv_mcovariance_dense", "sgdnet_cv_mcovariance_sparse", "sgdnet_cv_mnewton_dense", "sgdnet_cv_mnewton_sparse",
     "sgdnet_cv_wcovariance_dense", "sgdnet_cv_wcovariance_sparse", "sgdnet_cv_wmcovariance_dense", "sgdnet_cv_wmcovariance_sparse",
     "sgdnet_wnewton_probe", "sgdnet_wmnewton_probe", "sgdnet_cv_wnewton_dense", "sgdnet_cv_wnewton_sparse",
+    "sgdnet_cv_wmnewton_dense", "sgdnet_cv_wmnewton_sparse",
     "sgdnet_covariance_probe", "sgdnet_covariance_path_probe", "sgdnet_cv_covariance_probe", "sgdnet_cov_probe_field", "sgdnet_cov_probe_free",
 ]
 ABI_VERSION = 6   # include/sgdnet_hip.h: SGDNET_ABI_VERSION
@@ -319,6 +320,8 @@ def load():
     _cv_tail = _cv_tail[:-1] + [C.POINTER(CvMNewtonResult)]
     L.sgdnet_cv_mnewton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail
     L.sgdnet_cv_mnewton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
+    L.sgdnet_cv_wmnewton_dense.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64] + _cv_tail     # (sgdnet_cv_wmnewton_result is that struct)
+    L.sgdnet_cv_wmnewton_sparse.argtypes = [C.POINTER(Csc)] + _cv_tail
     L.sgdnet_mcovariance_max_features.argtypes = [C.c_int]
     L.sgdnet_mnewton_max_features.argtypes = [C.c_int]
     L.sgdnet_wmcovariance_max_features.argtypes = [C.c_int]

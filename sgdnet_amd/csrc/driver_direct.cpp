@@ -887,36 +887,47 @@ int fit_cv_newton(const CvNewtonMatrix& X, const double* y, const sgdnet_control
 // without an intercept) and its deviance, and regularization_path's penalties for the user's lambdas.  A training set
 // without a row of some class is refused: its separate fit would silently be a model of fewer classes.
 // Every refusal is decided before the first HIP call.
+//
+// wide (the stage behind sgdnet_cv_wmnewton_*, mnewton.hip: wmnewton_cv_run): every job is fit_mnewton in SGDNET_MODE_WMNEWTON
+// on x[T], y[T].  The same steps with the wide mode's feature limit, its dense-copy bound and the workspace bound of
+// mnewton.hpp's wmnewton_cv_bytes under the option "cv_wmnewton_moments"; no fall-back to the narrow loop or to separate fits.
 int fit_cv_mnewton(const CvNewtonMatrix& X, const double* y, const sgdnet_control* ctl, const int32_t* fold, int n_groups, int train_on_rest,
-                   int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mnewton_result* out) {
+                   int n_alpha, const double* alphas, const double* lambdas, sgdnet_cv_mnewton_result* out, bool wide = false) {
   const int64_t n = X.n, p = X.p;
+  const char* const who = wide ? "sgdnet_cv_wmnewton" : "sgdnet_cv_mnewton";
   if (!ctl || !out || !out->a0 || !out->beta || !out->dev_ratio || !out->return_codes || !out->nulldev || !out->npasses || !out->steps ||
       !out->halvings || !y || !fold || !alphas || !lambdas) {
-    set_error("sgdnet_cv_mnewton: null pointer");
+    set_error("%s: null pointer", who);
     return SGDNET_EINVAL;
   }
   if (n <= 0 || p <= 0 || n_groups <= 0 || n_alpha <= 0 || ctl->n_lambda <= 0 || ctl->max_iter == 0 || ctl->tol < 0.0 ||
       (train_on_rest && n_groups < 2)) {
-    set_error("sgdnet_cv_mnewton: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)");
+    set_error("%s: invalid size or control field (n, p, n_groups, n_alpha, n_lambda, max_iter, tol; train_on_rest needs two groups)", who);
     return SGDNET_EINVAL;
   }
   const int L = ctl->n_lambda, G = n_groups, K = ctl->n_classes;
   const bool sparse = X.dense == nullptr, rest = train_on_rest != 0;
-  const int limit = mnewton_max_features(K);
+  const int limit = wide ? wmnewton_max_features(K) : mnewton_max_features(K);
   const char* what = nullptr;
   if (ctl->family != SGDNET_MULTINOMIAL) what = "family = multinomial";
   else if (K < 2 || K >= 100) what = "2 to 99 classes";
   else if (ctl->type_multinomial != 0) what = "the ungrouped penalty (type_multinomial = 0)";
-  else if (p > limit) what = "no more features than sgdnet_mnewton_max_features(n_classes)";
+  else if (p > limit) what = wide ? "no more features than sgdnet_wmnewton_max_features(n_classes)" : "no more features than sgdnet_mnewton_max_features(n_classes)";
   else if (ctl->n_gpus > 1) what = "one GPU (n_gpus <= 1)";
   else if (ctl->debug) what = "debug = 0 (there are no epochs to report losses of)";
-  else if (sparse && (double)n * (double)p * 8.0 > (double)kMNewtonDenseCopyBytes)
+  else if (sparse && (double)n * (double)p * 8.0 > (double)(wide ? kWmnewtonDenseCopyBytes : kMNewtonDenseCopyBytes))
     what = "the dense copy of a sparse x (n_samples x n_features x 8 bytes) within 1 GiB";
   if (what) {
-    set_error("mode = mnewton needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d", what, ctl->family,
-              K, (long long)n, (long long)p, limit, ctl->n_gpus, ctl->debug);
+    set_error("%s needs %s: family %d, n_classes %d, %lld samples, %lld features (limit %d), n_gpus %d, debug %d",
+              wide ? "cv wmnewton" : "mode = mnewton", what, ctl->family, K, (long long)n, (long long)p, limit, ctl->n_gpus, ctl->debug);
     return SGDNET_EUNSUPPORTED;
   }
+  const int width = wide ? option(kOptWmnewtonWidth) : 0;
+  if (width != 0 && width != kWideNarrow && width != kWideFull) {
+    set_error("%s: the option wmnewton_width is %d; the inner solve runs on 256 or 1024 lanes (0: the rule)", who, width);
+    return SGDNET_EINVAL;
+  }
+  const bool mfma = wide && option(kOptCvWmnewtonMoments) == 1;     // the moments pass of mnewton_cv_mfma.hip
   int rc = validate_response(ctl, y, n);
   if (rc) return rc;
   std::vector<int64_t> count, start, to;
@@ -968,12 +979,30 @@ int fit_cv_mnewton(const CvNewtonMatrix& X, const double* y, const sgdnet_contro
     }
   }
   const int64_t class_pairs = (int64_t)K * (K + 1) / 2;
-  if ((int64_t)n_alpha * G > kNewtonCvMaxJobs || (int64_t)n_alpha * G * class_pairs > kMNewtonCvMaxGridZ) {
+  if (wide) {
+    const int64_t groups = wmnewton_cv_mfma_groups(n_alpha, K);
+    if ((int64_t)n_alpha * G > kNewtonCvMaxJobs || (int64_t)n_alpha * G * class_pairs > kWmnewtonCvMaxGrid ||
+        (mfma && (int64_t)G * groups > kWmnewtonCvMaxGrid)) {
+      set_error("cv wmnewton needs no more than %lld jobs, %lld jobs x class pairs and (cv_wmnewton_moments = 1) %lld groups x member groups "
+                "in one cross-validation call: %d mixes x %d groups x %lld class pairs, %lld member groups of 6 a training set",
+                (long long)kNewtonCvMaxJobs, (long long)kWmnewtonCvMaxGrid, (long long)kWmnewtonCvMaxGrid, n_alpha, G, (long long)class_pairs,
+                (long long)groups);
+      return SGDNET_EUNSUPPORTED;
+    }
+    const size_t bytes = wmnewton_cv_workspace_bytes(n, p, K, n_t.data(), G, n_alpha, L, mfma);
+    if (bytes > kWmnewtonCvBytes) {
+      set_error("cv wmnewton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of %lld rows, %lld features and %d classes (per "
+                "job %lld class pairs x ((features + 2)^2 moments + row-chunk partials) and H, (classes x (features + 1))^2 doubles; "
+                "cv_wmnewton_moments = %d) are %zu bytes", kWmnewtonCvBytes, n_alpha, G, (long long)n, (long long)p, K, (long long)class_pairs,
+                mfma ? 1 : 0, bytes);
+      return SGDNET_EUNSUPPORTED;
+    }
+  } else if ((int64_t)n_alpha * G > kNewtonCvMaxJobs || (int64_t)n_alpha * G * class_pairs > kMNewtonCvMaxGridZ) {
     set_error("mode = mnewton needs no more than %lld jobs and %lld jobs x class pairs in one cross-validation call: %d mixes x %d groups "
               "x %lld class pairs", (long long)kNewtonCvMaxJobs, (long long)kMNewtonCvMaxGridZ, n_alpha, G, (long long)class_pairs);
     return SGDNET_EUNSUPPORTED;
   }
-  const double workspace = mnewton_cv_workspace_bytes(n, p, K, n_t.data(), G, n_alpha, L);
+  const double workspace = wide ? 0.0 : mnewton_cv_workspace_bytes(n, p, K, n_t.data(), G, n_alpha, L);
   if (workspace > (double)kNewtonCvWorkspaceBytes) {
     set_error("mode = mnewton needs the jobs' workspace within %zu bytes: %d mixes x %d groups of (rows x %d classes + %lld class pairs x "
               "((%lld + 2)^2 moments + row-chunk partials) + %d lambdas x %lld coordinates) doubles are %.0f bytes", kNewtonCvWorkspaceBytes,
@@ -998,7 +1027,7 @@ int fit_cv_mnewton(const CvNewtonMatrix& X, const double* y, const sgdnet_contro
   std::vector<double>().swap(expanded);
   const bool centre = intercept || ctl->standardize != 0;
   pooled_centres_and_scales(abar, s1, s2, n_t, rest, centre, ctl->standardize != 0, mean, scale);
-  pt.mark("cv mnewton: rows sorted, moments");
+  pt.mark(wide ? "cv wmnewton: rows sorted, moments" : "cv mnewton: rows sorted, moments");
 
   // regularization_path for user lambdas and a multinomial response (its y_scale is 1)
   std::vector<double> l2((size_t)n_alpha * (size_t)L), l1(l2.size());
@@ -1032,7 +1061,7 @@ int fit_cv_mnewton(const CvNewtonMatrix& X, const double* y, const sgdnet_contro
   pb.max_iter = ctl->max_iter;
   pb.tol = ctl->tol;
   MNewtonCvResult nr;
-  rc = mnewton_cv_run(pb, pt.on, &nr);
+  rc = wide ? wmnewton_cv_run(pb, pt.on, &nr, width, mfma) : mnewton_cv_run(pb, pt.on, &nr);
   if (rc) return rc;
 
   const size_t P1 = P + 1, Q = (size_t)K * P1;
@@ -1074,11 +1103,15 @@ int fit_cv_mnewton(const CvNewtonMatrix& X, const double* y, const sgdnet_contro
       most_steps = std::max(most_steps, nr.steps[job] + nr.halvings[job]);
       most_halvings = std::max(most_halvings, nr.halvings[job]);
     }
-  if (pt.on)
+  if (pt.on && wide)
+    fprintf(stderr, "[sgdnet]   cv wmnewton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
+            "moments_ms %.3f (%s), scale_ms %.3f, cd_ms %.3f, state_ms %.3f\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
+            nr.moments_ms, nr.moments_kernel, nr.scale_ms, nr.cd_ms, nr.state_ms);
+  else if (pt.on)
     fprintf(stderr, "[sgdnet]   cv mnewton: %d jobs, %d rounds (the slowest job: %.0f steps + halvings; most halvings %.0f), %.0f sweeps; "
             "moments %.3f ms, inner solves %.3f ms, state %.3f ms\n", n_alpha * G, nr.rounds, most_steps, most_halvings, nr.sweeps,
             nr.moments_ms, nr.cd_ms, nr.state_ms);
-  pt.mark("cv mnewton (all folds)");
+  pt.mark(wide ? "cv wmnewton (all folds)" : "cv mnewton (all folds)");
   return SGDNET_OK;
 }
 
@@ -1332,6 +1365,38 @@ int sgdnet_cv_mnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t
   X.rowidx = x->rowidx;
   X.values = x->values;
   return fit_cv_mnewton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out);
+}
+
+int sgdnet_cv_wmnewton_dense(const double* x, int64_t n, int64_t p, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                             const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                             sgdnet_cv_wmnewton_result* out) {
+  if (!x) {
+    set_error("sgdnet_cv_wmnewton_dense: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  CvNewtonMatrix X;
+  X.n = n;
+  X.p = p;
+  X.dense = x;
+  return fit_cv_mnewton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
+}
+
+int sgdnet_cv_wmnewton_sparse(const sgdnet_csc* x, const double* y, const int32_t* fold, int n_groups, int train_on_rest,
+                              const sgdnet_control* ctl, int n_alpha, const double* alphas, const double* lambdas,
+                              sgdnet_cv_wmnewton_result* out) {
+  if (!x || x->n_rows <= 0 || x->n_cols <= 0 || !x->colptr || !x->rowidx || !x->values) {
+    set_error("sgdnet_cv_wmnewton_sparse: invalid matrix");
+    return SGDNET_EINVAL;
+  }
+  int rc;
+  if ((rc = validate_colptr(x)) || (rc = validate_rowidx(x))) return rc;
+  CvNewtonMatrix X;
+  X.n = x->n_rows;
+  X.p = x->n_cols;
+  X.colptr = x->colptr;
+  X.rowidx = x->rowidx;
+  X.values = x->values;
+  return fit_cv_mnewton(X, y, ctl, fold, n_groups, train_on_rest, n_alpha, alphas, lambdas, out, true);
 }
 
 // ---- diagnostics: one outer step of Newton mode (newton.hip: newton_probe) ----

@@ -41,6 +41,12 @@
 // dimension of the moments pass); the command, the job and the host's state machine per job are newton_cv_device.hpp's,
 // shared with newton.hip.
 //
+// Wide cross-validation (wmnewton_cv_run, include/sgdnet_hip.h: sgdnet_cv_wmnewton_*): the same loop around the wide inner
+// solve.  The state, finish, pair tile and pair reduce kernels are the ones above on the row chunks wmnewton_run would choose
+// for each job's rows; mnewton_cv_wide_scale_kernel, mnewton_cv_wide_cd_kernel and mnewton_cv_wide_blend_kernel are the wide
+// kernels with a job dimension, every job with its own H, diag H and q in global memory and one workgroup -- one compute
+// unit -- per round.  With the option "cv_wmnewton_moments" = 1 the moments pass of a round is mnewton_cv_mfma.hip's.
+//
 // x is dense, column-major: this mode's p is at most 98, and the driver expands sparse x before anything is computed from
 // it (driver.cpp: fit_sparse_impl), so that a sparse fit is the dense fit of the same matrix from the standard deviations
 // and lambda_max on, bit for bit.  No floating-point atomic anywhere and every reduction in an order fixed by (n, p, K):
@@ -56,6 +62,7 @@
 #include "common.hpp"
 #include "device_math.hpp"
 #include "mnewton.hpp"
+#include "mnewton_cv_mfma.hpp"
 #include "mnewton_mfma.hpp"
 #include "moments_device.hpp"
 #include "newton_cv_device.hpp"
@@ -571,14 +578,14 @@ __device__ __forceinline__ double mnewton_coord_new_u(double hjj, double uj, dou
 //            adds nothing.
 // max_sweeps bounds the list sweeps of the solve.  g[c] is updated by one lane from the same words in the same order
 // whatever kWidth is, and the candidate is published by the first wavefront alone: both widths give the same bits.
+// (the body of mnewton_wide_cd_kernel and of mnewton_cv_wide_cd_kernel, which runs it once per job; lds: the workgroup's
+// whole LDS, 16-byte aligned)
 template <int kWidth>
-__global__ __launch_bounds__(kWidth) void mnewton_wide_cd_kernel(const double* __restrict__ H, const double* __restrict__ Hd,
-                                                                  const double* __restrict__ q, const double* __restrict__ scale, int p, int K,
-                                                                  int ld, const double* __restrict__ u_cur, double al, double be, int ridge,
-                                                                  int fit_intercept, unsigned max_sweeps, double tol,
-                                                                  double* __restrict__ u_cand, double* __restrict__ a_cand,
-                                                                  double* __restrict__ rec) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kWmnewtonLdsBytes];
+__device__ __forceinline__ void mnewton_wide_cd_solve(unsigned char* lds, const double* __restrict__ H, const double* __restrict__ Hd,
+                                                      const double* __restrict__ q, const double* __restrict__ scale, int p, int K, int ld,
+                                                      const double* __restrict__ u_cur, double al, double be, int ridge, int fit_intercept,
+                                                      unsigned max_sweeps, double tol, double* __restrict__ u_cand,
+                                                      double* __restrict__ a_cand, double* __restrict__ rec) {
   const int lane = threadIdx.x, wave = lane >> 6, P = p + 1, Q = K * P;
   double* g = reinterpret_cast<double*>(lds);
   double* u = g + Q;
@@ -659,6 +666,91 @@ __global__ __launch_bounds__(kWidth) void mnewton_wide_cd_kernel(const double* _
       rec[kRecNegligible] = negligible ? 1.0 : 0.0;
     }
   }
+}
+
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void mnewton_wide_cd_kernel(const double* __restrict__ H, const double* __restrict__ Hd,
+                                                                  const double* __restrict__ q, const double* __restrict__ scale, int p, int K,
+                                                                  int ld, const double* __restrict__ u_cur, double al, double be, int ridge,
+                                                                  int fit_intercept, unsigned max_sweeps, double tol,
+                                                                  double* __restrict__ u_cand, double* __restrict__ a_cand,
+                                                                  double* __restrict__ rec) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kWmnewtonLdsBytes];
+  mnewton_wide_cd_solve<kWidth>(lds, H, Hd, q, scale, p, K, ld, u_cur, al, be, ridge, fit_intercept, max_sweeps, tol, u_cand, a_cand, rec);
+}
+
+// ---- wide cross-validation (wmnewton_cv_run): the wide kernels with a job dimension ----
+// The state, finish, pair tile and pair reduce kernels are the mnewton_cv_* ones above, on the row chunks wmnewton_run would
+// choose for n_t rows (MCvGeometry).  Every job has its own H (leading dimension ld = wide_leading_dim(Q)), diag H and q.
+
+// mnewton_wide_scale_kernel on a grid of (column of the joint Hessian, job): the job's pair moments into its H, diag H and
+// q, with its training set's scales and dn = n_t; only for a job that takes a step in this round
+__global__ __launch_bounds__(kBlock) void mnewton_cv_wide_scale_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                        const double* __restrict__ M_all, const double* __restrict__ scale_all,
+                                                                        int p, int K, int ld, double* __restrict__ H_all,
+                                                                        double* __restrict__ Hd_all, double* __restrict__ q_all) {
+  const int job = blockIdx.y;
+  if (cmd[job].action != kCvStep) return;
+  const int P = p + 1, nc = p + 2, Q = K * P;
+  const size_t block = (size_t)nc * (size_t)nc;
+  const double* __restrict__ M = M_all + (size_t)job * (size_t)(K * (K + 1) / 2) * block;
+  const double* __restrict__ scale = scale_all + (size_t)jobs[job].set * (size_t)p;
+  double* __restrict__ H = H_all + (size_t)job * (size_t)ld * (size_t)Q;
+  const double dn = (double)jobs[job].n_t;
+  const int c2 = blockIdx.x, l = c2 / P, b = c2 - l * P;
+  const double sb = b < p ? scale[b] : 1.0;
+  for (int c1 = threadIdx.x; c1 < ld; c1 += kBlock) {
+    double v = 0.0;
+    if (c1 < Q) {
+      const int k = c1 / P, a = c1 - k * P;
+      const int lo = a < b ? a : b, hi = a < b ? b : a;
+      const double sa = a < p ? scale[a] : 1.0;
+      const int pair = k <= l ? class_pair_index(k, l, K) : class_pair_index(l, k, K);
+      v = M[(size_t)pair * block + (size_t)lo * nc + hi] / dn / (sa * sb);      // (mnewton_wide_scale_kernel's arithmetic)
+    }
+    H[(size_t)c2 * ld + c1] = v;
+    if (c1 == c2) Hd_all[(size_t)job * (size_t)Q + c2] = v;
+  }
+  if (threadIdx.x == 0) q_all[(size_t)job * (size_t)Q + c2] = M[(size_t)class_pair_index(l, l, K) * block + (size_t)b * nc + p + 1] / dn / sb;
+}
+
+// mnewton_wide_blend_kernel for the job blockIdx.x: a halving (t = 1/2), or the path's start published as it is (t = 1)
+__global__ __launch_bounds__(64) void mnewton_cv_wide_blend_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                    const double* __restrict__ scale_all, int p, int Q, double* u_all,
+                                                                    double* __restrict__ a_all, double* __restrict__ rec_all) {
+  const int job = blockIdx.x;
+  const CvCmd c = cmd[job];
+  if (c.action != kCvHalve && c.action != kCvStart) return;
+  const double* u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)Q;
+  double* u_cand = u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)Q;
+  mnewton_publish(BlendedCandidate{u_cur, u_cand, c.action == kCvStart ? 1.0 : 0.5}, u_cur, scale_all + (size_t)jobs[job].set * (size_t)p, p,
+                  Q, u_cand, a_all + (size_t)job * (size_t)Q, rec_all + (size_t)job * kRecLen);
+}
+
+// mnewton_wide_cd_kernel for the job blockIdx.x: one workgroup per job, each declaring the whole LDS, so the jobs spread one
+// per CU (more jobs than CUs queue: no workgroup waits for another).  Before anything else it stores the current iterate
+// into U[slot] where the host says it answers a lambda.
+template <int kWidth>
+__global__ __launch_bounds__(kWidth) void mnewton_cv_wide_cd_kernel(const CvCmd* __restrict__ cmd, const CvJob* __restrict__ jobs,
+                                                                     const double* __restrict__ H_all, const double* __restrict__ Hd_all,
+                                                                     const double* __restrict__ q_all, const double* __restrict__ scale_all,
+                                                                     int p, int K, int ld, int n_lambda, int fit_intercept,
+                                                                     unsigned max_sweeps, double tol, double* __restrict__ u_all,
+                                                                     double* __restrict__ a_all, double* __restrict__ rec_all,
+                                                                     double* __restrict__ U_all) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kWmnewtonLdsBytes];
+  const int job = blockIdx.x, Q = K * (p + 1);
+  const CvCmd c = cmd[job];
+  const double* __restrict__ u_cur = u_all + ((size_t)job * 2 + (size_t)c.cur) * (size_t)Q;
+  if (c.slot >= 0) {
+    double* __restrict__ U = U_all + ((size_t)job * (size_t)n_lambda + (size_t)c.slot) * (size_t)Q;
+    for (int k = threadIdx.x; k < Q; k += kWidth) U[k] = u_cur[k];
+  }
+  if (c.action != kCvStep) return;
+  mnewton_wide_cd_solve<kWidth>(lds, H_all + (size_t)job * (size_t)ld * (size_t)Q, Hd_all + (size_t)job * (size_t)Q,
+                                q_all + (size_t)job * (size_t)Q, scale_all + (size_t)jobs[job].set * (size_t)p, p, K, ld, u_cur, c.l2, c.l1,
+                                c.ridge, fit_intercept, max_sweeps, tol, u_all + ((size_t)job * 2 + (size_t)(1 - c.cur)) * (size_t)Q,
+                                a_all + (size_t)job * (size_t)Q, rec_all + (size_t)job * kRecLen);
 }
 
 // The wide inner solve's workgroup.  Both instances give the same bits; profiles/wmnewton_path.txt has the inner solves'
@@ -963,14 +1055,19 @@ int wmnewton_run(const MNewtonProblem& pb, bool timed, MNewtonResult* out, int w
 
 namespace {
 
-// the geometry of a call's jobs: a function of (p, K, the groups, the number of mixes) alone
+// the geometry of a call's jobs: a function of (p, K, the groups, the number of mixes) alone.  wide: the row chunks of a
+// job are those wmnewton_run chooses for n_t rows (mnewton.hpp: wmnewton_rows_per_chunk), else mnewton_run's
+// (dense_rows_per_chunk).  mfma (wide only): the chunks and the 64 x 64 partial tiles of the matrix-core pass
+// (mnewton_cv_mfma.hip), those of a single fit with "wmnewton_moments" = 1
 struct MCvGeometry {
   int pairs = 0, class_pairs = 0, max_chunks = 0, max_state_blocks = 0;
+  size_t tile_doubles = kBlock;        // of one partial tile
   std::vector<CvJob> jobs;
   std::vector<int64_t> mu_at;          // jobs + 1: where a job's mu starts, in doubles
-  MCvGeometry(int64_t p, int K, const int64_t* n_t, int n_sets, int n_mix) {
+  MCvGeometry(int64_t p, int K, const int64_t* n_t, int n_sets, int n_mix, bool wide = false, bool mfma = false) {
     const int nc = (int)p + 2, T = (nc + kTileCols - 1) / kTileCols;
-    pairs = T * (T + 1) / 2;
+    pairs = mfma ? (int)wide_mfma_pairs(nc) : T * (T + 1) / 2;
+    if (mfma) tile_doubles = (size_t)kMfmaTileCols * kMfmaTileCols;
     class_pairs = K * (K + 1) / 2;
     jobs.resize((size_t)n_sets * (size_t)n_mix);
     mu_at.assign(jobs.size() + 1, 0);
@@ -981,7 +1078,9 @@ struct MCvGeometry {
         J = CvJob{};
         J.n_t = n_t[t];
         J.set = t;
-        J.rows_per_chunk = dense_rows_per_chunk(J.n_t, pairs * class_pairs);
+        J.rows_per_chunk = mfma   ? wmnewton_mfma_rows_per_chunk(J.n_t, nc, K)
+                           : wide ? wmnewton_rows_per_chunk(J.n_t, nc, K, kTileRows)
+                                  : dense_rows_per_chunk(J.n_t, pairs * class_pairs);
         J.chunks = (int32_t)((J.n_t + J.rows_per_chunk - 1) / J.rows_per_chunk);
         J.state_blocks = (int32_t)std::min<int64_t>(kStateMaxBlocks, (J.n_t + kBlock - 1) / kBlock);
         max_chunks = std::max(max_chunks, (int)J.chunks);
@@ -1001,13 +1100,23 @@ static_assert(kStateMaxBlocks == kMNewtonCvStateMaxBlocks && kRecLen == kMNewton
 // the records come back in one copy, and every job's state machine moves as mnewton_run moves its one
 // (newton_cv_device.hpp: cv_job_advance).  The loop ends when every job has finished its last lambda; one last launch
 // stores the iterates still owed.
-int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out) {
+// mnewton_cv_run and wmnewton_cv_run: one loop, one state machine per job.  wide: the jobs' row chunks follow
+// wmnewton_row_chunks, mnewton_cv_wide_scale_kernel writes every stepping job's H, diag H and q to global memory, the inner
+// solve is mnewton_cv_wide_cd_kernel<width> and the blend has no array of kMNewtonMaxCoordinates.  mfma (wide only; the option
+// "cv_wmnewton_moments" = 1): the moments pass of a round is mnewton_cv_mfma.hip's on its own row chunks, everything else in
+// the round as it is.  Not wide: exactly the launches the multinomial Newton cross-validation has always made.
+namespace {
+
+int mnewton_cv_loop(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out, bool wide, int width_wide, bool mfma) {
   const int p = (int)pb.p, P = p + 1, nc = p + 2, K = pb.K, L = pb.n_lambda, G = pb.n_sets;
   const int64_t n = pb.n;
-  if (n <= 0 || pb.p <= 0 || K < 2 || pb.p > mnewton_max_features(K) || L <= 0 || G <= 0 || pb.n_mix <= 0 || !pb.x_dense || !pb.y || !pb.start ||
+  const char* const who = wide ? "wmnewton_cv_run" : "mnewton_cv_run";
+  if (n <= 0 || pb.p <= 0 || K < 2 || pb.p > (wide ? wmnewton_max_features(K) : mnewton_max_features(K)) || L <= 0 || G <= 0 ||
+      pb.n_mix <= 0 || !pb.x_dense || !pb.y || !pb.start ||
       !pb.mean || !pb.scale || !pb.b0 || !pb.l2 || !pb.l1 || !pb.ridge || pb.max_iter == 0 || (int64_t)G * pb.n_mix > kNewtonCvMaxJobs ||
-      (int64_t)G * pb.n_mix * (K * (K + 1) / 2) > kMNewtonCvMaxGridZ) {
-    set_error("mnewton_cv_run: invalid problem");
+      (int64_t)G * pb.n_mix * (K * (K + 1) / 2) > kMNewtonCvMaxGridZ || (wide && width_wide != kWideNarrow && width_wide != kWideFull) ||
+      (mfma && (!wide || (int64_t)G * wmnewton_cv_mfma_groups(pb.n_mix, K) > kWmnewtonCvMaxGrid))) {
+    set_error("%s: invalid problem", who);
     return SGDNET_EINVAL;
   }
   const int Q = K * P;
@@ -1016,20 +1125,24 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
     const int64_t own = pb.start[t + 1] - pb.start[t];
     n_t[(size_t)t] = pb.train_on_rest ? n - own : own;
     if (own <= 0 || n_t[(size_t)t] <= 0) {
-      set_error("mnewton_cv_run: empty training set %d", t);
+      set_error("%s: empty training set %d", who, t);
       return SGDNET_EINVAL;
     }
   }
-  MCvGeometry geo(p, K, n_t.data(), G, pb.n_mix);
-  const int jobs = (int)geo.jobs.size(), class_pairs = geo.class_pairs;
+  MCvGeometry geo(p, K, n_t.data(), G, pb.n_mix, wide, mfma);
+  const int jobs = (int)geo.jobs.size(), class_pairs = geo.class_pairs, ld = (int)wide_leading_dim(Q);
   for (CvJob& J : geo.jobs) {
     cv_job_rows(J, pb.start, n, pb.train_on_rest);
-    if (J.chunks != mnewton_cv_chunks(J.n_t, (int64_t)geo.pairs * class_pairs)) {    // (what the caller sized the workspace with)
-      set_error("mnewton_cv_run: the row chunks of %lld rows differ from mnewton_cv_chunks", (long long)J.n_t);
+    // (what the caller sized the workspace with)
+    const int64_t sized = mfma   ? wmnewton_mfma_row_chunks(J.n_t, nc, K)
+                          : wide ? wmnewton_row_chunks(J.n_t, nc, K)
+                                 : mnewton_cv_chunks(J.n_t, (int64_t)geo.pairs * class_pairs);
+    if (J.chunks > sized || (!wide && J.chunks != sized)) {
+      set_error("%s: the row chunks of %lld rows differ from those the workspace was sized with", who, (long long)J.n_t);
       return SGDNET_EINVAL;
     }
   }
-  const int width = mnewton_cd_width(Q);
+  const int width = wide ? width_wide : mnewton_cd_width(Q);
 
   SGD_HIP_TRY(hipSetDevice(pb.device));
   Arena A;
@@ -1041,14 +1154,18 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
   const size_t o_cmd = A.reserve(sizeof(CvCmd) * (size_t)jobs);
   const size_t o_mu_at = A.reserve(sizeof(int64_t) * (size_t)jobs);
   const size_t o_mu = A.reserve(sizeof(double) * (size_t)geo.mu_at[(size_t)jobs]);
-  const size_t o_part = A.reserve(sizeof(double) * (size_t)jobs * (size_t)class_pairs * (size_t)geo.max_chunks * (size_t)geo.pairs * kBlock);
+  const size_t o_part = A.reserve(sizeof(double) * (size_t)jobs * (size_t)class_pairs * (size_t)geo.max_chunks * (size_t)geo.pairs * geo.tile_doubles);
   const size_t o_M = A.reserve(sizeof(double) * (size_t)jobs * (size_t)class_pairs * (size_t)nc * (size_t)nc);
   const size_t o_partial = A.reserve(sizeof(double) * (size_t)jobs * kStateMaxBlocks);
   const size_t o_rec = A.reserve(sizeof(double) * kRecLen * (size_t)jobs);
   const size_t o_u = A.reserve(sizeof(double) * 2 * (size_t)Q * (size_t)jobs);
   const size_t o_a = A.reserve(sizeof(double) * (size_t)Q * (size_t)jobs);
   const size_t o_U = A.reserve(sizeof(double) * (size_t)jobs * (size_t)L * (size_t)Q);
+  const size_t o_H = A.reserve(wide ? sizeof(double) * (size_t)jobs * (size_t)ld * (size_t)Q : 0);
+  const size_t o_Hd = A.reserve(wide ? sizeof(double) * (size_t)jobs * (size_t)Q : 0);
+  const size_t o_q = A.reserve(wide ? sizeof(double) * (size_t)jobs * (size_t)Q : 0);
   SGD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.base), A.used));
+  double *d_H = A.at<double>(o_H), *d_Hd = A.at<double>(o_Hd), *d_q = A.at<double>(o_q);
   double *d_x = A.at<double>(o_x), *d_y = A.at<double>(o_y), *d_m = A.at<double>(o_m), *d_scale = A.at<double>(o_scale),
          *d_mu = A.at<double>(o_mu), *d_part = A.at<double>(o_part), *d_M = A.at<double>(o_M), *d_partial = A.at<double>(o_partial),
          *d_rec = A.at<double>(o_rec), *d_u = A.at<double>(o_u), *d_a = A.at<double>(o_a), *d_U = A.at<double>(o_U);
@@ -1088,7 +1205,8 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
   out->halvings.assign((size_t)jobs, 0.0);
   out->sweeps = 0.0;
   out->rounds = 0;
-  out->moments_ms = out->cd_ms = out->state_ms = 0.f;
+  out->moments_ms = out->cd_ms = out->state_ms = out->scale_ms = 0.f;
+  out->moments_kernel = mfma ? "mnewton_cv_mfma_tile_kernel" : "mnewton_cv_pair_tile_kernel";
 
   std::vector<CvJobState> state((size_t)jobs);
   const int fit_intercept = pb.fit_intercept ? 1 : 0;
@@ -1108,7 +1226,9 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
     }
     SGD_HIP_TRY(hipMemcpyAsync(d_cmd, cmd, sizeof(CvCmd) * (size_t)jobs, hipMemcpyHostToDevice, st));
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[0], st));
-    if (any_step) {
+    if (any_step && mfma) {
+      wmnewton_cv_mfma_moments(d_cmd, d_jobs, d_mu_at, d_x, d_y, d_mu, d_m, n, p, K, G, pb.n_mix, geo.max_chunks, d_part, d_M, st);
+    } else if (any_step) {
       hipLaunchKernelGGL(mnewton_cv_pair_tile_kernel, dim3((unsigned)geo.pairs, (unsigned)geo.max_chunks, (unsigned)(jobs * class_pairs)),
                          dim3(kBlock), 0, st, d_cmd, d_jobs, d_mu_at, d_x, d_y, d_mu, d_m, n, p, K, geo.max_chunks, d_part);
       hipLaunchKernelGGL(mnewton_cv_pair_reduce_kernel, dim3((unsigned)geo.pairs, (unsigned)(jobs * class_pairs)), dim3(kBlock), 0, st, d_cmd,
@@ -1116,13 +1236,23 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
     }
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[1], st));
     // (the inner solve's kernel also stores the iterates owed to U: it runs in every round)
-    if (width == 256)
+    if (wide) {
+      if (any_step)
+        hipLaunchKernelGGL(mnewton_cv_wide_scale_kernel, dim3((unsigned)Q, (unsigned)jobs), dim3(kBlock), 0, st, d_cmd, d_jobs, d_M, d_scale,
+                           p, K, ld, d_H, d_Hd, d_q);
+      if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[4], st));
+      const auto kernel = width == kWideNarrow ? mnewton_cv_wide_cd_kernel<kWideNarrow> : mnewton_cv_wide_cd_kernel<kWideFull>;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)jobs), dim3((unsigned)width), 0, st, d_cmd, d_jobs, d_H, d_Hd, d_q, d_scale, p, K, ld, L,
+                         fit_intercept, kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
+    } else if (width == 256)
       hipLaunchKernelGGL(mnewton_cv_cd_kernel<256>, dim3((unsigned)jobs), dim3(256), 0, st, d_cmd, d_jobs, d_M, d_scale, p, K, L, fit_intercept,
                          kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
     else
       hipLaunchKernelGGL(mnewton_cv_cd_kernel<64>, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_M, d_scale, p, K, L, fit_intercept,
                          kNewtonMaxSweeps, pb.tol, d_u, d_a, d_rec, d_U);
-    if (any_blend)
+    if (any_blend && wide)
+      hipLaunchKernelGGL(mnewton_cv_wide_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, Q, d_u, d_a, d_rec);
+    else if (any_blend)
       hipLaunchKernelGGL(mnewton_cv_blend_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_cmd, d_jobs, d_scale, p, Q, d_u, d_a, d_rec);
     if (timed) SGD_HIP_TRY(hipEventRecord(sx.e[2], st));
     if (live > 0) {
@@ -1140,7 +1270,11 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
       float ms = 0.f;
       SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[0], sx.e[1]));
       out->moments_ms += ms;
-      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[2]));
+      if (wide) {
+        SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[1], sx.e[4]));
+        out->scale_ms += ms;
+      }
+      SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[wide ? 4 : 1], sx.e[2]));
       out->cd_ms += ms;
       SGD_HIP_TRY(hipEventElapsedTime(&ms, sx.e[2], sx.e[3]));
       out->state_ms += ms;
@@ -1156,6 +1290,15 @@ int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out)
   SGD_HIP_TRY(hipMemcpyAsync(out->u.data(), d_U, sizeof(double) * out->u.size(), hipMemcpyDeviceToHost, st));
   SGD_HIP_TRY(hipStreamSynchronize(st));
   return SGDNET_OK;
+}
+
+}  // namespace
+
+int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out) { return mnewton_cv_loop(pb, timed, out, false, 0, false); }
+
+int wmnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out, int width, bool mfma) {
+  const int64_t Q = (int64_t)pb.K * (pb.p + 1);
+  return mnewton_cv_loop(pb, timed, out, true, width != 0 ? width : wmnewton_cd_width((int)std::min<int64_t>(Q, kWmnewtonMaxCoordinates)), mfma);
 }
 
 // Diagnostics (include/sgdnet_hip.h): one outer step through the steps above, every output copied back.  The state is

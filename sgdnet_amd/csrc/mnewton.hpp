@@ -267,10 +267,92 @@ struct MNewtonCvResult {               // job-major
   double sweeps = 0.0;
   int rounds = 0;                      // rounds of the lock-step loop: launches shared by all jobs
   float moments_ms = 0.f, cd_ms = 0.f, state_ms = 0.f;   // (timed only)
+  float scale_ms = 0.f;                                  // wmnewton_cv_run only: mnewton_cv_wide_scale_kernel
+  const char* moments_kernel = "";                       // (SGDNET_TRACE) the kernel of the moments pass
 };
 
 // The lock-step loop.  The caller has checked the sizes, the feature limit, the job counts and the workspace.
 int mnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out);
+
+// ---- the same for the wide mode (mnewton.hip: wmnewton_cv_run) ----
+// Job (mix a, training set t) = a * n_sets + t is wmnewton_run on the rows of its training set: the lock-step loop above
+// around the wide inner solve, one workgroup -- one compute unit -- per job and round.  H depends on the iterate, so every
+// job keeps its own.  In doubles (Q = K (p + 1), ld = wide_leading_dim(Q), class pairs = K (K + 1) / 2), per job:
+//   mu by local row                n_t K
+//   the pair moments               class pairs x (p + 2)^2
+//   the row chunks' partial tiles  max_chunks x class pairs x wide_tile_pairs(p + 2) x 256, the chunks those wmnewton_run takes
+//                                  for n_t rows (wmnewton_row_chunks); with the option "cv_wmnewton_moments" = 1
+//                                  max_chunks x class pairs x wide_mfma_pairs(p + 2) x 64 x 64 on wmnewton_mfma_row_chunks
+//   H, diag H and q                ld Q + 2 Q
+//   the small vectors              the state pass's sums (1024), two iterates and the state-pass form (3 Q), the record
+//   the answers U                  n_lambda Q
+// and once per call x and y (n p + n).  5 mixes x 10 folds of 2000 x 1000 at K = 3 ("rest": 1800 rows a job, 100 lambdas):
+// 7.41 GB on the tile pass (one chunk) and 16.86 GB on the matrix-core pass (8 chunks of 256 rows: 26.7 M doubles of partial
+// tiles a job) -- within the bound, which is newton.hpp's kWnewtonCvBytes: 16 GiB.  At K = 2's feature limit (p = 2909) a job
+// is 0.58 GB on either pass (one chunk) and 29 jobs fit.
+constexpr size_t kWmnewtonCvBytes = kWnewtonCvBytes;
+// The matrix-core moments pass of this cross-validation (mnewton_cv_mfma.hip).  The MEMBERS of training set t are the pairs
+// (mix a, class pair c), numbered m = a * class pairs + c: Gram matrices of the same centred rows under another weight per
+// row.  A workgroup serves a group of kWmnewtonCvMfmaGroup consecutive members of one set: a group may span several mixes
+// (K = 2: two), begin in the middle of a mix's class pairs (K = 4: group 1 is the pairs 6 .. 9 of mix 0 and 0 .. 1 of mix 1)
+// and the last one may be partial.
+constexpr int kWmnewtonCvMfmaGroup = 6;
+static_assert(kWmnewtonCvMfmaGroup * kMfmaSlabRows <= 256, "a lane of the workgroup per (member, slab row) of the weight table");
+constexpr int64_t wmnewton_cv_mfma_groups(int64_t n_mix, int64_t K) {
+  return (n_mix * (K * (K + 1) / 2) + kWmnewtonCvMfmaGroup - 1) / kWmnewtonCvMfmaGroup;
+}
+// member g of group `group` -> its mix (n_mix or more: absent) and its class pair
+constexpr int64_t wmnewton_cv_member_mix(int64_t group, int64_t g, int64_t K) { return (group * kWmnewtonCvMfmaGroup + g) / (K * (K + 1) / 2); }
+constexpr int64_t wmnewton_cv_member_pair(int64_t group, int64_t g, int64_t K) { return (group * kWmnewtonCvMfmaGroup + g) % (K * (K + 1) / 2); }
+static_assert(wmnewton_cv_mfma_groups(2, 2) == 1 && wmnewton_cv_member_mix(0, 2, 2) == 0 && wmnewton_cv_member_mix(0, 3, 2) == 1 &&
+              wmnewton_cv_member_pair(0, 3, 2) == 0, "K = 2: a group spans two mixes");
+static_assert(wmnewton_cv_mfma_groups(2, 4) == 4 && wmnewton_cv_member_mix(1, 0, 4) == 0 && wmnewton_cv_member_pair(1, 0, 4) == 6 &&
+              wmnewton_cv_member_mix(1, 3, 4) == 0 && wmnewton_cv_member_pair(1, 3, 4) == 9 && wmnewton_cv_member_mix(1, 4, 4) == 1 &&
+              wmnewton_cv_member_pair(1, 4, 4) == 0 && wmnewton_cv_member_pair(1, 5, 4) == 1, "K = 4: group 1 begins in the middle of mix 0");
+static_assert(wmnewton_cv_mfma_groups(1, 2) == 1 && wmnewton_cv_member_mix(0, 3, 2) >= 1 && wmnewton_cv_mfma_groups(3, 2) == 2 &&
+              wmnewton_cv_member_mix(1, 3, 2) >= 3 && wmnewton_cv_mfma_groups(2, 4) * kWmnewtonCvMfmaGroup - 2 * 10 == 4,
+              "the last group may be partial: 3 of 6 members at one mix of K = 2, 3 at three mixes, 2 at two mixes of K = 4");
+constexpr size_t wmnewton_cv_partial_doubles(int64_t p, int64_t K, int64_t max_chunks, bool mfma) {
+  return (size_t)max_chunks * (size_t)(K * (K + 1) / 2) *
+         (mfma ? (size_t)wide_mfma_pairs(p + 2) * kMfmaTileCols * kMfmaTileCols : (size_t)wide_tile_pairs(p + 2) * 256);
+}
+// rows: the sum of n_t over the training sets (every mix keeps its own mu of each)
+constexpr size_t wmnewton_cv_bytes(int64_t n_mix, int64_t n_sets, int64_t rows, int64_t n, int64_t p, int64_t K, int64_t n_lambda,
+                                   int64_t max_chunks, bool mfma = false) {
+  const size_t Q = (size_t)K * (size_t)(p + 1);
+  return sizeof(double) * ((size_t)n_mix * (size_t)rows * (size_t)K +
+                           (size_t)n_mix * (size_t)n_sets *
+                               ((size_t)(K * (K + 1) / 2) * (size_t)(p + 2) * (size_t)(p + 2) + wmnewton_cv_partial_doubles(p, K, max_chunks, mfma) +
+                                (size_t)wide_leading_dim((int64_t)Q) * Q + 2 * Q + (size_t)kMNewtonCvStateMaxBlocks + 3 * Q +
+                                (size_t)kMNewtonCvRecordDoubles + (size_t)n_lambda * Q) +
+                           (size_t)n * (size_t)p + (size_t)n);
+}
+// n_t: the rows of each training set; mfma: the option "cv_wmnewton_moments"
+constexpr size_t wmnewton_cv_workspace_bytes(int64_t n, int64_t p, int K, const int64_t* n_t, int n_sets, int n_mix, int n_lambda, bool mfma) {
+  int64_t max_chunks = 0, rows = 0;
+  for (int t = 0; t < n_sets; ++t) {
+    const int64_t c = mfma ? wmnewton_mfma_row_chunks(n_t[t], p + 2, K) : wmnewton_row_chunks(n_t[t], p + 2, K);
+    max_chunks = c > max_chunks ? c : max_chunks;
+    rows += n_t[t];
+  }
+  return wmnewton_cv_bytes(n_mix, n_sets, rows, n, p, K, n_lambda, max_chunks, mfma);
+}
+static_assert(wmnewton_row_chunks(1800, 1002, 3) == 1 && wmnewton_mfma_row_chunks(1800, 1002, 3) == 8, "2000 x 1000, K = 3, \"rest\" of 10 folds");
+static_assert(wmnewton_cv_bytes(5, 10, 18000, 2000, 1000, 3, 100, 1) / 10000000 == 740 &&
+              wmnewton_cv_bytes(5, 10, 18000, 2000, 1000, 3, 100, 8, true) / 10000000 == 1686 &&
+              wmnewton_cv_bytes(5, 10, 18000, 2000, 1000, 3, 100, 8, true) <= kWmnewtonCvBytes, "the example above, under both options");
+static_assert(wmnewton_row_chunks(2000, 2911, 2) == 1 && wmnewton_mfma_row_chunks(2000, 2911, 2) == 1 &&
+              wmnewton_cv_bytes(29, 1, 2000, 2000, 2909, 2, 100, 1) <= kWmnewtonCvBytes &&
+              wmnewton_cv_bytes(30, 1, 2000, 2000, 2909, 2, 100, 1) > kWmnewtonCvBytes &&
+              wmnewton_cv_bytes(29, 1, 2000, 2000, 2909, 2, 100, 1, true) <= kWmnewtonCvBytes &&
+              wmnewton_cv_bytes(30, 1, 2000, 2000, 2909, 2, 100, 1, true) > kWmnewtonCvBytes, "K = 2's feature limit: 29 jobs fit");
+constexpr int64_t kWmnewtonCvMaxGrid = kMNewtonCvMaxGridZ;   // jobs x class pairs and sets x groups each ride in a grid dimension
+
+// The lock-step loop around the wide inner solve: pb as mnewton_cv_run takes it.  width as wmnewton_run's.  mfma: the moments
+// pass is mnewton_cv_mfma.hip's (the option "cv_wmnewton_moments" = 1, read by the caller with the width), else
+// mnewton_cv_pair_tile_kernel + mnewton_cv_pair_reduce_kernel on wmnewton_row_chunks.  The caller has checked the sizes, the
+// feature limit, the job counts, the width and the workspace.
+int wmnewton_cv_run(const MNewtonCvProblem& pb, bool timed, MNewtonCvResult* out, int width = 0, bool mfma = false);
 
 // Diagnostics (include/sgdnet_hip.h: sgdnet_mnewton_probe): one outer step through the host steps mnewton_run takes, every
 // output copied back.  pb: n, p, K, x_dense, y, centre, scale, device and n_lambda = 1; the rest is read from io.

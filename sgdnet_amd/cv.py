@@ -44,7 +44,12 @@ cv_sgdnet_wmcovariance() is the mgaussian CV whose fits are sgdnet_wmcovariance(
 fold_fits="batched" runs all fold fits through cv_wmcovariance_fits -> sgdnet_cv_wmcovariance_*: the group moments of the K
 responses from one pass, every training set's scaled Gram matrix and c~ pooled from them into device memory, one workgroup --
 one compute unit -- per path (csrc/covariance.hip: wmcovariance_cv_run).
-_cv() is the body the seven CVs share; they differ in the fit they inject.
+
+cv_sgdnet_wmnewton() is the multinomial CV whose fits are sgdnet_wmnewton() (beyond mnewton mode's feature limit); its
+fold_fits="batched" runs all fold fits through cv_wmnewton_fits -> sgdnet_cv_wmnewton_*: the same lock-step loop around the wide
+inner solve, every job with its own joint Hessian in device memory and one workgroup -- one compute unit -- per job and round
+(csrc/mnewton.hip: wmnewton_cv_run); the option "cv_wmnewton_moments" chooses the kernel of its class-pair moments pass.
+_cv() is the body the eight CVs share; they differ in the fit they inject.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
@@ -53,9 +58,10 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODE_WNEWTON, MODES, check, dptr
+from ._lib import (FAMILIES, MODE_MCOVARIANCE, MODE_MNEWTON, MODE_NEWTON, MODE_WCOVARIANCE, MODE_WMCOVARIANCE, MODE_WMNEWTON, MODE_WNEWTON, MODES, check,
+                   dptr)
 from .api import (SgdnetFit, _levels, sgdnet, sgdnet_mcovariance, sgdnet_mnewton, sgdnet_newton, sgdnet_wcovariance, sgdnet_wmcovariance,
-                  sgdnet_wnewton)
+                  sgdnet_wmnewton, sgdnet_wnewton)
 from .score import _MEASURES, score
 from .solver import RRng
 
@@ -222,6 +228,26 @@ def cv_mnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000
     alpha=alpha[a], lambda_=lambda_[a]) for the training set T of fold j, in the shapes sgdnet_mnewton returns (a0 (K, n_lambda)
     with its class mean removed, beta a list of K (p, n_lambda) arrays); its diagnostics hold the job's Newton steps and
     halvings over the path ("steps", "halvings")."""
+    return _multinomial_fold_fits(x, y, foldid, alpha, lambda_, train_on, maxit=maxit, standardize=standardize, intercept=intercept,
+                                  thresh=thresh, device=device, wide=False)
+
+
+def cv_wmnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000, standardize=True, intercept=True,
+                     thresh=0.001, device=0):
+    """Every fold fit of a multinomial cross-validation in wide multinomial Newton mode from one native call, all of them
+    advancing in lock-step.
+
+    The arguments are cv_mnewton_fits's, for up to wmnewton_max_features(K) features.  Returns a list of SgdnetFit, alpha-major:
+    entry a * nfolds + j is sgdnet_wmnewton(x[T], y[T], alpha=alpha[a], lambda_=lambda_[a]) for the training set T of fold j (the
+    same optimum, return codes and npasses; not the same bits); its diagnostics hold the job's Newton steps and halvings over the
+    path ("steps", "halvings").  Sparse x gives the bits of the dense call on the same matrix.  The option "cv_wmnewton_moments"
+    chooses the kernel of the class-pair moments pass (0: the tile kernel, 1: the f64 matrix-core kernel)."""
+    return _multinomial_fold_fits(x, y, foldid, alpha, lambda_, train_on, maxit=maxit, standardize=standardize, intercept=intercept,
+                                  thresh=thresh, device=device, wide=True)
+
+
+def _multinomial_fold_fits(x, y, foldid, alpha, lambda_, train_on, *, maxit, standardize, intercept, thresh, device, wide):
+    """cv_mnewton_fits and cv_wmnewton_fits: the response encoded once, over all samples"""
     y_arr = np.asarray(y)
     if y_arr.ndim > 1 and y_arr.shape[1] > 1:
         raise ValueError("response for multinomial regression must be one-dimensional.")
@@ -230,7 +256,7 @@ def cv_mnewton_fits(x, y, foldid, alpha, lambda_, train_on="fold", *, maxit=1000
         raise ValueError("only one class in response.")
     return _native_fold_fits(x, np.ascontiguousarray(codes), foldid, alpha, lambda_, train_on, family="multinomial",
                              classnames=[str(v) for v in levels], maxit=maxit, standardize=standardize, intercept=intercept,
-                             thresh=thresh, device=device, n_classes=int(levels.size))
+                             thresh=thresh, device=device, n_classes=int(levels.size), wide=wide)
 
 
 def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, classnames, maxit, standardize, intercept, thresh,
@@ -277,7 +303,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     ctl.intercept, ctl.standardize = int(intercept), int(standardize)
     ctl.standardize_response = int(bool(standardize_response))
     ctl.max_iter, ctl.tol, ctl.n_lambda, ctl.n_classes = int(maxit), float(thresh), nl, K
-    ctl.mode = (MODE_MNEWTON if mnewton else (MODE_WNEWTON if wide else MODE_NEWTON) if newton else (MODE_WMCOVARIANCE if wide else MODE_MCOVARIANCE) if multi
+    ctl.mode = ((MODE_WMNEWTON if wide else MODE_MNEWTON) if mnewton else (MODE_WNEWTON if wide else MODE_NEWTON) if newton else (MODE_WMCOVARIANCE if wide else MODE_MCOVARIANCE) if multi
                 else MODE_WCOVARIANCE if wide else MODES["covariance"])
     ctl.device = int(device)
     jobs = A * G
@@ -297,7 +323,7 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
     tail = (dptr(y_enc), fold.ctypes.data_as(C.POINTER(C.c_int32)), G, int(train_on == "rest"), C.byref(ctl), A, dptr(alphas),
             dptr(lam), C.byref(res))
     L = _lib.load()
-    stem = ("sgdnet_cv_mnewton" if mnewton else ("sgdnet_cv_wnewton" if wide else "sgdnet_cv_newton") if newton else ("sgdnet_cv_wmcovariance" if wide else "sgdnet_cv_mcovariance") if multi
+    stem = (("sgdnet_cv_wmnewton" if wide else "sgdnet_cv_mnewton") if mnewton else ("sgdnet_cv_wnewton" if wide else "sgdnet_cv_newton") if newton else ("sgdnet_cv_wmcovariance" if wide else "sgdnet_cv_mcovariance") if multi
             else "sgdnet_cv_wcovariance" if wide else "sgdnet_cv_covariance")
     if sp.issparse(x):
         xs = sp.csc_matrix(x, dtype=np.float64)
@@ -337,7 +363,9 @@ def _native_fold_fits(x, y_enc, foldid, alpha, lambda_, train_on, *, family, cla
                                   alpha=float(alphas[a]), offset=False, classnames=classnames, grouped=family == "mgaussian",
                                   nobs=int(n - counts[j] if train_on == "rest" else counts[j]), family=family,
                                   dfmat=dfmat, return_codes=rcodes[job].copy(), draws_used=0,
-                                  diagnostics=dict(steps=float(steps[job]), halvings=float(halvings[job])) if newton else {}))
+                                  diagnostics=(dict(steps=float(steps[job]), halvings=float(halvings[job]), passes=float(npasses[job]))
+                                               if mnewton and wide else
+                                               dict(steps=float(steps[job]), halvings=float(halvings[job])) if newton else {})))
     return fits
 
 
@@ -513,6 +541,29 @@ def cv_sgdnet_mnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_
 
     def batched_fits(xx, yy, foldid, alpha, lam, dev):
         return cv_mnewton_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
+
+    return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="multinomial", devices=[int(device)], rng=rng, seed=seed,
+               train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
+
+
+def cv_sgdnet_wmnewton(x, y, alpha=1, lambda_=None, nfolds=10, foldid=None, type_measure="deviance", *, rng=None, seed=0,
+                       train_on="fold", fold_fits="separate", device=0, nlambda=100, lambda_min_ratio=None, maxit=1000,
+                       standardize=True, intercept=True, thresh=0.001):
+    """cv_sgdnet(family="multinomial") with every fit a sgdnet_wmnewton(): cv_sgdnet_mnewton() beyond its feature limit, up to
+    wmnewton_max_features(K) features.  fold_fits="separate" (the default) runs one sgdnet_wmnewton per fold; "batched" runs all
+    fold fits of all alphas through ONE native call (cv_wmnewton_fits) with the full fits' lambdas."""
+    if fold_fits not in ("separate", "batched"):
+        raise ValueError("fold_fits must be 'separate' or 'batched'")
+    if train_on not in ("fold", "rest"):
+        raise ValueError("train_on must be 'fold' or 'rest'")
+    fit_args = dict(maxit=maxit, standardize=standardize, intercept=intercept, thresh=thresh)
+
+    def fit_one(xx, yy, lam, a, dev, fit_seed, rng, sequential):         # (draws nothing: neither the generator nor a seed)
+        return sgdnet_wmnewton(xx, yy, alpha=float(a), lambda_=lam, nlambda=nlambda, lambda_min_ratio=lambda_min_ratio, device=dev,
+                               **fit_args)
+
+    def batched_fits(xx, yy, foldid, alpha, lam, dev):
+        return cv_wmnewton_fits(xx, yy, foldid, alpha, lam, train_on=train_on, device=dev, **fit_args)
 
     return _cv(x, y, alpha, lambda_, nfolds, foldid, type_measure, family="multinomial", devices=[int(device)], rng=rng, seed=seed,
                train_on=train_on, densify=False, fit_one=fit_one, batched_fits=batched_fits if fold_fits == "batched" else None)
