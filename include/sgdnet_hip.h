@@ -390,6 +390,22 @@ int sgdnet_wmnewton_max_features(int n_classes);
 /*                        call).  The partial tiles are larger and count        */
 /*                        towards the same 16 GiB bound.  Read by those two     */
 /*                        entry points only                                     */
+/*   "mnewton_grouped"    0 (default): SGDNET_MODE_MNEWTON and _WMNEWTON refuse   */
+/*                        control.type_multinomial = 1; 1: such a fit takes the  */
+/*                        grouped penalty sum_j |w_.j|_2 over the classes of a   */
+/*                        feature: the inner solve moves a feature's K           */
+/*                        coefficients by one majorised proximal step and the    */
+/*                        fit returns the grouped optimum (elasticnet_mix = 0:   */
+/*                        the ridge fit, bit for bit the ungrouped one).  lambda */
+/*                        and nulldev are the ungrouped fit's.  The sgdnet_cv_*  */
+/*                        entry points and the probes refuse or ignore the       */
+/*                        grouped penalty whatever this option says              */
+/*   "mnewton_width"      0 (default): SGDNET_MODE_MNEWTON's inner solve runs on  */
+/*                        64 or 256 lanes by the library's rule; 64 or 256: on   */
+/*                        that many (same bits either way, under either          */
+/*                        penalty; any other value makes such a fit return       */
+/*                        SGDNET_EINVAL).  The cross-validation and the probe    */
+/*                        ignore it                                              */
 /* Unknown names and out-of-range values return SGDNET_EINVAL.  Options are  */
 /* read when a fit starts (exact_row_registers and fused_epoch: whenever     */
 /* sgdnet_solver_run / _enqueue_epochs is called, i.e. once per epoch block  */

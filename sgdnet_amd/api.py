@@ -6,6 +6,7 @@ names and defaults, same validation messages, same response encoding, the same
 same post-processing of the returned list (R/sgdnet.R:368-431).  The native
 backend is libsgdnet_hip.so (include/sgdnet_hip.h); nothing here computes.
 """
+import contextlib
 import ctypes as C
 from dataclasses import dataclass, field
 
@@ -126,7 +127,7 @@ def sgdnet_mcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda
 
 
 def sgdnet_mnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
-                   intercept=True, thresh=0.001, *, device=0):
+                   intercept=True, thresh=0.001, *, device=0, type_multinomial="ungrouped"):
     """The multinomial path of sgdnet(x, y, family="multinomial", ...) solved to its optimum by proximal Newton steps
     on the joint Hessian of all classes (SGDNET_MODE_MNEWTON, csrc/mnewton.hip): per step one pass over x for the class
     probabilities, one for the K (K + 1) / 2 weighted Gram matrices and the gradients, then coordinate descent on the
@@ -138,10 +139,17 @@ def sgdnet_mnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=No
     alpha = 1 and an even number of classes the optimum need not be unique in the coefficients: compare deviances and
     optimality residuals (kkt()) there, not coefficients.  It draws no samples (draws_used = 0); maxit bounds the
     Newton steps per lambda, thresh is the largest relative change of all coefficients and intercepts a last step may
-    make, npasses counts the passes that evaluated an iterate."""
+    make, npasses counts the passes that evaluated an iterate.
+
+    type_multinomial="grouped": the penalty lambda (alpha sum_j |w_.j|_2 + (1 - alpha) / 2 |w|^2) over the K classes of a
+    feature, which enters or leaves for all classes at once (csrc/mnewton_grouped.hip: the inner solve moves a feature's
+    K coefficients by one majorised proximal step).  The option "mnewton_grouped" is held at 1 for the call.  The
+    optimum is returned for every alpha, and at alpha = 1 it is unique in the coefficients (they sum to 0 over the
+    classes of a feature); alpha = 0 is the ungrouped fit bit for bit.  lambda_ stays the driver's: its largest
+    value is max |g_kj| / alpha over single coordinates, below max_j |g_.j|_2 / alpha, so a grouped path need not start at 0."""
     return _fit(x, y, "multinomial", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh, False,
                 debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="mnewton", modes={"mnewton": MODE_MNEWTON},
-                batch=0, device=device, devices=None, min_classes=2)
+                batch=0, device=device, devices=None, min_classes=2, type_multinomial=type_multinomial)
 
 
 def sgdnet_wcovariance(x, y, family="gaussian", alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000,
@@ -180,7 +188,7 @@ def sgdnet_wmcovariance(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambd
 
 
 def sgdnet_wmnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=None, maxit=1000, standardize=True,
-                    intercept=True, thresh=0.001, *, device=0):
+                    intercept=True, thresh=0.001, *, device=0, type_multinomial="ungrouped"):
     """The multinomial path of sgdnet_mnewton(x, y, ...) for up to wmnewton_max_features(K) = 5820 // K - 1 features
     (2909 at K = 2, 1939 at K = 3, 581 at K = 10), K <= 99 (SGDNET_MODE_WMNEWTON, csrc/mnewton.hip): sgdnet_mnewton()'s
     outer loop with the joint Hessian of all K (p + 1) coordinates kept in device memory and cyclic coordinate descent
@@ -189,14 +197,16 @@ def sgdnet_wmnewton(x, y, alpha=1, nlambda=100, lambda_min_ratio=None, lambda_=N
     is sgdnet_mnewton()'s (not its bits); neither falls back to the other.  Sparse x is expanded to a dense copy first
     (at most 1 GiB) and gives the dense fit's bits.  The arguments, their validation, the response encoding, the
     returned SgdnetFit, the class-centred a0, what maxit, thresh and npasses mean and the remark on alpha = 1 with an
-    even number of classes are sgdnet_mnewton()'s."""
+    even number of classes are sgdnet_mnewton()'s; so is type_multinomial="grouped": the blocks that can move are listed
+    and screened whole, and a block that moves reads its K columns of the Hessian in one pass."""
     return _fit(x, y, "multinomial", alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh, False,
                 debug=False, seed=0, rng=None, sample_stream=None, unif=None, mode="wmnewton", modes={"wmnewton": MODE_WMNEWTON},
-                batch=0, device=device, devices=None, min_classes=2)
+                batch=0, device=device, devices=None, min_classes=2, type_multinomial=type_multinomial)
 
 
 def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standardize, intercept, thresh,
-         standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3):
+         standardize_response, *, debug, seed, rng, sample_stream, unif, mode, modes, batch, device, devices, min_classes=3,
+         type_multinomial="ungrouped"):
     """Validation, response encoding, the native call and the post-processing behind sgdnet(), sgdnet_newton(),
     sgdnet_mcovariance(), sgdnet_mnewton(), sgdnet_wcovariance(), sgdnet_wnewton(), sgdnet_wmcovariance() and sgdnet_wmnewton(); modes: the mode strings the caller accepts and their SGDNET_MODE_* codes;
     min_classes: the fewest classes a multinomial response may have."""
@@ -244,8 +254,9 @@ def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standar
     if maxit <= 0:
         _stop("maximum number of iterations cannot be negative or zero.")
 
-    type_multinomial = "ungrouped"
-    grouped = False
+    if type_multinomial not in ("ungrouped", "grouped"):
+        _stop("type_multinomial must be 'ungrouped' or 'grouped'")
+    grouped = type_multinomial == "grouped"       # (only sgdnet_mnewton() and sgdnet_wmnewton() pass it on)
     if family not in _FAMILY_CHOICES:
         _stop("'arg' should be one of " + ", ".join(f"'{f}'" for f in _FAMILY_CHOICES))
 
@@ -308,6 +319,10 @@ def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standar
     ctl.standardize_response = int(standardize_response)
     ctl.tol = float(thresh)
     ctl.type_multinomial = 0 if type_multinomial == "ungrouped" else 1
+    held = contextlib.nullcontext()
+    if type_multinomial == "grouped":             # the modes take the grouped penalty while the option says so
+        from .solver import option
+        held = option("mnewton_grouped", 1)
     keep = []
     if sample_stream is not None:
         ss = np.ascontiguousarray(sample_stream, dtype=np.uint32)
@@ -358,11 +373,13 @@ def _fit(x, y, family, alpha, nlambda, lambda_min_ratio, lambda_, maxit, standar
         csc.colptr = colptr.ctypes.data_as(C.POINTER(C.c_int32))
         csc.rowidx = rowidx.ctypes.data_as(C.POINTER(C.c_int32))
         csc.values = dptr(vals)
-        check(L.sgdnet_fit_sparse(C.byref(csc), dptr(y_mat), y_mat.shape[1], C.byref(ctl),
-                                  C.byref(res)))
+        with held:
+            check(L.sgdnet_fit_sparse(C.byref(csc), dptr(y_mat), y_mat.shape[1], C.byref(ctl),
+                                      C.byref(res)))
     else:
-        check(L.sgdnet_fit_dense(dptr(x), n_samples, n_features, dptr(y_mat), y_mat.shape[1],
-                                 C.byref(ctl), C.byref(res)))
+        with held:
+            check(L.sgdnet_fit_dense(dptr(x), n_samples, n_features, dptr(y_mat), y_mat.shape[1],
+                                     C.byref(ctl), C.byref(res)))
 
     # ---- post-processing, R/sgdnet.R:368-431 ----
     dfmat = None

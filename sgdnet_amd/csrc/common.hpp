@@ -41,6 +41,7 @@ inline const char* exp_env_str(const char*) { return nullptr; }
 enum Option { kOptVirtualShards = 0, kOptRngGenerators, kOptWindowEigenvalue, kOptHostSetup, kOptExactEpochBlocks,
               kOptExactRowRegisters, kOptFusedEpoch, kOptWcovarianceWidth, kOptWnewtonWidth, kOptWmcovarianceWidth,
               kOptWmnewtonWidth, kOptWnewtonMoments, kOptWmnewtonMoments, kOptCvWnewtonMoments, kOptCvWmnewtonMoments,
+              kOptMnewtonGrouped, kOptMnewtonWidth,
               kOptCount };
 int option(Option o);
 

@@ -945,6 +945,7 @@ int fit_common(Features& X, const double* y_in, int Ky, const sgdnet_control* ct
     facts.on_device = X.dev != nullptr;
     facts.n = n;
     facts.p = p;
+    facts.grouped_newton = option(kOptMnewtonGrouped) == 1;
     const FitPlan plan = plan_fit(facts);
     if (plan.rc) {
       set_error("%s", plan.error.c_str());
@@ -1132,6 +1133,7 @@ int fit_sparse_impl(const sgdnet_csc* x, const double* y, int y_cols, const sgdn
     facts.sparse = true;
     facts.n = n;
     facts.p = p;
+    facts.grouped_newton = option(kOptMnewtonGrouped) == 1;
     const FitPlan plan = plan_fit(facts);
     if (plan.rc) {
       set_error("%s", plan.error.c_str());

@@ -225,7 +225,13 @@ int fit_mnewton(const Features& X, const Response& R, const Path& path, const Fi
   pb.y = R.y.data();
   pb.fit_intercept = ctl->intercept != 0;
   pb.b0 = R.b0.data();
-  static const int width = exp_env_int("SGDNET_MNEWTON_WIDTH", 0);  // (64 or 256 lanes: profiles/mnewton_path.txt)
+  pb.grouped = plan.penalty == SGDNET_GROUPLASSO;      // (plan_fit let it pass: the option "mnewton_grouped")
+  static const int env_width = exp_env_int("SGDNET_MNEWTON_WIDTH", 0);  // (64 or 256 lanes: profiles/mnewton_path.txt)
+  const int width = env_width ? env_width : option(kOptMnewtonWidth);      // the option "mnewton_width"; 0: the rule of mnewton.hip
+  if (!wide && width != 0 && width != 64 && width != 256) {
+    set_error("sgdnet_fit: the option mnewton_width is %d; the inner solve runs on 64 or 256 lanes (0: the rule)", width);
+    return SGDNET_EINVAL;
+  }
   MNewtonResult nr;
   const int rc = wide ? wmnewton_run(pb, pt.on, &nr, option(kOptWmnewtonWidth)) : mnewton_run(pb, pt.on, &nr, width);
   if (rc) return rc;

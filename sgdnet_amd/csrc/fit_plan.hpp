@@ -67,6 +67,7 @@ struct FitFacts {
   double norm_max = 0.0;       // largest squared row norm
   double l_f = 0.0;            // largest eigenvalue of X'X/n (or its bound); read only where wants_l_f() holds
   FitOptions opt;
+  bool grouped_newton = false; // the option "mnewton_grouped": mnewton / wmnewton take the grouped penalty (type_multinomial = 1)
 };
 
 // SGDNET_MODE_BATCHED means "batched where it is implemented": more than 64 classes run the exact
@@ -208,7 +209,8 @@ inline FitPlan plan_fit(const FitFacts& f) {
         break;
       default: {                        // SGDNET_MODE_MNEWTON: the joint Hessian in LDS; sparse x as for wnewton
         const char* classes = (K < 2 || K >= 100) ? "2 to 99 classes"
-                              : c.type_multinomial != 0 ? "the ungrouped penalty (type_multinomial = 0)" : nullptr;
+                              : (c.type_multinomial != 0 && !(c.type_multinomial == 1 && f.grouped_newton))
+                                  ? "the ungrouped penalty (type_multinomial = 0)" : nullptr;
         if (c.mode == SGDNET_MODE_WMNEWTON)     // ... with the joint Hessian in global memory: every p from 1 to its own limit
           plan_direct(P, f, {"wmnewton", SGDNET_MULTINOMIAL, "family = multinomial", classes, wmnewton_max_features(K),
                              "no more features than sgdnet_wmnewton_max_features(n_classes)", kWmnewtonDenseCopyBytes, DirectRule::kSamples});

@@ -34,6 +34,10 @@
 // (wide_cd_device.hpp) over the Q coordinates; the blend forms its value where it is read (mnewton_wide_blend_kernel).
 // Same optimum as the narrow mode, not the same bits; neither falls back to the other.
 //
+// The grouped penalty (MNewtonProblem::grouped; the option "mnewton_grouped"): sum_k |w_k|_1 becomes sum_j |w_.j|_2 over the K
+// classes of a feature.  The outer loop, the state, moments and scale passes are the ones above; the inner solves and the
+// publish are mnewton_grouped.hip's.  A single fit only: the cross-validations and the probes keep the ungrouped penalty.
+//
 // Cross-validation (mnewton_cv_run, include/sgdnet_hip.h: sgdnet_cv_mnewton_*): all fold fits of all mixes advance in
 // lock-step, as newton.hip's newton_cv_run runs the binomial ones.  The rows are sorted by group once, so a training set is
 // a range of rows or the complement of one; the mnewton_cv_* kernels are the narrow mode's kernels with a job dimension,
@@ -63,6 +67,7 @@
 #include "device_math.hpp"
 #include "mnewton.hpp"
 #include "mnewton_cv_mfma.hpp"
+#include "mnewton_grouped.hpp"
 #include "mnewton_mfma.hpp"
 #include "moments_device.hpp"
 #include "newton_cv_device.hpp"
@@ -787,6 +792,8 @@ struct MNewtonDevice {
   double *d_H = nullptr, *d_Hd = nullptr, *d_q = nullptr;
   // wide and the option "wmnewton_moments" = 1 (read in setup): the moments pass of mnewton_mfma.hip on its own row chunks
   bool mfma = false;
+  // the grouped penalty (set before setup; a fit only): the inner solves and the publish are mnewton_grouped.hip's
+  bool grouped = false;
   int pairs = 0;                       // the tile pairs and the row chunks (a function of n, p and K alone)
   int64_t rows_per_chunk = 0, chunks = 0;
   int state_blocks = 0;
@@ -877,7 +884,8 @@ struct MNewtonDevice {
 
   // publish / blend: d_cand <- d_cur + t (d_cand - d_cur), its state-pass form d_a and its record
   int publish(double t) {
-    if (wide) hipLaunchKernelGGL(mnewton_wide_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
+    if (grouped) mnewton_grouped_blend(wide, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec, st);
+    else if (wide) hipLaunchKernelGGL(mnewton_wide_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
     else hipLaunchKernelGGL(mnewton_blend_kernel, dim3(1), dim3(64), 0, st, d_cur, d_scale, p, Q, t, d_cand, d_a, d_rec);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
@@ -928,8 +936,12 @@ struct MNewtonDevice {
   // wide: the list solve on d_H, d_Hd and d_q about d_cur
   int wide_solve(double al, double be, bool ridge, bool fit_intercept, unsigned max_sweeps, double tol) {
     const auto kernel = width == kWideNarrow ? mnewton_wide_cd_kernel<kWideNarrow> : mnewton_wide_cd_kernel<kWideFull>;
-    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, K, ld, d_cur, al, be, ridge ? 1 : 0,
-                       fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
+    if (grouped)
+      mnewton_wide_grouped_cd(width, d_H, d_Hd, d_q, d_scale, p, K, ld, d_cur, al, be, fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec,
+                              st);
+    else
+      hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)width), 0, st, d_H, d_Hd, d_q, d_scale, p, K, ld, d_cur, al, be, ridge ? 1 : 0,
+                         fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
     SGD_HIP_TRY(hipGetLastError());
     return SGDNET_OK;
   }
@@ -940,7 +952,9 @@ struct MNewtonDevice {
       const int rc = wide_scale();
       return rc ? rc : wide_solve(al, be, ridge, fit_intercept, max_sweeps, tol);
     }
-    if (width == 256)
+    if (grouped)
+      mnewton_grouped_cd(width, d_M, d_scale, p, K, (double)n, d_cur, al, be, fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec, st);
+    else if (width == 256)
       hipLaunchKernelGGL(mnewton_cd_kernel<256>, dim3(1), dim3(256), 0, st, d_M, d_scale, p, K, (double)n, d_cur, al, be, ridge ? 1 : 0,
                          fit_intercept ? 1 : 0, max_sweeps, tol, d_cand, d_a, d_rec);
     else
@@ -971,6 +985,13 @@ int mnewton_loop(const MNewtonProblem& pb, bool timed, MNewtonResult* out, bool 
   for (int k = 0; k < K; ++k) start[(size_t)k * (size_t)P + (size_t)p] = pb.b0[k];
   MNewtonDevice D;
   D.wide = wide;
+  D.grouped = pb.grouped && !pb.ridge;     // (alpha = 0: the ridge functor, the ungrouped kernels and their bits)
+  // The grouped inner solves stop at tol / 10: their sweeps converge linearly, more slowly the more classes a block has, and a
+  // sweep's relative change then understates what is left.  At 20000 x 200, K = 10 and the default thresh the worst KKT ratio
+  // is 2.28 at tol (the ungrouped mode: 0.95), 0.36 at tol / 10 and 0.035 at tol / 100 (profiles/mnewton_grouped.txt, section 2;
+  // SGDNET_GROUPED_INNER_DIV in experiments builds).
+  static const int inner_div = exp_env_int("SGDNET_GROUPED_INNER_DIV", 10);
+  const double inner_tol = D.grouped && inner_div > 1 ? pb.tol / (double)inner_div : pb.tol;
   int rc = D.setup(pb, start.data(), start.data(), timed, width);
   if (rc) return rc;
   hipStream_t st = D.st;
@@ -993,7 +1014,7 @@ int mnewton_loop(const MNewtonProblem& pb, bool timed, MNewtonResult* out, bool 
     unsigned steps = 0;
     bool converged = false;
     while (steps < pb.max_iter && !converged) {
-      if ((rc = D.moments()) || (rc = D.inner_solve(al, be, pb.ridge, pb.fit_intercept, kNewtonMaxSweeps, pb.tol)) || (rc = D.state_pass()))
+      if ((rc = D.moments()) || (rc = D.inner_solve(al, be, pb.ridge, pb.fit_intercept, kNewtonMaxSweeps, inner_tol)) || (rc = D.state_pass()))
         return rc;
       if (timed) {
         float ms = 0.f;

@@ -106,6 +106,32 @@ static_assert(wmnewton_row_chunks((int64_t)1 << 40, 3, 2) * wmnewton_chunk_workg
 // Sparse x is expanded to a column-major dense copy by the driver, as for mnewton; the copy stays within this many bytes.
 constexpr size_t kWmnewtonDenseCopyBytes = (size_t)1 << 30;
 
+// ---- the grouped penalty (the option "mnewton_grouped" = 1 with type_multinomial = 1; mnewton_grouped.hip) ----
+// The penalty sum_j (al/2 |w_.j|^2 + be |w_.j|_2) couples the K coordinates k (p + 1) + j of a feature j: the inner solves
+// move such a BLOCK by one majorised proximal step, with t_j = max_k sum_l |H[(k, j), (l, j)]| (Gershgorin: at least the
+// largest eigenvalue of the block's K x K Hessian).  The intercepts stay scalar coordinates.
+//   narrow (mnewton_grouped_cd_kernel): mnewton_cd_kernel's LDS -- the packed triangle, U and g -- and behind them the p
+//       bounds t_j and the p change scales of the blocks, computed once per solve, and the K steps d_k of the block that
+//       moves: Q (Q + 1) / 2 + 2 Q + 2 p + K doubles.  K <= 99 divides Q, so Q <= 198 and 20 097 + 198 <= 20 480 at K = 2, p = 98.
+//   wide (mnewton_wide_grouped_cd_kernel): g | U | T | S | d | the list | its bits | the counts, where T holds t_j for j < p
+//       and the K intercept diagonals, S the p change scales, d the K steps, and the list's entries are BLOCKS (e < p) and
+//       intercepts (p + k): 8 (2 Q + 2 p + 2 K) + wide_list_bytes(p + K) bytes, less than wmnewton_state_bytes(Q) at every
+//       K's limit (at a handful of coordinates it is a few bytes more, far inside the LDS) and growing with p.
+constexpr int mnewton_grouped_state_doubles(int p, int K) { return mnewton_state_doubles(K * (p + 1)) + 2 * p + K; }
+constexpr int wmnewton_grouped_state_bytes(int p, int K) { return 8 * (2 * K * (p + 1) + 2 * p + 2 * K) + wide_list_bytes(p + K); }
+constexpr bool mnewton_grouped_fits() {
+  for (int K = 2; K <= kWmnewtonMaxClasses; ++K) {
+    if (mnewton_max_features(K) > 0 && mnewton_grouped_state_doubles(mnewton_max_features(K), K) > kNewtonLdsDoubles) return false;
+    if (wmnewton_grouped_state_bytes(wmnewton_max_features(K), K) > wmnewton_state_bytes(K * (wmnewton_max_features(K) + 1))) return false;
+    if (wmnewton_state_bytes(K * (wmnewton_max_features(K) + 1)) > kWmnewtonLdsBytes) return false;
+  }
+  return true;
+}
+static_assert(mnewton_grouped_fits(), "the LDS of the grouped inner solves at every K's feature limit (see above)");
+static_assert(mnewton_grouped_state_doubles(98, 2) == 20295 && mnewton_grouped_state_doubles(1, 99) == 20198 &&
+              wmnewton_grouped_state_bytes(2909, 2) == 139696 + 11644 + 364 + 128 && wmnewton_grouped_state_bytes(1, 2) == 256 &&
+              wmnewton_state_bytes(4) == 244, "the examples above");
+
 // class pair c = 0 .. K (K + 1) / 2 - 1 -> (k, l), k <= l, row by row of the upper triangle (the kernels call it too)
 constexpr void class_pair(int c, int K, int* k, int* l) {
   int kk = 0;
@@ -168,6 +194,7 @@ struct MNewtonProblem : DirectProblem {         // x_dense only (sparse x: the d
   const double* y = nullptr;           // n: class codes 0 .. K - 1
   bool fit_intercept = true;           // false: the intercepts stay at b0
   const double* b0 = nullptr;          // K: the null model's intercepts: where the path starts
+  bool grouped = false;                // the grouped penalty (plan.penalty == SGDNET_GROUPLASSO): mnewton_grouped.hip's inner solves
 };
 
 struct MNewtonResult {

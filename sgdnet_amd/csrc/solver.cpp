@@ -349,8 +349,9 @@ const OptionDef kOptionDefs[sgdnet::kOptCount] = {
     {"fused_epoch", 1, 0, 2},      {"wcovariance_width", 0, 0, 1024}, {"wnewton_width", 0, 0, 1024},
     {"wmcovariance_width", 0, 0, 1024}, {"wmnewton_width", 0, 0, 1024}, {"wnewton_moments", 0, 0, 1},
     {"wmnewton_moments", 0, 0, 1}, {"cv_wnewton_moments", 0, 0, 1}, {"cv_wmnewton_moments", 0, 0, 1},
+    {"mnewton_grouped", 0, 0, 1}, {"mnewton_width", 0, 0, 256},
 };
-std::atomic<int> g_options[sgdnet::kOptCount] = {{-1}, {0}, {1}, {0}, {1}, {1}, {1}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+std::atomic<int> g_options[sgdnet::kOptCount] = {{-1}, {0}, {1}, {0}, {1}, {1}, {1}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
 int find_option(const char* name) {
   if (name)
     for (int i = 0; i < sgdnet::kOptCount; ++i)

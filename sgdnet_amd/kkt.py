@@ -149,7 +149,7 @@ def evaluation_intercepts(fit, x_center=None, y_center=None, intercept=True):
     return np.asfortranarray(a0 + yc[:, None] - np.einsum("j,kjl->kl", xc, beta))
 
 
-def kkt_from_gradient(G, G0, fit, x_center=None, x_scale=None, y_scale=None, standardize=True, intercept=True):
+def kkt_from_gradient(G, G0, fit, x_center=None, x_scale=None, y_scale=None, standardize=True, intercept=True, grouped=False):
     """Optimality residual per lambda from the averaged loss gradient (pure numpy, no device).
 
     G (K, p, nlambda), G0 (K, nlambda): path_gradient's, taken at evaluation_intercepts().  x_center / x_scale: the
@@ -157,7 +157,8 @@ def kkt_from_gradient(G, G0, fit, x_center=None, x_scale=None, y_scale=None, sta
     (response_moments; 1 otherwise).  Returns {"coef", "intercept", "ratio"}, arrays of nlambda entries:
     coef = the largest violation over the coefficients (units of y per unit of standardised feature), intercept =
     max_k |G0[k]| (multinomial: after removing the class mean, the intercepts being defined up to a constant; 0
-    with intercept=False), ratio = coef / lambda."""
+    with intercept=False), ratio = coef / lambda.  grouped: a multinomial fit under the grouped penalty
+    (sgdnet_mnewton(..., type_multinomial="grouped")): the group-lasso conditions over the K classes of a feature."""
     _, beta = _stacked(fit)
     K, p, L = beta.shape
     G = np.asarray(G, dtype=np.float64).reshape(K, p, L)
@@ -178,7 +179,7 @@ def kkt_from_gradient(G, G0, fit, x_center=None, x_scale=None, y_scale=None, sta
     l2 = ((1.0 - mix) * lam / ys).reshape(1, 1, L)
     if mix == 0.0:                                              # fit_plan.hpp plan_fit: the ridge functor
         viol = np.abs(g + l2 * c)
-    elif fit.family == "mgaussian":                             # group lasso: rows over the K responses
+    elif fit.family == "mgaussian" or (grouped and fit.family == "multinomial"):   # group lasso: rows over the K responses
         nrm = np.sqrt((c ** 2).sum(axis=0, keepdims=True))
         live = nrm > 0
         unit = np.divide(c, nrm, out=np.zeros_like(c), where=live)
@@ -199,9 +200,10 @@ def kkt_from_gradient(G, G0, fit, x_center=None, x_scale=None, y_scale=None, sta
     return {"coef": coef, "intercept": icpt, "ratio": ratio}
 
 
-def kkt(fit, x, y, standardize=True, intercept=True, standardize_response=False, device=0):
+def kkt(fit, x, y, standardize=True, intercept=True, standardize_response=False, device=0, grouped=False):
     """The optimality certificate of a fitted path: kkt_from_gradient on the device's path_gradient.  standardize,
-    intercept and standardize_response are the fit's (SgdnetFit does not record them; sgdnet()'s defaults)."""
+    intercept and standardize_response are the fit's (SgdnetFit does not record them; sgdnet()'s defaults); grouped
+    as kkt_from_gradient takes it."""
     x_center, x_scale = feature_moments(x, standardize)
     y_center, y_scale = response_moments(fit, y, standardize_response)
     if fit.family == "mgaussian" and standardize_response:      # the coefficients live on the standardised response
@@ -211,4 +213,4 @@ def kkt(fit, x, y, standardize=True, intercept=True, standardize_response=False,
     a0 = evaluation_intercepts(fit, x_center, y_center, intercept)
     G, G0 = path_gradient(fit, x, y, device=device, a0=a0)
     return kkt_from_gradient(G, G0, fit, x_center=x_center, x_scale=x_scale, y_scale=y_scale, standardize=standardize,
-                             intercept=intercept)
+                             intercept=intercept, grouped=grouped)
